@@ -11,6 +11,13 @@ BENCH_SLOTS[config] paths are in flight per pixel (mcpt_set_path_slots; 24 on co
 the one-path-per-pixel oracle's within the north star's 1e-4 (tests/test_bench_layout.py runs
 this exact layout).  `--steady` reports the steady-state iteration rate beside it.
 
+A plain run sets up, renders the warmup and the timed frames and prints the line.  `--full` adds
+what takes runs of its own: the counting frame behind the roofline's per-ray figures and the
+roofline object, the measured copy ceiling, the CPU baseline (N = 1), and for N > 1 the frame-end
+gather with its check and the other split.  `--dump-outputs DIR` writes the last timed frame's film
+as DIR/*.npy (dump_outputs); scene, camera and seed are fixed, so two runs with the same arguments
+render the same inputs.
+
 Multi-GPU: one process per GPU.  `--gpus N` without an external launcher starts
 the N ranks itself (torch.distributed.run, before anything touches the GPU); under a launcher
 WORLD_SIZE must equal N.  Film tiles are dealt to ranks by (tx + ty) mod N (64 x 64 tiles for
@@ -22,10 +29,11 @@ N > 1: MULTI_TILE), and every rank holds path state for its own tiles only
   --scaling weak: `value` is a 1920 x 1080*N frame of the same view (N-fold vertical
       supersampling): every rank owns ~one 1080p frame of pixels with the 1-GPU run's sky /
       geometry mix.
-An N>1 run also times the other split as a sub-object ("weak" / "strong"; --no-weak / --no-strong
-skip it).  After timing, the strong frame is gathered into rank 0's device film (mcpt/parallel.py:
-point-to-point RCCL sends over xGMI) and rank 0 re-renders every other rank's tiles alone and
-compares them with the gathered pixels bit for bit (--no-gather / --no-verify-gather skip these).
+An N>1 run with --full also times the other split as a sub-object ("weak" / "strong"; --no-weak /
+--no-strong skip it).  After timing, the strong frame is gathered into rank 0's device film
+(mcpt/parallel.py: point-to-point RCCL sends over xGMI) and rank 0 re-renders every other rank's
+tiles alone and compares them with the gathered pixels bit for bit (--no-gather /
+--no-verify-gather skip these).
 No collective runs inside a timed region: tiles are independent.
 """
 from __future__ import annotations
@@ -124,6 +132,12 @@ def parse(argv=None):
     ap.add_argument("--scaling", choices=("weak", "strong"), default="strong",
                     help="N>1: which split `value` reports (the other is timed as a sub-object)")
     ap.add_argument("--spp", type=int, default=None, help="override the config's spp (not the BASELINE workload)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed frames also run everything beside the headline: the counting frame and the "
+                         "roofline, the measured copy ceiling, the CPU baseline (N = 1), the gather with its check and "
+                         "the other split (N > 1); the --no-* options below trim a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the film of the last timed frame (what a caller of render() reads back) to DIR/*.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-spp", type=int, default=12, help="spp of the full-frame CPU-oracle sample")
     ap.add_argument("--no-strong", action="store_true",
@@ -604,6 +618,34 @@ def gather_and_verify(pt, rc, rank, world, dist, spp, args, torch):
     return out
 
 
+DUMP_BYTES = 64 * 10 ** 6  # --dump-outputs: all ranks' files together stay below this
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(pt, out_dir, rank, world):
+    """--dump-outputs: the film the last timed frame left, as a caller of render() reads it back
+    (PathTracer.film()): film_Ld.npy, float32 (H, W, 3) radiance, and film_samples.npy,
+    float32 (H, W) sample counts (exact: counts stay far below 2^24).  N > 1: every rank writes its
+    own film (its tiles; zero elsewhere) as <name>_rank<r>.npy.  A film over the rank's share of
+    DUMP_BYTES is written as a fixed sample of its pixels instead (the same pixels in every run:
+    DUMP_SEED), with film_pixels.npy (float64) holding their row-major pixel indices."""
+    import numpy as np
+
+    Ld, smp = pt.film()
+    sfx = "" if world == 1 else f"_rank{rank}"
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"film_Ld": Ld.astype(np.float32, copy=False), "film_samples": smp.astype(np.float32)}
+    budget = DUMP_BYTES // world
+    npx = smp.size
+    if npx * (12 + 4) > budget:
+        keep = np.sort(np.random.default_rng(DUMP_SEED).choice(npx, budget // (12 + 4 + 8), replace=False))
+        arrays = {"film_Ld": arrays["film_Ld"].reshape(npx, 3)[keep],
+                  "film_samples": arrays["film_samples"].reshape(npx)[keep],
+                  "film_pixels": keep.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), a)
+
+
 def make_tracer(local, args, rc, spp):
     """The product path tracer on device `local` with the config's scene and camera."""
     import mcpt
@@ -696,6 +738,8 @@ def main(argv=None, tracer=make_tracer, torch_mod=None):
     dt, st = head["dt"], head["st"]
     dt_all, rays_all = head["dt_all"], head["rays_all"]
     slots, W, H, tile = head["layout"]["slots"], head["layout"]["frame"][0], head["layout"]["frame"][1], head["layout"]["tile"]
+    if args.dump_outputs:
+        dump_outputs(pt, args.dump_outputs, rank, world)
 
     # steady state (outside `value`): iterations with every pixel's paths in flight
     steady = None
@@ -714,9 +758,10 @@ def main(argv=None, tracer=make_tracer, torch_mod=None):
 
     # traversal work counters (node steps, triangle tests, hits) from one more, untimed frame with
     # the counting k_trace build (mcpt_set_work_counters): they feed the roofline's per-ray figures.
-    # --no-work-counters skips it (rocprofv3 passes: every launch then belongs to a timed or warmup frame)
+    # --full only, and --no-work-counters skips it (rocprofv3 passes: every launch then belongs to a
+    # timed or warmup frame)
     work = None
-    if rank == 0 and not args.no_work_counters:
+    if args.full and rank == 0 and not args.no_work_counters:
         pt.set_work_counters(True)
         pt.clear()
         work = Acc()
@@ -728,10 +773,11 @@ def main(argv=None, tracer=make_tracer, torch_mod=None):
     # The steps after the headline's timed frames (the gather and its check, the other split) run
     # guarded: an error on any rank lands in the line's gather.error / <split>.error, every rank
     # agrees on it before the next step (which is then skipped), and rank 0 prints the line anyway.
+    # They belong to --full: a plain run ends with its timed frames.
     gather = None
     extras_ok = True
     dev = dev_of(backend)
-    if dist and args.scaling == "strong" and not args.no_gather:
+    if args.full and dist and args.scaling == "strong" and not args.no_gather:
         gather, err = guarded(gather_and_verify, pt, rc, rank, world, dist, spp, args, torch)
         extras_ok = agree(dist, dev, err is None, torch)
         if err or not extras_ok:
@@ -739,7 +785,7 @@ def main(argv=None, tracer=make_tracer, torch_mod=None):
     other = None
     other_kind = "weak" if args.scaling == "strong" else "strong"
     skip_other = args.no_weak if other_kind == "weak" else args.no_strong
-    if dist and not skip_other:
+    if args.full and dist and not skip_other:
         if not extras_ok:
             other = {"error": "skipped: the gather failed"}
         else:
@@ -761,14 +807,16 @@ def main(argv=None, tracer=make_tracer, torch_mod=None):
         return
 
     K = args.steps
-    roof = roofline(st, st.ms_extend, st.ms_shade, args.config, slots, work, spp=spp)
-    roof["extend_shade"] = extend_shade(st, dt_all / K, K, args.config, slots, spp=spp)
-    tp = trace_phases(work)
-    if tp:
-        roof["k_trace_phases"] = tp
-    roof["measured_copy_GBps"] = round(pt.hbm_copy_gbps(1 << 30, 20), 1)  # one-pass dwordx4 copy ceiling
+    roof = None
+    if args.full:
+        roof = roofline(st, st.ms_extend, st.ms_shade, args.config, slots, work, spp=spp)
+        roof["extend_shade"] = extend_shade(st, dt_all / K, K, args.config, slots, spp=spp)
+        tp = trace_phases(work)
+        if tp:
+            roof["k_trace_phases"] = tp
+        roof["measured_copy_GBps"] = round(pt.hbm_copy_gbps(1 << 30, 20), 1)  # one-pass dwordx4 copy ceiling
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(scene.arrays(), cam, W, H, args.cpu_spp, rc.max_depth)
     value = rays_all / dt_all / 1e6
     kn = knobs()
@@ -788,6 +836,7 @@ def main(argv=None, tracer=make_tracer, torch_mod=None):
         "ms_per_step": round(dt_all * 1e3 / K, 3),
         "higher_is_better": True,
         "scaling": args.scaling,
+        "full": args.full,  # False: roofline, cpu_baseline, gather and the other split were not run
         "vs_baseline": None,
         "dtype": "f32",
         "data": "synthetic",

@@ -7,6 +7,7 @@
 set -o pipefail
 mkdir -p gpurun_out
 export TMPDIR=/tmp
+BENCH_ARGS="--full ${BENCH_ARGS}"  # the summary below prints the roofline's per-ray figures
 if [[ -n "$TEST" ]]; then
   timeout -k 10 900 python -u -m pytest tests/ -m gpu -x -q --timeout 300 --timeout-method thread ${TEST_ARGS} > gpurun_out/ab_test.log 2>&1 || { grep -E "FAILED|Error|differ" gpurun_out/ab_test.log | head -20; tail -5 gpurun_out/ab_test.log; exit 1; }
   grep -E "passed|failed" gpurun_out/ab_test.log | tail -1

@@ -28,7 +28,8 @@ CONFIG=${CONFIG:-2}
 TAG=${TAG:-r05}
 STEPS=${STEPS:-3}
 O=gpurun_out
-BARGS="--no-cpu-baseline --config $CONFIG --steps $STEPS --warmup 1 ${BENCH_ARGS}"
+# --full: the steps below read the roofline and its per-ray figures from the line
+BARGS="--full --no-cpu-baseline --config $CONFIG --steps $STEPS --warmup 1 ${BENCH_ARGS}"
 sfx=$([[ $CONFIG == 2 ]] && echo "$TAG" || echo "c${CONFIG}_$TAG")
 
 fail() { echo "step $1 failed"; tail -${2:-30} "$3"; exit 1; }

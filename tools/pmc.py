@@ -59,7 +59,7 @@ stamp = {"source_hash": bench.source_hash(), "config": cfg,
          "knobs": bench.knobs()}
 out = {"round": tag, "stamp": stamp,
        "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on "
-       f"'python3 bench.py {os.environ.get('PMC_ARGS', '--no-cpu-baseline')}'; durations from --kernel-trace --stats",
+       f"'python3 bench.py {os.environ.get('PMC_ARGS', '--full --no-cpu-baseline')}'; durations from --kernel-trace --stats",
        "correction": "hbm_bytes = (2*FETCH_SIZE + WRITE_SIZE) * 1024 (gfx950 FETCH_SIZE reads half of 16 B/lane streams)",
        "kernels": {}}
 for k, v in pmc.items():
