@@ -11,9 +11,10 @@ SRCS := $(PKG)/csrc/kernels.hip $(PKG)/csrc/bvh_build.hip $(PKG)/csrc/env_build.
         $(PKG)/csrc/host/scene.cpp $(PKG)/csrc/host/proxies.cpp $(PKG)/csrc/host/capi_host.cpp \
         $(PKG)/csrc/host/image_io.cpp
 OBJS := $(patsubst $(PKG)/csrc/%,$(BUILD)/%.o,$(SRCS))
-HDRS := include/mcpt.h $(PKG)/csrc/kernels.hpp $(PKG)/csrc/device/mcpt_core.hpp $(PKG)/csrc/host/host_internal.hpp
+HDRS := include/mcpt.h $(PKG)/csrc/kernels.hpp $(PKG)/csrc/device/mcpt_core.hpp \
+        $(PKG)/csrc/device/primary_beam.hpp $(PKG)/csrc/host/host_internal.hpp
 
-all: $(PKG)/libmcpt.so oracle/liboracle.so examples/mcpt_render tests/native/facade_test
+all: $(PKG)/libmcpt.so oracle/liboracle.so examples/mcpt_render tests/native/facade_test tests/native/primary_beam
 
 $(BUILD)/%.o: $(PKG)/csrc/% $(HDRS)
 	@mkdir -p $(dir $@)
@@ -32,11 +33,15 @@ example: examples/mcpt_render
 tests/native/facade_test: tests/native/facade_test.cpp include/mcpt.hpp include/mcpt.h $(PKG)/libmcpt.so
 	g++ -O2 -std=c++17 -Wall -Wextra -Iinclude $< -L$(PKG) -lmcpt -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -o $@
 
+# Host check of the primary beam's interval bounds (device/primary_beam.hpp) on the CPU
+tests/native/primary_beam: tests/native/primary_beam.cpp $(PKG)/csrc/device/primary_beam.hpp $(PKG)/csrc/device/mcpt_core.hpp
+	$(HIPCC) -O2 -std=c++17 -ffp-contract=off -fno-fast-math -Iinclude -I$(PKG)/csrc $< -o $@
+
 oracle/liboracle.so: oracle/mcpt_oracle.c oracle/mcpt_oracle.h
 	$(MAKE) -C oracle
 
 clean:
-	rm -rf $(BUILD) $(PKG)/libmcpt.so examples/mcpt_render tests/native/facade_test
+	rm -rf $(BUILD) $(PKG)/libmcpt.so examples/mcpt_render tests/native/facade_test tests/native/primary_beam
 	$(MAKE) -C oracle clean
 
 .PHONY: all clean

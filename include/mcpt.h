@@ -288,6 +288,12 @@ int mcpt_debug_occ_stats(const mcpt_ctx *ctx, uint64_t *resolved, int32_t *enabl
  * (the rest: NaN / zero directions and root-box misses resolved where the ray was made), any-hit
  * (shadow + BRDF visibility) rays, of them traversed, and of them resolved by the occluder cache. */
 int mcpt_debug_ray_counts(const mcpt_ctx *ctx, uint64_t *out);
+/* Primary-hit candidate table (MCPT_PRIMARY_HITS=0 at context creation turns it
+ * off), 4 values: pixels with a candidate list and pixels without one (overflow or no bound) in the
+ * current table, primary rays resolved from the table since the last film clear (they count as
+ * extension rays, not as traversed ones), and the last table build's milliseconds.  Returns the
+ * number of table builds of the context so far (a film clear alone never rebuilds), < 0 on error. */
+int mcpt_debug_primary_stats(const mcpt_ctx *ctx, double *out4);
 /* The traversal's loop-phase counts, recorded by the counting build (mcpt_set_work_counters on)
  * since the last film clear or reset (reset = 1 starts a new count after reading): out12[0] loop
  * trips, [1] refills, [2] lanes refilled, [3] node-phase wave iterations, [4] triangle phases,

@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "device/mcpt_core.hpp"
+#include "device/primary_beam.hpp"
 #include "kernels.hpp"
 
 using namespace mcpt;
@@ -775,7 +776,7 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
     }
     // ---- phase 1: logic + generate (one thread per pixel)
     MCPT_MARK("load");
-    bool gen_ext = false, gen_trivial = false, cont = false;
+    bool gen_ext = false, gen_trivial = false, gen_prim = false, prim_res = false, cont = false;
     bool d_logic = false, d_nee = false, d_gen = false;  // (MCPT_DIAG_SHADE)
     (void)d_logic; (void)d_nee; (void)d_gen;
     uint32_t cont_len = 0, cont_sidx = 0;
@@ -904,6 +905,22 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
                 a.p.hit_tri[pid] = -1;
                 gen_ext = false;
                 gen_trivial = true;
+            } else if (a.prim_cnt) {
+                // the pixel's candidate list decides the hit (k_primary) for a ray with a finite
+                // inverse direction (1 / 1e-30 is finite; the others are traversed); an empty list
+                // is a miss
+                const uint32_t pc = a.prim_cnt[pix];
+                if (pc != 0u && __builtin_fminf(__builtin_fminf(__builtin_fabsf(new_d.x), __builtin_fabsf(new_d.y)),
+                                                __builtin_fabsf(new_d.z)) >= 1e-30f) {
+                    gen_ext = false;
+                    prim_res = true;
+                    if (pc == 1u) {
+                        a.p.hit_tri[pid] = -1;
+                        gen_trivial = true;
+                    } else {
+                        gen_prim = true;
+                    }
+                }
             }
         }
         MCPT_MARK("flags");
@@ -924,20 +941,25 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
     const int shard = vb % kShards;  // the queues' capacity assumes <= kBlock pushes per block and shard
     uint32_t* sc_ctr = a.cnt->shard[shard];
     {
-        bool want[2] = {gen_ext, cont};
-        uint32_t* ctr[2] = {sc_ctr + C_EXT, sc_ctr + C_MAT};
-        uint32_t slot[2], total[2];
-        block_push<2>(want, ctr, slot, total);
+        bool want[3] = {gen_ext, cont, gen_prim};
+        uint32_t* ctr[3] = {sc_ctr + C_EXT, sc_ctr + C_MAT, sc_ctr + C_PRIM};
+        uint32_t slot[3], total[3];
+        block_push<3>(want, ctr, slot, total);
         if (gen_ext) st_q(a.ext_q + shard * a.ext_cap + slot[0], pid);
+        if (gen_prim) a.prim_q[shard * a.ext_cap + slot[2]] = make_uint2(pid, pix);
         if (cont) {
             const uint32_t qi = shard * a.ext_cap + slot[1];
             st_s(a.mat_rec + qi, make_uint4(pid, pix, cont_sidx | (cont_len << kRecLenShift), (uint32_t)cont_htri));
             st_s(a.mat_beta + qi, f4(beta_store, 0.f));
         }
     }
-    uint32_t n_ext = (gen_ext || gen_trivial) ? 1u : 0u;  // queued + resolved-in-place rays
+    uint32_t n_ext = (gen_ext || gen_trivial || gen_prim) ? 1u : 0u;  // queued + resolved-in-place + table rays
     for (int off = 32; off > 0; off >>= 1) n_ext += __shfl_xor(n_ext, off);
     if (lane == 0 && n_ext) atomicAdd(sc_ctr + C_EXT_RAYS, n_ext);
+    if (a.prim_cnt) {
+        const uint32_t n_prim = (uint32_t)__popcll(__ballot(prim_res));
+        if (lane == 0 && n_prim) atomicAdd(sc_ctr + C_PRIM_RAYS, n_prim);
+    }
     MCPT_MARK("background");
     if (bg) {  // wavefront_kernels.cu:129-140, len 1 and no hit: beta is (1,1,1)
         const int nbg = FIXED ? 1 : sc.nlights;  // the reference adds it once per light (A.4)
@@ -1815,6 +1837,146 @@ __global__ __launch_bounds__(kTraceBlock) MCPT_TRACE_ATTR void k_trace(TraceArgs
     }
 }
 
+// ---------------------------------------------------------------------------
+// Primary hits from per-pixel candidate lists.  The closest hit the
+// traversal returns is tree-independent: the triangle with the smallest accepted t (ties: lowest
+// scene id) among those whose own leaf box passes the slab test and that Moller-Trumbore accepts
+// with 0 <= t < K_HUGE -- every ancestor box passes whenever the leaf box does (boxes nest, the
+// rounded slab products are monotone in the box), and the culls skip no triangle that can be
+// accepted.  k_primary_build lists, per pixel, every triangle whose leaf box the pixel's rays do
+// not provably all fail (primary_beam.hpp); k_primary runs that acceptance over the list with the
+// traversal's arithmetic: pair_slab's products (finite inverse; k_shade queues only such rays),
+// tri_test_t, !(t < 0), t < best.  The list is in ascending scene-id order, so a tie keeps the
+// earlier candidate.  Dense over the primary queue like k_material: block b serves shard b mod
+// kShards.  Adjacent lanes hold adjacent pixels, so the 64-B candidate records are shared.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_primary(ShadeArgs a_kernarg) {
+    (void)a_kernarg;
+    const ShadeArgs& a = kernarg_fresh<ShadeArgs>();
+    if (a.cnt->idle) return;
+    const uint32_t shard = blockIdx.x % kShards, w_in = blockIdx.x / kShards, bps = gridDim.x / kShards;
+    const uint32_t n = a.cnt->shard[shard][C_PRIM];
+    const float4* rec = a.scene.occ_rec;
+    for (uint32_t i = w_in * kBlock + threadIdx.x; i < n; i += bps * kBlock) {
+        const uint2 q = a.prim_q[shard * a.ext_cap + i];  // {path, pixel}
+        const V3 o = ld3f4(a.p.ray_o + q.x), d = ld3f4(a.p.ray_d + q.x);
+        const uint32_t nc = (uint32_t)a.prim_cnt[q.y] - 1u;
+        const uint4* lp = reinterpret_cast<const uint4*>(a.prim_list + (size_t)kPrimLine * q.y);
+        const V3 inv = v3(1.f / d.x, 1.f / d.y, 1.f / d.z);  // k_trace's
+        float best = K_HUGE;
+        int32_t tri = -1;
+        for (uint32_t j0 = 0; j0 < nc; j0 += 4) {
+            const uint4 ids = lp[j0 >> 2];
+            const uint32_t id4[4] = {ids.x, ids.y, ids.z, ids.w};
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                if (j0 + k >= nc) break;
+                const float4* p = rec + kOccRecF4 * (size_t)id4[k];
+                const float4 bmn = p[0], bmx = p[1], r2 = p[2], r3 = p[3];
+                const float ax = (bmn.x - o.x) * inv.x, bx = (bmx.x - o.x) * inv.x;
+                const float ay = (bmn.y - o.y) * inv.y, by = (bmx.y - o.y) * inv.y;
+                const float az = (bmn.z - o.z) * inv.z, bz = (bmx.z - o.z) * inv.z;
+                const float t0 = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(ax, bx), __builtin_fminf(ay, by)),
+                                                 __builtin_fminf(az, bz));
+                const float t1 = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(ax, bx), __builtin_fmaxf(ay, by)),
+                                                 __builtin_fmaxf(az, bz));
+                float t;
+                if (t0 <= t1 && tri_test_t(o, d, v3(bmx.w, r2.x, r2.y), v3(r2.z, r2.w, r3.x), v3(r3.y, r3.z, r3.w), t) &&
+                    !(t < 0.f) && t < best) {
+                    best = t;
+                    tri = (int32_t)id4[k];
+                }
+            }
+        }
+        a.p.hit_tri[q.x] = tri;
+    }
+}
+
+// The candidate list of every pixel: a beam traversal of the BVH, one thread per pixel.  A subtree
+// is skipped when the beam provably fails its box (each ancestor box contains its leaf boxes); a
+// leaf's triangles are listed unless the whole beam sees them back-facing.  More than kPrimK
+// candidates, or no bound: the pixel gets no list.
+__global__ __launch_bounds__(64) void k_primary_build(PrimaryBuildArgs a) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (uint32_t)a.W * (uint32_t)a.H) return;
+    const DevScene& sc = a.scene;
+    const V3 cp = ld3f4(a.cam_px + i);
+    const Beam b = a.cam.lens_radius > 0.f ? beam_lens(a.cam, cp) : beam_point(cp, ld3f4(a.cam_dir + i));
+    uint32_t ids[kPrimK];
+    int sid[kPrimK];
+    int n = 0;
+    bool over = !b.ok;
+    if (!over) {
+        const BeamInv iv = beam_inv(b);
+        int stack[kMaxStack];
+        int sp = 0;
+        if (!beam_misses_box(b, iv, sc.root_mn[0], sc.root_mn[1], sc.root_mn[2], sc.root_mx[0], sc.root_mx[1], sc.root_mx[2]))
+            stack[sp++] = sc.root_ref;
+        while (sp > 0 && !over) {
+            const int ref = stack[--sp];
+            if (ref == kEnd) continue;
+            if (ref < 0) {  // leaf: 0x80000000 | (count - 1) << 24 | offset
+                const uint32_t off = (uint32_t)ref & 0xffffffu, cnt = (((uint32_t)ref >> 24) & 7u) + 1u;
+                for (uint32_t k = off; k < off + cnt && k < sc.ntri && !over; k++) {
+                    const float4* tr = sc.tri + kTriF4 * (size_t)k;
+                    const float4 w0 = tr[0], w1 = tr[1], w2 = tr[2];
+                    if (beam_backfacing(b, v3(w0.w, w1.x, w1.y), v3(w1.z, w1.w, w2.x))) continue;
+                    if (n == kPrimK) { over = true; break; }
+                    const int s = __float_as_int(w2.y);  // scene id: the list is kept in its order
+                    int j = n++;
+                    for (; j > 0 && sid[j - 1] > s; j--) { sid[j] = sid[j - 1]; ids[j] = ids[j - 1]; }
+                    sid[j] = s;
+                    ids[j] = k;
+                }
+                continue;
+            }
+            float mn[3][4], mx[3][4];
+            int rf[4];
+            int nch;
+            if (sc.width == 4) {
+                const float4* nd = sc.nodes + 8 * (size_t)ref;
+                const float4 q[7] = {nd[0], nd[1], nd[2], nd[3], nd[4], nd[5], nd[6]};
+                for (int ax = 0; ax < 3; ax++) {
+                    mn[ax][0] = q[2 * ax].x; mn[ax][1] = q[2 * ax].y; mn[ax][2] = q[2 * ax].z; mn[ax][3] = q[2 * ax].w;
+                    mx[ax][0] = q[2 * ax + 1].x; mx[ax][1] = q[2 * ax + 1].y; mx[ax][2] = q[2 * ax + 1].z; mx[ax][3] = q[2 * ax + 1].w;
+                }
+                rf[0] = __float_as_int(q[6].x); rf[1] = __float_as_int(q[6].y);
+                rf[2] = __float_as_int(q[6].z); rf[3] = __float_as_int(q[6].w);
+                nch = 4;
+            } else {
+                const float4* nd = sc.nodes + 4 * (size_t)ref;
+                const float4 q[4] = {nd[0], nd[1], nd[2], nd[3]};
+                for (int ax = 0; ax < 3; ax++) {
+                    mn[ax][0] = q[ax].x; mn[ax][1] = q[ax].y; mx[ax][0] = q[ax].z; mx[ax][1] = q[ax].w;
+                }
+                rf[0] = __float_as_int(q[3].x); rf[1] = __float_as_int(q[3].y);
+                nch = 2;
+            }
+            for (int k = 0; k < nch; k++) {
+                if (rf[k] == kEnd) continue;
+                if (beam_misses_box(b, iv, mn[0][k], mn[1][k], mn[2][k], mx[0][k], mx[1][k], mx[2][k])) continue;
+                if (sp == kMaxStack) { over = true; break; }
+                stack[sp++] = rf[k];
+            }
+        }
+    }
+    uint32_t* lp = a.list + (size_t)kPrimLine * i;
+    for (int k = 0; k < kPrimK; k++) lp[k] = (!over && k < n) ? ids[k] : 0u;
+    a.cnt[i] = over ? (uint8_t)0 : (uint8_t)(n + 1);
+    const uint64_t mo = __ballot(over), ml = __ballot(!over);
+    if ((threadIdx.x & 63) == 0) {
+        if (ml) atomicAdd(a.stats + 0, (uint32_t)__popcll(ml));
+        if (mo) atomicAdd(a.stats + 1, (uint32_t)__popcll(mo));
+    }
+}
+void launch_primary_build(const PrimaryBuildArgs& a, hipStream_t s) {
+    const uint32_t n = (uint32_t)a.W * (uint32_t)a.H;
+    if (n) hipLaunchKernelGGL(k_primary_build, dim3((n + 63) / 64), dim3(64), 0, s, a);
+}
+void launch_primary(const ShadeArgs& a, const LaunchGeom& g, hipStream_t s) {
+    if (a.prim_cnt) hipLaunchKernelGGL(k_primary, dim3(g.prim_blocks), dim3(kBlock), 0, s, a);
+}
+
 // Camera records of a W x H film: gen_ray_pixel of every pixel (ShadeArgs::cam_px / cam_dir)
 __global__ void k_cam_table(mcpt::CamView cam, int W, int H, float4* px, float4* dir) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1980,7 +2142,9 @@ __global__ void k_accumulate(CounterBlock* c, uint32_t nparts, uint32_t* occ_gat
         for (int off = 32; off > 0; off >>= 1) phw[k] += __shfl_xor(phw[k], off);
     }
     uint32_t er = c->shard[t][C_EXT_RAYS], ar = c->shard[t][C_ANY_RAYS], oc = c->shard[t][C_OCC],
-             ot = c->shard[t][C_OCC_TRY];
+             ot = c->shard[t][C_OCC_TRY], pr = c->shard[t][C_PRIM_RAYS];
+    c->shard[t][C_PRIM] = 0;
+    c->shard[t][C_PRIM_RAYS] = 0;
     c->shard[t][C_EXT_RAYS] = 0;
     c->shard[t][C_ANY_RAYS] = 0;
     c->shard[t][C_MAT] = 0;
@@ -1991,9 +2155,11 @@ __global__ void k_accumulate(CounterBlock* c, uint32_t nparts, uint32_t* occ_gat
         ar += __shfl_xor(ar, off);
         oc += __shfl_xor(oc, off);
         ot += __shfl_xor(ot, off);
+        pr += __shfl_xor(pr, off);
     }
     if (t == 0) {
         c->tot_ext += er;
+        c->tot_prim += pr;
         c->tot_any += ar;
         c->tot_occ += oc;
         // occluder-cache gate for the next iterations' k_material (a speed choice only)
@@ -2104,6 +2270,9 @@ int launch_geometry(int dev, LaunchGeom& g) {
     }
     g.mat_blocks[0] = (uint32_t)std::max(1, cus * std::max(1, mat0) / kShards) * (uint32_t)kShards;
     g.mat_blocks[1] = (uint32_t)std::max(1, cus * std::max(1, mat1) / kShards) * (uint32_t)kShards;
+    int prim = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&prim, k_primary, kBlock, 0) != hipSuccess) return -1;
+    g.prim_blocks = (uint32_t)std::max(1, cus * std::max(1, prim) / kShards) * (uint32_t)kShards;
     // k_shade grid: MCPT_SHADE_GRID times the resident blocks (0: one workgroup per shading block)
     g.shade_grid = (uint32_t)std::max(1, cus * std::max(1, sh0)) * env_u32("MCPT_SHADE_GRID", 16, 0, 1024);
     if (getenv("MCPT_SHADE_WGS")) g.shade_grid = env_u32("MCPT_SHADE_WGS", 0, 1, 1 << 30);  // tests: an absolute cap

@@ -136,9 +136,10 @@ struct DevPaths {
 constexpr int kShards = 64;
 constexpr int kMaxParts = kShards;  // k_trace work partitions (at most one per queue shard)
 enum : int { C_EXT = 0, C_ANY = 1, C_VIS = 2, C_STATS = 3, C_EXT_RAYS = 9, C_ANY_RAYS = 10, C_MAT = 11, C_OCC = 12,
-              C_OCC_TRY = 13, C_PH = 14, C_WORDS = 32 };  // C_STATS..+5; C_OCC / C_OCC_TRY: any-hit rays resolved by /
-                                                          // tested against the occluder cache; C_PH..+kPhaseWords-1:
-                                                          // k_trace's loop-phase counts (counting build, PH_*)
+              C_OCC_TRY = 13, C_PH = 14, C_PRIM = 26, C_PRIM_RAYS = 27, C_WORDS = 32 };
+// C_STATS..+5; C_OCC / C_OCC_TRY: any-hit rays resolved by / tested against the occluder cache;
+// C_PH..+kPhaseWords-1: k_trace's loop-phase counts (counting build, PH_*); C_PRIM: primary-queue
+// pushes (k_shade -> k_primary), C_PRIM_RAYS: primary rays resolved from the candidate table
 // k_trace loop-phase counts of the counting instantiation (mcpt_debug_trace_profile), per wave summed:
 enum : int {
     PH_TRIPS = 0,          // loop trips with a ray in the wave
@@ -167,7 +168,16 @@ struct CounterBlock {
     unsigned long long tot_stats[6];
     unsigned long long tot_ext_q, tot_any_q;  // rays queued to k_trace (the rest were resolved in place)
     unsigned long long tot_phase[kPhaseWords];  // k_trace loop-phase counts (PH_*; counting build only)
+    unsigned long long tot_prim;  // primary rays resolved from the candidate table (part of tot_ext)
 };
+static_assert(C_PH + kPhaseWords <= C_PRIM, "counter words overlap");
+
+// Primary-hit candidate table: per film pixel one 64-B line of up to
+// kPrimK triangle record indices in ascending scene-id order, and a byte prim_cnt[pixel]: 0 = no list
+// (overflow, or no bound: the pixel's rays are traversed), n + 1 = a list of n candidates.
+constexpr char kPrimaryHitsEnv[] = "MCPT_PRIMARY_HITS";  // "0" at context creation: the table is off
+constexpr int kPrimLine = 16;           // u32 per pixel
+constexpr int kPrimK = kPrimLine;       // candidates per pixel
 
 struct ShadeArgs {
     DevScene scene;
@@ -206,6 +216,21 @@ struct ShadeArgs {
     // pixel's focal point (thin lens) or pinhole origin in cam_px, the pinhole direction in cam_dir
     const float4* cam_px;
     const float4* cam_dir;
+    // Primary-hit candidate table (nullptr: off) and the primary queue {path, pixel} of generated
+    // rays that k_primary resolves from it (ext_cap entries per shard, counter C_PRIM)
+    const uint8_t* prim_cnt;
+    const uint32_t* prim_list;
+    uint2* prim_q;
+};
+// k_primary_build: the table of a W x H film.  stats: [0] pixels with a list, [1] overflow pixels.
+struct PrimaryBuildArgs {
+    DevScene scene;
+    mcpt::CamView cam;
+    int W, H;
+    const float4 *cam_px, *cam_dir;
+    uint8_t* cnt;
+    uint32_t* list;
+    uint32_t* stats;
 };
 
 // One ray set of a trace launch: rays ro/rd[rid] for queue entries
@@ -259,6 +284,7 @@ struct LaunchGeom {
     uint32_t trace_parts;    // k_trace work partitions, MCPT_TRACE_PARTS (1..kMaxParts)
     uint32_t ndies;          // XCDs
     uint32_t mat_blocks[2];  // k_material grid [reference mode, fixed mode]
+    uint32_t prim_blocks;    // k_primary grid (resident blocks, a multiple of the shard count)
     uint32_t shade_grid;     // k_shade grid cap (resident blocks x MCPT_SHADE_GRID; 0: one block per shading block)
     uint32_t refill_min, tri_min;  // MCPT_REFILL_MIN, MCPT_TRI_MIN
 };
@@ -267,6 +293,8 @@ void launch_shade(const ShadeArgs& a, int nblocks, const LaunchGeom& g, bool fix
 void launch_shade_stage(bool material_stage, const ShadeArgs& a, int nblocks, const LaunchGeom& g, bool fixed_mode,
                         hipStream_t s);
 void launch_trace(const TraceArgs& a, const LaunchGeom& g, hipStream_t s);
+void launch_primary(const ShadeArgs& a, const LaunchGeom& g, hipStream_t s);  // k_primary: after k_shade, before k_trace
+void launch_primary_build(const PrimaryBuildArgs& a, hipStream_t s);
 void launch_clear(const ClearArgs& a, hipStream_t s);
 // Occluder records (DevScene::occ_rec): for each triangle record t, {leaf mn, margin} {leaf mx,
 // v0.x} {v0.yz, e1.xy} {e1.z, e2} of the leaf that holds it (nodes: nnodes nodes of the given

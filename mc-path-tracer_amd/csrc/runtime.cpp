@@ -58,6 +58,26 @@ struct mcpt_ctx {
     uint32_t cam_tab_W = 0, cam_tab_H = 0;
     mcpt::CamView cam_tab_cam{};
     bool cam_tab_ok = false;
+    // Primary-hit candidate table (prim_table): built for (scene upload, camera, film size); a film
+    // clear keeps it.  Best-effort: any failure leaves it off and the primary rays are traversed.
+    // (MCPT_PRIMARY_HITS=0: off, for A/B runs and tests.  bench.py has no entry for the switch and
+    // stamps a run that sets it as an unknown knob, i.e. not the product.)
+    bool prim_on = [] { const char* e = getenv(kPrimaryHitsEnv); return !(e && e[0] == '0' && e[1] == 0); }();
+    uint8_t* prim_cnt = nullptr;
+    uint32_t* prim_list = nullptr;
+    uint32_t* prim_stats_d = nullptr;  // k_primary_build's two counters
+    size_t prim_cap = 0;               // pixels allocated
+    uint2* prim_q = nullptr;
+    size_t prim_q_cap = 0;             // entries allocated
+    bool prim_ok = false;              // the table is valid for the key below
+    bool prim_failed = false;          // the build for the key below failed: not retried until the key changes
+    uint64_t prim_scene_gen = 0;
+    uint32_t prim_W = 0, prim_H = 0;
+    mcpt::CamView prim_cam{};
+    uint64_t scene_gen = 0;            // scene uploads so far
+    uint64_t prim_builds = 0;          // table builds so far
+    uint32_t prim_lists = 0, prim_over = 0;  // the current table: pixels with a list / overflow pixels
+    float prim_build_ms = 0.f;         // the last build
     // Film observes camera and scene (Film::update -> clear(), Film.cu:278-281; notified by
     // Camera::update, Camera.cu:207, and Scene::notify, Scene.cu:534-545): a change marks the
     // film stale and the next iteration clears it first (unless MCPT_FLAG_NO_AUTO_CLEAR).
@@ -119,6 +139,18 @@ static int set_err(mcpt_ctx* c, int rc, const std::string& msg) {
             return set_err((c), MCPT_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_));  \
     } while (0)
 
+static void prim_free(mcpt_ctx* c) {
+    if (c->prim_cnt) (void)hipFree(c->prim_cnt);
+    if (c->prim_list) (void)hipFree(c->prim_list);
+    if (c->prim_stats_d) (void)hipFree(c->prim_stats_d);
+    if (c->prim_q) (void)hipFree(c->prim_q);
+    c->prim_cnt = nullptr;
+    c->prim_list = nullptr;
+    c->prim_stats_d = nullptr;
+    c->prim_q = nullptr;
+    c->prim_cap = c->prim_q_cap = 0;
+    c->prim_ok = false;
+}
 static void free_list(std::vector<void*>& v) {
     for (void* q : v)
         if (q) (void)hipFree(q);
@@ -204,6 +236,7 @@ void mcpt_destroy(mcpt_ctx* c) {
     if (c->mat_q) (void)hipFree(c->mat_q);
     if (c->any_ray) (void)hipFree(c->any_ray);
     if (c->cam_tab) (void)hipFree(c->cam_tab);
+    prim_free(c);
     for (auto e : c->events) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -783,22 +816,35 @@ static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
         if (const char* e = getenv("MCPT_OCC_B")) B = atoi(e);
         // the index G^3 * 6 * B^2 must fit 32 bits
         // (off unless every box nests in its parent's: occ_test relies on it, see cull_ok above)
-        if (G > 0 && G <= 64 && B > 0 && B <= 64 && (uint64_t)G * G * G * 6 * B * B <= 0xffffffffull && d->ntri > 0 &&
-            c->occ_nest_ok) {
-            float4* lbx;
-            uint32_t* occ;
-            const size_t ne = occ_entries(G, B);
-            if ((rc = dalloc(c, c->scene_bufs, &lbx, kOccRecF4 * (size_t)d->ntri)) ||
-                (rc = dalloc(c, c->scene_bufs, &occ, ne + kOccGateWords)))
-                return rc;
+        const bool occ_want = G > 0 && G <= 64 && B > 0 && B <= 64 && (uint64_t)G * G * G * 6 * B * B <= 0xffffffffull;
+        // The per-triangle leaf-box records serve the occluder cache and the primary-hit table alike
+        // (either switch alone keeps them).  For the table alone they are best-effort.
+        float4* lbx = nullptr;
+        if (d->ntri > 0 && c->occ_nest_ok && (occ_want || c->prim_on)) {
+            void* q = nullptr;
+            if (hipMalloc(&q, kOccRecF4 * (size_t)d->ntri * sizeof(float4)) == hipSuccess) {
+                c->scene_bufs.push_back(q);
+                lbx = (float4*)q;
+            } else {
+                (void)hipGetLastError();
+                if (occ_want) return set_err(c, MCPT_E_NOMEM, "hipMalloc: occluder records");
+            }
+        }
+        if (lbx) {
             // NaN boxes (all-ones bytes) for a record no leaf holds: occ_test's slab then fails
             HIPCHK(c, hipMemsetAsync(lbx, 0xff, kOccRecF4 * (size_t)d->ntri * sizeof(float4), c->stream));
-            HIPCHK(c, hipMemsetAsync(occ, 0xff, ne * sizeof(uint32_t), c->stream));
-            HIPCHK(c, hipMemsetAsync(occ + ne, 0, kOccGateWords * sizeof(uint32_t), c->stream));  // the lookup gate: on
             launch_occ_records(s, nnodes, lbx, c->stream);
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipStreamSynchronize(c->stream));
             s.occ_rec = lbx;
+        }
+        if (occ_want && lbx) {
+            uint32_t* occ;
+            const size_t ne = occ_entries(G, B);
+            if ((rc = dalloc(c, c->scene_bufs, &occ, ne + kOccGateWords))) return rc;
+            HIPCHK(c, hipMemsetAsync(occ, 0xff, ne * sizeof(uint32_t), c->stream));
+            HIPCHK(c, hipMemsetAsync(occ + ne, 0, kOccGateWords * sizeof(uint32_t), c->stream));  // the lookup gate: on
+            HIPCHK(c, hipStreamSynchronize(c->stream));
             s.occ = occ;
             s.occ_gate = occ + ne;
             c->occ_entries_n = ne;
@@ -811,6 +857,7 @@ static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
         }
     }
     c->scene = s;
+    c->scene_gen++;  // with the scene itself: the previous scene's primary-hit table is stale (prim_table)
     c->ntri = d->ntri;
     c->occ_init = nullptr;  // (the previous scene's copy went with scene_bufs)
     if (s.occ) {
@@ -890,6 +937,14 @@ int mcpt_debug_ray_counts(const mcpt_ctx* c, uint64_t* out) {
     out[3] = ok ? t.tot_any_q : 0;  // any-hit rays k_trace traversed
     out[4] = ok ? t.tot_occ : 0;    // any-hit rays the occluder cache resolved in k_material
     return MCPT_OK;
+}
+int mcpt_debug_primary_stats(const mcpt_ctx* c, double* out4) {
+    if (!c || !out4) return MCPT_E_INVALID;
+    out4[0] = c->prim_ok ? (double)c->prim_lists : 0.0;
+    out4[1] = c->prim_ok ? (double)c->prim_over : 0.0;
+    out4[2] = c->totals_ok ? (double)c->totals.tot_prim : 0.0;
+    out4[3] = (double)c->prim_build_ms;
+    return (int)std::min<uint64_t>(c->prim_builds, 0x7fffffffull);
 }
 int mcpt_debug_occ_stats(const mcpt_ctx* c, uint64_t* resolved, int32_t* enabled) {
     if (!c) return MCPT_E_INVALID;
@@ -1171,6 +1226,89 @@ static int cam_table(mcpt_ctx* c, uint32_t W, uint32_t H, const float4** px, con
     return MCPT_OK;
 }
 
+// The primary-hit candidate table of the W x H film under the current scene and camera
+// (k_primary_build over the camera records), built on the context's stream when one of the three
+// changed; a film clear leaves it alone.  Best-effort: when a precondition is missing (no leaf-box
+// records: MCPT_PRIMARY_HITS=0, or boxes that do not nest), or an allocation or the launch fails, sa's
+// table pointers stay null and the primary rays are traversed as before.  Never an error.
+static void prim_table(mcpt_ctx* c, ShadeArgs& sa) {
+    sa.prim_cnt = nullptr;
+    sa.prim_list = nullptr;
+    sa.prim_q = nullptr;
+    if (!c->prim_on || !c->scene.occ_rec || !c->occ_nest_ok || c->scene.ntri == 0) return;
+    const uint32_t W = c->W, H = c->H;
+    const size_t n = (size_t)W * H;
+    const bool same = c->prim_scene_gen == c->scene_gen && c->prim_W == W && c->prim_H == H &&
+                      memcmp(&c->prim_cam, &c->cam, sizeof(c->cam)) == 0;
+    if (same && c->prim_failed) return;
+    const size_t qn = (size_t)kShards * c->ext_cap;
+    auto fail = [&]() {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(c->stream);
+        prim_free(c);
+        c->prim_failed = true;
+        c->prim_lists = c->prim_over = 0;
+    };
+    if (!same) {
+        c->prim_scene_gen = c->scene_gen;
+        c->prim_W = W;
+        c->prim_H = H;
+        c->prim_cam = c->cam;
+        c->prim_failed = false;
+        c->prim_ok = false;
+    }
+    if (!c->prim_ok) {
+        if (n > c->prim_cap || !c->prim_stats_d) {
+            (void)hipStreamSynchronize(c->stream);
+            prim_free(c);
+            if (hipMalloc(&c->prim_cnt, std::max<size_t>(n, 16)) != hipSuccess ||
+                hipMalloc(&c->prim_list, n * kPrimLine * sizeof(uint32_t)) != hipSuccess ||
+                hipMalloc(&c->prim_stats_d, 16) != hipSuccess)
+                return fail();
+            c->prim_cap = n;
+        }
+        PrimaryBuildArgs ba{};
+        ba.scene = c->scene;
+        ba.cam = c->cam;
+        ba.W = (int)W;
+        ba.H = (int)H;
+        ba.cam_px = sa.cam_px;
+        ba.cam_dir = sa.cam_dir;
+        ba.cnt = c->prim_cnt;
+        ba.list = c->prim_list;
+        ba.stats = c->prim_stats_d;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        uint32_t st[2] = {0, 0};
+        float ms = 0.f;
+        const bool ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess &&
+                        hipMemsetAsync(c->prim_stats_d, 0, 16, c->stream) == hipSuccess &&
+                        hipEventRecord(e0, c->stream) == hipSuccess &&
+                        (launch_primary_build(ba, c->stream), hipGetLastError() == hipSuccess) &&
+                        hipEventRecord(e1, c->stream) == hipSuccess &&
+                        hipMemcpyAsync(st, c->prim_stats_d, sizeof(st), hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
+                        hipStreamSynchronize(c->stream) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        if (!ok) return fail();
+        c->prim_ok = true;
+        c->prim_builds++;
+        c->prim_lists = st[0];
+        c->prim_over = st[1];
+        c->prim_build_ms = ms;
+    }
+    if (qn > c->prim_q_cap) {  // the primary queue follows the ray queues' capacity (set_tiles_internal)
+        (void)hipStreamSynchronize(c->stream);
+        if (c->prim_q) (void)hipFree(c->prim_q);
+        c->prim_q = nullptr;
+        c->prim_q_cap = 0;
+        if (hipMalloc(&c->prim_q, qn * sizeof(uint2)) != hipSuccess) return fail();
+        c->prim_q_cap = qn;
+    }
+    sa.prim_cnt = c->prim_cnt;
+    sa.prim_list = c->prim_list;
+    sa.prim_q = c->prim_q;
+}
+
 static int check_ready(mcpt_ctx* c) {
     if (!c) return MCPT_E_INVALID;
     if (!c->has_scene) return set_err(c, MCPT_E_INVALID, "no scene uploaded");
@@ -1211,11 +1349,14 @@ static int enqueue_iteration(mcpt_ctx* c, size_t evbase, bool timing, const int2
     sa.cnt = c->cnt;
     sa.blk_done = c->blk_done_off ? nullptr : c->blk_done;
     if (int rc = cam_table(c, c->W, c->H, &sa.cam_px, &sa.cam_dir)) return rc;
+    prim_table(c, sa);
     const int bpt = shade_blocks_per_tile((int)(c->tile_w * c->tile_h), (int)c->slots);
     if (timing) HIPCHK(c, hipEventRecord(ev(c, evbase + 0), c->stream));
     if (sa.ntiles > 0)
         launch_shade(sa, sa.ntiles * bpt, c->geom, (c->cfg.flags & MCPT_FLAG_FIXED) != 0, c->stream);
     if (timing) HIPCHK(c, hipEventRecord(ev(c, evbase + 1), c->stream));
+    // primary rays with a candidate list (part of the extend stage's time)
+    if (sa.ntiles > 0) launch_primary(sa, c->geom, c->stream);
     // extension (closest hit) and any-hit rays in one persistent launch
     TraceArgs ta{};
     ta.scene = c->scene;

@@ -142,6 +142,7 @@ ABI = {
     "mcpt_debug_node_layout": (C.c_int, [C.c_void_p]),
     "mcpt_debug_occ_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
     "mcpt_debug_ray_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mcpt_debug_primary_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "mcpt_set_work_counters": (C.c_int, [C.c_void_p, C.c_int32]),
     "mcpt_scene_upload_gpu_bvh": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mcpt_set_gpu_bvh_builder": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -422,6 +423,15 @@ class PathTracer:
             self._ck(lib().mcpt_debug_ray_counts(self.h, v))  # (an older variant library: zeros)
         return dict(zip(("extension", "extension_traversed", "any_hit", "any_hit_traversed", "any_hit_occluder_cache"),
                         [int(x) for x in v]))
+
+    def primary_stats(self) -> dict:
+        """Primary-hit candidate table (mcpt_debug_primary_stats): pixels with a list, overflow pixels,
+        rays resolved since the last film clear, the last build's ms, and the builds so far."""
+        v = (C.c_double * 4)()
+        n = lib().mcpt_debug_primary_stats(self.h, v)
+        if n < 0:
+            raise McptError(f"mcpt_debug_primary_stats failed ({n})")
+        return dict(lists=int(v[0]), overflow=int(v[1]), resolved=int(v[2]), build_ms=float(v[3]), builds=int(n))
 
     def occ_stats(self):
         """(any-hit rays the occluder cache resolved since the last film clear, cache enabled)."""
