@@ -3,8 +3,10 @@
 // INTEGRATION.md): build a BASELINE config scene with the host builder, upload it,
 // run the wavefront iterations until every pixel has its samples, write PNG + PFM.
 //
-//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S]
+//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]]
 //
+// --denoise renders the first-hit guide buffers (default 4 guide samples per pixel), filters the film
+// with the default parameters and writes <out_prefix>_denoised.png beside the raw image.
 // --tiles-per-call uses the reference orchestration (one 256x256 tile per call,
 // wavefront_kernels.cu:377-442 + Film::update_tile_position) instead of batch mode.
 #include <stdio.h>
@@ -20,7 +22,7 @@ struct Cfg { int w, h, spp, depth; float pos[3], pitch; const char* env; };
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S]\n", argv[0]);
+        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]]\n", argv[0]);
         return 2;
     }
     const Cfg cfgs[6] = {{0, 0, 0, 0, {0, 0, 0}, 0, ""},
@@ -35,13 +37,17 @@ int main(int argc, char** argv) {
     if (argc > 2 && argv[2][0] != '-') c.spp = atoi(argv[2]);
     std::string out = (argc > 3 && argv[3][0] != '-') ? argv[3] : "mcpt_render";
     bool gpu_bvh = false, ref_bvh = false, fixed = false, per_tile = false;
-    uint32_t slots = 1;
+    uint32_t slots = 1, guide_samples = 0;  // guide_samples > 0: denoise
     for (int i = 2; i < argc; i++) {
         if (!strcmp(argv[i], "--gpu-bvh")) gpu_bvh = true;
         if (!strcmp(argv[i], "--reference-bvh")) ref_bvh = true;
         if (!strcmp(argv[i], "--fixed")) fixed = true;
         if (!strcmp(argv[i], "--tiles-per-call")) per_tile = true;
         if (!strcmp(argv[i], "--slots") && i + 1 < argc) slots = (uint32_t)atoi(argv[++i]);
+        if (!strcmp(argv[i], "--denoise")) {
+            guide_samples = 4;
+            if (i + 1 < argc && argv[i + 1][0] >= '1' && argv[i + 1][0] <= '9') guide_samples = (uint32_t)atoi(argv[++i]);
+        }
     }
     const char* assets = getenv("MCPT_ASSETS") ? getenv("MCPT_ASSETS") : "assets";
 
@@ -104,6 +110,13 @@ int main(int argc, char** argv) {
         (rc = mcpt_film_write_pfm(ctx, (out + ".pfm").c_str()))) {
         fprintf(stderr, "write: %s\n", mcpt_last_error(ctx));
         return 1;
+    }
+    if (guide_samples) {  // film -> guides -> filter -> display
+        if ((rc = mcpt_guides_render(ctx, guide_samples)) || (rc = mcpt_film_denoise(ctx, nullptr)) ||
+            (rc = mcpt_denoised_write_png(ctx, 1.f, (out + "_denoised.png").c_str()))) {
+            fprintf(stderr, "denoise: %s\n", mcpt_last_error(ctx));
+            return 1;
+        }
     }
     mcpt_destroy(ctx);
     mcpt_scene_free(s);

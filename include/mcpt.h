@@ -257,6 +257,57 @@ int mcpt_film_write_png(mcpt_ctx *ctx, float exposure, const char *path);
 int mcpt_film_write_pfm(mcpt_ctx *ctx, const char *path);
 int mcpt_image_write_png(const char *path, uint32_t w, uint32_t h, const uint8_t *rgba8);
 int mcpt_image_write_pfm(const char *path, uint32_t w, uint32_t h, const float *rgb);
+/* ---- preview denoiser: first-hit guide buffers + an edge-avoiding a-trous
+ * wavelet filter (Dammertz et al. 2010) between the film and the display.  A context that never
+ * calls these allocates and launches nothing for them.
+ *
+ * Guides: per pixel the sums over guide samples of the first hit's albedo (the material's base
+ * rgb), normal and distance t; a miss adds albedo (1,1,1), normal 0 and depth 0.  Guide sample s of
+ * a pixel is traced along the camera ray of film sample s (same seed, pixel and sample key), over
+ * exactly the pixels the renderer renders (x < W-1 && y < H-1) of the whole film, whatever the tile
+ * set or path layout; other pixels keep count 0 and zeros.  With lens_radius == 0 every sample's ray
+ * is the same, so one is traced and the count is 1.  1 <= nsamples < 2^19 - 256; needs a scene, a
+ * camera and a film.  The path state, the queues, the ray counters and the occluder cache are not
+ * touched.  The rays are traced in chunks whose temporary buffers stay under 64 MiB
+ * (MCPT_GUIDE_CHUNK_BYTES overrides the budget; the result does not depend on it).  The guides are
+ * stale after mcpt_camera_set with a different camera, a scene upload or mcpt_film_resize; a film
+ * clear leaves them valid. */
+int mcpt_guides_render(mcpt_ctx *ctx, uint32_t nsamples);
+/* Guide sums (3*W*H, 3*W*H, W*H floats) and sample counts (W*H); any pointer may be NULL.
+ * MCPT_E_INVALID without valid guides. */
+int mcpt_guides_read(mcpt_ctx *ctx, float *albedo_rgb, float *normal_xyz, float *depth, uint32_t *count);
+/* Filter parameters.  Pass i (0 <= i < passes) visits the 25 taps q = p + 2^i (dx, dy), dx, dy in
+ * -2..2, row by row, skips taps outside the film or invalid (no samples, or a colour that is not
+ * finite) and weights the rest by h[dy] h[dx] exp(-x), h = {1/16, 1/4, 3/8, 1/4, 1/16},
+ *   x = |C(p)-C(q)|^2 / sc_i^2 + |N(p)-N(q)|^2 / sn^2 + |A(p)-A(q)|^2 / sa^2 + (Z(p)-Z(q))^2 / (sz^2 max(Z(p)^2, 1e-12))
+ * with sc_i = sigma_color 2^-i; the centre tap has x = 0, and a tap whose x is not a finite number
+ * >= 0 has weight 0.  C is the mean radiance, N / A / Z the mean guides.  An invalid pixel outputs 0. */
+typedef struct mcpt_denoise_params {
+    int32_t passes;        /* 1..8; pass i taps at stride 2^i */
+    float sigma_color;     /* pass 0; halves every pass.  A sigma <= 0 disables its term */
+    float sigma_normal, sigma_albedo, sigma_depth;
+} mcpt_denoise_params;
+int mcpt_denoise_default_params(mcpt_denoise_params *p);
+/* The filter over host images of means (w*h pixels: rgb / albedo / normal 3 floats each, depth 1,
+ * samples 1 or NULL = every pixel has samples) into out_rgb (3*w*h): the kernels mcpt_film_denoise
+ * runs, for parity tests and for frames gathered elsewhere.  Needs neither a scene nor a film. */
+int mcpt_denoise_run(mcpt_ctx *ctx, uint32_t w, uint32_t h, const float *rgb, const uint32_t *samples,
+                     const float *albedo, const float *normal, const float *depth, const mcpt_denoise_params *p,
+                     float *out_rgb);
+/* Filter the film as its readers see it (every path slot summed, the compact layout scattered, a
+ * root's gathered frame) with the context's guides; p == NULL: the defaults.  MCPT_E_INVALID when the
+ * guides are missing or stale (call mcpt_guides_render first).  The film itself is not changed. */
+int mcpt_film_denoise(mcpt_ctx *ctx, const mcpt_denoise_params *p);
+/* The last mcpt_film_denoise result: rgb (3*W*H floats); device-to-device as W*H float4 (rgb, 1 for a
+ * valid pixel / 0); Reinhard-tonemapped like mcpt_film_tonemap_rgba8 (with samples = 1); as PNG.
+ * MCPT_E_INVALID until a denoise has run since the last mcpt_film_resize. */
+int mcpt_denoised_read(mcpt_ctx *ctx, float *rgb);
+int mcpt_denoised_read_device(mcpt_ctx *ctx, void *d_rgb);
+int mcpt_denoised_tonemap_rgba8(mcpt_ctx *ctx, float exposure, uint8_t *out);
+int mcpt_denoised_write_png(mcpt_ctx *ctx, float exposure, const char *path);
+/* Device times (ms) of the last mcpt_guides_render (out10[0]) and of the last mcpt_film_denoise /
+ * mcpt_denoise_run: the plane set-up (out10[1]) and each pass (out10[2 + i]; 0 beyond the passes run). */
+int mcpt_debug_denoise_ms(const mcpt_ctx *ctx, float *out10);
 int mcpt_sync(mcpt_ctx *ctx);
 int mcpt_device_name(mcpt_ctx *ctx, char *buf, int32_t len);
 /* diagnostics: rays of the current extension (which=0) or any-hit (which=1) queue, and the

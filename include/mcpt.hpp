@@ -567,6 +567,23 @@ public:
     void write_pfm(const std::string& path) {
         detail::check(mcpt_film_write_pfm(ctx_, path.c_str()), ctx_, "write_pfm");
     }
+    // Preview denoiser: first-hit guide buffers of the current camera (guide_samples per pixel; they
+    // stay valid until the camera, the scene or the film size changes, so an unchanged view passes
+    // 0 to reuse them) and the a-trous filter over the film; params == nullptr: the defaults.  The
+    // film is not changed: the result is read with denoised() or written with write_denoised_png.
+    void denoise(uint32_t guide_samples = 4, const mcpt_denoise_params* params = nullptr) {
+        if (guide_samples) detail::check(mcpt_guides_render(ctx_, guide_samples), ctx_, "guides");
+        detail::check(mcpt_film_denoise(ctx_, params), ctx_, "denoise");
+    }
+    void denoised(std::vector<float>& rgb) {
+        uint32_t w = 0, h = 0;
+        detail::check(mcpt_film_size(ctx_, &w, &h), ctx_, "denoised");
+        rgb.resize((size_t)w * h * 3);
+        detail::check(mcpt_denoised_read(ctx_, rgb.data()), ctx_, "denoised");
+    }
+    void write_denoised_png(const std::shared_ptr<Film>& film, const std::string& path) {
+        detail::check(mcpt_denoised_write_png(ctx_, film->get_exposure(), path.c_str()), ctx_, "write_denoised_png");
+    }
 
 private:
     // Bring the context up to date with the host objects.  Order as the reference's observer

@@ -1,0 +1,133 @@
+// denoise.hpp -- arithmetic of the edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika,
+// Lensch: "Edge-Avoiding A-Trous Wavelet Transform for fast Global Illumination Filtering", HPG 2010)
+// over the film and its first-hit guide buffers (albedo, normal, depth).
+//
+// __host__ __device__, add / mul / IEEE div only, one rounding per operation under the project's
+// flags (-ffp-contract=off, correctly rounded division): the host build and the gfx950 kernels
+// (denoise.hip) agree bit for bit, as with mcpt_core.hpp.  tests/denoise_ref.py restates every
+// expression below in numpy float32, in the same order.
+//
+// Planes (float4 per pixel):
+//   colour  (r, g, b, valid)   valid = 1: the pixel has samples and a finite colour; 0: skipped as a
+//                              tap and written as (0, 0, 0, 0)
+//   guide   (nx, ny, nz, z)    mean first-hit normal and depth
+//   albedo  (r, g, b, rz)      mean first-hit albedo; rz = 1 / max(z * z, 1e-12)
+#pragma once
+#include "mcpt_core.hpp"
+
+namespace mcpt {
+
+// exp(-x) for x >= 0 without libm: k = nearest integer to x log2(e), r = x - k ln 2 in two exact
+// steps (Cody-Waite: k <= 126 has 7 bits, LN2_HI 10, and x - k LN2_HI cancels exactly), f = r log2(e)
+// in [-1/2, 1/2], 2^-f by the degree-7 Taylor polynomial of exp(-f ln 2) (remainder < 2^-27), and
+// 2^-k built as an exponent field.  Exactly 1 at 0; 0 where the result would be subnormal (and for
+// x > 87.5, a NaN included), so no subnormal is ever produced; a negative x saturates at 1.
+constexpr float DN_LOG2E = 1.44269504088896341f;
+constexpr float DN_LN2_HI = 0.693359375f;         // 355 / 512
+constexpr float DN_LN2_LO = -2.12194440e-4f;      // ln 2 - LN2_HI
+constexpr float DN_EXP_MAX = 87.5f;               // exp(-87.5) < 2^-126
+constexpr float DN_FLT_MIN = 1.17549435e-38f;     // 2^-126
+MCPT_HD float dexp_neg(float x) {
+    if (!(x <= DN_EXP_MAX)) return 0.f;
+    if (!(x > 0.f)) return 1.f;
+    const int k = (int)(x * DN_LOG2E + 0.5f);     // truncation: the operand is positive
+    const float kf = (float)k;
+    float r = x - kf * DN_LN2_HI;
+    r = r - kf * DN_LN2_LO;
+    const float f = r * DN_LOG2E;
+    float p = -1.52527338e-5f * f;                // (-ln 2)^n / n!, n = 7 .. 1
+    p = p + 1.54035304e-4f;
+    p = p * f;
+    p = p + -1.33335581e-3f;
+    p = p * f;
+    p = p + 9.61812911e-3f;
+    p = p * f;
+    p = p + -5.55041087e-2f;
+    p = p * f;
+    p = p + 2.40226507e-1f;
+    p = p * f;
+    p = p + -6.93147181e-1f;
+    p = p * f;
+    p = p + 1.f;
+    const float scale = __builtin_bit_cast(float, (uint32_t)(127 - k) << 23);  // 2^-k, k in 0..126
+    const float e = p * scale;
+    return e < DN_FLT_MIN ? 0.f : e;
+}
+
+// One pass: taps at stride 2^i, k = 1 / (sigma * sigma) per term (0: the term is off)
+struct DenoisePass {
+    float kc, kn, ka, kz;
+    int stride;
+};
+MCPT_HD float dn_k(float sigma) { return sigma > 0.f ? 1.f / (sigma * sigma) : 0.f; }
+// the B3 spline taps h = {1/16, 1/4, 3/8, 1/4, 1/16} (exact, and so are their products)
+MCPT_HD float dn_h(int d) { return d == 0 ? 0.375f : (d == 1 || d == -1) ? 0.25f : 0.0625f; }
+
+MCPT_HD bool dn_finite(float v) { return v - v == 0.f; }
+MCPT_HD float dn_rz(float z) {
+    const float z2 = z * z;
+    return 1.f / (z2 > 1e-12f ? z2 : 1e-12f);
+}
+// The three planes of a pixel from its mean colour, whether it has samples, and its mean guides
+MCPT_HD void dn_planes(float r, float g, float b, bool has_samples, float nx, float ny, float nz, float z, float ar,
+                       float ag, float ab, float4& col, float4& gd, float4& al) {
+    const bool valid = has_samples && dn_finite(r) && dn_finite(g) && dn_finite(b);
+    col = valid ? make_float4(r, g, b, 1.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+    gd = make_float4(nx, ny, nz, z);
+    al = make_float4(ar, ag, ab, dn_rz(z));
+}
+
+struct DnAcc {
+    float w, r, g, b;
+};
+MCPT_HD float dn_sq3(float ax, float ay, float az, float bx, float by, float bz) {
+    const float dx = ax - bx, dy = ay - by, dz = az - bz;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+// Tap q = p + stride (dx, dy) of a valid pixel p; cq.w != 0 (the caller skips invalid taps and taps
+// outside the film).  The centre's exponent is 0 by definition; elsewhere an exponent that is not
+// a finite number >= 0 gives weight 0.
+MCPT_HD void dn_tap(const DenoisePass& k, int dx, int dy, const float4& cp, const float4& gp, const float4& ap,
+                    const float4& cq, const float4& gq, const float4& aq, DnAcc& acc) {
+    float e = 1.f;
+    if (dx != 0 || dy != 0) {
+        const float dc = dn_sq3(cp.x, cp.y, cp.z, cq.x, cq.y, cq.z);
+        const float dn = dn_sq3(gp.x, gp.y, gp.z, gq.x, gq.y, gq.z);
+        const float da = dn_sq3(ap.x, ap.y, ap.z, aq.x, aq.y, aq.z);
+        const float dz = gp.w - gq.w;
+        const float x = ((k.kc * dc + k.kn * dn) + k.ka * da) + (k.kz * (dz * dz)) * ap.w;
+        e = (x >= 0.f && x <= 3.402823466e+38f) ? dexp_neg(x) : 0.f;
+    }
+    const float w = (dn_h(dy) * dn_h(dx)) * e;
+    acc.w = acc.w + w;
+    acc.r = acc.r + w * cq.x;
+    acc.g = acc.g + w * cq.y;
+    acc.b = acc.b + w * cq.z;
+}
+MCPT_HD float4 dn_finish(const DnAcc& acc) { return make_float4(acc.r / acc.w, acc.g / acc.w, acc.b / acc.w, 1.f); }
+
+// Host form of one pass over W x H planes (the kernels' parity reference; tests/native/denoise_host.cpp)
+inline void denoise_pass_host(const DenoisePass& k, int W, int H, const float4* col, const float4* gd, const float4* al,
+                              float4* out) {
+    for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++) {
+            const size_t p = (size_t)y * W + x;
+            const float4 cp = col[p];
+            if (cp.w == 0.f) {
+                out[p] = make_float4(0.f, 0.f, 0.f, 0.f);
+                continue;
+            }
+            DnAcc acc{0.f, 0.f, 0.f, 0.f};
+            for (int dy = -2; dy <= 2; dy++)
+                for (int dx = -2; dx <= 2; dx++) {
+                    const long qx = (long)x + (long)dx * k.stride, qy = (long)y + (long)dy * k.stride;
+                    if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+                    const size_t q = (size_t)qy * W + (size_t)qx;
+                    if (col[q].w == 0.f) continue;
+                    dn_tap(k, dx, dy, cp, gd[p], al[p], col[q], gd[q], al[q], acc);
+                }
+            out[p] = dn_finish(acc);
+        }
+}
+
+}  // namespace mcpt

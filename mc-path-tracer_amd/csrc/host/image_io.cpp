@@ -114,6 +114,15 @@ int mcpt_film_write_png(mcpt_ctx* ctx, float exposure, const char* path) {
     return mcpt_image_write_png(path, w, h, px.data());
 }
 
+int mcpt_denoised_write_png(mcpt_ctx* ctx, float exposure, const char* path) {
+    uint32_t w = 0, h = 0;
+    int rc = mcpt_film_size(ctx, &w, &h);
+    if (rc) return rc;
+    std::vector<uint8_t> px((size_t)w * h * 4);
+    if ((rc = mcpt_denoised_tonemap_rgba8(ctx, exposure, px.data()))) return rc;
+    return mcpt_image_write_png(path, w, h, px.data());
+}
+
 int mcpt_film_write_pfm(mcpt_ctx* ctx, const char* path) {
     uint32_t w = 0, h = 0;
     int rc = mcpt_film_size(ctx, &w, &h);

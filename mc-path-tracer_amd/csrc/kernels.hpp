@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "device/denoise.hpp"
 #include "device/mcpt_core.hpp"
 
 namespace mcpt_dev {
@@ -355,5 +356,44 @@ void launch_resolve(const ResolveArgs& a, hipStream_t s);
 void launch_accumulate(CounterBlock* c, uint32_t nparts, uint32_t* occ_gate, hipStream_t s);
 void launch_pack(const PackArgs& a, hipStream_t s);
 void launch_unpack(const UnpackArgs& a, hipStream_t s);
+
+// ---- preview denoiser (denoise.hip) ----
+// Its two switches, for A/B runs and tests; neither changes a result.  (As with kPrimaryHitsEnv, bench.py
+// has no entry for them and stamps a run that sets one as an unknown knob, i.e. not the product.)
+constexpr char kDenoiseLdsEnv[] = "MCPT_DENOISE_LDS_MAX";     // 0 / 1 / 2: the widest stride that takes the LDS kernel
+constexpr char kGuideChunkEnv[] = "MCPT_GUIDE_CHUNK_BYTES";   // the guide pass's temporary-buffer budget
+// One a-trous pass over W x H planes: col -> out (the two colour planes ping-pong), gd / al read only
+struct DenoiseArgs {
+    mcpt::DenoisePass k;
+    int W, H;
+    const float4 *col, *gd, *al;
+    float4* out;
+};
+// The filter's planes of n pixels.  Ld != nullptr: from the film (Ld, samples) and the guide sums
+// g_alb (albedo rgb, sample count) / g_nz (normal xyz, depth); else from caller images of means (rgb,
+// normal, albedo: 3 floats per pixel; depth 1; samples may be nullptr: every pixel has samples)
+struct DenoisePrepArgs {
+    const float4* Ld; const uint32_t* samples; const float4 *g_alb, *g_nz;
+    const float *rgb, *normal, *albedo, *depth;
+    float4 *col, *gd, *al; uint32_t n;
+};
+// One chunk of the guide pass: pixels p0 .. p0 + np of the W x H film, film samples s0 .. s0 + ns;
+// ray (s - s0) * np + (p - p0).  k_guide_rays writes ro / rd, k_guide_accum adds the chunk's hit
+// records (hit_p.w = t, hit_n = normal and material bits, as k_hit_record writes them) to the sums.
+struct GuideArgs {
+    mcpt::CamView cam;
+    const float4 *cam_px, *cam_dir;
+    int W, H;
+    uint64_t seed;
+    uint32_t p0, np, s0, ns;
+    float4 *ro, *rd;
+    const float4 *hit_p, *hit_n;
+    const float* mats;
+    float4 *g_alb, *g_nz;
+};
+void launch_denoise_pass(const DenoiseArgs& a, int lds_max_stride, hipStream_t s);
+void launch_denoise_prep(const DenoisePrepArgs& a, hipStream_t s);
+void launch_guide_rays(const GuideArgs& a, hipStream_t s);
+void launch_guide_accum(const GuideArgs& a, hipStream_t s);
 
 }  // namespace mcpt_dev

@@ -125,6 +125,18 @@ struct mcpt_ctx {
     int gpu_bvh_builder = MCPT_GPU_BVH_PLOC;  // mcpt_set_gpu_bvh_builder
     bool tiny_stack = false;  // mcpt_debug_tiny_lds_stack: k_trace with a 2-entry LDS stack (tests)
     unsigned long long phase_base[kPhaseWords] = {};  // mcpt_debug_trace_profile's reset point
+    // Preview denoiser.  Guide sums of the W x H film: g_alb (albedo rgb, sample
+    // count), g_nz (normal xyz, depth), allocated by the first mcpt_guides_render, valid for the
+    // (scene upload, camera, film size) they were rendered for.  dn_*: the filter's planes of the film
+    // (two colour planes in ping-pong, guides, albedo), allocated by the first mcpt_film_denoise;
+    // dn_result: the colour plane that holds the last result (-1: none).  All freed with the film.
+    float4 *g_alb = nullptr, *g_nz = nullptr;
+    bool guides_ok = false;
+    uint64_t guides_scene_gen = 0;
+    mcpt::CamView guides_cam{};
+    float4 *dn_col[2] = {nullptr, nullptr}, *dn_gd = nullptr, *dn_al = nullptr;
+    int dn_result = -1;
+    float guides_ms = 0.f, dn_ms[9] = {};  // device times of the last guide pass / filter set-up and passes
 };
 
 static int set_err(mcpt_ctx* c, int rc, const std::string& msg) {
@@ -150,6 +162,15 @@ static void prim_free(mcpt_ctx* c) {
     c->prim_q = nullptr;
     c->prim_cap = c->prim_q_cap = 0;
     c->prim_ok = false;
+}
+// guide sums and filter planes: they belong to the film size
+static void denoise_free(mcpt_ctx* c) {
+    for (float4** q : {&c->g_alb, &c->g_nz, &c->dn_col[0], &c->dn_col[1], &c->dn_gd, &c->dn_al}) {
+        if (*q) (void)hipFree(*q);
+        *q = nullptr;
+    }
+    c->guides_ok = false;
+    c->dn_result = -1;
 }
 static void free_list(std::vector<void*>& v) {
     for (void* q : v)
@@ -237,6 +258,7 @@ void mcpt_destroy(mcpt_ctx* c) {
     if (c->any_ray) (void)hipFree(c->any_ray);
     if (c->cam_tab) (void)hipFree(c->cam_tab);
     prim_free(c);
+    denoise_free(c);
     for (auto e : c->events) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1099,6 +1121,7 @@ int mcpt_film_resize(mcpt_ctx* c, uint32_t w, uint32_t h, uint32_t tw, uint32_t 
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     free_list(c->film_bufs);
+    denoise_free(c);
     c->P = 0;
     c->npx = 0;
     c->p = DevPaths{};  // (set_tiles_internal below re-points the any-hit ray buffers)
@@ -2219,3 +2242,324 @@ int mcpt_debug_shade_sections(mcpt_ctx* c, uint64_t* out, int n, int reset) {
     return shade_sections(reinterpret_cast<unsigned long long*>(out), n, reset);
 }
 }
+
+// ---------------------------------------------------------------------------
+// Preview denoiser: first-hit guide buffers and the a-trous filter
+// (device/denoise.hpp, denoise.hip) between the film and the display.
+// ---------------------------------------------------------------------------
+static bool guides_valid(const mcpt_ctx* c) {
+    return c->guides_ok && c->g_alb && c->g_nz && c->guides_scene_gen == c->scene_gen &&
+           memcmp(&c->guides_cam, &c->cam, sizeof(c->cam)) == 0;
+}
+static int denoise_check_params(mcpt_ctx* c, const mcpt_denoise_params* p) {
+    if (p->passes < 1 || p->passes > 8) return set_err(c, MCPT_E_INVALID, "denoise: passes must be 1..8");
+    return MCPT_OK;
+}
+// The passes over planes of a W x H image; *result = the colour plane that holds the last pass
+static int denoise_passes(mcpt_ctx* c, const mcpt_denoise_params& p, uint32_t W, uint32_t H, float4* const col[2],
+                          const float4* gd, const float4* al, int* result) {
+    int lds_max = 2;  // MCPT_DENOISE_LDS_MAX: the widest stride that takes the LDS kernel (A/B; same bits)
+    if (const char* e = getenv(kDenoiseLdsEnv))
+        if (e[0] >= '0' && e[0] <= '2' && e[1] == 0) lds_max = e[0] - '0';
+    for (int i = 0; i < 8; i++) c->dn_ms[1 + i] = 0.f;
+    int src = 0;
+    for (int i = 0; i < p.passes; i++) {
+        DenoiseArgs a{};
+        float sc = p.sigma_color;
+        for (int k = 0; k < i; k++) sc = sc * 0.5f;  // sigma_color 2^-i
+        a.k.kc = mcpt::dn_k(sc);
+        a.k.kn = mcpt::dn_k(p.sigma_normal);
+        a.k.ka = mcpt::dn_k(p.sigma_albedo);
+        a.k.kz = mcpt::dn_k(p.sigma_depth);
+        a.k.stride = 1 << i;
+        a.W = (int)W;
+        a.H = (int)H;
+        a.col = col[src];
+        a.gd = gd;
+        a.al = al;
+        a.out = col[src ^ 1];
+        HIPCHK(c, hipEventRecord(ev(c, 1 + (size_t)i), c->stream));
+        launch_denoise_pass(a, lds_max, c->stream);
+        src ^= 1;
+    }
+    HIPCHK(c, hipEventRecord(ev(c, 1 + (size_t)p.passes), c->stream));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipEventElapsedTime(&c->dn_ms[0], c->events[0], c->events[1]));
+    for (int i = 0; i < p.passes; i++) HIPCHK(c, hipEventElapsedTime(&c->dn_ms[1 + i], c->events[1 + i], c->events[2 + i]));
+    *result = src;
+    return MCPT_OK;
+}
+
+extern "C" {
+
+int mcpt_denoise_default_params(mcpt_denoise_params* p) {
+    if (!p) return MCPT_E_INVALID;
+    // the best row of profiles/denoise_defaults.txt (4 spp against 1024 spp; configs 1, 2, cube)
+    p->passes = 5;
+    p->sigma_color = 2.0f;
+    p->sigma_normal = 0.3f;
+    p->sigma_albedo = 0.3f;
+    p->sigma_depth = 0.1f;
+    return MCPT_OK;
+}
+
+int mcpt_guides_render(mcpt_ctx* c, uint32_t nsamples) {
+    int rc = check_ready(c);
+    if (rc) return rc;
+    if (nsamples < 1 || nsamples >= kMaxSpp - 256) return set_err(c, MCPT_E_INVALID, "guides: nsamples must be 1 .. 2^19 - 257");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->guides_ok = false;
+    const size_t P = c->P;
+    if (!c->g_alb || !c->g_nz) {
+        denoise_free(c);  // (the filter's planes go too: they are re-made on demand)
+        if (hipMalloc(&c->g_alb, P * sizeof(float4)) != hipSuccess || hipMalloc(&c->g_nz, P * sizeof(float4)) != hipSuccess) {
+            (void)hipGetLastError();
+            denoise_free(c);
+            return set_err(c, MCPT_E_NOMEM, "guides: buffer allocation failed");
+        }
+    }
+    // Chunk: np pixels x ns samples of rays; per ray 2 float4 (ray), 2 float4 (hit record), 1 index
+    constexpr size_t kRayBytes = 4 * sizeof(float4) + sizeof(int32_t);
+    size_t budget = (size_t)64 << 20;
+    if (const char* e = getenv(kGuideChunkEnv)) {
+        const long long v = atoll(e);
+        if (v > 0) budget = (size_t)v;
+    }
+    const size_t R = std::min<size_t>(std::max<size_t>(budget / kRayBytes, 1), (size_t)1 << 24);
+    const uint32_t n_eff = c->cam.lens_radius > 0.f ? nsamples : 1u;  // a pinhole's samples share one ray
+    const uint32_t np_max = (uint32_t)std::min<size_t>(P, R);
+    const uint32_t ns_max = (uint32_t)std::min<size_t>(n_eff, std::max<size_t>(R / np_max, 1));
+    const size_t nr = (size_t)np_max * ns_max;
+    free_list(c->tmp_bufs);
+    float4 *ro, *rd, *hp, *hn;
+    int32_t* ht;
+    if ((rc = dalloc(c, c->tmp_bufs, &ro, nr)) || (rc = dalloc(c, c->tmp_bufs, &rd, nr)) ||
+        (rc = dalloc(c, c->tmp_bufs, &hp, nr)) || (rc = dalloc(c, c->tmp_bufs, &hn, nr)) ||
+        (rc = dalloc(c, c->tmp_bufs, &ht, nr))) {
+        (void)hipGetLastError();
+        free_list(c->tmp_bufs);
+        return rc;
+    }
+    GuideArgs ga{};
+    ga.cam = c->cam;
+    if ((rc = cam_table(c, c->W, c->H, &ga.cam_px, &ga.cam_dir))) return rc;
+    ga.W = (int)c->W;
+    ga.H = (int)c->H;
+    ga.seed = c->cfg.seed;
+    ga.ro = ro;
+    ga.rd = rd;
+    ga.hit_p = hp;
+    ga.hit_n = hn;
+    ga.mats = c->scene.mats;
+    ga.g_alb = c->g_alb;
+    ga.g_nz = c->g_nz;
+    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->g_alb, 0, P * sizeof(float4), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->g_nz, 0, P * sizeof(float4), c->stream));
+    bool drained = true;
+    for (size_t p0 = 0; p0 < P; p0 += np_max) {
+        ga.p0 = (uint32_t)p0;
+        ga.np = (uint32_t)std::min<size_t>(np_max, P - p0);
+        for (uint32_t s0 = 0; s0 < n_eff; s0 += ns_max) {
+            ga.s0 = s0;
+            ga.ns = std::min<uint32_t>(ns_max, n_eff - s0);
+            const uint32_t n = ga.np * ga.ns;
+            launch_guide_rays(ga, c->stream);
+            // closest hits as mcpt_stage_run(EXTEND) traces them: no occluder cache, unfiltered rays
+            TraceArgs ta{};
+            ta.scene = c->scene;
+            ta.scene.occ = nullptr;
+            ta.nshards = 1;
+            TraceSet& ts = ta.set[0];
+            ts.ro = ro;
+            ts.rd = rd;
+            ts.count = n;
+            ts.shard_cap = n;
+            ta.hit_tri = ht;
+            ta.grab = &c->cnt->grab[0][0];
+            ta.tiny_stack = c->tiny_stack ? 1 : 0;
+            launch_trace(ta, c->geom, c->stream);
+            HIPCHK(c, hipMemcpyAsync(&c->cnt_host->grab[0][0], &c->cnt->grab[0][0], sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemsetAsync(c->cnt->grab, 0, sizeof(c->cnt->grab), c->stream));  // hand-out counters back to 0
+            HitRecordArgs ha{c->scene, ro, rd, ht, hp, hn, ht, n};
+            launch_hit_record(ha, c->stream);
+            launch_guide_accum(ga, c->stream);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipStreamSynchronize(c->stream));  // the next chunk reuses the buffers (and the staging word)
+            if (c->cnt_host->grab[0][0] < n) drained = false;
+        }
+    }
+    HIPCHK(c, hipEventRecord(ev(c, 1), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipEventElapsedTime(&c->guides_ms, c->events[0], c->events[1]));
+    free_list(c->tmp_bufs);
+    if (!drained) return set_err(c, MCPT_E_HIP, "guides: k_trace left rays untraced");
+    c->guides_scene_gen = c->scene_gen;
+    c->guides_cam = c->cam;
+    c->guides_ok = true;
+    return MCPT_OK;
+}
+
+int mcpt_guides_read(mcpt_ctx* c, float* albedo, float* normal, float* depth, uint32_t* count) {
+    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    if (!guides_valid(c)) return set_err(c, MCPT_E_INVALID, "no valid guide buffers: call mcpt_guides_render first");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<float4> a(c->P), n(c->P);
+    HIPCHK(c, hipMemcpy(a.data(), c->g_alb, c->P * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(n.data(), c->g_nz, c->P * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < c->P; i++) {
+        if (albedo) { albedo[3 * i] = a[i].x; albedo[3 * i + 1] = a[i].y; albedo[3 * i + 2] = a[i].z; }
+        if (normal) { normal[3 * i] = n[i].x; normal[3 * i + 1] = n[i].y; normal[3 * i + 2] = n[i].z; }
+        if (depth) depth[i] = n[i].w;
+        if (count) count[i] = (uint32_t)a[i].w;
+    }
+    return MCPT_OK;
+}
+
+int mcpt_denoise_run(mcpt_ctx* c, uint32_t w, uint32_t h, const float* rgb, const uint32_t* samples, const float* albedo,
+                     const float* normal, const float* depth, const mcpt_denoise_params* pp, float* out_rgb) {
+    if (!c || !rgb || !albedo || !normal || !depth || !out_rgb || !pp) return set_err(c, MCPT_E_INVALID, "denoise: null argument");
+    if (w == 0 || h == 0 || (uint64_t)w * h >= (1ull << 28)) return set_err(c, MCPT_E_INVALID, "denoise: bad image size");
+    int rc = denoise_check_params(c, pp);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = (size_t)w * h;
+    free_list(c->tmp_bufs);
+    auto& L = c->tmp_bufs;
+    float *d_rgb, *d_al, *d_n, *d_z;
+    uint32_t* d_s = nullptr;
+    float4 *col[2], *gd, *al;
+    if ((rc = dupload(c, L, &d_rgb, rgb, 3 * n)) || (rc = dupload(c, L, &d_al, albedo, 3 * n)) ||
+        (rc = dupload(c, L, &d_n, normal, 3 * n)) || (rc = dupload(c, L, &d_z, depth, n)) ||
+        (samples && (rc = dupload(c, L, &d_s, samples, n))) || (rc = dalloc(c, L, &col[0], n)) ||
+        (rc = dalloc(c, L, &col[1], n)) || (rc = dalloc(c, L, &gd, n)) || (rc = dalloc(c, L, &al, n))) {
+        free_list(L);
+        return rc;
+    }
+    DenoisePrepArgs pa{};
+    pa.samples = d_s;
+    pa.rgb = d_rgb;
+    pa.normal = d_n;
+    pa.albedo = d_al;
+    pa.depth = d_z;
+    pa.col = col[0];
+    pa.gd = gd;
+    pa.al = al;
+    pa.n = (uint32_t)n;
+    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
+    launch_denoise_prep(pa, c->stream);
+    int res = 0;
+    if ((rc = denoise_passes(c, *pp, w, h, col, gd, al, &res))) return rc;
+    std::vector<float4> o(n);
+    HIPCHK(c, hipMemcpy(o.data(), col[res], n * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) { out_rgb[3 * i] = o[i].x; out_rgb[3 * i + 1] = o[i].y; out_rgb[3 * i + 2] = o[i].z; }
+    free_list(L);
+    return MCPT_OK;
+}
+
+int mcpt_film_denoise(mcpt_ctx* c, const mcpt_denoise_params* pp) {
+    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    mcpt_denoise_params p;
+    if (pp) p = *pp;
+    else (void)mcpt_denoise_default_params(&p);
+    int rc = denoise_check_params(c, &p);
+    if (rc) return rc;
+    if (!guides_valid(c))
+        return set_err(c, MCPT_E_INVALID, "denoise: guide buffers missing or stale (camera, scene or film changed): call mcpt_guides_render first");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->dn_col[0] || !c->dn_col[1] || !c->dn_gd || !c->dn_al) {
+        c->dn_result = -1;
+        bool ok = true;
+        for (float4** q : {&c->dn_col[0], &c->dn_col[1], &c->dn_gd, &c->dn_al})
+            if (!*q && ok) ok = hipMalloc(q, c->P * sizeof(float4)) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            for (float4** q : {&c->dn_col[0], &c->dn_col[1], &c->dn_gd, &c->dn_al}) {
+                if (*q) (void)hipFree(*q);
+                *q = nullptr;
+            }
+            return set_err(c, MCPT_E_NOMEM, "denoise: plane allocation failed");
+        }
+    }
+    c->dn_result = -1;
+    DenoisePrepArgs pa{};
+    if ((rc = film_view(c, &pa.Ld, &pa.samples))) return rc;
+    pa.g_alb = c->g_alb;
+    pa.g_nz = c->g_nz;
+    pa.col = c->dn_col[0];
+    pa.gd = c->dn_gd;
+    pa.al = c->dn_al;
+    pa.n = (uint32_t)c->P;
+    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
+    launch_denoise_prep(pa, c->stream);
+    int res = 0;
+    if ((rc = denoise_passes(c, p, c->W, c->H, c->dn_col, c->dn_gd, c->dn_al, &res))) return rc;
+    c->dn_result = res;
+    return MCPT_OK;
+}
+
+static int denoised_check(mcpt_ctx* c) {
+    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    if (c->dn_result < 0) return set_err(c, MCPT_E_INVALID, "no denoised frame: call mcpt_film_denoise first");
+    return MCPT_OK;
+}
+
+int mcpt_denoised_read(mcpt_ctx* c, float* rgb) {
+    int rc = denoised_check(c);
+    if (rc) return rc;
+    if (!rgb) return set_err(c, MCPT_E_INVALID, "null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<float4> o(c->P);
+    HIPCHK(c, hipMemcpy(o.data(), c->dn_col[c->dn_result], c->P * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < c->P; i++) { rgb[3 * i] = o[i].x; rgb[3 * i + 1] = o[i].y; rgb[3 * i + 2] = o[i].z; }
+    return MCPT_OK;
+}
+
+int mcpt_denoised_read_device(mcpt_ctx* c, void* d_rgb) {
+    int rc = denoised_check(c);
+    if (rc) return rc;
+    if (!d_rgb) return set_err(c, MCPT_E_INVALID, "null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(d_rgb, c->dn_col[c->dn_result], c->P * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MCPT_OK;
+}
+
+int mcpt_denoised_tonemap_rgba8(mcpt_ctx* c, float exposure, uint8_t* out) {
+    int rc = denoised_check(c);
+    if (rc) return rc;
+    if (!out) return set_err(c, MCPT_E_INVALID, "null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    // k_tonemap over the denoised means with a sample count of 1 per pixel
+    uchar4* d = nullptr;
+    uint32_t* ones = nullptr;
+    if (hipMalloc(&d, c->P * sizeof(uchar4)) != hipSuccess || hipMalloc(&ones, c->P * sizeof(uint32_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        if (d) (void)hipFree(d);
+        return set_err(c, MCPT_E_NOMEM, "tonemap buffers");
+    }
+    hipError_t e = hipMemsetD32Async((hipDeviceptr_t)ones, 1, c->P, c->stream);
+    if (e == hipSuccess) {
+        TonemapArgs a{c->dn_col[c->dn_result], ones, d, exposure, (uint32_t)c->P};
+        launch_tonemap(a, c->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(out, d, c->P * sizeof(uchar4), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    (void)hipFree(ones);
+    if (e != hipSuccess) return set_err(c, MCPT_E_HIP, std::string("tonemap: ") + hipGetErrorString(e));
+    return MCPT_OK;
+}
+
+int mcpt_debug_denoise_ms(const mcpt_ctx* c, float* out10) {
+    if (!c || !out10) return MCPT_E_INVALID;
+    out10[0] = c->guides_ms;
+    for (int i = 0; i < 9; i++) out10[1 + i] = c->dn_ms[i];
+    return MCPT_OK;
+}
+
+}  // extern "C"

@@ -74,6 +74,11 @@ class StageStats(C.Structure):
         return int(self.extend_rays + self.shadow_rays + self.vis_rays)
 
 
+class DenoiseParams(C.Structure):  # mcpt_denoise_params
+    _fields_ = [("passes", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float)]
+
+
 class PathView(C.Structure):  # mcpt_path_view: path state at the shading stages' boundary
     _fields_ = [("film_w", C.c_uint32), ("film_h", C.c_uint32), ("flags", _u), ("samples", _u), ("hit_tri", _i),
                 ("ray_o", _f), ("ray_d", _f), ("beta", _f), ("nee0", _f), ("nee1", _f),
@@ -132,6 +137,16 @@ ABI = {
     "mcpt_film_pack_tiles": (C.c_int, [C.c_void_p, C.c_void_p, _u]),
     "mcpt_film_unpack_tiles": (C.c_int, [C.c_void_p, C.c_void_p, _u, C.c_uint32]),
     "mcpt_film_tonemap_rgba8": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(C.c_uint8)]),
+    "mcpt_guides_render": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "mcpt_guides_read": (C.c_int, [C.c_void_p, _f, _f, _f, _u]),
+    "mcpt_denoise_default_params": (C.c_int, [C.POINTER(DenoiseParams)]),
+    "mcpt_denoise_run": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _f, _u, _f, _f, _f, C.POINTER(DenoiseParams), _f]),
+    "mcpt_film_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams)]),
+    "mcpt_denoised_read": (C.c_int, [C.c_void_p, _f]),
+    "mcpt_denoised_read_device": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mcpt_denoised_tonemap_rgba8": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(C.c_uint8)]),
+    "mcpt_denoised_write_png": (C.c_int, [C.c_void_p, C.c_float, C.c_char_p]),
+    "mcpt_debug_denoise_ms": (C.c_int, [C.c_void_p, _f]),
     "mcpt_sync": (C.c_int, [C.c_void_p]),
     "mcpt_device_name": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
     "mcpt_debug_queue_rays": (C.c_int, [C.c_void_p, C.c_int, _f, _f, _u]),
@@ -521,10 +536,48 @@ class PathTracer:
         self._ck(lib().mcpt_film_read(self.h, fptr(Ld), s.ctypes.data_as(_u)))
         return Ld.reshape(self.H, self.W, 3), s.reshape(self.H, self.W)
 
-    def tonemap(self, exposure=1.0):
+    def tonemap(self, exposure=1.0, denoised=False):
+        """Reinhard-tonemapped RGBA8 of the film, or with denoised=True of the last denoise()."""
         out = np.zeros(self.W * self.H * 4, np.uint8)
-        self._ck(lib().mcpt_film_tonemap_rgba8(self.h, exposure, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        fn = lib().mcpt_denoised_tonemap_rgba8 if denoised else lib().mcpt_film_tonemap_rgba8
+        self._ck(fn(self.h, exposure, out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out.reshape(self.H, self.W, 4)
+
+    def render_guides(self, n=1):
+        """First-hit guide buffers of the film under the current camera (mcpt_guides_render): n guide
+        samples per pixel along the camera rays of film samples 0..n-1."""
+        self._ck(lib().mcpt_guides_render(self.h, n))
+
+    def guides(self) -> dict:
+        """Guide sums and counts (mcpt_guides_read): albedo / normal (H, W, 3), depth / count (H, W)."""
+        P = self.W * self.H
+        a, n = np.zeros(3 * P, np.float32), np.zeros(3 * P, np.float32)
+        z, cnt = np.zeros(P, np.float32), np.zeros(P, np.uint32)
+        self._ck(lib().mcpt_guides_read(self.h, fptr(a), fptr(n), fptr(z), cnt.ctypes.data_as(_u)))
+        return {"albedo": a.reshape(self.H, self.W, 3), "normal": n.reshape(self.H, self.W, 3),
+                "depth": z.reshape(self.H, self.W), "count": cnt.reshape(self.H, self.W)}
+
+    def denoise(self, **params):
+        """A-trous filter of the film with the context's guides (mcpt_film_denoise); keyword
+        arguments override the default parameters (passes, sigma_color, sigma_normal, ...)."""
+        p = denoise_params(**params) if params else None
+        self._ck(lib().mcpt_film_denoise(self.h, C.byref(p) if p is not None else None))
+
+    def denoised(self):
+        """The last denoise() result as (H, W, 3) float32 (mcpt_denoised_read)."""
+        out = np.zeros(3 * self.W * self.H, np.float32)
+        self._ck(lib().mcpt_denoised_read(self.h, fptr(out)))
+        return out.reshape(self.H, self.W, 3)
+
+    def write_denoised_png(self, path, exposure=1.0):
+        """Tonemapped denoised frame as 8-bit RGB PNG (mcpt_denoised_write_png)."""
+        self._ck(lib().mcpt_denoised_write_png(self.h, exposure, os.fsencode(path)))
+
+    def denoise_ms(self) -> dict:
+        """Device times of the last guide pass and the last filter run (mcpt_debug_denoise_ms)."""
+        v = (C.c_float * 10)()
+        self._ck(lib().mcpt_debug_denoise_ms(self.h, v))
+        return {"guides": float(v[0]), "prepare": float(v[1]), "passes": [float(x) for x in v[2:]]}
 
     def trace_closest(self, ro, rd, steps=False):
         ro = np.ascontiguousarray(ro, np.float32).reshape(-1, 3)
@@ -611,6 +664,33 @@ class PathTracer:
         rd = np.zeros((n.value, 3), np.float32)
         self._ck(lib().mcpt_debug_queue_rays(self.h, 0, fptr(ro), fptr(rd), C.byref(n)))
         return ro[: n.value], rd[: n.value]
+
+
+def denoise_params(**kw) -> DenoiseParams:
+    """mcpt_denoise_default_params with keyword overrides."""
+    p = DenoiseParams()
+    _check(lib().mcpt_denoise_default_params(C.byref(p)))
+    for k, v in kw.items():
+        if k not in dict(DenoiseParams._fields_):
+            raise TypeError(f"unknown denoise parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def denoise_run(pt, rgb, albedo, normal, depth, samples=None, **params):
+    """mcpt_denoise_run on PathTracer pt: the filter over host images of means ((H, W, 3) rgb, albedo
+    and normal, (H, W) depth and optional sample counts); returns the filtered (H, W, 3) image."""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    H, W = rgb.shape[:2]
+    al = np.ascontiguousarray(albedo, np.float32).reshape(H, W, 3)
+    nm = np.ascontiguousarray(normal, np.float32).reshape(H, W, 3)
+    z = np.ascontiguousarray(depth, np.float32).reshape(H, W)
+    sm = None if samples is None else np.ascontiguousarray(samples, np.uint32).reshape(H, W)
+    out = np.zeros((H, W, 3), np.float32)
+    p = denoise_params(**params)
+    _check(lib().mcpt_denoise_run(pt.h, W, H, fptr(rgb), None if sm is None else sm.ctypes.data_as(_u), fptr(al),
+                                  fptr(nm), fptr(z), C.byref(p), fptr(out)), pt.h)
+    return out
 
 
 def gather(tracers, root=0):
