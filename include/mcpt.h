@@ -217,6 +217,14 @@ int mcpt_set_trace_partitions(mcpt_ctx *ctx, uint32_t nparts);
  * k_trace's counting build, off (0, the default) leaves them 0.  The counting build holds six more
  * per-lane registers, which the 64-VGPR 8-wave traversal cannot afford without spilling. */
 int mcpt_set_work_counters(mcpt_ctx *ctx, int32_t on);
+/* Continuation rays the next logic pass is certain to discard: on = 1 (the
+ * default) does not make them.  A path that Russian roulette will end at its next vertex -- the
+ * decision reads only the throughput stored now and a keyed draw -- gets no continuation sample and
+ * no extension ray; a path whose next vertex lies beyond max_depth ends at once, without its
+ * material evaluation and its three rays.  Films, sample counts and every ray count are the same
+ * with 0 and 1 (the rays are counted as the reference traces them and appear as resolved in place);
+ * mcpt_stage_run always runs the stages without it.  May be changed between calls, mid-frame too. */
+int mcpt_set_skip_discarded(mcpt_ctx *ctx, int32_t on);
 int mcpt_set_tiles(mcpt_ctx *ctx, const uint32_t *tile_xy, uint32_t ntiles); /* batch tile set; NULL = all */
 /* Path-state layout (default 0, full: one path per pixel of the whole W x H film per slot, path id =
  * pixel id as in the reference, wavefront_kernels.cu:108,114; Film.cu:254-275 sizes the pool at
@@ -345,6 +353,13 @@ int mcpt_debug_ray_counts(const mcpt_ctx *ctx, uint64_t *out);
  * extension rays, not as traversed ones), and the last table build's milliseconds.  Returns the
  * number of table builds of the context so far (a film clear alone never rebuilds), < 0 on error. */
 int mcpt_debug_primary_stats(const mcpt_ctx *ctx, double *out4);
+/* mcpt_set_skip_discarded, 4 values since the last film clear: [0] extension rays counted but not
+ * made (whether or not they would have entered the scene's box), [1] any-hit rays likewise, [2]
+ * material evaluations not run (paths ended one vertex short of max_depth + 1: each is one of [0]
+ * and one or two of [1]; [0] - [2] are the roulette's), and, counted only while the switch is off,
+ * [3] the extension rays of such paths that were resolved in place, i.e. that the switch would not
+ * have saved the traversal. */
+int mcpt_debug_discard_stats(const mcpt_ctx *ctx, uint64_t *out4);
 /* The traversal's loop-phase counts, recorded by the counting build (mcpt_set_work_counters on)
  * since the last film clear or reset (reset = 1 starts a new count after reading): out12[0] loop
  * trips, [1] refills, [2] lanes refilled, [3] node-phase wave iterations, [4] triangle phases,

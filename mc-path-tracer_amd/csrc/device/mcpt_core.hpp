@@ -234,6 +234,15 @@ struct Rng {
     uint32_t key, len;
     MCPT_HD float operator()(uint32_t slot) const { return rngf(key, len, slot); }
 };
+// Russian roulette of wf_logic at the vertex r.len (wavefront_kernels.cu:189-196): by is the
+// throughput's y the mode tests (reference: before the vertex's update; fixed: after it), q the
+// termination probability.  true: the path ends here.  The one copy of the rule: the logic pass
+// calls it, and so does the prediction one iteration earlier (k_shade / k_material, with r.len + 1
+// and the throughput the next pass will read), so a NaN or out-of-range by decides both alike.
+MCPT_HD bool rr_terminates(const Rng& r, float by, float& q) {
+    q = fmx(0.05f, 1.f - by);
+    return r(SL_RR) < q;
+}
 
 // ---------------------------------------------------------------------------
 // Quotients with a shared denominator.  The reference divides in IEEE fp32:

@@ -520,6 +520,8 @@ __device__ inline bool occ_hit1(const DevScene& sc, V3 o, V3 d, uint2 e) {
 // ---------------------------------------------------------------------------
 struct MatOut {
     bool want_ext, want_l, want_b, trivial_ext, vis_ray, need_cb;
+    bool skip_ext;        // the extension ray is counted, not made: the next logic pass ends the path (ShadeArgs::skip)
+    bool doomed_inplace;  // switch off: such a path's extension ray, resolved in place (C_SKIP_INPLACE)
     uint32_t trivial_any;
     uint2 el, eb;  // occluder-cache entries of the light / BRDF rays (loads issued inside material())
     // the BRDF sample's light terms are finished by material_brdf_terms after the occluder cache
@@ -540,7 +542,7 @@ struct MatOut {
 // Gram-Schmidt (A.9), env sampling/pdf on matched, clamped cells (A.11).
 template <bool FIXED>
 __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix, uint32_t sidx, uint32_t len,
-                                 V3 beta_store, int32_t htri, float4* stage, bool occ_on) {
+                                 V3 beta_store, int32_t htri, float4* stage, bool occ_on, bool no_cont) {
     const DevScene& sc = a.scene;
     const uint2 none = make_uint2(kOccEmpty, kOccEmpty);
     MatOut mo{};
@@ -564,7 +566,15 @@ __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix
     // (:335-343) wait for the occluder cache (material_brdf_terms).
     uint32_t nf = 0;
     V3 rr;
-    {
+    if (no_cont) {
+        // k_shade's mark (reference mode): the next logic pass adds this vertex's MIS terms and then
+        // ends the path by roulette, so the continuation sample is never read.  The pass multiplies
+        // the MIS sum by beta.xyz; the ratio slots hold 0, F_FZERO stays clear, and ray_o / ray_d /
+        // hit_tri keep their last values (hit_tri >= 0: this vertex's hit).
+        rr = v3(0.f, 0.f, 0.f);
+        st_s(a.p.beta + pid, f4(beta_store, 0.f));
+        mo.skip_ext = true;
+    } else {
         MCPT_MARK("m_cont");
         V3 wi_s = brdf_sample_wi<FIXED>(m, n, wo, r, SL_CONT_E0, r(SL_CONT_LOBE) < 0.5f);  // spec : diff
         float pdf_s;
@@ -574,13 +584,30 @@ __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix
         rr = f_s / pdf_s;
         const V3 new_o = pos + n * 0.001f;  // :358
         st_s(a.p.beta + pid, f4(beta_store, rr.x));
-        st_s(a.p.ray_o + pid, f4(new_o, 0.f));
-        st_s(a.p.ray_d + pid, f4(wi_s, 0.f));
-        mo.want_ext = true;
-        if (ray_misses_scene(sc, new_o, wi_s)) {  // resolved here: isect stays "not found"
-            a.p.hit_tri[pid] = -1;
-            mo.want_ext = false;
-            mo.trivial_ext = true;
+        // Will the logic pass at len + 1 end the path whatever the ray finds?  Fixed mode decides here:
+        // its roulette tests the throughput after that pass's update, the same fp32 product.  With
+        // the switch off the answer only feeds a count (C_SKIP_INPLACE).
+        bool doomed = false;
+        if (FIXED || !a.skip) {
+            doomed = len + 1u > (uint32_t)a.max_depth;
+            if (!doomed && len + 1u > (uint32_t)a.rr_depth) {
+                const Rng r1{r.key, len + 1u};
+                float q;
+                doomed = rr_terminates(r1, FIXED ? (beta_store * rr).y : beta_store.y, q);
+            }
+        }
+        if (doomed && a.skip) {
+            mo.skip_ext = true;  // the ratios stay: the next pass recomputes the same product
+        } else {
+            st_s(a.p.ray_o + pid, f4(new_o, 0.f));
+            st_s(a.p.ray_d + pid, f4(wi_s, 0.f));
+            mo.want_ext = true;
+            if (ray_misses_scene(sc, new_o, wi_s)) {  // resolved here: isect stays "not found"
+                a.p.hit_tri[pid] = -1;
+                mo.want_ext = false;
+                mo.trivial_ext = true;
+                mo.doomed_inplace = doomed;
+            }
         }
     }
     MCPT_MARK("m_light");
@@ -777,6 +804,8 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
     // ---- phase 1: logic + generate (one thread per pixel)
     MCPT_MARK("load");
     bool gen_ext = false, gen_trivial = false, gen_prim = false, prim_res = false, cont = false;
+    bool no_cont = false;             // continuing, and the next pass's roulette ends it (kRecNoCont)
+    bool dd = false, dd_vis = false;  // ended here, one vertex short of max_depth + 1; its BRDF visibility ray
     bool d_logic = false, d_nee = false, d_gen = false;  // (MCPT_DIAG_SHADE)
     (void)d_logic; (void)d_nee; (void)d_gen;
     uint32_t cont_len = 0, cont_sidx = 0;
@@ -853,14 +882,13 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
                     terminate = true;
                 } else {
                     beta_store = B * v3(b4.w, n0.w, n1.w);  // paths->beta *= f_sample / pdf_sample (:187)
-                    if (len > (uint32_t)a.rr_depth) {        // :189-196
+                    if (len > (uint32_t)a.rr_depth) {        // :189-196 (rr_terminates)
+                        float q;
                         if (FIXED) {  // q from the updated throughput, survivors reweighted (A.5)
-                            float q = fmx(0.05f, 1.f - beta_store.y);
-                            if (r(SL_RR) < q) terminate = true;
+                            if (rr_terminates(r, beta_store.y, q)) terminate = true;
                             else beta_store = beta_store / (1.f - q);
                         } else {
-                            float q = fmx(0.05f, 1.f - B.y);
-                            if (r(SL_RR) < q) terminate = true;
+                            if (rr_terminates(r, B.y, q)) terminate = true;
                         }
                     }
                 }
@@ -870,6 +898,27 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
                             __float_as_uint(film.y) != __float_as_uint(ld4.y) ||
                             __float_as_uint(film.z) != __float_as_uint(ld4.z)))
                 st_s(a.p.Ld + pid, f4(film, 0.f));
+            // A continuing path the next logic pass (vertex len + 1) is certain to end (ShadeArgs::skip).
+            if (a.skip && !terminate) {
+                if (len + 1u > (uint32_t)a.max_depth) {
+                    // Beyond max_depth the next pass adds nothing (no MIS terms, :142-146): the path
+                    // ends here with all its film contributions made, its material evaluation is not
+                    // run, and the rays that evaluation makes are counted: the extension ray, the
+                    // light ray, and the BRDF visibility ray unless the drawn light (material()'s
+                    // expression) is a delta light.
+                    int l_id = (int)(r(SL_LIGHT) * (float)(sc.nlights - 0) + (float)0);
+                    dd = true;
+                    dd_vis = !(((l_id == sc.nlights) ? 0 : l_id) > 0);
+                    terminate = true;
+                } else if (!FIXED && len + 1u > (uint32_t)a.rr_depth) {
+                    // Its roulette reads the throughput this pass stores and a keyed draw: decided now,
+                    // k_material makes no continuation sample.  (Fixed mode tests the throughput after
+                    // the next update: k_material decides once it has f_s / pdf_s.)
+                    const Rng r1{r.key, len + 1u};
+                    float q;
+                    no_cont = rr_terminates(r1, beta_store.y, q);
+                }
+            }
             if (terminate) {  // :199-204
                 dead = true;
                 samples++;
@@ -949,13 +998,26 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
         if (gen_prim) a.prim_q[shard * a.ext_cap + slot[2]] = make_uint2(pid, pix);
         if (cont) {
             const uint32_t qi = shard * a.ext_cap + slot[1];
-            st_s(a.mat_rec + qi, make_uint4(pid, pix, cont_sidx | (cont_len << kRecLenShift), (uint32_t)cont_htri));
+            st_s(a.mat_rec + qi, make_uint4(pid, pix, cont_sidx | (no_cont ? kRecNoCont : 0u) | (cont_len << kRecLenShift),
+                                            (uint32_t)cont_htri));
             st_s(a.mat_beta + qi, f4(beta_store, 0.f));
         }
     }
-    uint32_t n_ext = (gen_ext || gen_trivial || gen_prim) ? 1u : 0u;  // queued + resolved-in-place + table rays
+    // queued + resolved-in-place + table rays, and the extension ray of a path ended short of
+    // max_depth + 1 (counted in the iteration that would have made it: the tile set is not idle)
+    uint32_t n_ext = ((gen_ext || gen_trivial || gen_prim) ? 1u : 0u) + (dd ? 1u : 0u);
     for (int off = 32; off > 0; off >>= 1) n_ext += __shfl_xor(n_ext, off);
     if (lane == 0 && n_ext) atomicAdd(sc_ctr + C_EXT_RAYS, n_ext);
+    if (a.skip) {
+        const uint32_t n_dd = (uint32_t)__popcll(__ballot(dd)), n_ddv = (uint32_t)__popcll(__ballot(dd_vis));
+        if (lane == 0 && n_dd) {
+            atomicAdd(sc_ctr + C_ANY_RAYS, n_dd + n_ddv);
+            if (n_ddv) atomicAdd(sc_ctr + C_VIS, n_ddv);
+            atomicAdd(sc_ctr + C_SKIP_EXT, n_dd);
+            atomicAdd(sc_ctr + C_SKIP_ANY, n_dd + n_ddv);
+            atomicAdd(sc_ctr + C_SKIP_MAT, n_dd);
+        }
+    }
     if (a.prim_cnt) {
         const uint32_t n_prim = (uint32_t)__popcll(__ballot(prim_res));
         if (lane == 0 && n_prim) atomicAdd(sc_ctr + C_PRIM_RAYS, n_prim);
@@ -1022,7 +1084,7 @@ __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_k
     uint32_t* sc_ctr = a.cnt->shard[shard];
     const uint32_t n = sc_ctr[C_MAT];
     const int lane = threadIdx.x & 63;
-    uint32_t n_ext = 0, n_any = 0, n_vis = 0, n_occ = 0, occ_try = 0;
+    uint32_t n_ext = 0, n_any = 0, n_vis = 0, n_occ = 0, occ_try = 0, n_skip = 0, n_inpl = 0;
     const bool occ_on = a.scene.occ && a.scene.occ_gate[0] == 0 && a.scene.occ_gate[2] != 0;  // see DevScene::occ_gate
     // Any-hit rays are staged here (light ray o/d, BRDF visibility ray o/d) and stored after
     // the block push at their queue positions: the block's rays of one kind land contiguously,
@@ -1039,8 +1101,8 @@ __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_k
             const uint4 q = ld_s(a.mat_rec + shard * a.ext_cap + i);  // {pid, pixel, sample index | len << 24, hit_tri}
             const float4 b4 = ld_s(a.mat_beta + shard * a.ext_cap + i);
             mpid = q.x;
-            mo = material<FIXED>(a, mpid, q.y, q.z & ((1u << kRecLenShift) - 1u), q.z >> kRecLenShift, xyz(b4),
-                                 (int32_t)q.w, &s_any[0][0], occ_on);
+            mo = material<FIXED>(a, mpid, q.y, q.z & (kRecNoCont - 1u), q.z >> kRecLenShift, xyz(b4), (int32_t)q.w,
+                                 &s_any[0][0], occ_on, (q.z & kRecNoCont) != 0u);
             // the occluder cache (see occ_hit1), before the BRDF sample's light terms: a ray it
             // resolves gets its wf_shadow result here and is not queued
             MCPT_MARK("m_occ");
@@ -1098,7 +1160,10 @@ __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_k
         // next trip's material())
         n_occ += (uint32_t)(__popcll(__ballot(occ_l)) + __popcll(__ballot(occ_b)));
         occ_try += (uint32_t)(__popcll(__ballot(try_l)) + __popcll(__ballot(try_b)));
-        n_ext += (uint32_t)__popcll(__ballot(mo.want_ext || mo.trivial_ext));  // queued + resolved-in-place rays
+        // queued + resolved-in-place rays + those the next logic pass would discard (counted, not made)
+        n_ext += (uint32_t)__popcll(__ballot(mo.want_ext || mo.trivial_ext || mo.skip_ext));
+        n_skip += (uint32_t)__popcll(__ballot(mo.skip_ext));
+        n_inpl += (uint32_t)__popcll(__ballot(mo.doomed_inplace));
         n_any += (uint32_t)(__popcll(__ballot(mo.want_l)) + __popcll(__ballot(mo.want_b)) +
                             __popcll(__ballot(mo.trivial_any >= 1u)) + __popcll(__ballot(mo.trivial_any >= 2u)));
         n_vis += (uint32_t)__popcll(__ballot(mo.vis_ray));
@@ -1109,6 +1174,8 @@ __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_k
         if (n_vis) atomicAdd(sc_ctr + C_VIS, n_vis);
         if (n_occ) atomicAdd(sc_ctr + C_OCC, n_occ);
         if (occ_try) atomicAdd(sc_ctr + C_OCC_TRY, occ_try);
+        if (n_skip) atomicAdd(sc_ctr + C_SKIP_EXT, n_skip);
+        if (n_inpl) atomicAdd(sc_ctr + C_SKIP_INPLACE, n_inpl);
     }
 }
 
@@ -2143,6 +2210,14 @@ __global__ void k_accumulate(CounterBlock* c, uint32_t nparts, uint32_t* occ_gat
     }
     uint32_t er = c->shard[t][C_EXT_RAYS], ar = c->shard[t][C_ANY_RAYS], oc = c->shard[t][C_OCC],
              ot = c->shard[t][C_OCC_TRY], pr = c->shard[t][C_PRIM_RAYS];
+    const int skw[4] = {C_SKIP_EXT, C_SKIP_ANY, C_SKIP_MAT, C_SKIP_INPLACE};
+    uint32_t sk[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        sk[k] = c->shard[t][skw[k]];
+        if (sk[k]) c->shard[t][skw[k]] = 0;
+        for (int off = 32; off > 0; off >>= 1) sk[k] += __shfl_xor(sk[k], off);
+    }
     c->shard[t][C_PRIM] = 0;
     c->shard[t][C_PRIM_RAYS] = 0;
     c->shard[t][C_EXT_RAYS] = 0;
@@ -2160,6 +2235,7 @@ __global__ void k_accumulate(CounterBlock* c, uint32_t nparts, uint32_t* occ_gat
     if (t == 0) {
         c->tot_ext += er;
         c->tot_prim += pr;
+        for (int k = 0; k < 4; k++) c->tot_skip[k] += sk[k];
         c->tot_any += ar;
         c->tot_occ += oc;
         // occluder-cache gate for the next iterations' k_material (a speed choice only)

@@ -59,6 +59,11 @@ enum : uint32_t {
 constexpr uint32_t kMaxSpp = 1u << (32 - F_SIDX_SHIFT);  // sample indices must fit the flags word
 constexpr int kRecLenShift = 24;  // material record word 2: sample index (< kMaxSpp) | len << 24 (len < 256)
 static_assert(kMaxSpp <= (1u << kRecLenShift), "sample index and len share a record word");
+// Material record word 2, "no continuation" (between the sample index and len): the next logic pass is
+// certain to end the path by Russian roulette, so k_material evaluates no continuation sample
+// (ShadeArgs::skip)
+constexpr uint32_t kRecNoCont = 1u << 23;
+static_assert(kMaxSpp <= kRecNoCont && kRecNoCont < (1u << kRecLenShift), "the mark lies between sample index and len");
 
 // k_shade blocks: kBlock consecutive pixels of one path slot; slot k's blocks follow slot k-1's
 __host__ __device__ constexpr int shade_blocks_per_tile(int tile_px, int slots) {
@@ -137,10 +142,14 @@ struct DevPaths {
 constexpr int kShards = 64;
 constexpr int kMaxParts = kShards;  // k_trace work partitions (at most one per queue shard)
 enum : int { C_EXT = 0, C_ANY = 1, C_VIS = 2, C_STATS = 3, C_EXT_RAYS = 9, C_ANY_RAYS = 10, C_MAT = 11, C_OCC = 12,
-              C_OCC_TRY = 13, C_PH = 14, C_PRIM = 26, C_PRIM_RAYS = 27, C_WORDS = 32 };
+              C_OCC_TRY = 13, C_PH = 14, C_SKIP_INPLACE = 25, C_PRIM = 26, C_PRIM_RAYS = 27, C_SKIP_EXT = 28,
+              C_SKIP_ANY = 29, C_SKIP_MAT = 30, C_WORDS = 32 };
 // C_STATS..+5; C_OCC / C_OCC_TRY: any-hit rays resolved by / tested against the occluder cache;
 // C_PH..+kPhaseWords-1: k_trace's loop-phase counts (counting build, PH_*); C_PRIM: primary-queue
 // pushes (k_shade -> k_primary), C_PRIM_RAYS: primary rays resolved from the candidate table
+// C_SKIP_EXT / C_SKIP_ANY / C_SKIP_MAT: extension rays, any-hit rays and material evaluations of
+// paths the next logic pass discards, counted as rays but not made (ShadeArgs::skip);
+// C_SKIP_INPLACE: with the switch off, such paths' extension rays that were resolved in place
 // k_trace loop-phase counts of the counting instantiation (mcpt_debug_trace_profile), per wave summed:
 enum : int {
     PH_TRIPS = 0,          // loop trips with a ray in the wave
@@ -170,8 +179,9 @@ struct CounterBlock {
     unsigned long long tot_ext_q, tot_any_q;  // rays queued to k_trace (the rest were resolved in place)
     unsigned long long tot_phase[kPhaseWords];  // k_trace loop-phase counts (PH_*; counting build only)
     unsigned long long tot_prim;  // primary rays resolved from the candidate table (part of tot_ext)
+    unsigned long long tot_skip[4];  // C_SKIP_EXT, C_SKIP_ANY, C_SKIP_MAT, C_SKIP_INPLACE
 };
-static_assert(C_PH + kPhaseWords <= C_PRIM, "counter words overlap");
+static_assert(C_PH + kPhaseWords <= C_SKIP_INPLACE, "counter words overlap");
 
 // Primary-hit candidate table: per film pixel one 64-B line of up to
 // kPrimK triangle record indices in ascending scene-id order, and a byte prim_cnt[pixel]: 0 = no list
@@ -222,6 +232,12 @@ struct ShadeArgs {
     const uint8_t* prim_cnt;
     const uint32_t* prim_list;
     uint2* prim_q;
+    // 1 (mcpt_set_skip_discarded, the default): a continuing path whose next logic pass is certain to
+    // end it makes no extension ray (Russian roulette: k_shade marks its record kRecNoCont in
+    // reference mode, k_material decides in fixed mode) or ends at once without its material
+    // evaluation (the next vertex lies beyond max_depth).  The rays are counted as the reference
+    // traces them.  0: every stage as the reference runs it (mcpt_stage_run always)
+    int skip;
 };
 // k_primary_build: the table of a W x H film.  stats: [0] pixels with a list, [1] overflow pixels.
 struct PrimaryBuildArgs {

@@ -49,6 +49,9 @@ struct mcpt_ctx {
     // per-lane counters cost the fast one its spill-free registers -- off by default
     bool count_work = getenv("MCPT_WORK_COUNTERS") != nullptr;
     int node_layout = 0;  // pair-node numbering the last upload used (mcpt_debug_node_layout)
+    // mcpt_set_skip_discarded: paths the next logic pass is certain to end make no extension ray
+    // (ShadeArgs::skip); results and ray counts are the same either way
+    bool skip_discarded = true;
     // camera
     mcpt::CamView cam{};
     bool has_cam = false;
@@ -968,6 +971,11 @@ int mcpt_debug_primary_stats(const mcpt_ctx* c, double* out4) {
     out4[3] = (double)c->prim_build_ms;
     return (int)std::min<uint64_t>(c->prim_builds, 0x7fffffffull);
 }
+int mcpt_debug_discard_stats(const mcpt_ctx* c, uint64_t* out4) {
+    if (!c || !out4) return MCPT_E_INVALID;
+    for (int k = 0; k < 4; k++) out4[k] = c->totals_ok ? c->totals.tot_skip[k] : 0;
+    return MCPT_OK;
+}
 int mcpt_debug_occ_stats(const mcpt_ctx* c, uint64_t* resolved, int32_t* enabled) {
     if (!c) return MCPT_E_INVALID;
     if (resolved) *resolved = c->totals_ok ? c->totals.tot_occ : 0;
@@ -1371,6 +1379,7 @@ static int enqueue_iteration(mcpt_ctx* c, size_t evbase, bool timing, const int2
     sa.any_cap = c->any_cap;
     sa.cnt = c->cnt;
     sa.blk_done = c->blk_done_off ? nullptr : c->blk_done;
+    sa.skip = c->skip_discarded ? 1 : 0;
     if (int rc = cam_table(c, c->W, c->H, &sa.cam_px, &sa.cam_dir)) return rc;
     prim_table(c, sa);
     const int bpt = shade_blocks_per_tile((int)(c->tile_w * c->tile_h), (int)c->slots);
@@ -1930,6 +1939,12 @@ int mcpt_set_path_slots(mcpt_ctx* c, uint32_t slots) {
 int mcpt_set_work_counters(mcpt_ctx* c, int32_t on) {
     if (!c) return MCPT_E_INVALID;
     c->count_work = on != 0;
+    return MCPT_OK;
+}
+
+int mcpt_set_skip_discarded(mcpt_ctx* c, int32_t on) {
+    if (!c) return MCPT_E_INVALID;
+    c->skip_discarded = on != 0;  // read per iteration (enqueue_iteration): may change between calls
     return MCPT_OK;
 }
 

@@ -159,6 +159,8 @@ ABI = {
     "mcpt_debug_ray_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mcpt_debug_primary_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "mcpt_set_work_counters": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mcpt_set_skip_discarded": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mcpt_debug_discard_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mcpt_scene_upload_gpu_bvh": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mcpt_set_gpu_bvh_builder": (C.c_int, [C.c_void_p, C.c_int32]),
     "mcpt_film_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
@@ -447,6 +449,22 @@ class PathTracer:
         if n < 0:
             raise McptError(f"mcpt_debug_primary_stats failed ({n})")
         return dict(lists=int(v[0]), overflow=int(v[1]), resolved=int(v[2]), build_ms=float(v[3]), builds=int(n))
+
+    def set_skip_discarded(self, on=True):
+        """Continuation rays the next logic pass is certain to discard are not made
+        (mcpt_set_skip_discarded; on by default, the same results either way)."""
+        if hasattr(lib(), "mcpt_set_skip_discarded") or not os.environ.get("MCPT_LIB"):
+            self._ck(lib().mcpt_set_skip_discarded(self.h, int(bool(on))))  # (an older variant library: never skips)
+
+    def discard_stats(self) -> dict:
+        """mcpt_debug_discard_stats since the last film clear: extension rays and any-hit rays counted
+        but not made, material evaluations not run, and (switch off only) the extension rays of
+        discarded paths that were resolved in place."""
+        v = (C.c_uint64 * 4)()
+        if hasattr(lib(), "mcpt_debug_discard_stats") or not os.environ.get("MCPT_LIB"):
+            self._ck(lib().mcpt_debug_discard_stats(self.h, v))  # (an older variant library: zeros)
+        return dict(zip(("extension_untraced", "any_hit_untraced", "evaluations_not_run", "doomed_in_place"),
+                        [int(x) for x in v]))
 
     def occ_stats(self):
         """(any-hit rays the occluder cache resolved since the last film clear, cache enabled)."""
