@@ -3,10 +3,14 @@
 // INTEGRATION.md): build a BASELINE config scene with the host builder, upload it,
 // run the wavefront iterations until every pixel has its samples, write PNG + PFM.
 //
-//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]]
+//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--adaptive <target> <min> <max> [rounds]]
 //
 // --denoise renders the first-hit guide buffers (default 4 guide samples per pixel), filters the film
 // with the default parameters and writes <out_prefix>_denoised.png beside the raw image.
+// --adaptive renders every pixel to <min> samples, then [rounds] (default 2) times estimates the
+// film's error from the path slots, builds per-pixel budgets that aim at the relative standard error
+// <target> within [<min>, <max>] and renders on; it needs --slots >= 2 (8 if
+// --slots is not given) and replaces [spp].  It combines with --denoise.
 // --tiles-per-call uses the reference orchestration (one 256x256 tile per call,
 // wavefront_kernels.cu:377-442 + Film::update_tile_position) instead of batch mode.
 #include <stdio.h>
@@ -22,7 +26,7 @@ struct Cfg { int w, h, spp, depth; float pos[3], pitch; const char* env; };
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]]\n", argv[0]);
+        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--adaptive <target> <min> <max> [rounds]]\n", argv[0]);
         return 2;
     }
     const Cfg cfgs[6] = {{0, 0, 0, 0, {0, 0, 0}, 0, ""},
@@ -38,17 +42,31 @@ int main(int argc, char** argv) {
     std::string out = (argc > 3 && argv[3][0] != '-') ? argv[3] : "mcpt_render";
     bool gpu_bvh = false, ref_bvh = false, fixed = false, per_tile = false;
     uint32_t slots = 1, guide_samples = 0;  // guide_samples > 0: denoise
+    bool adaptive = false, slots_given = false;
+    mcpt_sample_budget_params ap;
+    mcpt_sample_budget_default_params(&ap);
+    uint32_t rounds = 2;
     for (int i = 2; i < argc; i++) {
         if (!strcmp(argv[i], "--gpu-bvh")) gpu_bvh = true;
         if (!strcmp(argv[i], "--reference-bvh")) ref_bvh = true;
         if (!strcmp(argv[i], "--fixed")) fixed = true;
         if (!strcmp(argv[i], "--tiles-per-call")) per_tile = true;
-        if (!strcmp(argv[i], "--slots") && i + 1 < argc) slots = (uint32_t)atoi(argv[++i]);
+        if (!strcmp(argv[i], "--slots") && i + 1 < argc) { slots = (uint32_t)atoi(argv[++i]); slots_given = true; }
+        if (!strcmp(argv[i], "--adaptive")) {
+            if (i + 3 >= argc) { fprintf(stderr, "--adaptive needs <target> <min> <max>\n"); return 2; }
+            adaptive = true;
+            ap.target_rel_err = (float)atof(argv[++i]);
+            ap.min_spp = (uint32_t)atoi(argv[++i]);
+            ap.max_spp = (uint32_t)atoi(argv[++i]);
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') rounds = (uint32_t)atoi(argv[++i]);
+        }
         if (!strcmp(argv[i], "--denoise")) {
             guide_samples = 4;
             if (i + 1 < argc && argv[i + 1][0] >= '1' && argv[i + 1][0] <= '9') guide_samples = (uint32_t)atoi(argv[++i]);
         }
     }
+    if (adaptive && !slots_given) slots = 8;  // the estimate is the spread of the path slots' means
+    if (adaptive) c.spp = (int)ap.min_spp;    // the first pass
     const char* assets = getenv("MCPT_ASSETS") ? getenv("MCPT_ASSETS") : "assets";
 
     // Scene::load + BVHAccel + EnvironmentLight (host builder)
@@ -100,6 +118,18 @@ int main(int argc, char** argv) {
         st.ms_total = (float)ms;
     } else {
         rc = mcpt_render(ctx, &st);  // batch: every tile per iteration until all pixels have spp
+        // adaptive: estimate -> budget -> render on, `rounds` times
+        for (uint32_t r = 0; adaptive && r < rounds && !rc; r++) {
+            uint64_t b3[3] = {0, 0, 0};
+            mcpt_stage_stats more{};
+            if ((rc = mcpt_film_error(ctx)) || (rc = mcpt_budget_from_error(ctx, &ap, b3)) || (rc = mcpt_render(ctx, &more))) break;
+            printf("adaptive round %u: %llu samples budgeted, largest budget %llu, %llu pixels left at their count\n", r + 1,
+                   (unsigned long long)b3[0], (unsigned long long)b3[1], (unsigned long long)b3[2]);
+            st.extend_rays += more.extend_rays;
+            st.shadow_rays += more.shadow_rays;
+            st.vis_rays += more.vis_rays;
+            st.ms_total += more.ms_total;
+        }
     }
     if (rc) { fprintf(stderr, "render: %s\n", mcpt_last_error(ctx)); return 1; }
     const uint64_t rays = per_tile ? st.extend_rays : st.extend_rays + st.shadow_rays + st.vis_rays;

@@ -316,6 +316,69 @@ int mcpt_denoised_write_png(mcpt_ctx *ctx, float exposure, const char *path);
 /* Device times (ms) of the last mcpt_guides_render (out10[0]) and of the last mcpt_film_denoise /
  * mcpt_denoise_run: the plane set-up (out10[1]) and each pass (out10[2 + i]; 0 beyond the passes run). */
 int mcpt_debug_denoise_ms(const mcpt_ctx *ctx, float *out10);
+/* ---- adaptive sampling: per-pixel sample budgets, "continue rendering", and
+ * an error estimate of the film.  A context that never calls these allocates and launches nothing
+ * for them, and renders with the kernels it always did.
+ *
+ * Composition property: every sample is keyed by (pixel, sample index) and pixels never share an
+ * accumulator, so with budget map m, pixel p of the film equals pixel p of a uniform render at
+ * spp = m[p] with the same path-slot count, bit for bit (Ld and samples), and a frame continued from
+ * n to n' samples equals a direct n' render.
+ *
+ * Known bias: a budget computed from the samples a pixel already has stops the pixel when those
+ * samples happen to agree, so the expected pixel value is no longer the plain mean's (Kirk and Arvo,
+ * "Unbiased sampling techniques for image synthesis", SIGGRAPH 1991).  Not corrected here: min_spp
+ * bounds it, and a two-pass scheme (budgets from one render, the image from a fresh one) avoids it.
+ *
+ * mcpt_set_sample_budget installs budget[y * W + x] (W*H entries, copied) in place of the uniform spp:
+ * pixel p is sampled until it has budget[p] samples, 0 = never; NULL removes the map.  A budget below
+ * a pixel's completed count stops the pixel and removes nothing.  mcpt_set_spp changes the uniform
+ * count of a live context (bounds as in mcpt_config).  Neither clears the film; both make the next
+ * mcpt_iterate / mcpt_render pick raised counts up.  Rejected with MCPT_E_INVALID, the previous map
+ * and spp staying in place: an entry above 2^19 - 256, and any call while paths are in flight (the
+ * last iteration since the film clear left live paths).  The map is keyed by film pixel: film
+ * clears, mcpt_set_path_slots, mcpt_set_tiles and mcpt_set_compact_paths keep it, mcpt_film_resize
+ * drops it.  mcpt_render sizes its batches by the largest budget.  mcpt_stage_run never uses it. */
+int mcpt_set_sample_budget(mcpt_ctx *ctx, const uint32_t *budget);
+int mcpt_sample_budget_read(mcpt_ctx *ctx, uint32_t *out);   /* W*H; MCPT_E_INVALID when no map is installed */
+int mcpt_set_spp(mcpt_ctx *ctx, int32_t spp);
+/* Error estimate from the path slots (>= 2 slots, no path in flight): slot k of a pixel holds the
+ * samples k, k + S, ... in its own accumulator (Ld_k, n_k), so the slot means are estimates from
+ * disjoint samples.  Over the slots with n_k > 0, in ascending order, K of them:
+ *   y_k = lum(Ld_k) / n_k,  ybar = (sum y_k) / K,  s2 = sum (y_k - ybar)^2 / (K - 1),  se = sqrt(s2 / K)
+ * in fp32, lum = 0.299 r + 0.587 g + 0.114 b.  Per pixel {se, ybar, (float)K, (float)n}, n = sum n_k;
+ * K < 2: se = -1 (no estimate).  Pixels that are not the context's own (outside its tile set, or
+ * scattered in by mcpt_film_unpack_tiles / mcpt_gather) get K = 0.  Non-finite radiance propagates.
+ * mcpt_film_error_read copies the last result (4*W*H floats). */
+int mcpt_film_error(mcpt_ctx *ctx);
+int mcpt_film_error_read(mcpt_ctx *ctx, float *out4);
+/* The same kernel over host images, slot-major: Ld_slots 3*w*h floats per slot, samples_slots w*h per
+ * slot, out4 4*w*h.  Needs neither a scene nor a film (the counterpart of mcpt_denoise_run). */
+int mcpt_error_run(mcpt_ctx *ctx, uint32_t w, uint32_t h, uint32_t slots, const float *Ld_slots,
+                   const uint32_t *samples_slots, float *out4);
+/* One path slot's accumulators as W x H images (3*W*H / W*H; either may be NULL), zero where the pixel
+ * is not the context's own: summed in slot order they are mcpt_film_read's film. */
+int mcpt_debug_film_read_slot(mcpt_ctx *ctx, uint32_t slot, float *Ld_rgb, uint32_t *samples);
+/* Budgets from the last mcpt_film_error result, built on the device and installed like
+ * mcpt_set_sample_budget's.  Per pixel, in fp32, with tau = target_rel_err and lo = max(n, min_spp):
+ *   r = se / (ybar + lum_floor),  q = r / tau,  want = n * (q * q)
+ *   budget = max(ceil(want), lo), or max(max_spp, lo) unless want < max_spp (the large value is never
+ *   converted); lo where r <= tau or there is no estimate (se < 0); n where r is not finite (a NaN
+ *   pixel cannot converge and is not fed); 0 for the never-rendered last row and column and for
+ *   pixels that are not the context's own.
+ * out3 (may be NULL): the sum of the budgets, the largest, and the context's pixels left at their
+ * current count.  p == NULL: the defaults.  target_rel_err > 0, min_spp <= max_spp <= 2^19 - 256. */
+typedef struct mcpt_sample_budget_params {
+    float target_rel_err;   /* tau: the standard error aimed at, relative to mean luminance + lum_floor */
+    float lum_floor;        /* default 0.01: keeps dark pixels from demanding every sample */
+    uint32_t min_spp, max_spp;
+} mcpt_sample_budget_params;
+int mcpt_sample_budget_default_params(mcpt_sample_budget_params *p);
+int mcpt_budget_from_error(mcpt_ctx *ctx, const mcpt_sample_budget_params *p, uint64_t *out3);
+/* Device bytes the context holds for adaptive sampling (0 until one of the calls above needs some),
+ * and the device times (ms) of the last error kernel (out2[0]) and budget kernel (out2[1]). */
+int64_t mcpt_debug_adaptive_bytes(const mcpt_ctx *ctx);
+int mcpt_debug_adaptive_ms(const mcpt_ctx *ctx, float *out2);
 int mcpt_sync(mcpt_ctx *ctx);
 int mcpt_device_name(mcpt_ctx *ctx, char *buf, int32_t len);
 /* diagnostics: rays of the current extension (which=0) or any-hit (which=1) queue, and the

@@ -584,6 +584,56 @@ public:
     void write_denoised_png(const std::shared_ptr<Film>& film, const std::string& path) {
         detail::check(mcpt_denoised_write_png(ctx_, film->get_exposure(), path.c_str()), ctx_, "write_denoised_png");
     }
+    // Adaptive sampling (mcpt.h): a per-pixel sample budget (W*H entries; empty: remove it) in place of
+    // the uniform spp, and the uniform spp of the live context.  Neither clears the film: the next
+    // render_frame renders on.  Call them once the film's size is the context's (after a render).
+    void set_sample_budget(const std::vector<uint32_t>& budget) {
+        if (!budget.empty()) {
+            uint32_t w = 0, h = 0;
+            detail::check(mcpt_film_size(ctx_, &w, &h), ctx_, "set_sample_budget");
+            if (budget.size() != (size_t)w * h) throw Error(MCPT_E_INVALID, "set_sample_budget: the map must hold W*H entries");
+        }
+        detail::check(mcpt_set_sample_budget(ctx_, budget.empty() ? nullptr : budget.data()), ctx_, "set_sample_budget");
+    }
+    void sample_budget(std::vector<uint32_t>& budget) {
+        uint32_t w = 0, h = 0;
+        detail::check(mcpt_film_size(ctx_, &w, &h), ctx_, "sample_budget");
+        budget.resize((size_t)w * h);
+        detail::check(mcpt_sample_budget_read(ctx_, budget.data()), ctx_, "sample_budget");
+    }
+    void set_spp(int32_t spp) {
+        detail::check(mcpt_set_spp(ctx_, spp), ctx_, "set_spp");
+        cfg_.spp = spp;
+    }
+    // The film's error estimate from the path slots (>= 2): per pixel {se, mean luminance, K, n}
+    void film_error(std::vector<float>& out4) {
+        uint32_t w = 0, h = 0;
+        detail::check(mcpt_film_size(ctx_, &w, &h), ctx_, "film_error");
+        out4.resize((size_t)w * h * 4);
+        detail::check(mcpt_film_error(ctx_), ctx_, "film_error");
+        detail::check(mcpt_film_error_read(ctx_, out4.data()), ctx_, "film_error");
+    }
+    // Render to min_spp, then `rounds` times: estimate -> budgets -> render on.  params == nullptr:
+    // the defaults.  Returns the samples budgeted by the last round.
+    uint64_t render_adaptive(const std::shared_ptr<Scene>& scene, const std::shared_ptr<Camera>& camera,
+                             const std::shared_ptr<Film>& film, const mcpt_sample_budget_params* params = nullptr,
+                             uint32_t rounds = 2) {
+        mcpt_sample_budget_params p;
+        if (params) p = *params;
+        else detail::check(mcpt_sample_budget_default_params(&p), ctx_, "render_adaptive");
+        sync(*scene, *camera, *film);
+        detail::check(mcpt_set_sample_budget(ctx_, nullptr), ctx_, "render_adaptive");
+        set_spp((int32_t)p.min_spp);
+        detail::check(mcpt_render(ctx_, &stats_), ctx_, "render_adaptive");
+        uint64_t b3[3] = {0, 0, 0};
+        for (uint32_t r = 0; r < rounds; r++) {
+            detail::check(mcpt_film_error(ctx_), ctx_, "render_adaptive");
+            detail::check(mcpt_budget_from_error(ctx_, &p, b3), ctx_, "render_adaptive");
+            detail::check(mcpt_render(ctx_, &stats_), ctx_, "render_adaptive");
+        }
+        if (display_) tonemap(*film);
+        return b3[0];
+    }
 
 private:
     // Bring the context up to date with the host objects.  Order as the reference's observer

@@ -780,7 +780,9 @@ __device__ inline uint32_t udiv_small(uint32_t n, uint32_t d, float rcp) {
 }
 
 // One shading block: logic + generate for kBlock pixels of a path slot, then the block's pushes.
-template <bool FIXED>
+// MAP: the pixel's sample budget (ShadeArgs::budget) stands in for spp.  An instantiation of its own,
+// so the no-map kernel is the code it was.
+template <bool FIXED, bool MAP>
 __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeArgs& a, int vb, const VBlk& v) {
     const DevScene& sc = a.scene;
     const int slot = (int)(v.sr & 0xffu);
@@ -840,7 +842,10 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
         const float4 n0 = ld_s(a.p.nee0 + (need_nee ? pid : 0u)), n1 = ld_s(a.p.nee1 + (need_nee ? pid : 0u));
         const uchar2 vv = reinterpret_cast<const uchar2*>(a.p.vis)[need_nee ? pid : 0u];
         bool dead = (fl & F_DEAD) != 0;
-        const uint32_t spp = (uint32_t)a.spp;
+        // the sample count the pixel renders to: the budget map's entry joins the load round above
+        uint32_t spp;
+        if constexpr (MAP) spp = a.budget[pix];  // (a plain load: every slot of the pixel reads the entry)
+        else spp = (uint32_t)a.spp;
         // this slot's sample index (slot k runs samples k, k + S, ...; S = 1: the count itself):
         // the flags word carries it, the one in progress for a live path (k_material keys its
         // draws with it) and the next one for a dead path (k_clear: the slot's first), so the
@@ -1043,7 +1048,7 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
 // (one workgroup per shading block, G = the block count) paid ~0.2 ms per launch just to dispatch
 // and retire config 2's 246K workgroups once they had all finished (the frame's last ~20
 // iterations; 64 iterations per frame).
-template <bool FIXED>
+template <bool FIXED, bool MAP>
 __global__ __launch_bounds__(kBlock) MCPT_SHADE_ATTR void k_shade(ShadeArgs a) {
     if (a.cnt->idle) return;  // the tile set is complete (an earlier iteration of the call traced no ray)
     __shared__ uint64_t s_live[kBlock / 64];
@@ -1064,7 +1069,7 @@ __global__ __launch_bounds__(kBlock) MCPT_SHADE_ATTR void k_shade(ShadeArgs a) {
         if (!((s_live[j >> 6] >> (j & 63)) & 1ull)) continue;
         // the arguments re-read per shading block (kernarg_fresh): hoisted out of the loop, the
         // struct's fields took the SGPR file and spilled (89 SGPRs, 54 -> 86 VGPRs)
-        shade_vblock<FIXED>(kernarg_fresh<ShadeArgs>(), (int)(blockIdx.x + j * G), s_vb[j]);
+        shade_vblock<FIXED, MAP>(kernarg_fresh<ShadeArgs>(), (int)(blockIdx.x + j * G), s_vb[j]);
     }
 }
 
@@ -2327,7 +2332,7 @@ int launch_geometry(int dev, LaunchGeom& g) {
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ[1][1], k_trace<4, kLdsStackDeep, false>, kTraceBlock, 0) != hipSuccess ||
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&mat0, k_material<false>, kBlock, 0) != hipSuccess ||
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&mat1, k_material<true>, kBlock, 0) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&sh0, k_shade<false>, kBlock, 0) != hipSuccess)
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&sh0, k_shade<false, false>, kBlock, 0) != hipSuccess)
         return -1;
     if (cus <= 0) cus = 256;
     per_cu = 32;
@@ -2367,10 +2372,12 @@ void launch_shade(const ShadeArgs& args, int nblocks, const LaunchGeom& g, bool 
     a.shade_vblocks = (uint32_t)nblocks;
     const uint32_t G = shade_grid((uint32_t)nblocks, g);
     if (fixed_mode) {
-        hipLaunchKernelGGL(k_shade<true>, dim3(G), dim3(kBlock), 0, s, a);
+        if (a.budget) hipLaunchKernelGGL((k_shade<true, true>), dim3(G), dim3(kBlock), 0, s, a);
+        else hipLaunchKernelGGL((k_shade<true, false>), dim3(G), dim3(kBlock), 0, s, a);
         hipLaunchKernelGGL(k_material<true>, dim3(g.mat_blocks[1]), dim3(kBlock), 0, s, a);
     } else {
-        hipLaunchKernelGGL(k_shade<false>, dim3(G), dim3(kBlock), 0, s, a);
+        if (a.budget) hipLaunchKernelGGL((k_shade<false, true>), dim3(G), dim3(kBlock), 0, s, a);
+        else hipLaunchKernelGGL((k_shade<false, false>), dim3(G), dim3(kBlock), 0, s, a);
         hipLaunchKernelGGL(k_material<false>, dim3(g.mat_blocks[0]), dim3(kBlock), 0, s, a);
     }
 }
@@ -2381,8 +2388,8 @@ void launch_shade_stage(bool material_stage, const ShadeArgs& args, int nblocks,
     a.shade_vblocks = (uint32_t)nblocks;
     if (!material_stage) {
         const uint32_t G = shade_grid((uint32_t)nblocks, g);
-        if (fixed_mode) hipLaunchKernelGGL(k_shade<true>, dim3(G), dim3(kBlock), 0, s, a);
-        else hipLaunchKernelGGL(k_shade<false>, dim3(G), dim3(kBlock), 0, s, a);
+        if (fixed_mode) hipLaunchKernelGGL((k_shade<true, false>), dim3(G), dim3(kBlock), 0, s, a);
+        else hipLaunchKernelGGL((k_shade<false, false>), dim3(G), dim3(kBlock), 0, s, a);
     } else {
         if (fixed_mode) hipLaunchKernelGGL(k_material<true>, dim3(g.mat_blocks[1]), dim3(kBlock), 0, s, a);
         else hipLaunchKernelGGL(k_material<false>, dim3(g.mat_blocks[0]), dim3(kBlock), 0, s, a);

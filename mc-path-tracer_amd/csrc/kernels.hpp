@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "device/adaptive.hpp"
 #include "device/denoise.hpp"
 #include "device/mcpt_core.hpp"
 
@@ -238,6 +239,10 @@ struct ShadeArgs {
     // evaluation (the next vertex lies beyond max_depth).  The rays are counted as the reference
     // traces them.  0: every stage as the reference runs it (mcpt_stage_run always)
     int skip;
+    // Per-pixel sample budget of the W x H film (mcpt_set_sample_budget; nullptr: none).  Where it is
+    // installed, launch_shade runs k_shade's map instantiation, which reads budget[pixel] in place of
+    // spp; the no-map instantiation never looks at this field.
+    const uint32_t* budget;
 };
 // k_primary_build: the table of a W x H film.  stats: [0] pixels with a list, [1] overflow pixels.
 struct PrimaryBuildArgs {
@@ -411,5 +416,40 @@ void launch_denoise_pass(const DenoiseArgs& a, int lds_max_stride, hipStream_t s
 void launch_denoise_prep(const DenoisePrepArgs& a, hipStream_t s);
 void launch_guide_rays(const GuideArgs& a, hipStream_t s);
 void launch_guide_accum(const GuideArgs& a, hipStream_t s);
+
+// ---- adaptive sampling (adaptive.hip) ----
+// Which accumulator holds a film pixel.  own == nullptr: every pixel is the caller's and pixel o's
+// accumulator is o (mcpt_error_run).  Else own[film tile] < 0: not the context's (outside its tile
+// set, or scattered in from another context); >= 0: the tile's place in the compact layout's order
+// (accumulator = place * tile pixels + the pixel's index in its tile), ignored in the full layout
+// (accumulator = pixel id).
+struct OwnMap {
+    const int32_t* own;
+    int compact, tile_w, tile_h, W, H;
+};
+// k_film_error: out[o] = film_error_pixel of film pixel o over `slots` accumulators `stride` apart
+struct FilmErrorArgs {
+    const float4* Ld; const uint32_t* samples; size_t stride; int slots;
+    OwnMap m;
+    float4* out;
+};
+// k_budget: budget[o] = budget_pixel(err[o]); cnt[0] += the budgets, cnt[1] = max, cnt[2] += pixels of
+// the context whose budget equals their sample count
+struct BudgetArgs {
+    const float4* err;
+    OwnMap m;
+    mcpt::BudgetParams p;
+    uint32_t* budget;
+    unsigned long long* cnt;
+};
+// k_slot_image: one slot's accumulators as W x H images (zero where the pixel is not the context's)
+struct SlotImageArgs {
+    const float4* Ld; const uint32_t* samples;  // the slot's first accumulator
+    OwnMap m;
+    float4* out_Ld; uint32_t* out_samples;
+};
+void launch_film_error(const FilmErrorArgs& a, hipStream_t s);
+void launch_budget(const BudgetArgs& a, hipStream_t s);
+void launch_slot_image(const SlotImageArgs& a, hipStream_t s);
 
 }  // namespace mcpt_dev

@@ -140,6 +140,22 @@ struct mcpt_ctx {
     float4 *dn_col[2] = {nullptr, nullptr}, *dn_gd = nullptr, *dn_al = nullptr;
     int dn_result = -1;
     float guides_ms = 0.f, dn_ms[9] = {};  // device times of the last guide pass / filter set-up and passes
+    // Adaptive sampling, all keyed by film pixel and allocated by the first call
+    // that needs them: budget, the per-pixel sample budget k_shade reads in place of cfg.spp while
+    // budget_on (budget_max: its largest entry, which sizes mcpt_render's batches); err4, the last
+    // mcpt_film_error result {se, mean, K, n} (err_ok); own_map, the film tiles' ownership (OwnMap) as
+    // of the last call that used it; bud_cnt, k_budget's three counters.  Film clears, slot, tile-set
+    // and layout changes keep them; mcpt_film_resize frees them.
+    uint32_t* budget = nullptr;
+    bool budget_on = false;
+    uint32_t budget_max = 0;
+    float4* err4 = nullptr;
+    bool err_ok = false;
+    int32_t* own_map = nullptr;
+    size_t own_map_cap = 0;
+    unsigned long long* bud_cnt = nullptr;
+    size_t adaptive_bytes = 0;     // device bytes held by the above (mcpt_debug_adaptive_bytes)
+    float err_ms = 0.f, budget_ms = 0.f;  // device times of the last k_film_error / k_budget
 };
 
 static int set_err(mcpt_ctx* c, int rc, const std::string& msg) {
@@ -175,6 +191,20 @@ static void denoise_free(mcpt_ctx* c) {
     c->guides_ok = false;
     c->dn_result = -1;
 }
+static void adaptive_free(mcpt_ctx* c) {
+    if (c->budget) (void)hipFree(c->budget);
+    if (c->err4) (void)hipFree(c->err4);
+    if (c->own_map) (void)hipFree(c->own_map);
+    if (c->bud_cnt) (void)hipFree(c->bud_cnt);
+    c->budget = nullptr;
+    c->err4 = nullptr;
+    c->own_map = nullptr;
+    c->bud_cnt = nullptr;
+    c->own_map_cap = 0;
+    c->budget_on = c->err_ok = false;
+    c->budget_max = 0;
+    c->adaptive_bytes = 0;
+}
 static void free_list(std::vector<void*>& v) {
     for (void* q : v)
         if (q) (void)hipFree(q);
@@ -195,6 +225,20 @@ static int dupload(mcpt_ctx* c, std::vector<void*>& list, T** out, const T* src,
     int rc = dalloc(c, list, out, count);
     if (rc) return rc;
     if (count) HIPCHK(c, hipMemcpy(*out, src, count * sizeof(T), hipMemcpyHostToDevice));
+    return MCPT_OK;
+}
+
+// device memory of adaptive sampling, counted (mcpt_debug_adaptive_bytes); a buffer that exists is kept
+template <class T>
+static int adaptive_alloc(mcpt_ctx* c, T** out, size_t count) {
+    if (*out) return MCPT_OK;
+    const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
+    hipError_t e = hipMalloc((void**)out, bytes);
+    if (e != hipSuccess) {
+        *out = nullptr;
+        return set_err(c, MCPT_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    }
+    c->adaptive_bytes += bytes;
     return MCPT_OK;
 }
 
@@ -262,6 +306,7 @@ void mcpt_destroy(mcpt_ctx* c) {
     if (c->cam_tab) (void)hipFree(c->cam_tab);
     prim_free(c);
     denoise_free(c);
+    adaptive_free(c);
     for (auto e : c->events) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1122,7 +1167,8 @@ static int alloc_film_state(mcpt_ctx* c) {
     return MCPT_OK;
 }
 
-int mcpt_film_resize(mcpt_ctx* c, uint32_t w, uint32_t h, uint32_t tw, uint32_t th) {
+// (mcpt_set_path_slots re-sizes the full layout's film through this: the sample budget stays)
+static int film_resize(mcpt_ctx* c, uint32_t w, uint32_t h, uint32_t tw, uint32_t th) {
     if (!c || w == 0 || h == 0 || tw == 0 || th == 0) return set_err(c, MCPT_E_INVALID, "bad film size");
     if ((uint64_t)w * h >= (1ull << 31)) return set_err(c, MCPT_E_INVALID, "film too large");
     if ((uint64_t)tw * th > (1ull << 26)) return set_err(c, MCPT_E_INVALID, "tile too large");
@@ -1148,6 +1194,15 @@ int mcpt_film_resize(mcpt_ctx* c, uint32_t w, uint32_t h, uint32_t tw, uint32_t 
     if ((rc = alloc_film_state(c))) return rc;
     c->P = (size_t)w * h;
     return mcpt_film_clear(c);
+}
+int mcpt_film_resize(mcpt_ctx* c, uint32_t w, uint32_t h, uint32_t tw, uint32_t th) {
+    if (!c || w == 0 || h == 0 || tw == 0 || th == 0) return set_err(c, MCPT_E_INVALID, "bad film size");
+    if (c->budget || c->err4 || c->own_map || c->bud_cnt) {  // the sample budget and the estimate belong to the film size
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        adaptive_free(c);
+    }
+    return film_resize(c, w, h, tw, th);
 }
 
 // A new tile set.  In the compact layout the path state follows the tile set: it is re-allocated and
@@ -1380,6 +1435,7 @@ static int enqueue_iteration(mcpt_ctx* c, size_t evbase, bool timing, const int2
     sa.cnt = c->cnt;
     sa.blk_done = c->blk_done_off ? nullptr : c->blk_done;
     sa.skip = c->skip_discarded ? 1 : 0;
+    sa.budget = c->budget_on ? c->budget : nullptr;
     if (int rc = cam_table(c, c->W, c->H, &sa.cam_px, &sa.cam_dir)) return rc;
     prim_table(c, sa);
     const int bpt = shade_blocks_per_tile((int)(c->tile_w * c->tile_h), (int)c->slots);
@@ -1531,14 +1587,16 @@ int mcpt_render(mcpt_ctx* c, mcpt_stage_stats* st) {
     int rc = check_ready(c);
     if (rc) return rc;
     mcpt_stage_stats acc{}, one{};
-    const uint64_t cap = (uint64_t)(c->cfg.spp + 1) * (uint64_t)(c->cfg.max_depth + 2) + 16;
+    // the largest sample count in force: the budget map's maximum where one is installed
+    const uint64_t spp = c->budget_on ? (uint64_t)c->budget_max : (uint64_t)c->cfg.spp;
+    const uint64_t cap = (spp + 1) * (uint64_t)(c->cfg.max_depth + 2) + 16;
     uint64_t done = 0;
     // Iterations per batch (one host synchronisation each).  Once the film is done, the rest of a
     // batch are no-op launches (~24 us per iteration, mostly dispatching k_shade's grid), so the
     // first batch is sized to the expected frame -- samples per path slot x (max depth + 1)
     // iterations, the lockstep schedule of paths that all start together -- and later ones are
     // short.  (Config 2 at N = 8: 12 iterations of work ran in a batch of 32.)
-    const uint64_t expect = (uint64_t)((c->cfg.spp + c->slots - 1) / c->slots) * (uint64_t)(c->cfg.max_depth + 1);
+    const uint64_t expect = ((spp + c->slots - 1) / c->slots) * (uint64_t)(c->cfg.max_depth + 1);
     for (;;) {
         const uint32_t batch = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(8, expect > done ? expect - done : 0));
         if ((rc = run_iterations(c, batch, &one))) return rc;
@@ -1926,11 +1984,11 @@ int mcpt_set_path_slots(mcpt_ctx* c, uint32_t slots) {
         c->P = P;
         return mcpt_film_clear(c);
     }
-    int rc = mcpt_film_resize(c, c->W, c->H, c->tile_w, c->tile_h);  // clears the film
+    int rc = film_resize(c, c->W, c->H, c->tile_w, c->tile_h);  // clears the film
     if (rc != MCPT_OK) {  // e.g. out of memory: back to the old slot count and its (cleared) film
         const std::string err = c->err;
         c->slots = old;
-        (void)mcpt_film_resize(c, c->W, c->H, c->tile_w, c->tile_h);
+        (void)film_resize(c, c->W, c->H, c->tile_w, c->tile_h);
         return set_err(c, rc, err);
     }
     return MCPT_OK;
@@ -2574,6 +2632,251 @@ int mcpt_debug_denoise_ms(const mcpt_ctx* c, float* out10) {
     if (!c || !out10) return MCPT_E_INVALID;
     out10[0] = c->guides_ms;
     for (int i = 0; i < 9; i++) out10[1 + i] = c->dn_ms[i];
+    return MCPT_OK;
+}
+
+// ---- adaptive sampling ----
+
+// Whether the last iteration since the film clear left live paths (the counters' host copy)
+static int paths_in_flight(mcpt_ctx* c, bool* live) {
+    if (!c->totals_ok) {
+        HIPCHK(c, hipMemcpyAsync(c->cnt_host, c->cnt, sizeof(CounterBlock), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->totals = *c->cnt_host;
+        c->totals_ok = true;
+    }
+    *live = c->totals.last_live != 0;
+    return MCPT_OK;
+}
+// What a finished frame leaves behind that would keep raised sample counts from being picked up: the
+// k_shade block done flags and the counter block's idle word (run_iterations resets the latter per
+// call too).  The film, the flags words' next sample indices and the ray counters stay.
+static int frame_done_reset(mcpt_ctx* c) {
+    if (c->blk_done) HIPCHK(c, hipMemsetAsync(c->blk_done, 0, c->blk_done_n, c->stream));
+    HIPCHK(c, hipMemsetAsync(&c->cnt->idle, 0, sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MCPT_OK;
+}
+// The film tiles' ownership for the current tile set and layout (OwnMap), uploaded
+static int own_map_build(mcpt_ctx* c, OwnMap* m) {
+    const uint32_t ntx = (c->W + c->tile_w - 1) / c->tile_w, nty = (c->H + c->tile_h - 1) / c->tile_h;
+    std::vector<int32_t> own((size_t)ntx * nty, -1);
+    for (size_t i = 0; i < c->tiles_h.size(); i++) own[(size_t)c->tiles_h[i].y * ntx + (size_t)c->tiles_h[i].x] = (int32_t)i;
+    for (const int2& t : c->unpacked) own[(size_t)t.y * ntx + (size_t)t.x] = -1;  // another context's pixels
+    if (own.size() > c->own_map_cap) {
+        if (c->own_map) {
+            (void)hipFree(c->own_map);
+            c->adaptive_bytes -= std::max<size_t>(c->own_map_cap * sizeof(int32_t), 16);
+            c->own_map = nullptr;
+            c->own_map_cap = 0;
+        }
+        int rc = adaptive_alloc(c, &c->own_map, own.size());
+        if (rc) return rc;
+        c->own_map_cap = own.size();
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(c->own_map, own.data(), own.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    *m = OwnMap{c->own_map, c->compact ? 1 : 0, (int)c->tile_w, (int)c->tile_h, (int)c->W, (int)c->H};
+    return MCPT_OK;
+}
+
+int mcpt_set_sample_budget(mcpt_ctx* c, const uint32_t* budget) {
+    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    HIPCHK(c, hipSetDevice(c->device));
+    bool live = false;
+    int rc = paths_in_flight(c, &live);
+    if (rc) return rc;
+    if (live) return set_err(c, MCPT_E_INVALID, "sample budget: paths are in flight (finish the render or clear the film)");
+    uint32_t mx = 0;
+    if (budget) {
+        for (size_t i = 0; i < c->P; i++) mx = std::max(mx, budget[i]);
+        if (mx > kMaxSpp - 256) return set_err(c, MCPT_E_INVALID, "sample budget: an entry exceeds 2^19 - 256");
+        if ((rc = adaptive_alloc(c, &c->budget, c->P))) return rc;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpy(c->budget, budget, c->P * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    c->budget_on = budget != nullptr;
+    c->budget_max = mx;
+    return frame_done_reset(c);
+}
+
+int mcpt_sample_budget_read(mcpt_ctx* c, uint32_t* out) {
+    if (!c || !out) return set_err(c, MCPT_E_INVALID, "null argument");
+    if (!c->budget_on) return set_err(c, MCPT_E_INVALID, "no sample budget installed");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, c->budget, c->P * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return MCPT_OK;
+}
+
+int mcpt_set_spp(mcpt_ctx* c, int32_t spp) {
+    if (!c) return MCPT_E_INVALID;
+    if (spp < 0 || (uint32_t)spp > kMaxSpp - 256) return set_err(c, MCPT_E_INVALID, "spp must be 0..2^19-256");
+    if (c->P) {
+        HIPCHK(c, hipSetDevice(c->device));
+        bool live = false;
+        int rc = paths_in_flight(c, &live);
+        if (rc) return rc;
+        if (live) return set_err(c, MCPT_E_INVALID, "set_spp: paths are in flight (finish the render or clear the film)");
+    }
+    c->cfg.spp = spp;
+    return c->P ? frame_done_reset(c) : MCPT_OK;
+}
+
+int mcpt_film_error(mcpt_ctx* c) {
+    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    if (c->slots < 2) return set_err(c, MCPT_E_INVALID, "film error: needs at least 2 path slots (mcpt_set_path_slots)");
+    HIPCHK(c, hipSetDevice(c->device));
+    bool live = false;
+    int rc = paths_in_flight(c, &live);
+    if (rc) return rc;
+    if (live) return set_err(c, MCPT_E_INVALID, "film error: paths are in flight");
+    if ((rc = adaptive_alloc(c, &c->err4, c->P))) return rc;
+    FilmErrorArgs a{};
+    if ((rc = own_map_build(c, &a.m))) return rc;
+    a.Ld = c->p.Ld;
+    a.samples = c->p.samples;
+    a.stride = c->npx;
+    a.slots = (int)c->slots;
+    a.out = c->err4;
+    c->err_ok = false;
+    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
+    launch_film_error(a, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev(c, 1), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipEventElapsedTime(&c->err_ms, c->events[0], c->events[1]));
+    c->err_ok = true;
+    return MCPT_OK;
+}
+
+int mcpt_film_error_read(mcpt_ctx* c, float* out4) {
+    if (!c || !out4) return set_err(c, MCPT_E_INVALID, "null argument");
+    if (!c->err_ok) return set_err(c, MCPT_E_INVALID, "no film error estimate (call mcpt_film_error first)");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out4, c->err4, c->P * sizeof(float4), hipMemcpyDeviceToHost));
+    return MCPT_OK;
+}
+
+int mcpt_error_run(mcpt_ctx* c, uint32_t w, uint32_t h, uint32_t slots, const float* Ld_slots, const uint32_t* samples_slots,
+                   float* out4) {
+    if (!c || !Ld_slots || !samples_slots || !out4) return set_err(c, MCPT_E_INVALID, "error run: null argument");
+    if (w == 0 || h == 0 || slots == 0 || slots > 256 || (uint64_t)w * h * slots >= (1ull << 28))
+        return set_err(c, MCPT_E_INVALID, "error run: bad image size or slot count");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = (size_t)w * h;
+    std::vector<float4> L4(n * slots);
+    for (size_t i = 0; i < n * slots; i++) L4[i] = make_float4(Ld_slots[3 * i], Ld_slots[3 * i + 1], Ld_slots[3 * i + 2], 0.f);
+    free_list(c->tmp_bufs);
+    auto& L = c->tmp_bufs;
+    float4 *d_L, *d_out;
+    uint32_t* d_s;
+    int rc;
+    if ((rc = dupload(c, L, &d_L, L4.data(), n * slots)) || (rc = dupload(c, L, &d_s, samples_slots, n * slots)) ||
+        (rc = dalloc(c, L, &d_out, n))) {
+        free_list(L);
+        return rc;
+    }
+    FilmErrorArgs a{};
+    a.m = OwnMap{nullptr, 0, (int)w, (int)h, (int)w, (int)h};
+    a.Ld = d_L;
+    a.samples = d_s;
+    a.stride = n;
+    a.slots = (int)slots;
+    a.out = d_out;
+    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
+    launch_film_error(a, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev(c, 1), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipEventElapsedTime(&c->err_ms, c->events[0], c->events[1]));
+    HIPCHK(c, hipMemcpy(out4, d_out, n * sizeof(float4), hipMemcpyDeviceToHost));
+    free_list(L);
+    return MCPT_OK;
+}
+
+int mcpt_debug_film_read_slot(mcpt_ctx* c, uint32_t slot, float* Ld, uint32_t* samples) {
+    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    if (slot >= c->slots) return set_err(c, MCPT_E_INVALID, "slot out of range");
+    HIPCHK(c, hipSetDevice(c->device));
+    SlotImageArgs a{};
+    int rc = own_map_build(c, &a.m);
+    if (rc) return rc;
+    free_list(c->tmp_bufs);
+    auto& L = c->tmp_bufs;
+    if ((rc = dalloc(c, L, &a.out_Ld, c->P)) || (rc = dalloc(c, L, &a.out_samples, c->P))) {
+        free_list(L);
+        return rc;
+    }
+    a.Ld = c->p.Ld + (size_t)slot * c->npx;
+    a.samples = c->p.samples + (size_t)slot * c->npx;
+    launch_slot_image(a, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (Ld) {
+        std::vector<float4> tmp(c->P);
+        HIPCHK(c, hipMemcpy(tmp.data(), a.out_Ld, c->P * sizeof(float4), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < c->P; i++) { Ld[3 * i] = tmp[i].x; Ld[3 * i + 1] = tmp[i].y; Ld[3 * i + 2] = tmp[i].z; }
+    }
+    if (samples) HIPCHK(c, hipMemcpy(samples, a.out_samples, c->P * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    free_list(L);
+    return MCPT_OK;
+}
+
+int mcpt_sample_budget_default_params(mcpt_sample_budget_params* p) {
+    if (!p) return MCPT_E_INVALID;
+    // target_rel_err: see DESIGN.md section 11 for the rows it was chosen from
+    p->target_rel_err = 0.05f;
+    p->lum_floor = 0.01f;
+    p->min_spp = 32;
+    p->max_spp = 256;
+    return MCPT_OK;
+}
+
+int mcpt_budget_from_error(mcpt_ctx* c, const mcpt_sample_budget_params* pp, uint64_t* out3) {
+    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    mcpt_sample_budget_params p;
+    if (pp) p = *pp;
+    else (void)mcpt_sample_budget_default_params(&p);
+    if (!(p.target_rel_err > 0.f) || !(p.target_rel_err <= 3.402823466e+38f) || !(p.lum_floor >= 0.f) ||
+        !(p.lum_floor <= 3.402823466e+38f) || p.min_spp > p.max_spp || p.max_spp > kMaxSpp - 256)
+        return set_err(c, MCPT_E_INVALID, "budget: bad parameters (target_rel_err > 0, lum_floor >= 0, min_spp <= max_spp <= 2^19-256)");
+    if (!c->err_ok) return set_err(c, MCPT_E_INVALID, "budget: no film error estimate (call mcpt_film_error first)");
+    HIPCHK(c, hipSetDevice(c->device));
+    bool live = false;
+    int rc = paths_in_flight(c, &live);
+    if (rc) return rc;
+    if (live) return set_err(c, MCPT_E_INVALID, "budget: paths are in flight");
+    if ((rc = adaptive_alloc(c, &c->budget, c->P)) || (rc = adaptive_alloc(c, &c->bud_cnt, 4))) return rc;
+    BudgetArgs a{};
+    if ((rc = own_map_build(c, &a.m))) return rc;
+    a.err = c->err4;
+    a.p = mcpt::BudgetParams{p.target_rel_err, p.lum_floor, p.min_spp, p.max_spp};
+    a.budget = c->budget;
+    a.cnt = c->bud_cnt;
+    HIPCHK(c, hipMemsetAsync(c->bud_cnt, 0, 4 * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
+    launch_budget(a, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev(c, 1), c->stream));
+    unsigned long long cnt[4] = {};
+    HIPCHK(c, hipMemcpyAsync(cnt, c->bud_cnt, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipEventElapsedTime(&c->budget_ms, c->events[0], c->events[1]));
+    // (an entry past a pixel's n > max_spp is that n: still a count the film holds, below 2^19)
+    c->budget_on = true;
+    c->budget_max = (uint32_t)cnt[1];
+    if (out3) { out3[0] = cnt[0]; out3[1] = cnt[1]; out3[2] = cnt[2]; }
+    return frame_done_reset(c);
+}
+
+int64_t mcpt_debug_adaptive_bytes(const mcpt_ctx* c) { return c ? (int64_t)c->adaptive_bytes : (int64_t)MCPT_E_INVALID; }
+
+int mcpt_debug_adaptive_ms(const mcpt_ctx* c, float* out2) {
+    if (!c || !out2) return MCPT_E_INVALID;
+    out2[0] = c->err_ms;
+    out2[1] = c->budget_ms;
     return MCPT_OK;
 }
 

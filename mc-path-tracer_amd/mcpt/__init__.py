@@ -79,6 +79,10 @@ class DenoiseParams(C.Structure):  # mcpt_denoise_params
                 ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float)]
 
 
+class SampleBudgetParams(C.Structure):  # mcpt_sample_budget_params
+    _fields_ = [("target_rel_err", C.c_float), ("lum_floor", C.c_float), ("min_spp", C.c_uint32), ("max_spp", C.c_uint32)]
+
+
 class PathView(C.Structure):  # mcpt_path_view: path state at the shading stages' boundary
     _fields_ = [("film_w", C.c_uint32), ("film_h", C.c_uint32), ("flags", _u), ("samples", _u), ("hit_tri", _i),
                 ("ray_o", _f), ("ray_d", _f), ("beta", _f), ("nee0", _f), ("nee1", _f),
@@ -147,6 +151,17 @@ ABI = {
     "mcpt_denoised_tonemap_rgba8": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(C.c_uint8)]),
     "mcpt_denoised_write_png": (C.c_int, [C.c_void_p, C.c_float, C.c_char_p]),
     "mcpt_debug_denoise_ms": (C.c_int, [C.c_void_p, _f]),
+    "mcpt_set_sample_budget": (C.c_int, [C.c_void_p, _u]),
+    "mcpt_sample_budget_read": (C.c_int, [C.c_void_p, _u]),
+    "mcpt_set_spp": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mcpt_film_error": (C.c_int, [C.c_void_p]),
+    "mcpt_film_error_read": (C.c_int, [C.c_void_p, _f]),
+    "mcpt_error_run": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, _f, _u, _f]),
+    "mcpt_debug_film_read_slot": (C.c_int, [C.c_void_p, C.c_uint32, _f, _u]),
+    "mcpt_sample_budget_default_params": (C.c_int, [C.POINTER(SampleBudgetParams)]),
+    "mcpt_budget_from_error": (C.c_int, [C.c_void_p, C.POINTER(SampleBudgetParams), C.POINTER(C.c_uint64)]),
+    "mcpt_debug_adaptive_bytes": (C.c_int64, [C.c_void_p]),
+    "mcpt_debug_adaptive_ms": (C.c_int, [C.c_void_p, _f]),
     "mcpt_sync": (C.c_int, [C.c_void_p]),
     "mcpt_device_name": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
     "mcpt_debug_queue_rays": (C.c_int, [C.c_void_p, C.c_int, _f, _f, _u]),
@@ -597,6 +612,80 @@ class PathTracer:
         self._ck(lib().mcpt_debug_denoise_ms(self.h, v))
         return {"guides": float(v[0]), "prepare": float(v[1]), "passes": [float(x) for x in v[2:]]}
 
+    # ---- adaptive sampling ----
+    def set_sample_budget(self, budget=None):
+        """Per-pixel sample budget ((H, W) uint32; mcpt_set_sample_budget) in place of the uniform spp;
+        None removes it.  The film is not cleared: the next render() picks raised budgets up."""
+        if budget is None:
+            self._ck(lib().mcpt_set_sample_budget(self.h, None))
+            return
+        b = np.ascontiguousarray(budget, np.uint32)
+        if b.shape != (self.H, self.W):
+            raise ValueError(f"budget must be ({self.H}, {self.W}), got {b.shape}")
+        self._ck(lib().mcpt_set_sample_budget(self.h, b.ctypes.data_as(_u)))
+
+    def sample_budget(self):
+        """The installed budget map as (H, W) uint32 (mcpt_sample_budget_read; raises when there is none)."""
+        out = np.zeros((self.H, self.W), np.uint32)
+        self._ck(lib().mcpt_sample_budget_read(self.h, out.ctypes.data_as(_u)))
+        return out
+
+    def set_spp(self, spp):
+        """Uniform sample count of the live context (mcpt_set_spp); the film is kept, so a following
+        render() continues the frame."""
+        self._ck(lib().mcpt_set_spp(self.h, int(spp)))
+        self.cfg.spp = int(spp)
+
+    def film_error(self):
+        """Error estimate from the path slots (mcpt_film_error + mcpt_film_error_read): (H, W, 4)
+        float32 {standard error of the mean luminance (-1: none), mean luminance, slots with samples,
+        samples}."""
+        self._ck(lib().mcpt_film_error(self.h))
+        out = np.zeros((self.H, self.W, 4), np.float32)
+        self._ck(lib().mcpt_film_error_read(self.h, fptr(out)))
+        return out
+
+    def film_slot(self, slot):
+        """One path slot's accumulators as images (mcpt_debug_film_read_slot): (H, W, 3) Ld, (H, W) samples."""
+        Ld = np.zeros((self.H, self.W, 3), np.float32)
+        s = np.zeros((self.H, self.W), np.uint32)
+        self._ck(lib().mcpt_debug_film_read_slot(self.h, slot, fptr(Ld), s.ctypes.data_as(_u)))
+        return Ld, s
+
+    def budget_from_error(self, **params) -> dict:
+        """Budgets from the last film_error(), installed (mcpt_budget_from_error); keyword arguments
+        override the default parameters (target_rel_err, lum_floor, min_spp, max_spp)."""
+        p = sample_budget_params(**params)
+        v = (C.c_uint64 * 3)()
+        self._ck(lib().mcpt_budget_from_error(self.h, C.byref(p), v))
+        return dict(total=int(v[0]), max=int(v[1]), unchanged=int(v[2]))
+
+    def render_adaptive(self, target=None, min_spp=None, max_spp=None, rounds=2):
+        """Render to min_spp, then `rounds` times: estimate the film's error, build budgets that aim at
+        a relative standard error `target` within [min_spp, max_spp], and render on.  Needs >= 2 path
+        slots.  Returns the render() statistics of every pass and the budget summaries."""
+        kw = {k: v for k, v in (("target_rel_err", target), ("min_spp", min_spp), ("max_spp", max_spp)) if v is not None}
+        p = sample_budget_params(**kw)
+        self.set_sample_budget(None)
+        self.set_spp(p.min_spp)
+        stats, budgets = [self.render()], []
+        for _ in range(rounds):
+            self._ck(lib().mcpt_film_error(self.h))
+            budgets.append(self.budget_from_error(**kw))
+            stats.append(self.render())
+        return stats, budgets
+
+    @property
+    def adaptive_bytes(self) -> int:
+        """Device bytes held for adaptive sampling (mcpt_debug_adaptive_bytes)."""
+        return int(lib().mcpt_debug_adaptive_bytes(self.h))
+
+    def adaptive_ms(self) -> dict:
+        """Device times of the last error and budget kernels (mcpt_debug_adaptive_ms)."""
+        v = (C.c_float * 2)()
+        self._ck(lib().mcpt_debug_adaptive_ms(self.h, v))
+        return {"error": float(v[0]), "budget": float(v[1])}
+
     def trace_closest(self, ro, rd, steps=False):
         ro = np.ascontiguousarray(ro, np.float32).reshape(-1, 3)
         rd = np.ascontiguousarray(rd, np.float32).reshape(-1, 3)
@@ -693,6 +782,28 @@ def denoise_params(**kw) -> DenoiseParams:
             raise TypeError(f"unknown denoise parameter {k!r}")
         setattr(p, k, v)
     return p
+
+
+def sample_budget_params(**kw) -> SampleBudgetParams:
+    """mcpt_sample_budget_default_params with keyword overrides."""
+    p = SampleBudgetParams()
+    _check(lib().mcpt_sample_budget_default_params(C.byref(p)))
+    for k, v in kw.items():
+        if k not in dict(SampleBudgetParams._fields_):
+            raise TypeError(f"unknown sample budget parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def error_run(pt, Ld_slots, samples_slots):
+    """mcpt_error_run on PathTracer pt: the error estimate over host slot images ((S, H, W, 3) radiance
+    sums and (S, H, W) sample counts); returns (H, W, 4) float32."""
+    L = np.ascontiguousarray(Ld_slots, np.float32)
+    S, H, W = L.shape[:3]
+    n = np.ascontiguousarray(samples_slots, np.uint32).reshape(S, H, W)
+    out = np.zeros((H, W, 4), np.float32)
+    _check(lib().mcpt_error_run(pt.h, W, H, S, fptr(L), n.ctypes.data_as(_u), fptr(out)), pt.h)
+    return out
 
 
 def denoise_run(pt, rgb, albedo, normal, depth, samples=None, **params):
