@@ -3,10 +3,13 @@
 // INTEGRATION.md): build a BASELINE config scene with the host builder, upload it,
 // run the wavefront iterations until every pixel has its samples, write PNG + PFM.
 //
-//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--adaptive <target> <min> <max> [rounds]]
+//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]]
 //
 // --denoise renders the first-hit guide buffers (default 4 guide samples per pixel), filters the film
 // with the default parameters and writes <out_prefix>_denoised.png beside the raw image.
+// --denoise-guided does the same with the variance-guided filter and writes
+// <out_prefix>_denoised_guided.png; its variance comes from the path slots, so it needs --slots >= 2
+// (4 if --slots is not given).  It combines with --denoise and with --adaptive.
 // --adaptive renders every pixel to <min> samples, then [rounds] (default 2) times estimates the
 // film's error from the path slots, builds per-pixel budgets that aim at the relative standard error
 // <target> within [<min>, <max>] and renders on; it needs --slots >= 2 (8 if
@@ -26,7 +29,7 @@ struct Cfg { int w, h, spp, depth; float pos[3], pitch; const char* env; };
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--adaptive <target> <min> <max> [rounds]]\n", argv[0]);
+        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]]\n", argv[0]);
         return 2;
     }
     const Cfg cfgs[6] = {{0, 0, 0, 0, {0, 0, 0}, 0, ""},
@@ -41,7 +44,7 @@ int main(int argc, char** argv) {
     if (argc > 2 && argv[2][0] != '-') c.spp = atoi(argv[2]);
     std::string out = (argc > 3 && argv[3][0] != '-') ? argv[3] : "mcpt_render";
     bool gpu_bvh = false, ref_bvh = false, fixed = false, per_tile = false;
-    uint32_t slots = 1, guide_samples = 0;  // guide_samples > 0: denoise
+    uint32_t slots = 1, guide_samples = 0, guided_samples = 0;  // guide_samples / guided_samples > 0: denoise [guided]
     bool adaptive = false, slots_given = false;
     mcpt_sample_budget_params ap;
     mcpt_sample_budget_default_params(&ap);
@@ -64,7 +67,12 @@ int main(int argc, char** argv) {
             guide_samples = 4;
             if (i + 1 < argc && argv[i + 1][0] >= '1' && argv[i + 1][0] <= '9') guide_samples = (uint32_t)atoi(argv[++i]);
         }
+        if (!strcmp(argv[i], "--denoise-guided")) {
+            guided_samples = 4;
+            if (i + 1 < argc && argv[i + 1][0] >= '1' && argv[i + 1][0] <= '9') guided_samples = (uint32_t)atoi(argv[++i]);
+        }
     }
+    if (guided_samples && !slots_given) slots = 4;  // the variance is the spread of the path slots' means
     if (adaptive && !slots_given) slots = 8;  // the estimate is the spread of the path slots' means
     if (adaptive) c.spp = (int)ap.min_spp;    // the first pass
     const char* assets = getenv("MCPT_ASSETS") ? getenv("MCPT_ASSETS") : "assets";
@@ -145,6 +153,14 @@ int main(int argc, char** argv) {
         if ((rc = mcpt_guides_render(ctx, guide_samples)) || (rc = mcpt_film_denoise(ctx, nullptr)) ||
             (rc = mcpt_denoised_write_png(ctx, 1.f, (out + "_denoised.png").c_str()))) {
             fprintf(stderr, "denoise: %s\n", mcpt_last_error(ctx));
+            return 1;
+        }
+    }
+    if (guided_samples) {  // film + its error estimate -> guides -> guided filter -> display
+        if (((guided_samples != guide_samples) && (rc = mcpt_guides_render(ctx, guided_samples))) ||
+            (rc = mcpt_film_denoise_guided(ctx, nullptr)) ||
+            (rc = mcpt_denoised_write_png(ctx, 1.f, (out + "_denoised_guided.png").c_str()))) {
+            fprintf(stderr, "denoise-guided: %s\n", mcpt_last_error(ctx));
             return 1;
         }
     }

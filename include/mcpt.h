@@ -316,6 +316,40 @@ int mcpt_denoised_write_png(mcpt_ctx *ctx, float exposure, const char *path);
 /* Device times (ms) of the last mcpt_guides_render (out10[0]) and of the last mcpt_film_denoise /
  * mcpt_denoise_run: the plane set-up (out10[1]) and each pass (out10[2 + i]; 0 beyond the passes run). */
 int mcpt_debug_denoise_ms(const mcpt_ctx *ctx, float *out10);
+/* ---- variance-guided denoising: the a-trous filter above steered by a
+ * per-pixel variance of the mean luminance, as SVGF's spatial filter is (Schied et al. 2017, 4.4).
+ * A second path beside the plain one: a context that never calls these allocates and launches
+ * nothing for them, and mcpt_film_denoise / mcpt_denoise_run compute what they always did.
+ *
+ * Each pixel carries a variance v (-1: unknown) and its luminance l.  In pass i a pixel p with a
+ * variance replaces the plain filter's colour term by
+ *   |l(p) - l(q)| / (sigma_lum sqrt(vt(p)) + lum_eps)
+ * with vt the 3 x 3 Gaussian ({1/4, 1/8, 1/16}, stride 1) of the known variances around p, and its
+ * variance becomes sum w^2 v(q) / (sum w)^2 (v(p) for a tap without one).  A pixel without a variance
+ * takes the plain term with sigma_color 2^-i and stays without one.  With lum_eps = 0 the result is
+ * equivariant under radiance scaling by powers of two, and a pixel of zero variance is left alone. */
+typedef struct mcpt_denoise_guided_params {
+    int32_t passes;        /* 1..8 */
+    float sigma_lum;       /* > 0 */
+    float lum_eps;         /* >= 0 */
+    float sigma_color;     /* the plain term of pixels without a variance */
+    float sigma_normal, sigma_albedo, sigma_depth;
+} mcpt_denoise_guided_params;
+int mcpt_denoise_guided_default_params(mcpt_denoise_guided_params *p);
+/* The counterpart of mcpt_denoise_run: host images as there plus variance (w*h floats; a value that is
+ * not in [0, FLT_MAX] is "unknown"); out_variance (w*h floats, -1 where unknown) may be NULL. */
+int mcpt_denoise_guided_run(mcpt_ctx *ctx, uint32_t w, uint32_t h, const float *rgb, const uint32_t *samples,
+                            const float *variance, const float *albedo, const float *normal, const float *depth,
+                            const mcpt_denoise_guided_params *p, float *out_rgb, float *out_variance);
+/* Filter the film as mcpt_film_denoise does, with v = se^2 of a fresh mcpt_film_error estimate (which
+ * it runs itself and leaves readable through mcpt_film_error_read): needs valid guides, >= 2 path
+ * slots and no paths in flight.  Pixels without an estimate (fewer than 2 slots with samples; pixels
+ * scattered in from another context) take the plain term.  The result replaces the last denoised
+ * frame: the mcpt_denoised_* readers serve it. */
+int mcpt_film_denoise_guided(mcpt_ctx *ctx, const mcpt_denoise_guided_params *p);
+/* The filtered variances (W*H floats, -1 where unknown) of the last denoise; MCPT_E_INVALID unless
+ * that was mcpt_film_denoise_guided. */
+int mcpt_denoised_variance_read(mcpt_ctx *ctx, float *var);
 /* ---- adaptive sampling: per-pixel sample budgets, "continue rendering", and
  * an error estimate of the film.  A context that never calls these allocates and launches nothing
  * for them, and renders with the kernels it always did.

@@ -575,6 +575,19 @@ public:
         if (guide_samples) detail::check(mcpt_guides_render(ctx_, guide_samples), ctx_, "guides");
         detail::check(mcpt_film_denoise(ctx_, params), ctx_, "denoise");
     }
+    // The variance-guided filter (mcpt.h): as denoise(), with the squared standard error of a fresh
+    // film error estimate steering the colour term; needs >= 2 path slots (set_path_slots).  The
+    // result is read like denoise()'s, its filtered variances (-1: unknown) with denoised_variance().
+    void denoise_guided(uint32_t guide_samples = 4, const mcpt_denoise_guided_params* params = nullptr) {
+        if (guide_samples) detail::check(mcpt_guides_render(ctx_, guide_samples), ctx_, "guides");
+        detail::check(mcpt_film_denoise_guided(ctx_, params), ctx_, "denoise_guided");
+    }
+    void denoised_variance(std::vector<float>& var) {
+        uint32_t w = 0, h = 0;
+        detail::check(mcpt_film_size(ctx_, &w, &h), ctx_, "denoised_variance");
+        var.resize((size_t)w * h);
+        detail::check(mcpt_denoised_variance_read(ctx_, var.data()), ctx_, "denoised_variance");
+    }
     void denoised(std::vector<float>& rgb) {
         uint32_t w = 0, h = 0;
         detail::check(mcpt_film_size(ctx_, &w, &h), ctx_, "denoised");

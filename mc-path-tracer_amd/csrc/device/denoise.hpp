@@ -130,4 +130,110 @@ inline void denoise_pass_host(const DenoisePass& k, int W, int H, const float4* 
         }
 }
 
+// ---- variance-guided form ----
+// SVGF's spatial filter (Schied et al., HPG 2017, section 4.4): the a-trous filter above with the
+// colour term replaced by |l(p) - l(q)| / (sigma_lum sqrt(prefiltered variance of p) + lum_eps), and
+// the variance of the pixel's mean luminance filtered along with the colour.  Beside the three planes
+// a pixel carries (float2)
+//   vl  (v, l)   v: variance of its mean luminance, -1 where unknown (always -1 for an invalid pixel);
+//                l = luminance(colour), evaluated once per pixel and pass (0 for an invalid pixel)
+// A pixel without a variance takes the plain filter's colour term, so with every variance unknown the
+// colours are dn_tap's bit for bit.  Beside add / mul / div this part takes one correctly rounded square
+// root per pixel and pass, and luminance() computes in double (tests/denoise_guided_ref.py restates it).
+struct DenoiseGuidedPass {
+    DenoisePass k;            // k.kc: the fallback term of a pixel without a variance
+    float sigma_lum, lum_eps;
+};
+MCPT_HD bool dn_known(float v) { return v >= 0.f; }
+MCPT_HD float2 dn_vl(const float4& col, float var) {
+    const bool valid = col.w != 0.f;
+    return make_float2(valid && var >= 0.f && var <= 3.402823466e+38f ? var : -1.f,
+                       valid ? luminance(V3{col.x, col.y, col.z}) : 0.f);
+}
+// Prefilter of a pixel with a known variance: the 3 x 3 Gaussian {1/4, 1/8, 1/16} over the neighbours
+// at stride 1 (whatever the pass) whose variance is known, row-major; the caller skips the others
+struct DnPre {
+    float gs, gv;
+};
+MCPT_HD void dn_pre_tap(int dx, int dy, float vr, DnPre& a) {
+    const float g = (dx == 0 && dy == 0) ? 0.25f : (dx == 0 || dy == 0) ? 0.125f : 0.0625f;
+    a.gs = a.gs + g;
+    a.gv = a.gv + g * vr;
+}
+// 1 / (sigma_lum sqrt(vt) + lum_eps); vt = 0 with lum_eps = 0 gives +Inf, which leaves only the centre tap
+MCPT_HD float dn_pre_rcp(const DenoiseGuidedPass& k, const DnPre& a) {
+    const float vt = a.gv / a.gs;
+    return 1.f / (k.sigma_lum * __builtin_sqrtf(vt) + k.lum_eps);
+}
+struct DnAccV {
+    float w, r, g, b, v;
+};
+// dn_tap with the variance: known = dn_known(vlp.x), rcp = dn_pre_rcp of p (any finite value
+// otherwise).  Both colour terms and the variance sum are evaluated whatever `known` is and selected,
+// so the kernels' taps stay free of branches; acc.v of a pixel without a variance is never used.
+MCPT_HD void dn_tap_guided(const DenoiseGuidedPass& k, int dx, int dy, bool known, float rcp, const float4& cp,
+                           const float2& vlp, const float4& gp, const float4& ap, const float4& cq, const float2& vlq,
+                           const float4& gq, const float4& aq, DnAccV& acc) {
+    float e = 1.f;
+    if (dx != 0 || dy != 0) {
+        const float xl = __builtin_fabsf(vlp.y - vlq.y) * rcp;
+        const float xp = k.k.kc * dn_sq3(cp.x, cp.y, cp.z, cq.x, cq.y, cq.z);
+        const float xc = known ? xl : xp;
+        const float dn = dn_sq3(gp.x, gp.y, gp.z, gq.x, gq.y, gq.z);
+        const float da = dn_sq3(ap.x, ap.y, ap.z, aq.x, aq.y, aq.z);
+        const float dz = gp.w - gq.w;
+        const float x = ((xc + k.k.kn * dn) + k.k.ka * da) + (k.k.kz * (dz * dz)) * ap.w;
+        e = (x >= 0.f && x <= 3.402823466e+38f) ? dexp_neg(x) : 0.f;
+    }
+    const float w = (dn_h(dy) * dn_h(dx)) * e;
+    acc.w = acc.w + w;
+    acc.r = acc.r + w * cq.x;
+    acc.g = acc.g + w * cq.y;
+    acc.b = acc.b + w * cq.z;
+    acc.v = acc.v + (w * w) * (dn_known(vlq.x) ? vlq.x : vlp.x);
+}
+MCPT_HD void dn_finish_guided(const DnAccV& acc, bool known, float4& col, float2& vl) {
+    col = make_float4(acc.r / acc.w, acc.g / acc.w, acc.b / acc.w, 1.f);
+    vl = make_float2(known ? acc.v / (acc.w * acc.w) : -1.f, luminance(V3{col.x, col.y, col.z}));
+}
+
+// Host form of one guided pass (tests/native/denoise_guided_host.cpp)
+inline void denoise_guided_pass_host(const DenoiseGuidedPass& k, int W, int H, const float4* col, const float2* vl,
+                                     const float4* gd, const float4* al, float4* out, float2* out_vl) {
+    for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++) {
+            const size_t p = (size_t)y * W + x;
+            const float4 cp = col[p];
+            if (cp.w == 0.f) {
+                out[p] = make_float4(0.f, 0.f, 0.f, 0.f);
+                out_vl[p] = make_float2(-1.f, 0.f);
+                continue;
+            }
+            const float2 vlp = vl[p];
+            const bool known = dn_known(vlp.x);
+            float rcp = 0.f;
+            if (known) {
+                DnPre pre{0.f, 0.f};
+                for (int dy = -1; dy <= 1; dy++)
+                    for (int dx = -1; dx <= 1; dx++) {
+                        const int rx = x + dx, ry = y + dy;
+                        if (rx < 0 || rx >= W || ry < 0 || ry >= H) continue;
+                        const float vr = vl[(size_t)ry * W + (size_t)rx].x;
+                        if (dn_known(vr)) dn_pre_tap(dx, dy, vr, pre);
+                    }
+                rcp = dn_pre_rcp(k, pre);
+            }
+            DnAccV acc{0.f, 0.f, 0.f, 0.f, 0.f};
+            for (int dy = -2; dy <= 2; dy++)
+                for (int dx = -2; dx <= 2; dx++) {
+                    const long qx = (long)x + (long)dx * k.k.stride, qy = (long)y + (long)dy * k.k.stride;
+                    if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+                    const size_t q = (size_t)qy * W + (size_t)qx;
+                    if (col[q].w == 0.f) continue;
+                    dn_tap_guided(k, dx, dy, known, rcp, cp, vlp, gd[p], al[p], col[q], vl[q], gd[q], al[q], acc);
+                }
+            dn_finish_guided(acc, known, out[p], out_vl[p]);
+        }
+}
+
 }  // namespace mcpt

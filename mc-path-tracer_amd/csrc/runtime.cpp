@@ -139,6 +139,11 @@ struct mcpt_ctx {
     mcpt::CamView guides_cam{};
     float4 *dn_col[2] = {nullptr, nullptr}, *dn_gd = nullptr, *dn_al = nullptr;
     int dn_result = -1;
+    // Variance-guided form: the {variance, luminance} planes in ping-pong beside
+    // dn_col, allocated by the first mcpt_film_denoise_guided; dn_guided: dn_result is a guided result,
+    // whose variances are dn_vl[dn_result]
+    float2* dn_vl[2] = {nullptr, nullptr};
+    bool dn_guided = false;
     float guides_ms = 0.f, dn_ms[9] = {};  // device times of the last guide pass / filter set-up and passes
     // Adaptive sampling, all keyed by film pixel and allocated by the first call
     // that needs them: budget, the per-pixel sample budget k_shade reads in place of cfg.spp while
@@ -188,8 +193,13 @@ static void denoise_free(mcpt_ctx* c) {
         if (*q) (void)hipFree(*q);
         *q = nullptr;
     }
+    for (float2** q : {&c->dn_vl[0], &c->dn_vl[1]}) {
+        if (*q) (void)hipFree(*q);
+        *q = nullptr;
+    }
     c->guides_ok = false;
     c->dn_result = -1;
+    c->dn_guided = false;
 }
 static void adaptive_free(mcpt_ctx* c) {
     if (c->budget) (void)hipFree(c->budget);
@@ -2364,6 +2374,54 @@ static int denoise_passes(mcpt_ctx* c, const mcpt_denoise_params& p, uint32_t W,
     return MCPT_OK;
 }
 
+static int denoise_guided_check_params(mcpt_ctx* c, const mcpt_denoise_guided_params* p) {
+    if (p->passes < 1 || p->passes > 8) return set_err(c, MCPT_E_INVALID, "guided denoise: passes must be 1..8");
+    if (!(p->sigma_lum > 0.f) || !(p->sigma_lum <= 3.402823466e+38f))
+        return set_err(c, MCPT_E_INVALID, "guided denoise: sigma_lum must be > 0");
+    if (!(p->lum_eps >= 0.f) || !(p->lum_eps <= 3.402823466e+38f))
+        return set_err(c, MCPT_E_INVALID, "guided denoise: lum_eps must be >= 0");
+    return MCPT_OK;
+}
+// denoise_passes for the guided kernels: vl ping-pongs with col
+static int denoise_guided_passes(mcpt_ctx* c, const mcpt_denoise_guided_params& p, uint32_t W, uint32_t H,
+                                 float4* const col[2], float2* const vl[2], const float4* gd, const float4* al, int* result) {
+    int lds_max = 2;  // MCPT_DENOISE_LDS_MAX, as in denoise_passes
+    if (const char* e = getenv(kDenoiseLdsEnv))
+        if (e[0] >= '0' && e[0] <= '2' && e[1] == 0) lds_max = e[0] - '0';
+    for (int i = 0; i < 8; i++) c->dn_ms[1 + i] = 0.f;
+    int src = 0;
+    for (int i = 0; i < p.passes; i++) {
+        DenoiseGuidedArgs a{};
+        float sc = p.sigma_color;
+        for (int k = 0; k < i; k++) sc = sc * 0.5f;  // sigma_color 2^-i
+        a.k.k.kc = mcpt::dn_k(sc);
+        a.k.k.kn = mcpt::dn_k(p.sigma_normal);
+        a.k.k.ka = mcpt::dn_k(p.sigma_albedo);
+        a.k.k.kz = mcpt::dn_k(p.sigma_depth);
+        a.k.k.stride = 1 << i;
+        a.k.sigma_lum = p.sigma_lum;
+        a.k.lum_eps = p.lum_eps;
+        a.W = (int)W;
+        a.H = (int)H;
+        a.col = col[src];
+        a.vl = vl[src];
+        a.gd = gd;
+        a.al = al;
+        a.out = col[src ^ 1];
+        a.out_vl = vl[src ^ 1];
+        HIPCHK(c, hipEventRecord(ev(c, 1 + (size_t)i), c->stream));
+        launch_denoise_guided_pass(a, lds_max, c->stream);
+        src ^= 1;
+    }
+    HIPCHK(c, hipEventRecord(ev(c, 1 + (size_t)p.passes), c->stream));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipEventElapsedTime(&c->dn_ms[0], c->events[0], c->events[1]));
+    for (int i = 0; i < p.passes; i++) HIPCHK(c, hipEventElapsedTime(&c->dn_ms[1 + i], c->events[1 + i], c->events[2 + i]));
+    *result = src;
+    return MCPT_OK;
+}
+
 extern "C" {
 
 int mcpt_denoise_default_params(mcpt_denoise_params* p) {
@@ -2557,6 +2615,7 @@ int mcpt_film_denoise(mcpt_ctx* c, const mcpt_denoise_params* pp) {
         }
     }
     c->dn_result = -1;
+    c->dn_guided = false;
     DenoisePrepArgs pa{};
     if ((rc = film_view(c, &pa.Ld, &pa.samples))) return rc;
     pa.g_alb = c->g_alb;
@@ -2625,6 +2684,142 @@ int mcpt_denoised_tonemap_rgba8(mcpt_ctx* c, float exposure, uint8_t* out) {
     (void)hipFree(d);
     (void)hipFree(ones);
     if (e != hipSuccess) return set_err(c, MCPT_E_HIP, std::string("tonemap: ") + hipGetErrorString(e));
+    return MCPT_OK;
+}
+
+// ---- variance-guided form ----
+
+int mcpt_denoise_guided_default_params(mcpt_denoise_guided_params* p) {
+    if (!p) return MCPT_E_INVALID;
+    // sigma_lum / lum_eps: the best row of profiles/denoise_guided_defaults.txt (4 and 16 spp and an
+    // adaptive frame against 1024 spp; configs 1, 2, cube).  The rest: mcpt_denoise_default_params
+    p->passes = 5;
+    p->sigma_lum = 8.0f;
+    p->lum_eps = 0.f;
+    p->sigma_color = 2.0f;
+    p->sigma_normal = 0.3f;
+    p->sigma_albedo = 0.3f;
+    p->sigma_depth = 0.1f;
+    return MCPT_OK;
+}
+
+int mcpt_denoise_guided_run(mcpt_ctx* c, uint32_t w, uint32_t h, const float* rgb, const uint32_t* samples, const float* variance,
+                            const float* albedo, const float* normal, const float* depth, const mcpt_denoise_guided_params* pp,
+                            float* out_rgb, float* out_variance) {
+    if (!c || !rgb || !variance || !albedo || !normal || !depth || !out_rgb || !pp)
+        return set_err(c, MCPT_E_INVALID, "guided denoise: null argument");
+    if (w == 0 || h == 0 || (uint64_t)w * h >= (1ull << 28)) return set_err(c, MCPT_E_INVALID, "guided denoise: bad image size");
+    int rc = denoise_guided_check_params(c, pp);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = (size_t)w * h;
+    free_list(c->tmp_bufs);
+    auto& L = c->tmp_bufs;
+    float *d_rgb, *d_al, *d_n, *d_z, *d_v;
+    uint32_t* d_s = nullptr;
+    float4 *col[2], *gd, *al;
+    float2* vl[2];
+    if ((rc = dupload(c, L, &d_rgb, rgb, 3 * n)) || (rc = dupload(c, L, &d_al, albedo, 3 * n)) ||
+        (rc = dupload(c, L, &d_n, normal, 3 * n)) || (rc = dupload(c, L, &d_z, depth, n)) ||
+        (rc = dupload(c, L, &d_v, variance, n)) || (samples && (rc = dupload(c, L, &d_s, samples, n))) ||
+        (rc = dalloc(c, L, &col[0], n)) || (rc = dalloc(c, L, &col[1], n)) || (rc = dalloc(c, L, &gd, n)) ||
+        (rc = dalloc(c, L, &al, n)) || (rc = dalloc(c, L, &vl[0], n)) || (rc = dalloc(c, L, &vl[1], n))) {
+        free_list(L);
+        return rc;
+    }
+    DenoiseGuidedPrepArgs pa{};
+    pa.base.samples = d_s;
+    pa.base.rgb = d_rgb;
+    pa.base.normal = d_n;
+    pa.base.albedo = d_al;
+    pa.base.depth = d_z;
+    pa.base.col = col[0];
+    pa.base.gd = gd;
+    pa.base.al = al;
+    pa.base.n = (uint32_t)n;
+    pa.variance = d_v;
+    pa.vl = vl[0];
+    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
+    launch_denoise_guided_prep(pa, c->stream);
+    int res = 0;
+    if ((rc = denoise_guided_passes(c, *pp, w, h, col, vl, gd, al, &res))) return rc;
+    std::vector<float4> o(n);
+    HIPCHK(c, hipMemcpy(o.data(), col[res], n * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) { out_rgb[3 * i] = o[i].x; out_rgb[3 * i + 1] = o[i].y; out_rgb[3 * i + 2] = o[i].z; }
+    if (out_variance) {
+        std::vector<float2> ov(n);
+        HIPCHK(c, hipMemcpy(ov.data(), vl[res], n * sizeof(float2), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; i++) out_variance[i] = ov[i].x;
+    }
+    free_list(L);
+    return MCPT_OK;
+}
+
+int mcpt_film_denoise_guided(mcpt_ctx* c, const mcpt_denoise_guided_params* pp) {
+    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    mcpt_denoise_guided_params p;
+    if (pp) p = *pp;
+    else (void)mcpt_denoise_guided_default_params(&p);
+    int rc = denoise_guided_check_params(c, &p);
+    if (rc) return rc;
+    if (!guides_valid(c))
+        return set_err(c, MCPT_E_INVALID, "denoise: guide buffers missing or stale (camera, scene or film changed): call mcpt_guides_render first");
+    // a fresh estimate, on mcpt_film_error's own path (its checks: >= 2 path slots, no paths in flight)
+    if ((rc = mcpt_film_error(c))) return rc;
+    bool fresh = false;
+    for (float4** q : {&c->dn_col[0], &c->dn_col[1], &c->dn_gd, &c->dn_al})
+        if (!*q) {
+            if (hipMalloc(q, c->P * sizeof(float4)) != hipSuccess) *q = nullptr;
+            fresh = true;
+        }
+    for (float2** q : {&c->dn_vl[0], &c->dn_vl[1]})
+        if (!*q && hipMalloc(q, c->P * sizeof(float2)) != hipSuccess) *q = nullptr;
+    if (fresh) c->dn_result = -1;
+    if (!c->dn_col[0] || !c->dn_col[1] || !c->dn_gd || !c->dn_al || !c->dn_vl[0] || !c->dn_vl[1]) {
+        (void)hipGetLastError();
+        for (float4** q : {&c->dn_col[0], &c->dn_col[1], &c->dn_gd, &c->dn_al}) {
+            if (*q) (void)hipFree(*q);
+            *q = nullptr;
+        }
+        for (float2** q : {&c->dn_vl[0], &c->dn_vl[1]}) {
+            if (*q) (void)hipFree(*q);
+            *q = nullptr;
+        }
+        c->dn_result = -1;
+        c->dn_guided = false;
+        return set_err(c, MCPT_E_NOMEM, "guided denoise: plane allocation failed");
+    }
+    c->dn_result = -1;
+    c->dn_guided = false;
+    DenoiseGuidedPrepArgs pa{};
+    if ((rc = film_view(c, &pa.base.Ld, &pa.base.samples))) return rc;
+    pa.base.g_alb = c->g_alb;
+    pa.base.g_nz = c->g_nz;
+    pa.base.col = c->dn_col[0];
+    pa.base.gd = c->dn_gd;
+    pa.base.al = c->dn_al;
+    pa.base.n = (uint32_t)c->P;
+    pa.err = c->err4;
+    pa.vl = c->dn_vl[0];
+    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
+    launch_denoise_guided_prep(pa, c->stream);
+    int res = 0;
+    if ((rc = denoise_guided_passes(c, p, c->W, c->H, c->dn_col, c->dn_vl, c->dn_gd, c->dn_al, &res))) return rc;
+    c->dn_result = res;
+    c->dn_guided = true;
+    return MCPT_OK;
+}
+
+int mcpt_denoised_variance_read(mcpt_ctx* c, float* var) {
+    int rc = denoised_check(c);
+    if (rc) return rc;
+    if (!c->dn_guided) return set_err(c, MCPT_E_INVALID, "no denoised variance: the last denoise was not mcpt_film_denoise_guided");
+    if (!var) return set_err(c, MCPT_E_INVALID, "null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<float2> o(c->P);
+    HIPCHK(c, hipMemcpy(o.data(), c->dn_vl[c->dn_result], c->P * sizeof(float2), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < c->P; i++) var[i] = o[i].x;
     return MCPT_OK;
 }
 

@@ -79,6 +79,11 @@ class DenoiseParams(C.Structure):  # mcpt_denoise_params
                 ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float)]
 
 
+class DenoiseGuidedParams(C.Structure):  # mcpt_denoise_guided_params
+    _fields_ = [("passes", C.c_int32), ("sigma_lum", C.c_float), ("lum_eps", C.c_float), ("sigma_color", C.c_float),
+                ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float)]
+
+
 class SampleBudgetParams(C.Structure):  # mcpt_sample_budget_params
     _fields_ = [("target_rel_err", C.c_float), ("lum_floor", C.c_float), ("min_spp", C.c_uint32), ("max_spp", C.c_uint32)]
 
@@ -151,6 +156,11 @@ ABI = {
     "mcpt_denoised_tonemap_rgba8": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(C.c_uint8)]),
     "mcpt_denoised_write_png": (C.c_int, [C.c_void_p, C.c_float, C.c_char_p]),
     "mcpt_debug_denoise_ms": (C.c_int, [C.c_void_p, _f]),
+    "mcpt_denoise_guided_default_params": (C.c_int, [C.POINTER(DenoiseGuidedParams)]),
+    "mcpt_denoise_guided_run": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _f, _u, _f, _f, _f, _f,
+                                          C.POINTER(DenoiseGuidedParams), _f, _f]),
+    "mcpt_film_denoise_guided": (C.c_int, [C.c_void_p, C.POINTER(DenoiseGuidedParams)]),
+    "mcpt_denoised_variance_read": (C.c_int, [C.c_void_p, _f]),
     "mcpt_set_sample_budget": (C.c_int, [C.c_void_p, _u]),
     "mcpt_sample_budget_read": (C.c_int, [C.c_void_p, _u]),
     "mcpt_set_spp": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -602,6 +612,20 @@ class PathTracer:
         self._ck(lib().mcpt_denoised_read(self.h, fptr(out)))
         return out.reshape(self.H, self.W, 3)
 
+    def denoise_guided(self, **params):
+        """Variance-guided a-trous filter of the film (mcpt_film_denoise_guided): the variance is the
+        squared standard error of a fresh film error estimate (>= 2 path slots).  The result is read
+        like denoise()'s; keyword arguments override the defaults (passes, sigma_lum, lum_eps, ...)."""
+        p = denoise_guided_params(**params) if params else None
+        self._ck(lib().mcpt_film_denoise_guided(self.h, C.byref(p) if p is not None else None))
+
+    def denoised_variance(self):
+        """The filtered variances of the last denoise_guided() as (H, W) float32, -1 where unknown
+        (mcpt_denoised_variance_read)."""
+        out = np.zeros(self.W * self.H, np.float32)
+        self._ck(lib().mcpt_denoised_variance_read(self.h, fptr(out)))
+        return out.reshape(self.H, self.W)
+
     def write_denoised_png(self, path, exposure=1.0):
         """Tonemapped denoised frame as 8-bit RGB PNG (mcpt_denoised_write_png)."""
         self._ck(lib().mcpt_denoised_write_png(self.h, exposure, os.fsencode(path)))
@@ -784,6 +808,17 @@ def denoise_params(**kw) -> DenoiseParams:
     return p
 
 
+def denoise_guided_params(**kw) -> DenoiseGuidedParams:
+    """mcpt_denoise_guided_default_params with keyword overrides."""
+    p = DenoiseGuidedParams()
+    _check(lib().mcpt_denoise_guided_default_params(C.byref(p)))
+    for k, v in kw.items():
+        if k not in dict(DenoiseGuidedParams._fields_):
+            raise TypeError(f"unknown guided denoise parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
 def sample_budget_params(**kw) -> SampleBudgetParams:
     """mcpt_sample_budget_default_params with keyword overrides."""
     p = SampleBudgetParams()
@@ -820,6 +855,25 @@ def denoise_run(pt, rgb, albedo, normal, depth, samples=None, **params):
     _check(lib().mcpt_denoise_run(pt.h, W, H, fptr(rgb), None if sm is None else sm.ctypes.data_as(_u), fptr(al),
                                   fptr(nm), fptr(z), C.byref(p), fptr(out)), pt.h)
     return out
+
+
+def denoise_guided_run(pt, rgb, variance, albedo, normal, depth, samples=None, **params):
+    """mcpt_denoise_guided_run on PathTracer pt: denoise_run's images plus an (H, W) variance of the
+    mean luminance (a value outside [0, FLT_MAX]: unknown); returns the filtered (H, W, 3) image and
+    the filtered (H, W) variances (-1 where unknown)."""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    H, W = rgb.shape[:2]
+    var = np.ascontiguousarray(variance, np.float32).reshape(H, W)
+    al = np.ascontiguousarray(albedo, np.float32).reshape(H, W, 3)
+    nm = np.ascontiguousarray(normal, np.float32).reshape(H, W, 3)
+    z = np.ascontiguousarray(depth, np.float32).reshape(H, W)
+    sm = None if samples is None else np.ascontiguousarray(samples, np.uint32).reshape(H, W)
+    out = np.zeros((H, W, 3), np.float32)
+    out_v = np.zeros((H, W), np.float32)
+    p = denoise_guided_params(**params)
+    _check(lib().mcpt_denoise_guided_run(pt.h, W, H, fptr(rgb), None if sm is None else sm.ctypes.data_as(_u), fptr(var),
+                                         fptr(al), fptr(nm), fptr(z), C.byref(p), fptr(out), fptr(out_v)), pt.h)
+    return out, out_v
 
 
 def gather(tracers, root=0):

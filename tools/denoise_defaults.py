@@ -6,6 +6,12 @@ Renders BASELINE configs 1 and 2 and the cube scene at 64x48 and 4 spp, denoises
 the renderer's own 1024-spp frame of the same film: MSE over the pixels that have samples and a finite
 reference.  Rows are ranked by the geometric mean over the three scenes of MSE(denoised) / MSE(raw);
 the defaults (mcpt_denoise_default_params) are the best row.  A sigma of 0 turns its term off.
+
+--guided sweeps the variance-guided filter's (sigma_lum, lum_eps) instead
+(profiles/denoise_guided_defaults.txt): the same scenes and size with 4 path slots, frames at 4 and 16
+spp and one render_adaptive frame at its defaults each, five passes, the guide sigmas at their current
+defaults, ranked by the geometric mean over the nine frames; the plain filter's row on the same frames
+is printed beside it.  The best row is mcpt_denoise_guided_default_params.
 """
 import argparse
 import itertools
@@ -46,10 +52,81 @@ def tracer(scene, cam, spp, depth):
     return pt
 
 
+GUIDED_SLOTS = 4
+GUIDED_SPP = (4, 16, "adaptive")
+SIGMA_LUM = (1.0, 2.0, 4.0, 8.0)
+LUM_EPS = (0.0, 1e-6, 1e-4, 1e-2)
+
+
+def guided(out):
+    cands = list(itertools.product(SIGMA_LUM, LUM_EPS))
+    frames, raw_mse = [], []
+    cols, plain = [], []
+    for name, scene, cam, depth in scenes():
+        rp = tracer(scene, cam, REF_SPP, depth)
+        Lr, sr = rp.film()
+        rp.close()
+        with np.errstate(all="ignore"):
+            ref = Lr / sr[..., None].astype(np.float32)
+        for spp in GUIDED_SPP:
+            pt = mcpt.PathTracer(0, mcpt.default_config(spp=4 if spp == "adaptive" else spp, max_depth=depth, tile=64))
+            pt.upload_scene(scene)
+            pt.set_camera(cam)
+            pt.resize(W, H, 64, 64)
+            pt.set_path_slots(GUIDED_SLOTS)
+            if spp == "adaptive":
+                pt.render_adaptive()
+            else:
+                pt.render()
+            pt.render_guides(GUIDES)
+            Ln, sn = pt.film()
+            with np.errstate(all="ignore"):
+                raw = Ln / sn[..., None].astype(np.float32)
+            keep = (sn > 0) & (sr > 0) & np.isfinite(ref).all(axis=2)
+            r64 = ref[keep].astype(np.float64)
+            m = float(np.mean((raw[keep] - r64) ** 2))
+            frames.append(f"{name}/{spp}")
+            raw_mse.append(m)
+            pt.denoise(passes=PASSES)
+            plain.append(float(np.mean((pt.denoised()[keep] - r64) ** 2)) / m)
+            col = []
+            for sl, eps in cands:
+                pt.denoise_guided(passes=PASSES, sigma_lum=sl, lum_eps=eps)
+                col.append(float(np.mean((pt.denoised()[keep] - r64) ** 2)) / m)
+            cols.append(col)
+            pt.close()
+    ratios = np.array(cols).T  # candidate x frame
+    gm = lambda r: float(np.exp(np.mean(np.log(r))))  # noqa: E731
+    score = np.array([gm(r) for r in ratios])
+    order = np.argsort(score)
+    d = mcpt.denoise_guided_params()
+    lines = [f"# guided denoiser defaults: {W}x{H}, {GUIDED_SLOTS} path slots, {GUIDES} guide samples, {PASSES} passes, "
+             f"against {REF_SPP} spp",
+             "# frames (scene/spp): " + " ".join(frames),
+             "# MSE(raw): " + " ".join(f"{m:.6g}" for m in raw_mse),
+             "# columns: sigma_lum lum_eps | MSE(denoised) / MSE(raw) per frame | geometric mean",
+             f"# built-in defaults: passes {d.passes}, sigma_lum {d.sigma_lum:g}, lum_eps {d.lum_eps:g}; guide sigmas "
+             f"{d.sigma_color:g} {d.sigma_normal:g} {d.sigma_albedo:g} {d.sigma_depth:g}",
+             "plain filter   | " + " ".join(f"{r:9.5f}" for r in plain) + f" | {gm(plain):9.5f}"]
+    for i in order:
+        sl, eps = cands[i]
+        mark = "  <- defaults" if abs(sl - d.sigma_lum) < 1e-6 and abs(eps - d.lum_eps) < 1e-9 else ""
+        lines.append(f"{sl:5g} {eps:8g} | " + " ".join(f"{r:9.5f}" for r in ratios[i]) + f" | {score[i]:9.5f}{mark}")
+    with open(out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+    b = cands[order[0]]
+    print(f"best: sigma_lum {b[0]:g} lum_eps {b[1]:g}")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "denoise_defaults.txt"))
+    ap.add_argument("--guided", action="store_true", help="sweep the variance-guided filter's sigma_lum and lum_eps")
+    ap.add_argument("--out")
     a = ap.parse_args()
+    if a.guided:
+        return guided(a.out or os.path.join(REPO, "profiles", "denoise_guided_defaults.txt"))
+    a.out = a.out or os.path.join(REPO, "profiles", "denoise_defaults.txt")
     cands = list(itertools.product(COLOR, NORMAL, ALBEDO, DEPTH))
     ratios = np.zeros((len(cands), 3))
     raw_mse, names = [], []
