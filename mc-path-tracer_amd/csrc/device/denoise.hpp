@@ -79,56 +79,43 @@ MCPT_HD void dn_planes(float r, float g, float b, bool has_samples, float nx, fl
 
 struct DnAcc {
     float w, r, g, b;
+    float v;  // the guided form's variance sum (the plain form leaves it alone)
 };
 MCPT_HD float dn_sq3(float ax, float ay, float az, float bx, float by, float bz) {
     const float dx = ax - bx, dy = ay - by, dz = az - bz;
     return (dx * dx + dy * dy) + dz * dz;
 }
-// Tap q = p + stride (dx, dy) of a valid pixel p; cq.w != 0 (the caller skips invalid taps and taps
-// outside the film).  The centre's exponent is 0 by definition; elsewhere an exponent that is not
-// a finite number >= 0 gives weight 0.
-MCPT_HD void dn_tap(const DenoisePass& k, int dx, int dy, const float4& cp, const float4& gp, const float4& ap,
-                    const float4& cq, const float4& gq, const float4& aq, DnAcc& acc) {
+// The plain colour term of a tap: kc |C(p) - C(q)|^2
+MCPT_HD float dn_xc(const DenoisePass& k, const float4& cp, const float4& cq) {
+    return k.kc * dn_sq3(cp.x, cp.y, cp.z, cq.x, cq.y, cq.z);
+}
+// Weight of tap q = p + stride (dx, dy) of a valid pixel p, given its colour term xc (dn_xc, or the
+// guided form's).  The centre's exponent is 0 by definition (its xc is not looked at); elsewhere an
+// exponent that is not a finite number >= 0 gives weight 0.
+MCPT_HD float dn_weight(const DenoisePass& k, int dx, int dy, float xc, const float4& gp, const float4& ap,
+                        const float4& gq, const float4& aq) {
     float e = 1.f;
     if (dx != 0 || dy != 0) {
-        const float dc = dn_sq3(cp.x, cp.y, cp.z, cq.x, cq.y, cq.z);
         const float dn = dn_sq3(gp.x, gp.y, gp.z, gq.x, gq.y, gq.z);
         const float da = dn_sq3(ap.x, ap.y, ap.z, aq.x, aq.y, aq.z);
         const float dz = gp.w - gq.w;
-        const float x = ((k.kc * dc + k.kn * dn) + k.ka * da) + (k.kz * (dz * dz)) * ap.w;
+        const float x = ((xc + k.kn * dn) + k.ka * da) + (k.kz * (dz * dz)) * ap.w;
         e = (x >= 0.f && x <= 3.402823466e+38f) ? dexp_neg(x) : 0.f;
     }
-    const float w = (dn_h(dy) * dn_h(dx)) * e;
+    return (dn_h(dy) * dn_h(dx)) * e;
+}
+MCPT_HD void dn_add(float w, const float4& cq, DnAcc& acc) {
     acc.w = acc.w + w;
     acc.r = acc.r + w * cq.x;
     acc.g = acc.g + w * cq.y;
     acc.b = acc.b + w * cq.z;
 }
-MCPT_HD float4 dn_finish(const DnAcc& acc) { return make_float4(acc.r / acc.w, acc.g / acc.w, acc.b / acc.w, 1.f); }
-
-// Host form of one pass over W x H planes (the kernels' parity reference; tests/native/denoise_host.cpp)
-inline void denoise_pass_host(const DenoisePass& k, int W, int H, const float4* col, const float4* gd, const float4* al,
-                              float4* out) {
-    for (int y = 0; y < H; y++)
-        for (int x = 0; x < W; x++) {
-            const size_t p = (size_t)y * W + x;
-            const float4 cp = col[p];
-            if (cp.w == 0.f) {
-                out[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-                continue;
-            }
-            DnAcc acc{0.f, 0.f, 0.f, 0.f};
-            for (int dy = -2; dy <= 2; dy++)
-                for (int dx = -2; dx <= 2; dx++) {
-                    const long qx = (long)x + (long)dx * k.stride, qy = (long)y + (long)dy * k.stride;
-                    if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
-                    const size_t q = (size_t)qy * W + (size_t)qx;
-                    if (col[q].w == 0.f) continue;
-                    dn_tap(k, dx, dy, cp, gd[p], al[p], col[q], gd[q], al[q], acc);
-                }
-            out[p] = dn_finish(acc);
-        }
+// The plain tap; cq.w != 0 (the caller skips invalid taps and taps outside the film)
+MCPT_HD void dn_tap(const DenoisePass& k, int dx, int dy, const float4& cp, const float4& gp, const float4& ap,
+                    const float4& cq, const float4& gq, const float4& aq, DnAcc& acc) {
+    dn_add(dn_weight(k, dx, dy, dn_xc(k, cp, cq), gp, ap, gq, aq), cq, acc);
 }
+MCPT_HD float4 dn_finish(const DnAcc& acc) { return make_float4(acc.r / acc.w, acc.g / acc.w, acc.b / acc.w, 1.f); }
 
 // ---- variance-guided form ----
 // SVGF's spatial filter (Schied et al., HPG 2017, section 4.4): the a-trous filter above with the
@@ -140,9 +127,13 @@ inline void denoise_pass_host(const DenoisePass& k, int W, int H, const float4* 
 // A pixel without a variance takes the plain filter's colour term, so with every variance unknown the
 // colours are dn_tap's bit for bit.  Beside add / mul / div this part takes one correctly rounded square
 // root per pixel and pass, and luminance() computes in double (tests/denoise_guided_ref.py restates it).
-struct DenoiseGuidedPass {
-    DenoisePass k;            // k.kc: the fallback term of a pixel without a variance
+//
+// The guided part of a pass: the colour term's two parameters and the vl planes, vl -> out_vl in
+// ping-pong beside the colour
+struct DenoiseVar {
     float sigma_lum, lum_eps;
+    const float2* vl;
+    float2* out_vl;
 };
 MCPT_HD bool dn_known(float v) { return v >= 0.f; }
 MCPT_HD float2 dn_vl(const float4& col, float var) {
@@ -161,79 +152,82 @@ MCPT_HD void dn_pre_tap(int dx, int dy, float vr, DnPre& a) {
     a.gv = a.gv + g * vr;
 }
 // 1 / (sigma_lum sqrt(vt) + lum_eps); vt = 0 with lum_eps = 0 gives +Inf, which leaves only the centre tap
-MCPT_HD float dn_pre_rcp(const DenoiseGuidedPass& k, const DnPre& a) {
+MCPT_HD float dn_pre_rcp(const DenoiseVar& k, const DnPre& a) {
     const float vt = a.gv / a.gs;
     return 1.f / (k.sigma_lum * __builtin_sqrtf(vt) + k.lum_eps);
 }
-struct DnAccV {
-    float w, r, g, b, v;
-};
 // dn_tap with the variance: known = dn_known(vlp.x), rcp = dn_pre_rcp of p (any finite value
 // otherwise).  Both colour terms and the variance sum are evaluated whatever `known` is and selected,
 // so the kernels' taps stay free of branches; acc.v of a pixel without a variance is never used.
-MCPT_HD void dn_tap_guided(const DenoiseGuidedPass& k, int dx, int dy, bool known, float rcp, const float4& cp,
-                           const float2& vlp, const float4& gp, const float4& ap, const float4& cq, const float2& vlq,
-                           const float4& gq, const float4& aq, DnAccV& acc) {
-    float e = 1.f;
-    if (dx != 0 || dy != 0) {
-        const float xl = __builtin_fabsf(vlp.y - vlq.y) * rcp;
-        const float xp = k.k.kc * dn_sq3(cp.x, cp.y, cp.z, cq.x, cq.y, cq.z);
-        const float xc = known ? xl : xp;
-        const float dn = dn_sq3(gp.x, gp.y, gp.z, gq.x, gq.y, gq.z);
-        const float da = dn_sq3(ap.x, ap.y, ap.z, aq.x, aq.y, aq.z);
-        const float dz = gp.w - gq.w;
-        const float x = ((xc + k.k.kn * dn) + k.k.ka * da) + (k.k.kz * (dz * dz)) * ap.w;
-        e = (x >= 0.f && x <= 3.402823466e+38f) ? dexp_neg(x) : 0.f;
-    }
-    const float w = (dn_h(dy) * dn_h(dx)) * e;
-    acc.w = acc.w + w;
-    acc.r = acc.r + w * cq.x;
-    acc.g = acc.g + w * cq.y;
-    acc.b = acc.b + w * cq.z;
+MCPT_HD void dn_tap_guided(const DenoisePass& k, int dx, int dy, bool known, float rcp, const float4& cp, const float2& vlp,
+                           const float4& gp, const float4& ap, const float4& cq, const float2& vlq, const float4& gq,
+                           const float4& aq, DnAcc& acc) {
+    const float xl = __builtin_fabsf(vlp.y - vlq.y) * rcp;
+    const float xp = dn_xc(k, cp, cq);
+    const float w = dn_weight(k, dx, dy, known ? xl : xp, gp, ap, gq, aq);
+    dn_add(w, cq, acc);
     acc.v = acc.v + (w * w) * (dn_known(vlq.x) ? vlq.x : vlp.x);
 }
-MCPT_HD void dn_finish_guided(const DnAccV& acc, bool known, float4& col, float2& vl) {
-    col = make_float4(acc.r / acc.w, acc.g / acc.w, acc.b / acc.w, 1.f);
-    vl = make_float2(known ? acc.v / (acc.w * acc.w) : -1.f, luminance(V3{col.x, col.y, col.z}));
+// The vl of a filtered pixel: col = dn_finish(acc)
+MCPT_HD float2 dn_finish_vl(const DnAcc& acc, bool known, const float4& col) {
+    return make_float2(known ? acc.v / (acc.w * acc.w) : -1.f, luminance(V3{col.x, col.y, col.z}));
 }
 
-// Host form of one guided pass (tests/native/denoise_guided_host.cpp)
-inline void denoise_guided_pass_host(const DenoiseGuidedPass& k, int W, int H, const float4* col, const float2* vl,
-                                     const float4* gd, const float4* al, float4* out, float2* out_vl) {
+// Host form of one pass over W x H planes, guided where v != nullptr (the kernels' parity reference;
+// tests/native/denoise_host.cpp, denoise_guided_host.cpp)
+inline void denoise_pass_host(const DenoisePass& k, int W, int H, const float4* col, const float4* gd, const float4* al,
+                              float4* out, const DenoiseVar* v = nullptr) {
     for (int y = 0; y < H; y++)
         for (int x = 0; x < W; x++) {
             const size_t p = (size_t)y * W + x;
             const float4 cp = col[p];
             if (cp.w == 0.f) {
                 out[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-                out_vl[p] = make_float2(-1.f, 0.f);
+                if (v) v->out_vl[p] = make_float2(-1.f, 0.f);
                 continue;
             }
-            const float2 vlp = vl[p];
-            const bool known = dn_known(vlp.x);
+            float2 vlp = make_float2(-1.f, 0.f);
+            bool known = false;
             float rcp = 0.f;
+            if (v) {
+                vlp = v->vl[p];
+                known = dn_known(vlp.x);
+            }
             if (known) {
                 DnPre pre{0.f, 0.f};
                 for (int dy = -1; dy <= 1; dy++)
                     for (int dx = -1; dx <= 1; dx++) {
                         const int rx = x + dx, ry = y + dy;
                         if (rx < 0 || rx >= W || ry < 0 || ry >= H) continue;
-                        const float vr = vl[(size_t)ry * W + (size_t)rx].x;
+                        const float vr = v->vl[(size_t)ry * W + (size_t)rx].x;
                         if (dn_known(vr)) dn_pre_tap(dx, dy, vr, pre);
                     }
-                rcp = dn_pre_rcp(k, pre);
+                rcp = dn_pre_rcp(*v, pre);
             }
-            DnAccV acc{0.f, 0.f, 0.f, 0.f, 0.f};
+            DnAcc acc{0.f, 0.f, 0.f, 0.f, 0.f};
             for (int dy = -2; dy <= 2; dy++)
                 for (int dx = -2; dx <= 2; dx++) {
-                    const long qx = (long)x + (long)dx * k.k.stride, qy = (long)y + (long)dy * k.k.stride;
+                    const long qx = (long)x + (long)dx * k.stride, qy = (long)y + (long)dy * k.stride;
                     if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
                     const size_t q = (size_t)qy * W + (size_t)qx;
                     if (col[q].w == 0.f) continue;
-                    dn_tap_guided(k, dx, dy, known, rcp, cp, vlp, gd[p], al[p], col[q], vl[q], gd[q], al[q], acc);
+                    if (v) dn_tap_guided(k, dx, dy, known, rcp, cp, vlp, gd[p], al[p], col[q], v->vl[q], gd[q], al[q], acc);
+                    else dn_tap(k, dx, dy, cp, gd[p], al[p], col[q], gd[q], al[q], acc);
                 }
-            dn_finish_guided(acc, known, out[p], out_vl[p]);
+            out[p] = dn_finish(acc);
+            if (v) v->out_vl[p] = dn_finish_vl(acc, known, out[p]);
         }
+}
+
+// The guided pass by its own name and parameter struct (tests/native/denoise_guided_host.cpp)
+struct DenoiseGuidedPass {
+    DenoisePass k;            // k.kc: the fallback term of a pixel without a variance
+    float sigma_lum, lum_eps;
+};
+inline void denoise_guided_pass_host(const DenoiseGuidedPass& k, int W, int H, const float4* col, const float2* vl,
+                                     const float4* gd, const float4* al, float4* out, float2* out_vl) {
+    const DenoiseVar v{k.sigma_lum, k.lum_eps, vl, out_vl};
+    denoise_pass_host(k.k, W, H, col, gd, al, out, &v);
 }
 
 }  // namespace mcpt

@@ -412,28 +412,22 @@ struct GuideArgs {
     const float* mats;
     float4 *g_alb, *g_nz;
 };
-void launch_denoise_pass(const DenoiseArgs& a, int lds_max_stride, hipStream_t s);
-void launch_denoise_prep(const DenoisePrepArgs& a, hipStream_t s);
 // The variance-guided form: beside the colour planes a float2 plane {variance
-// of the mean luminance or -1, luminance} in ping-pong (vl -> out_vl)
-struct DenoiseGuidedArgs {
-    mcpt::DenoiseGuidedPass k;
-    int W, H;
-    const float4 *col, *gd, *al;
-    const float2* vl;
-    float4* out;
-    float2* out_vl;
+// of the mean luminance or -1, luminance} in ping-pong (v.vl -> v.out_vl).  The plain kernels take
+// the DenoiseArgs part alone.
+struct DenoiseGuidedArgs : DenoiseArgs {
+    mcpt::DenoiseVar v;
 };
-// Its planes: DenoisePrepArgs' plus vl, from the film's error plane err {se, mean, K, n} (with base.Ld:
+// Its planes: DenoisePrepArgs' plus vl, from the film's error plane err {se, mean, K, n} (with Ld:
 // variance = se se, unknown where se < 0 or not finite) or from a caller image of variances
-struct DenoiseGuidedPrepArgs {
-    DenoisePrepArgs base;
+struct DenoiseGuidedPrepArgs : DenoisePrepArgs {
     const float4* err;
     const float* variance;
     float2* vl;
 };
-void launch_denoise_guided_pass(const DenoiseGuidedArgs& a, int lds_max_stride, hipStream_t s);
-void launch_denoise_guided_prep(const DenoiseGuidedPrepArgs& a, hipStream_t s);
+// Both launch the guided kernels where the vl plane is set and the plain ones where it is nullptr
+void launch_denoise_pass(const DenoiseGuidedArgs& a, int lds_max_stride, hipStream_t s);
+void launch_denoise_prep(const DenoiseGuidedPrepArgs& a, hipStream_t s);
 void launch_guide_rays(const GuideArgs& a, hipStream_t s);
 void launch_guide_accum(const GuideArgs& a, hipStream_t s);
 

@@ -131,8 +131,9 @@ struct mcpt_ctx {
     // Preview denoiser.  Guide sums of the W x H film: g_alb (albedo rgb, sample
     // count), g_nz (normal xyz, depth), allocated by the first mcpt_guides_render, valid for the
     // (scene upload, camera, film size) they were rendered for.  dn_*: the filter's planes of the film
-    // (two colour planes in ping-pong, guides, albedo), allocated by the first mcpt_film_denoise;
-    // dn_result: the colour plane that holds the last result (-1: none).  All freed with the film.
+    // (two colour planes in ping-pong, guides, albedo), allocated by the first mcpt_film_denoise[_guided]
+    // (denoise_planes_ensure); dn_result: the colour plane that holds the last result (-1: none).  All
+    // freed with the film.
     float4 *g_alb = nullptr, *g_nz = nullptr;
     bool guides_ok = false;
     uint64_t guides_scene_gen = 0;
@@ -187,19 +188,45 @@ static void prim_free(mcpt_ctx* c) {
     c->prim_cap = c->prim_q_cap = 0;
     c->prim_ok = false;
 }
-// guide sums and filter planes: they belong to the film size
-static void denoise_free(mcpt_ctx* c) {
-    for (float4** q : {&c->g_alb, &c->g_nz, &c->dn_col[0], &c->dn_col[1], &c->dn_gd, &c->dn_al}) {
+// The filter's planes of the film: four float4 planes, and the guided form's two float2 planes
+static void denoise_planes_free(mcpt_ctx* c) {
+    for (void** q : {(void**)&c->dn_col[0], (void**)&c->dn_col[1], (void**)&c->dn_gd, (void**)&c->dn_al, (void**)&c->dn_vl[0],
+                     (void**)&c->dn_vl[1]}) {
         if (*q) (void)hipFree(*q);
         *q = nullptr;
     }
-    for (float2** q : {&c->dn_vl[0], &c->dn_vl[1]}) {
+    c->dn_result = -1;
+    c->dn_guided = false;
+}
+// Allocates those that are missing, the float2 planes only with_vl, and forgets the last result.
+// false: an allocation failed and every plane was freed.
+static bool denoise_planes_ensure(mcpt_ctx* c, bool with_vl) {
+    c->dn_result = -1;
+    c->dn_guided = false;
+    bool ok = true;
+    const auto need = [&](void** q, size_t bytes) {
+        if (ok && !*q && hipMalloc(q, bytes) != hipSuccess) {
+            *q = nullptr;
+            ok = false;
+        }
+    };
+    for (float4** q : {&c->dn_col[0], &c->dn_col[1], &c->dn_gd, &c->dn_al}) need((void**)q, c->P * sizeof(float4));
+    if (with_vl)
+        for (float2** q : {&c->dn_vl[0], &c->dn_vl[1]}) need((void**)q, c->P * sizeof(float2));
+    if (!ok) {
+        (void)hipGetLastError();
+        denoise_planes_free(c);
+    }
+    return ok;
+}
+// guide sums and filter planes: they belong to the film size
+static void denoise_free(mcpt_ctx* c) {
+    denoise_planes_free(c);
+    for (float4** q : {&c->g_alb, &c->g_nz}) {
         if (*q) (void)hipFree(*q);
         *q = nullptr;
     }
     c->guides_ok = false;
-    c->dn_result = -1;
-    c->dn_guided = false;
 }
 static void adaptive_free(mcpt_ctx* c) {
     if (c->budget) (void)hipFree(c->budget);
@@ -2334,20 +2361,40 @@ static bool guides_valid(const mcpt_ctx* c) {
     return c->guides_ok && c->g_alb && c->g_nz && c->guides_scene_gen == c->scene_gen &&
            memcmp(&c->guides_cam, &c->cam, sizeof(c->cam)) == 0;
 }
-static int denoise_check_params(mcpt_ctx* c, const mcpt_denoise_params* p) {
-    if (p->passes < 1 || p->passes > 8) return set_err(c, MCPT_E_INVALID, "denoise: passes must be 1..8");
+// One filter request, from either parameter struct: the plain parameters, and with `guided` the
+// variance-guided form's two; `who` heads its error texts
+struct DenoiseRequest {
+    mcpt_denoise_params p;
+    bool guided;
+    float sigma_lum, lum_eps;
+    const char* who;
+};
+static DenoiseRequest denoise_request(const mcpt_denoise_params& p) { return {p, false, 0.f, 0.f, "denoise"}; }
+static DenoiseRequest denoise_request(const mcpt_denoise_guided_params& q) {
+    return {{q.passes, q.sigma_color, q.sigma_normal, q.sigma_albedo, q.sigma_depth}, true, q.sigma_lum, q.lum_eps,
+            "guided denoise"};
+}
+static int denoise_check_params(mcpt_ctx* c, const DenoiseRequest& r) {
+    if (r.p.passes < 1 || r.p.passes > 8) return set_err(c, MCPT_E_INVALID, std::string(r.who) + ": passes must be 1..8");
+    if (!r.guided) return MCPT_OK;
+    if (!(r.sigma_lum > 0.f) || !(r.sigma_lum <= 3.402823466e+38f))
+        return set_err(c, MCPT_E_INVALID, "guided denoise: sigma_lum must be > 0");
+    if (!(r.lum_eps >= 0.f) || !(r.lum_eps <= 3.402823466e+38f))
+        return set_err(c, MCPT_E_INVALID, "guided denoise: lum_eps must be >= 0");
     return MCPT_OK;
 }
-// The passes over planes of a W x H image; *result = the colour plane that holds the last pass
-static int denoise_passes(mcpt_ctx* c, const mcpt_denoise_params& p, uint32_t W, uint32_t H, float4* const col[2],
-                          const float4* gd, const float4* al, int* result) {
+// The passes over planes of a W x H image: col ping-pongs, and vl with it where the request is guided
+// (vl is not looked at otherwise); *result = the plane that holds the last pass
+static int denoise_passes(mcpt_ctx* c, const DenoiseRequest& r, uint32_t W, uint32_t H, float4* const col[2],
+                          float2* const vl[2], const float4* gd, const float4* al, int* result) {
+    const mcpt_denoise_params& p = r.p;
     int lds_max = 2;  // MCPT_DENOISE_LDS_MAX: the widest stride that takes the LDS kernel (A/B; same bits)
     if (const char* e = getenv(kDenoiseLdsEnv))
         if (e[0] >= '0' && e[0] <= '2' && e[1] == 0) lds_max = e[0] - '0';
     for (int i = 0; i < 8; i++) c->dn_ms[1 + i] = 0.f;
     int src = 0;
     for (int i = 0; i < p.passes; i++) {
-        DenoiseArgs a{};
+        DenoiseGuidedArgs a{};
         float sc = p.sigma_color;
         for (int k = 0; k < i; k++) sc = sc * 0.5f;  // sigma_color 2^-i
         a.k.kc = mcpt::dn_k(sc);
@@ -2361,6 +2408,7 @@ static int denoise_passes(mcpt_ctx* c, const mcpt_denoise_params& p, uint32_t W,
         a.gd = gd;
         a.al = al;
         a.out = col[src ^ 1];
+        if (r.guided) a.v = {r.sigma_lum, r.lum_eps, vl[src], vl[src ^ 1]};
         HIPCHK(c, hipEventRecord(ev(c, 1 + (size_t)i), c->stream));
         launch_denoise_pass(a, lds_max, c->stream);
         src ^= 1;
@@ -2373,52 +2421,97 @@ static int denoise_passes(mcpt_ctx* c, const mcpt_denoise_params& p, uint32_t W,
     *result = src;
     return MCPT_OK;
 }
-
-static int denoise_guided_check_params(mcpt_ctx* c, const mcpt_denoise_guided_params* p) {
-    if (p->passes < 1 || p->passes > 8) return set_err(c, MCPT_E_INVALID, "guided denoise: passes must be 1..8");
-    if (!(p->sigma_lum > 0.f) || !(p->sigma_lum <= 3.402823466e+38f))
-        return set_err(c, MCPT_E_INVALID, "guided denoise: sigma_lum must be > 0");
-    if (!(p->lum_eps >= 0.f) || !(p->lum_eps <= 3.402823466e+38f))
-        return set_err(c, MCPT_E_INVALID, "guided denoise: lum_eps must be >= 0");
+// Read-back of a device plane: the rgb of n float4 / the first component of n float2
+static int read_rgb(mcpt_ctx* c, const float4* d, size_t n, float* rgb) {
+    std::vector<float4> o(n);
+    HIPCHK(c, hipMemcpy(o.data(), d, n * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) { rgb[3 * i] = o[i].x; rgb[3 * i + 1] = o[i].y; rgb[3 * i + 2] = o[i].z; }
     return MCPT_OK;
 }
-// denoise_passes for the guided kernels: vl ping-pongs with col
-static int denoise_guided_passes(mcpt_ctx* c, const mcpt_denoise_guided_params& p, uint32_t W, uint32_t H,
-                                 float4* const col[2], float2* const vl[2], const float4* gd, const float4* al, int* result) {
-    int lds_max = 2;  // MCPT_DENOISE_LDS_MAX, as in denoise_passes
-    if (const char* e = getenv(kDenoiseLdsEnv))
-        if (e[0] >= '0' && e[0] <= '2' && e[1] == 0) lds_max = e[0] - '0';
-    for (int i = 0; i < 8; i++) c->dn_ms[1 + i] = 0.f;
-    int src = 0;
-    for (int i = 0; i < p.passes; i++) {
-        DenoiseGuidedArgs a{};
-        float sc = p.sigma_color;
-        for (int k = 0; k < i; k++) sc = sc * 0.5f;  // sigma_color 2^-i
-        a.k.k.kc = mcpt::dn_k(sc);
-        a.k.k.kn = mcpt::dn_k(p.sigma_normal);
-        a.k.k.ka = mcpt::dn_k(p.sigma_albedo);
-        a.k.k.kz = mcpt::dn_k(p.sigma_depth);
-        a.k.k.stride = 1 << i;
-        a.k.sigma_lum = p.sigma_lum;
-        a.k.lum_eps = p.lum_eps;
-        a.W = (int)W;
-        a.H = (int)H;
-        a.col = col[src];
-        a.vl = vl[src];
-        a.gd = gd;
-        a.al = al;
-        a.out = col[src ^ 1];
-        a.out_vl = vl[src ^ 1];
-        HIPCHK(c, hipEventRecord(ev(c, 1 + (size_t)i), c->stream));
-        launch_denoise_guided_pass(a, lds_max, c->stream);
-        src ^= 1;
+static int read_x(mcpt_ctx* c, const float2* d, size_t n, float* x) {
+    std::vector<float2> o(n);
+    HIPCHK(c, hipMemcpy(o.data(), d, n * sizeof(float2), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) x[i] = o[i].x;
+    return MCPT_OK;
+}
+
+// mcpt_denoise_run / mcpt_denoise_guided_run (whose null checks come first): upload, planes, passes,
+// read-back.  variance and out_variance are the guided form's; out_variance may be nullptr.
+static int denoise_run(mcpt_ctx* c, const DenoiseRequest& r, uint32_t w, uint32_t h, const float* rgb, const uint32_t* samples,
+                       const float* variance, const float* albedo, const float* normal, const float* depth, float* out_rgb,
+                       float* out_variance) {
+    if (w == 0 || h == 0 || (uint64_t)w * h >= (1ull << 28))
+        return set_err(c, MCPT_E_INVALID, std::string(r.who) + ": bad image size");
+    int rc = denoise_check_params(c, r);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = (size_t)w * h;
+    free_list(c->tmp_bufs);
+    auto& L = c->tmp_bufs;
+    float *d_rgb, *d_al, *d_n, *d_z, *d_v = nullptr;
+    uint32_t* d_s = nullptr;
+    float4 *col[2], *gd, *al;
+    float2* vl[2] = {nullptr, nullptr};
+    if ((rc = dupload(c, L, &d_rgb, rgb, 3 * n)) || (rc = dupload(c, L, &d_al, albedo, 3 * n)) ||
+        (rc = dupload(c, L, &d_n, normal, 3 * n)) || (rc = dupload(c, L, &d_z, depth, n)) ||
+        (samples && (rc = dupload(c, L, &d_s, samples, n))) || (rc = dalloc(c, L, &col[0], n)) ||
+        (rc = dalloc(c, L, &col[1], n)) || (rc = dalloc(c, L, &gd, n)) || (rc = dalloc(c, L, &al, n)) ||
+        (r.guided && ((rc = dupload(c, L, &d_v, variance, n)) || (rc = dalloc(c, L, &vl[0], n)) || (rc = dalloc(c, L, &vl[1], n))))) {
+        free_list(L);
+        return rc;
     }
-    HIPCHK(c, hipEventRecord(ev(c, 1 + (size_t)p.passes), c->stream));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipEventElapsedTime(&c->dn_ms[0], c->events[0], c->events[1]));
-    for (int i = 0; i < p.passes; i++) HIPCHK(c, hipEventElapsedTime(&c->dn_ms[1 + i], c->events[1 + i], c->events[2 + i]));
-    *result = src;
+    DenoiseGuidedPrepArgs pa{};
+    pa.samples = d_s;
+    pa.rgb = d_rgb;
+    pa.normal = d_n;
+    pa.albedo = d_al;
+    pa.depth = d_z;
+    pa.col = col[0];
+    pa.gd = gd;
+    pa.al = al;
+    pa.n = (uint32_t)n;
+    pa.variance = d_v;
+    pa.vl = vl[0];
+    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
+    launch_denoise_prep(pa, c->stream);
+    int res = 0;
+    if ((rc = denoise_passes(c, r, w, h, col, vl, gd, al, &res))) return rc;
+    if ((rc = read_rgb(c, col[res], n, out_rgb))) return rc;
+    if (out_variance && (rc = read_x(c, vl[res], n, out_variance))) return rc;
+    free_list(L);
+    return MCPT_OK;
+}
+
+// mcpt_film_denoise / mcpt_film_denoise_guided: the film and the context's guides through the
+// context's planes.  Guided: the variance is se^2 of a fresh mcpt_film_error estimate, on that
+// call's own path (its checks: >= 2 path slots, no paths in flight).
+static int film_denoise(mcpt_ctx* c, const DenoiseRequest& r) {
+    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    int rc = denoise_check_params(c, r);
+    if (rc) return rc;
+    if (!guides_valid(c))
+        return set_err(c, MCPT_E_INVALID, "denoise: guide buffers missing or stale (camera, scene or film changed): call mcpt_guides_render first");
+    if (r.guided && (rc = mcpt_film_error(c))) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!denoise_planes_ensure(c, r.guided)) return set_err(c, MCPT_E_NOMEM, std::string(r.who) + ": plane allocation failed");
+    DenoiseGuidedPrepArgs pa{};
+    if ((rc = film_view(c, &pa.Ld, &pa.samples))) return rc;
+    pa.g_alb = c->g_alb;
+    pa.g_nz = c->g_nz;
+    pa.col = c->dn_col[0];
+    pa.gd = c->dn_gd;
+    pa.al = c->dn_al;
+    pa.n = (uint32_t)c->P;
+    if (r.guided) {
+        pa.err = c->err4;
+        pa.vl = c->dn_vl[0];
+    }
+    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
+    launch_denoise_prep(pa, c->stream);
+    int res = 0;
+    if ((rc = denoise_passes(c, r, c->W, c->H, c->dn_col, c->dn_vl, c->dn_gd, c->dn_al, &res))) return rc;
+    c->dn_result = res;
+    c->dn_guided = r.guided;
     return MCPT_OK;
 }
 
@@ -2552,84 +2645,14 @@ int mcpt_guides_read(mcpt_ctx* c, float* albedo, float* normal, float* depth, ui
 int mcpt_denoise_run(mcpt_ctx* c, uint32_t w, uint32_t h, const float* rgb, const uint32_t* samples, const float* albedo,
                      const float* normal, const float* depth, const mcpt_denoise_params* pp, float* out_rgb) {
     if (!c || !rgb || !albedo || !normal || !depth || !out_rgb || !pp) return set_err(c, MCPT_E_INVALID, "denoise: null argument");
-    if (w == 0 || h == 0 || (uint64_t)w * h >= (1ull << 28)) return set_err(c, MCPT_E_INVALID, "denoise: bad image size");
-    int rc = denoise_check_params(c, pp);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t n = (size_t)w * h;
-    free_list(c->tmp_bufs);
-    auto& L = c->tmp_bufs;
-    float *d_rgb, *d_al, *d_n, *d_z;
-    uint32_t* d_s = nullptr;
-    float4 *col[2], *gd, *al;
-    if ((rc = dupload(c, L, &d_rgb, rgb, 3 * n)) || (rc = dupload(c, L, &d_al, albedo, 3 * n)) ||
-        (rc = dupload(c, L, &d_n, normal, 3 * n)) || (rc = dupload(c, L, &d_z, depth, n)) ||
-        (samples && (rc = dupload(c, L, &d_s, samples, n))) || (rc = dalloc(c, L, &col[0], n)) ||
-        (rc = dalloc(c, L, &col[1], n)) || (rc = dalloc(c, L, &gd, n)) || (rc = dalloc(c, L, &al, n))) {
-        free_list(L);
-        return rc;
-    }
-    DenoisePrepArgs pa{};
-    pa.samples = d_s;
-    pa.rgb = d_rgb;
-    pa.normal = d_n;
-    pa.albedo = d_al;
-    pa.depth = d_z;
-    pa.col = col[0];
-    pa.gd = gd;
-    pa.al = al;
-    pa.n = (uint32_t)n;
-    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
-    launch_denoise_prep(pa, c->stream);
-    int res = 0;
-    if ((rc = denoise_passes(c, *pp, w, h, col, gd, al, &res))) return rc;
-    std::vector<float4> o(n);
-    HIPCHK(c, hipMemcpy(o.data(), col[res], n * sizeof(float4), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; i++) { out_rgb[3 * i] = o[i].x; out_rgb[3 * i + 1] = o[i].y; out_rgb[3 * i + 2] = o[i].z; }
-    free_list(L);
-    return MCPT_OK;
+    return denoise_run(c, denoise_request(*pp), w, h, rgb, samples, nullptr, albedo, normal, depth, out_rgb, nullptr);
 }
 
 int mcpt_film_denoise(mcpt_ctx* c, const mcpt_denoise_params* pp) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
     mcpt_denoise_params p;
     if (pp) p = *pp;
     else (void)mcpt_denoise_default_params(&p);
-    int rc = denoise_check_params(c, &p);
-    if (rc) return rc;
-    if (!guides_valid(c))
-        return set_err(c, MCPT_E_INVALID, "denoise: guide buffers missing or stale (camera, scene or film changed): call mcpt_guides_render first");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!c->dn_col[0] || !c->dn_col[1] || !c->dn_gd || !c->dn_al) {
-        c->dn_result = -1;
-        bool ok = true;
-        for (float4** q : {&c->dn_col[0], &c->dn_col[1], &c->dn_gd, &c->dn_al})
-            if (!*q && ok) ok = hipMalloc(q, c->P * sizeof(float4)) == hipSuccess;
-        if (!ok) {
-            (void)hipGetLastError();
-            for (float4** q : {&c->dn_col[0], &c->dn_col[1], &c->dn_gd, &c->dn_al}) {
-                if (*q) (void)hipFree(*q);
-                *q = nullptr;
-            }
-            return set_err(c, MCPT_E_NOMEM, "denoise: plane allocation failed");
-        }
-    }
-    c->dn_result = -1;
-    c->dn_guided = false;
-    DenoisePrepArgs pa{};
-    if ((rc = film_view(c, &pa.Ld, &pa.samples))) return rc;
-    pa.g_alb = c->g_alb;
-    pa.g_nz = c->g_nz;
-    pa.col = c->dn_col[0];
-    pa.gd = c->dn_gd;
-    pa.al = c->dn_al;
-    pa.n = (uint32_t)c->P;
-    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
-    launch_denoise_prep(pa, c->stream);
-    int res = 0;
-    if ((rc = denoise_passes(c, p, c->W, c->H, c->dn_col, c->dn_gd, c->dn_al, &res))) return rc;
-    c->dn_result = res;
-    return MCPT_OK;
+    return film_denoise(c, denoise_request(p));
 }
 
 static int denoised_check(mcpt_ctx* c) {
@@ -2644,10 +2667,7 @@ int mcpt_denoised_read(mcpt_ctx* c, float* rgb) {
     if (!rgb) return set_err(c, MCPT_E_INVALID, "null argument");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::vector<float4> o(c->P);
-    HIPCHK(c, hipMemcpy(o.data(), c->dn_col[c->dn_result], c->P * sizeof(float4), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < c->P; i++) { rgb[3 * i] = o[i].x; rgb[3 * i + 1] = o[i].y; rgb[3 * i + 2] = o[i].z; }
-    return MCPT_OK;
+    return read_rgb(c, c->dn_col[c->dn_result], c->P, rgb);
 }
 
 int mcpt_denoised_read_device(mcpt_ctx* c, void* d_rgb) {
@@ -2708,106 +2728,14 @@ int mcpt_denoise_guided_run(mcpt_ctx* c, uint32_t w, uint32_t h, const float* rg
                             float* out_rgb, float* out_variance) {
     if (!c || !rgb || !variance || !albedo || !normal || !depth || !out_rgb || !pp)
         return set_err(c, MCPT_E_INVALID, "guided denoise: null argument");
-    if (w == 0 || h == 0 || (uint64_t)w * h >= (1ull << 28)) return set_err(c, MCPT_E_INVALID, "guided denoise: bad image size");
-    int rc = denoise_guided_check_params(c, pp);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t n = (size_t)w * h;
-    free_list(c->tmp_bufs);
-    auto& L = c->tmp_bufs;
-    float *d_rgb, *d_al, *d_n, *d_z, *d_v;
-    uint32_t* d_s = nullptr;
-    float4 *col[2], *gd, *al;
-    float2* vl[2];
-    if ((rc = dupload(c, L, &d_rgb, rgb, 3 * n)) || (rc = dupload(c, L, &d_al, albedo, 3 * n)) ||
-        (rc = dupload(c, L, &d_n, normal, 3 * n)) || (rc = dupload(c, L, &d_z, depth, n)) ||
-        (rc = dupload(c, L, &d_v, variance, n)) || (samples && (rc = dupload(c, L, &d_s, samples, n))) ||
-        (rc = dalloc(c, L, &col[0], n)) || (rc = dalloc(c, L, &col[1], n)) || (rc = dalloc(c, L, &gd, n)) ||
-        (rc = dalloc(c, L, &al, n)) || (rc = dalloc(c, L, &vl[0], n)) || (rc = dalloc(c, L, &vl[1], n))) {
-        free_list(L);
-        return rc;
-    }
-    DenoiseGuidedPrepArgs pa{};
-    pa.base.samples = d_s;
-    pa.base.rgb = d_rgb;
-    pa.base.normal = d_n;
-    pa.base.albedo = d_al;
-    pa.base.depth = d_z;
-    pa.base.col = col[0];
-    pa.base.gd = gd;
-    pa.base.al = al;
-    pa.base.n = (uint32_t)n;
-    pa.variance = d_v;
-    pa.vl = vl[0];
-    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
-    launch_denoise_guided_prep(pa, c->stream);
-    int res = 0;
-    if ((rc = denoise_guided_passes(c, *pp, w, h, col, vl, gd, al, &res))) return rc;
-    std::vector<float4> o(n);
-    HIPCHK(c, hipMemcpy(o.data(), col[res], n * sizeof(float4), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; i++) { out_rgb[3 * i] = o[i].x; out_rgb[3 * i + 1] = o[i].y; out_rgb[3 * i + 2] = o[i].z; }
-    if (out_variance) {
-        std::vector<float2> ov(n);
-        HIPCHK(c, hipMemcpy(ov.data(), vl[res], n * sizeof(float2), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < n; i++) out_variance[i] = ov[i].x;
-    }
-    free_list(L);
-    return MCPT_OK;
+    return denoise_run(c, denoise_request(*pp), w, h, rgb, samples, variance, albedo, normal, depth, out_rgb, out_variance);
 }
 
 int mcpt_film_denoise_guided(mcpt_ctx* c, const mcpt_denoise_guided_params* pp) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
     mcpt_denoise_guided_params p;
     if (pp) p = *pp;
     else (void)mcpt_denoise_guided_default_params(&p);
-    int rc = denoise_guided_check_params(c, &p);
-    if (rc) return rc;
-    if (!guides_valid(c))
-        return set_err(c, MCPT_E_INVALID, "denoise: guide buffers missing or stale (camera, scene or film changed): call mcpt_guides_render first");
-    // a fresh estimate, on mcpt_film_error's own path (its checks: >= 2 path slots, no paths in flight)
-    if ((rc = mcpt_film_error(c))) return rc;
-    bool fresh = false;
-    for (float4** q : {&c->dn_col[0], &c->dn_col[1], &c->dn_gd, &c->dn_al})
-        if (!*q) {
-            if (hipMalloc(q, c->P * sizeof(float4)) != hipSuccess) *q = nullptr;
-            fresh = true;
-        }
-    for (float2** q : {&c->dn_vl[0], &c->dn_vl[1]})
-        if (!*q && hipMalloc(q, c->P * sizeof(float2)) != hipSuccess) *q = nullptr;
-    if (fresh) c->dn_result = -1;
-    if (!c->dn_col[0] || !c->dn_col[1] || !c->dn_gd || !c->dn_al || !c->dn_vl[0] || !c->dn_vl[1]) {
-        (void)hipGetLastError();
-        for (float4** q : {&c->dn_col[0], &c->dn_col[1], &c->dn_gd, &c->dn_al}) {
-            if (*q) (void)hipFree(*q);
-            *q = nullptr;
-        }
-        for (float2** q : {&c->dn_vl[0], &c->dn_vl[1]}) {
-            if (*q) (void)hipFree(*q);
-            *q = nullptr;
-        }
-        c->dn_result = -1;
-        c->dn_guided = false;
-        return set_err(c, MCPT_E_NOMEM, "guided denoise: plane allocation failed");
-    }
-    c->dn_result = -1;
-    c->dn_guided = false;
-    DenoiseGuidedPrepArgs pa{};
-    if ((rc = film_view(c, &pa.base.Ld, &pa.base.samples))) return rc;
-    pa.base.g_alb = c->g_alb;
-    pa.base.g_nz = c->g_nz;
-    pa.base.col = c->dn_col[0];
-    pa.base.gd = c->dn_gd;
-    pa.base.al = c->dn_al;
-    pa.base.n = (uint32_t)c->P;
-    pa.err = c->err4;
-    pa.vl = c->dn_vl[0];
-    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
-    launch_denoise_guided_prep(pa, c->stream);
-    int res = 0;
-    if ((rc = denoise_guided_passes(c, p, c->W, c->H, c->dn_col, c->dn_vl, c->dn_gd, c->dn_al, &res))) return rc;
-    c->dn_result = res;
-    c->dn_guided = true;
-    return MCPT_OK;
+    return film_denoise(c, denoise_request(p));
 }
 
 int mcpt_denoised_variance_read(mcpt_ctx* c, float* var) {
@@ -2817,10 +2745,7 @@ int mcpt_denoised_variance_read(mcpt_ctx* c, float* var) {
     if (!var) return set_err(c, MCPT_E_INVALID, "null argument");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::vector<float2> o(c->P);
-    HIPCHK(c, hipMemcpy(o.data(), c->dn_vl[c->dn_result], c->P * sizeof(float2), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < c->P; i++) var[i] = o[i].x;
-    return MCPT_OK;
+    return read_x(c, c->dn_vl[c->dn_result], c->P, var);
 }
 
 int mcpt_debug_denoise_ms(const mcpt_ctx* c, float* out10) {

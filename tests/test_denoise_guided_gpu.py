@@ -302,6 +302,31 @@ def test_error_codes_name_the_missing_step(mcpt_mod, scene_c1):
     pt.close()
 
 
+def test_a_refused_guided_call_keeps_the_plain_result(mcpt_mod, scene_c1):
+    """Both forms share the context's planes.  A guided call that is refused (bad parameters, paths in
+    flight) comes back before it touches them: the plain result stays readable, bit for bit, and the
+    guided call that succeeds afterwards gets its variance planes then."""
+    W, H = 17, 13
+    cam = mcpt_mod.make_camera((0.0, 0.0, 4.0), -90.0, 0.0, aspect=f32(W) / f32(H))
+    pt = make_pt(mcpt_mod, scene_c1[0], cam, W, H, spp=2, depth=3, slots=2)
+    pt.render()
+    pt.render_guides(1)
+    pt.denoise()
+    d1 = pt.denoised()
+    with pytest.raises(mcpt_mod.McptError, match="passes"):
+        pt.denoise_guided(passes=0)
+    assert same_bits(pt.denoised(), d1)
+    pt.clear()
+    assert pt.iterate(1).live_paths > 0
+    with pytest.raises(mcpt_mod.McptError, match="in flight"):
+        pt.denoise_guided()
+    assert same_bits(pt.denoised(), d1)
+    pt.render()
+    pt.denoise_guided()
+    assert pt.denoised_variance().shape == (H, W) and pt.denoised().shape == (H, W, 3)
+    pt.close()
+
+
 def test_guided_denoise_beats_the_plain_one_on_an_8spp_frame(mcpt_mod, scene_c2):
     """Config 2's proxy at 64 x 48, 8 spp in 4 path slots, 4 guide samples, against the renderer's own
     1024-spp frame: MSE(guided) < MSE(plain filter at its defaults) < MSE(raw), with the guided filter
