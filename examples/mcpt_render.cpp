@@ -3,7 +3,7 @@
 // INTEGRATION.md): build a BASELINE config scene with the host builder, upload it,
 // run the wavefront iterations until every pixel has its samples, write PNG + PFM.
 //
-//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]]
+//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>]
 //
 // --denoise renders the first-hit guide buffers (default 4 guide samples per pixel), filters the film
 // with the default parameters and writes <out_prefix>_denoised.png beside the raw image.
@@ -14,6 +14,10 @@
 // film's error from the path slots, builds per-pixel budgets that aim at the relative standard error
 // <target> within [<min>, <max>] and renders on; it needs --slots >= 2 (8 if
 // --slots is not given) and replaces [spp].  It combines with --denoise.
+// --temporal renders <frames> frames at [spp] while the camera yaws by <yaw_step_deg> per frame, gives
+// every frame its own seed, accumulates each into the temporal history and filters it (DESIGN.md section
+// 13); it writes the last frame's <out_prefix>_temporal.png beside that frame's single-frame
+// <out_prefix>_denoised.png.  It uses 2 path slots if --slots is not given (the variance).
 // --tiles-per-call uses the reference orchestration (one 256x256 tile per call,
 // wavefront_kernels.cu:377-442 + Film::update_tile_position) instead of batch mode.
 #include <stdio.h>
@@ -29,7 +33,7 @@ struct Cfg { int w, h, spp, depth; float pos[3], pitch; const char* env; };
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]]\n", argv[0]);
+        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>]\n", argv[0]);
         return 2;
     }
     const Cfg cfgs[6] = {{0, 0, 0, 0, {0, 0, 0}, 0, ""},
@@ -49,7 +53,14 @@ int main(int argc, char** argv) {
     mcpt_sample_budget_params ap;
     mcpt_sample_budget_default_params(&ap);
     uint32_t rounds = 2;
+    uint32_t t_frames = 0;  // > 0: --temporal
+    float t_yaw = 0.f;
     for (int i = 2; i < argc; i++) {
+        if (!strcmp(argv[i], "--temporal")) {
+            if (i + 2 >= argc || atoi(argv[i + 1]) < 1) { fprintf(stderr, "--temporal needs <frames> <yaw_step_deg>\n"); return 2; }
+            t_frames = (uint32_t)atoi(argv[++i]);
+            t_yaw = (float)atof(argv[++i]);
+        }
         if (!strcmp(argv[i], "--gpu-bvh")) gpu_bvh = true;
         if (!strcmp(argv[i], "--reference-bvh")) ref_bvh = true;
         if (!strcmp(argv[i], "--fixed")) fixed = true;
@@ -73,6 +84,7 @@ int main(int argc, char** argv) {
         }
     }
     if (guided_samples && !slots_given) slots = 4;  // the variance is the spread of the path slots' means
+    if (t_frames && !slots_given) slots = 2;  // the variance is the spread of the path slots' means
     if (adaptive && !slots_given) slots = 8;  // the estimate is the spread of the path slots' means
     if (adaptive) c.spp = (int)ap.min_spp;    // the first pass
     const char* assets = getenv("MCPT_ASSETS") ? getenv("MCPT_ASSETS") : "assets";
@@ -124,6 +136,27 @@ int main(int argc, char** argv) {
         }
         st.extend_rays = rays;
         st.ms_total = (float)ms;
+    } else if (t_frames) {  // a preview loop: camera, seed, render, guides, accumulate, filter
+        for (uint32_t f = 0; f < t_frames && !rc; f++) {
+            cp.yaw_deg = -90.f + (float)f * t_yaw;
+            mcpt_stage_stats one{};
+            // (a seed per frame that differs in every bit field: seeds one apart repeat each other's samples)
+            if ((rc = mcpt_camera_make(&cp, &cam)) || (rc = mcpt_camera_set(ctx, &cam)) ||
+                (rc = mcpt_set_seed(ctx, 0x9E3779B97F4A7C15ull * (uint64_t)(f + 1))) || (rc = mcpt_render(ctx, &one)) ||
+                (rc = mcpt_guides_render(ctx, 4)) || (rc = mcpt_film_temporal(ctx, nullptr)) ||
+                (rc = mcpt_temporal_denoise(ctx, nullptr)))
+                break;
+            st.extend_rays += one.extend_rays;
+            st.shadow_rays += one.shadow_rays;
+            st.vis_rays += one.vis_rays;
+            st.ms_total += one.ms_total;
+        }
+        float tms = 0.f;
+        if (!rc) rc = mcpt_debug_temporal_ms(ctx, &tms);
+        if (!rc) rc = mcpt_denoised_write_png(ctx, 1.f, (out + "_temporal.png").c_str());
+        if (!rc) rc = mcpt_film_denoise(ctx, nullptr);  // the last frame alone, for comparison
+        if (!rc) rc = mcpt_denoised_write_png(ctx, 1.f, (out + "_denoised.png").c_str());
+        if (!rc) printf("temporal: %u frames, %.2f degrees per frame, last accumulation %.3f ms\n", t_frames, t_yaw, tms);
     } else {
         rc = mcpt_render(ctx, &st);  // batch: every tile per iteration until all pixels have spp
         // adaptive: estimate -> budget -> render on, `rounds` times

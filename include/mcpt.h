@@ -413,6 +413,66 @@ int mcpt_budget_from_error(mcpt_ctx *ctx, const mcpt_sample_budget_params *p, ui
  * and the device times (ms) of the last error kernel (out2[0]) and budget kernel (out2[1]). */
 int64_t mcpt_debug_adaptive_bytes(const mcpt_ctx *ctx);
 int mcpt_debug_adaptive_ms(const mcpt_ctx *ctx, float *out2);
+/* ---- temporal accumulation: the previous accumulated frame reprojected into
+ * the current one, SVGF's temporal half (Schied et al. 2017, 4.1 - 4.2), between the film and the
+ * a-trous passes.  Opt-in: a context that never calls these allocates and launches nothing for them.
+ *
+ * mcpt_set_seed sets the seed of a live context and clears the film: a sample is keyed by (seed, pixel,
+ * sample index), so frames after a clear repeat their noise unless the seed changes, and temporal reuse
+ * needs frames that do not.  MCPT_E_INVALID while paths are in flight.  The guide buffers become stale
+ * (lens guide rays are keyed by the seed); the temporal history stays.  The seed is XORed onto
+ * (pixel << 32 | sample index) before it is hashed, so seeds that differ in their low bits alone hand a
+ * pixel the same samples in another order (k and k ^ 1 at 2 spp): give successive frames seeds that
+ * differ in every bit field, e.g. (frame + 1) * 0x9E3779B97F4A7C15. */
+int mcpt_set_seed(mcpt_ctx *ctx, uint64_t seed);
+/* Host only: proj * view = inverse(cam->inv_view_proj), column-major, by cofactors in double rounded
+ * once.  The matrix mcpt_film_temporal stores as VP_prev, and the one mcpt_temporal_run takes. */
+int mcpt_camera_view_proj(const mcpt_camera *cam, float *out16);
+/* Per pixel: X = world position of the first hit (pinhole ray origin + depth * direction; with a lens
+ * the centre-of-lens ray), projected with VP_prev to the previous frame's pixel grid; a bilinear tap of
+ * the previous accumulated colour whose corners must lie inside the film, hold a history, and agree in
+ * position (|X_q - X| <= pos_tol * depth) and normal (|n_q - n| <= nrm_tol); then with s the pixel's
+ * sample count and N_h the tap's:
+ *   N_c = min(N_h, max_history),  alpha = max(s / (N_c + s), alpha_min),
+ *   c' = h + alpha (c - h),  N' = N_c + s,  v' = (1 - alpha)^2 v_h + alpha^2 v_c
+ * v' is known only where both variances are.  Without an accepted corner (a disocclusion, the first
+ * call, a pixel whose depth is not a finite number > 0): c' = c, N' = s, v' = v_c. */
+typedef struct mcpt_temporal_params {
+    float pos_tol;       /* >= 0, relative to the pixel's depth */
+    float nrm_tol;       /* >= 0 */
+    float max_history;   /* >= 0, in samples */
+    float alpha_min;     /* 0..1 */
+} mcpt_temporal_params;
+int mcpt_temporal_default_params(mcpt_temporal_params *p);
+/* Accumulate the film into the history (p == NULL: the defaults): needs valid guides and no paths in
+ * flight; with >= 2 path slots v_c = se^2 of a fresh mcpt_film_error estimate, with 1 slot every
+ * variance is unknown.  Uses the camera and planes the previous call stored, then stores this call's.
+ * The first call, and any call after a reset, accumulates nothing.  mcpt_temporal_reset drops the
+ * history, and so do a scene upload and mcpt_film_resize; film clears, mcpt_set_seed, camera changes
+ * and mcpt_set_path_slots keep it. */
+int mcpt_film_temporal(mcpt_ctx *ctx, const mcpt_temporal_params *p);
+int mcpt_temporal_reset(mcpt_ctx *ctx);
+/* The last accumulated frame: rgb 3*W*H, nsamples W*H (N'), variance W*H (-1 unknown), position 3*W*H
+ * (zero where the pixel was not reprojectable); any may be NULL.  MCPT_E_INVALID before the first
+ * accumulation. */
+int mcpt_temporal_read(mcpt_ctx *ctx, float *rgb, float *nsamples, float *variance, float *position);
+/* The guided a-trous passes over the last accumulated frame (p == NULL: the guided defaults), under the
+ * camera it was accumulated at; the mcpt_denoised_* readers and mcpt_denoised_variance_read serve the
+ * result. */
+int mcpt_temporal_denoise(mcpt_ctx *ctx, const mcpt_denoise_guided_params *p);
+/* The same kernel over host images (the counterpart of mcpt_denoise_guided_run; needs neither a scene
+ * nor a film).  Current frame: rgb / position / normal 3*w*h, samples / variance / depth w*h.  History:
+ * hcol {r, g, b, N}, hpos {X, v}, hnrm {n, depth}, 4*w*h each, as a previous call returned them (all
+ * zero: none).  Out: col {r, g, b, valid} 4*w*h, vl {variance, luminance} 2*w*h, and the new history. */
+int mcpt_temporal_run(mcpt_ctx *ctx, uint32_t w, uint32_t h, const float *rgb, const uint32_t *samples,
+                      const float *variance, const float *position, const float *normal, const float *depth,
+                      const float *hcol, const float *hpos, const float *hnrm, const float *vp_prev16,
+                      const mcpt_temporal_params *p, float *out_col, float *out_vl, float *out_hcol, float *out_hpos,
+                      float *out_hnrm);
+/* Device bytes held for the temporal stage (0 until the first mcpt_film_temporal) and the device time
+ * (ms) of the last k_temporal launch. */
+int64_t mcpt_debug_temporal_bytes(const mcpt_ctx *ctx);
+int mcpt_debug_temporal_ms(const mcpt_ctx *ctx, float *out1);
 int mcpt_sync(mcpt_ctx *ctx);
 int mcpt_device_name(mcpt_ctx *ctx, char *buf, int32_t len);
 /* diagnostics: rays of the current extension (which=0) or any-hit (which=1) queue, and the

@@ -597,6 +597,32 @@ public:
     void write_denoised_png(const std::shared_ptr<Film>& film, const std::string& path) {
         detail::check(mcpt_denoised_write_png(ctx_, film->get_exposure(), path.c_str()), ctx_, "write_denoised_png");
     }
+    // Temporal accumulation (mcpt.h): set_seed gives the next frame its own noise (it clears the film and
+    // makes the guides stale; seeds of successive frames should differ in more than their low bits);
+    // temporal_accumulate renders the guides of the current camera and blends the film into the
+    // history the previous call left; temporal_denoise runs the guided passes over the accumulated
+    // frame, read like denoise()'s result; temporal_reset drops the history.
+    void set_seed(uint64_t seed) {
+        detail::check(mcpt_set_seed(ctx_, seed), ctx_, "set_seed");
+        cfg_.seed = seed;
+    }
+    void temporal_accumulate(uint32_t guide_samples = 4, const mcpt_temporal_params* params = nullptr) {
+        if (guide_samples) detail::check(mcpt_guides_render(ctx_, guide_samples), ctx_, "guides");
+        detail::check(mcpt_film_temporal(ctx_, params), ctx_, "temporal_accumulate");
+    }
+    // rgb 3*W*H, nsamples / variance W*H (variance -1: unknown)
+    void temporal(std::vector<float>& rgb, std::vector<float>& nsamples, std::vector<float>& variance) {
+        uint32_t w = 0, h = 0;
+        detail::check(mcpt_film_size(ctx_, &w, &h), ctx_, "temporal");
+        rgb.resize((size_t)w * h * 3);
+        nsamples.resize((size_t)w * h);
+        variance.resize((size_t)w * h);
+        detail::check(mcpt_temporal_read(ctx_, rgb.data(), nsamples.data(), variance.data(), nullptr), ctx_, "temporal");
+    }
+    void temporal_denoise(const mcpt_denoise_guided_params* params = nullptr) {
+        detail::check(mcpt_temporal_denoise(ctx_, params), ctx_, "temporal_denoise");
+    }
+    void temporal_reset() { detail::check(mcpt_temporal_reset(ctx_), ctx_, "temporal_reset"); }
     // Adaptive sampling (mcpt.h): a per-pixel sample budget (W*H entries; empty: remove it) in place of
     // the uniform spp, and the uniform spp of the live context.  Neither clears the film: the next
     // render_frame renders on.  Call them once the film's size is the context's (after a render).

@@ -27,6 +27,7 @@
 #include "device/adaptive.hpp"
 #include "device/denoise.hpp"
 #include "device/mcpt_core.hpp"
+#include "device/temporal.hpp"
 
 namespace mcpt_dev {
 
@@ -465,5 +466,33 @@ struct SlotImageArgs {
 void launch_film_error(const FilmErrorArgs& a, hipStream_t s);
 void launch_budget(const BudgetArgs& a, hipStream_t s);
 void launch_slot_image(const SlotImageArgs& a, hipStream_t s);
+
+// ---- temporal accumulation (temporal.hip) ----
+// k_temporal over a W x H frame: the previous call's history planes hcol / hpos / hnrm and VP_prev in,
+// the colour and vl planes for the spatial passes and the new history planes out.  The current frame
+// comes from the film (Ld != nullptr: Ld / samples, err {se, ...} or nullptr without an estimate, the
+// guide sums and the camera records) or from caller images of means (rgb / position / normal 3 floats
+// per pixel, variance / depth 1, samples).
+struct TemporalArgs {
+    int W, H;
+    mcpt::TemporalParams k;
+    float vp_prev[16];
+    const uint32_t* samples;
+    const float4 *Ld, *err, *g_alb, *g_nz, *cam_px, *cam_dir;
+    mcpt::CamView cam;
+    const float *rgb, *variance, *position, *normal, *depth;
+    const float4 *hcol, *hpos, *hnrm;
+    float4* col;
+    float2* vl;
+    float4 *out_hcol, *out_hpos, *out_hnrm;
+};
+// The spatial passes' planes of n pixels from an accumulated frame: its colour and vl planes copied, the
+// guide and albedo planes from the guide sums as k_denoise_prep_film forms them
+struct TemporalPrepArgs {
+    const float4* tcol; const float2* tvl; const float4 *g_alb, *g_nz;
+    float4 *col, *gd, *al; float2* vl; uint32_t n;
+};
+void launch_temporal(const TemporalArgs& a, hipStream_t s);
+void launch_temporal_prep(const TemporalPrepArgs& a, hipStream_t s);
 
 }  // namespace mcpt_dev

@@ -162,6 +162,21 @@ struct mcpt_ctx {
     unsigned long long* bud_cnt = nullptr;
     size_t adaptive_bytes = 0;     // device bytes held by the above (mcpt_debug_adaptive_bytes)
     float err_ms = 0.f, budget_ms = 0.f;  // device times of the last k_film_error / k_budget
+    // Temporal accumulation, allocated by the first mcpt_film_temporal: two sets
+    // of history planes {hcol, hpos, hnrm} in ping-pong (a call gathers from one and writes the other;
+    // tp_set: the one that holds the last accumulated frame), that frame's colour and vl planes for
+    // the spatial passes, and its camera (tp_ok: there is such a frame).  Film clears, seed, camera and
+    // slot changes keep them; a scene upload and mcpt_temporal_reset forget the frame, mcpt_film_resize
+    // frees everything.
+    float4* tp_h[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+    float4* tp_col = nullptr;
+    float2* tp_vl = nullptr;
+    int tp_set = 0;
+    bool tp_ok = false;
+    mcpt::CamView tp_cam{};
+    size_t tp_bytes = 0;  // device bytes held by the above (mcpt_debug_temporal_bytes)
+    float tp_ms = 0.f;    // device time of the last k_temporal
+    uint64_t guides_seed = 0;  // the seed the guides were rendered with (their lens rays are keyed by it)
 };
 
 static int set_err(mcpt_ctx* c, int rc, const std::string& msg) {
@@ -241,6 +256,15 @@ static void adaptive_free(mcpt_ctx* c) {
     c->budget_on = c->err_ok = false;
     c->budget_max = 0;
     c->adaptive_bytes = 0;
+}
+static void temporal_free(mcpt_ctx* c) {
+    for (void** q : {(void**)&c->tp_h[0][0], (void**)&c->tp_h[0][1], (void**)&c->tp_h[0][2], (void**)&c->tp_h[1][0],
+                     (void**)&c->tp_h[1][1], (void**)&c->tp_h[1][2], (void**)&c->tp_col, (void**)&c->tp_vl}) {
+        if (*q) (void)hipFree(*q);
+        *q = nullptr;
+    }
+    c->tp_ok = false;
+    c->tp_bytes = 0;
 }
 static void free_list(std::vector<void*>& v) {
     for (void* q : v)
@@ -344,6 +368,7 @@ void mcpt_destroy(mcpt_ctx* c) {
     prim_free(c);
     denoise_free(c);
     adaptive_free(c);
+    temporal_free(c);
     for (auto e : c->events) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -965,6 +990,7 @@ static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
     }
     c->scene = s;
     c->scene_gen++;  // with the scene itself: the previous scene's primary-hit table is stale (prim_table)
+    c->tp_ok = false;  // ... and so is the temporal history (no motion vectors for moved geometry)
     c->ntri = d->ntri;
     c->occ_init = nullptr;  // (the previous scene's copy went with scene_bufs)
     if (s.occ) {
@@ -1238,6 +1264,11 @@ int mcpt_film_resize(mcpt_ctx* c, uint32_t w, uint32_t h, uint32_t tw, uint32_t 
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         adaptive_free(c);
+    }
+    if (c->tp_bytes) {  // ... and so does the temporal history
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        temporal_free(c);
     }
     return film_resize(c, w, h, tw, th);
 }
@@ -2358,7 +2389,7 @@ int mcpt_debug_shade_sections(mcpt_ctx* c, uint64_t* out, int n, int reset) {
 // (device/denoise.hpp, denoise.hip) between the film and the display.
 // ---------------------------------------------------------------------------
 static bool guides_valid(const mcpt_ctx* c) {
-    return c->guides_ok && c->g_alb && c->g_nz && c->guides_scene_gen == c->scene_gen &&
+    return c->guides_ok && c->g_alb && c->g_nz && c->guides_scene_gen == c->scene_gen && c->guides_seed == c->cfg.seed &&
            memcmp(&c->guides_cam, &c->cam, sizeof(c->cam)) == 0;
 }
 // One filter request, from either parameter struct: the plain parameters, and with `guided` the
@@ -2621,6 +2652,7 @@ int mcpt_guides_render(mcpt_ctx* c, uint32_t nsamples) {
     if (!drained) return set_err(c, MCPT_E_HIP, "guides: k_trace left rays untraced");
     c->guides_scene_gen = c->scene_gen;
     c->guides_cam = c->cam;
+    c->guides_seed = c->cfg.seed;
     c->guides_ok = true;
     return MCPT_OK;
 }
@@ -2997,6 +3029,233 @@ int mcpt_debug_adaptive_ms(const mcpt_ctx* c, float* out2) {
     if (!c || !out2) return MCPT_E_INVALID;
     out2[0] = c->err_ms;
     out2[1] = c->budget_ms;
+    return MCPT_OK;
+}
+
+// ---- temporal accumulation ----
+
+int mcpt_set_seed(mcpt_ctx* c, uint64_t seed) {
+    if (!c) return MCPT_E_INVALID;
+    if (c->P) {
+        HIPCHK(c, hipSetDevice(c->device));
+        bool live = false;
+        int rc = paths_in_flight(c, &live);
+        if (rc) return rc;
+        if (live) return set_err(c, MCPT_E_INVALID, "set_seed: paths are in flight (finish the render or clear the film)");
+    }
+    c->cfg.seed = seed;  // (guides_valid compares it: the guides are stale from here on)
+    return c->P ? mcpt_film_clear(c) : MCPT_OK;
+}
+
+int mcpt_camera_view_proj(const mcpt_camera* cam, float* out16) {
+    if (!cam || !out16) return MCPT_E_INVALID;
+    mcpt::tp_view_proj(cam->inv_view_proj, out16);
+    return MCPT_OK;
+}
+
+int mcpt_temporal_default_params(mcpt_temporal_params* p) {
+    if (!p) return MCPT_E_INVALID;
+    // the best row of profiles/temporal_defaults.txt (8 frames of 2 spp against 1024 spp; configs 1, 2, cube).
+    // With 2-spp frames max_history 8 bounds alpha at 0.2 from below, SVGF's value; the rows that reach
+    // that bound through alpha_min tie with it exactly.
+    p->pos_tol = 0.1f;
+    p->nrm_tol = 1.0f;
+    p->max_history = 8.f;
+    p->alpha_min = 0.f;
+    return MCPT_OK;
+}
+
+static int temporal_check_params(mcpt_ctx* c, const mcpt_temporal_params& p) {
+    const auto bad = [](float v) { return !(v >= 0.f) || !(v <= 3.402823466e+38f); };
+    if (bad(p.pos_tol)) return set_err(c, MCPT_E_INVALID, "temporal: pos_tol must be a finite number >= 0");
+    if (bad(p.nrm_tol)) return set_err(c, MCPT_E_INVALID, "temporal: nrm_tol must be a finite number >= 0");
+    if (bad(p.max_history)) return set_err(c, MCPT_E_INVALID, "temporal: max_history must be a finite number >= 0");
+    if (bad(p.alpha_min) || p.alpha_min > 1.f) return set_err(c, MCPT_E_INVALID, "temporal: alpha_min must be in [0, 1]");
+    return MCPT_OK;
+}
+static mcpt::TemporalParams temporal_params(const mcpt_temporal_params& p) {
+    return mcpt::TemporalParams{p.pos_tol, p.nrm_tol, p.max_history, p.alpha_min};
+}
+// k_temporal between events 0 and 1 of the context's stream; its device time -> tp_ms
+static int temporal_launch(mcpt_ctx* c, const TemporalArgs& a) {
+    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
+    launch_temporal(a, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev(c, 1), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipEventElapsedTime(&c->tp_ms, c->events[0], c->events[1]));
+    return MCPT_OK;
+}
+
+int mcpt_film_temporal(mcpt_ctx* c, const mcpt_temporal_params* pp) {
+    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    mcpt_temporal_params p;
+    if (pp) p = *pp;
+    else (void)mcpt_temporal_default_params(&p);
+    int rc = temporal_check_params(c, p);
+    if (rc) return rc;
+    if (!guides_valid(c))
+        return set_err(c, MCPT_E_INVALID, "temporal: guide buffers missing or stale (camera, scene, seed or film changed): call mcpt_guides_render first");
+    HIPCHK(c, hipSetDevice(c->device));
+    bool live = false;
+    if ((rc = paths_in_flight(c, &live))) return rc;
+    if (live) return set_err(c, MCPT_E_INVALID, "temporal: paths are in flight");
+    if (c->slots >= 2 && (rc = mcpt_film_error(c))) return rc;
+    if (!c->tp_bytes) {
+        bool ok = true;
+        const auto need = [&](void** q, size_t bytes) {
+            if (ok && hipMalloc(q, bytes) != hipSuccess) {
+                *q = nullptr;
+                ok = false;
+            }
+        };
+        for (int s = 0; s < 2; s++)
+            for (int k = 0; k < 3; k++) need((void**)&c->tp_h[s][k], c->P * sizeof(float4));
+        need((void**)&c->tp_col, c->P * sizeof(float4));
+        need((void**)&c->tp_vl, c->P * sizeof(float2));
+        if (!ok) {
+            (void)hipGetLastError();
+            temporal_free(c);
+            return set_err(c, MCPT_E_NOMEM, "temporal: plane allocation failed");
+        }
+        c->tp_bytes = c->P * (7 * sizeof(float4) + sizeof(float2));
+    }
+    const int prev = c->tp_set, next = prev ^ 1;
+    if (!c->tp_ok)  // no history: N = 0 everywhere, and every tap is rejected
+        for (int k = 0; k < 3; k++) HIPCHK(c, hipMemsetAsync(c->tp_h[prev][k], 0, c->P * sizeof(float4), c->stream));
+    TemporalArgs a{};
+    a.W = (int)c->W;
+    a.H = (int)c->H;
+    a.k = temporal_params(p);
+    mcpt::tp_view_proj(c->tp_ok ? c->tp_cam.ivp : c->cam.ivp, a.vp_prev);
+    if ((rc = film_view(c, &a.Ld, &a.samples))) return rc;
+    a.err = c->slots >= 2 ? c->err4 : nullptr;
+    a.g_alb = c->g_alb;
+    a.g_nz = c->g_nz;
+    if ((rc = cam_table(c, c->W, c->H, &a.cam_px, &a.cam_dir))) return rc;
+    a.cam = c->cam;
+    a.hcol = c->tp_h[prev][0];
+    a.hpos = c->tp_h[prev][1];
+    a.hnrm = c->tp_h[prev][2];
+    a.col = c->tp_col;
+    a.vl = c->tp_vl;
+    a.out_hcol = c->tp_h[next][0];
+    a.out_hpos = c->tp_h[next][1];
+    a.out_hnrm = c->tp_h[next][2];
+    c->tp_ok = false;
+    if ((rc = temporal_launch(c, a))) return rc;
+    c->tp_set = next;
+    c->tp_cam = c->cam;
+    c->tp_ok = true;
+    return MCPT_OK;
+}
+
+int mcpt_temporal_reset(mcpt_ctx* c) {
+    if (!c) return MCPT_E_INVALID;
+    c->tp_ok = false;
+    return MCPT_OK;
+}
+
+int mcpt_temporal_read(mcpt_ctx* c, float* rgb, float* nsamples, float* variance, float* position) {
+    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    if (!c->tp_ok) return set_err(c, MCPT_E_INVALID, "no accumulated frame: call mcpt_film_temporal first");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<float4> hc(c->P), hp(c->P);
+    HIPCHK(c, hipMemcpy(hc.data(), c->tp_h[c->tp_set][0], c->P * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(hp.data(), c->tp_h[c->tp_set][1], c->P * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < c->P; i++) {
+        if (rgb) { rgb[3 * i] = hc[i].x; rgb[3 * i + 1] = hc[i].y; rgb[3 * i + 2] = hc[i].z; }
+        if (nsamples) nsamples[i] = hc[i].w;
+        if (variance) variance[i] = hp[i].w;
+        if (position) { position[3 * i] = hp[i].x; position[3 * i + 1] = hp[i].y; position[3 * i + 2] = hp[i].z; }
+    }
+    return MCPT_OK;
+}
+
+int mcpt_temporal_denoise(mcpt_ctx* c, const mcpt_denoise_guided_params* pp) {
+    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    mcpt_denoise_guided_params p;
+    if (pp) p = *pp;
+    else (void)mcpt_denoise_guided_default_params(&p);
+    const DenoiseRequest r = denoise_request(p);
+    int rc = denoise_check_params(c, r);
+    if (rc) return rc;
+    if (!c->tp_ok) return set_err(c, MCPT_E_INVALID, "temporal denoise: no accumulated frame: call mcpt_film_temporal first");
+    if (!guides_valid(c) || memcmp(&c->tp_cam, &c->cam, sizeof(c->cam)) != 0)
+        return set_err(c, MCPT_E_INVALID, "temporal denoise: the camera, scene or seed changed since the frame was accumulated: call mcpt_guides_render and mcpt_film_temporal first");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!denoise_planes_ensure(c, true)) return set_err(c, MCPT_E_NOMEM, "temporal denoise: plane allocation failed");
+    const TemporalPrepArgs pa{c->tp_col, c->tp_vl, c->g_alb, c->g_nz, c->dn_col[0], c->dn_gd, c->dn_al, c->dn_vl[0], (uint32_t)c->P};
+    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
+    launch_temporal_prep(pa, c->stream);
+    int res = 0;
+    if ((rc = denoise_passes(c, r, c->W, c->H, c->dn_col, c->dn_vl, c->dn_gd, c->dn_al, &res))) return rc;
+    c->dn_result = res;
+    c->dn_guided = true;
+    return MCPT_OK;
+}
+
+int mcpt_temporal_run(mcpt_ctx* c, uint32_t w, uint32_t h, const float* rgb, const uint32_t* samples, const float* variance,
+                      const float* position, const float* normal, const float* depth, const float* hcol, const float* hpos,
+                      const float* hnrm, const float* vp_prev16, const mcpt_temporal_params* pp, float* out_col, float* out_vl,
+                      float* out_hcol, float* out_hpos, float* out_hnrm) {
+    if (!c || !rgb || !samples || !variance || !position || !normal || !depth || !hcol || !hpos || !hnrm || !vp_prev16 || !pp ||
+        !out_col || !out_vl || !out_hcol || !out_hpos || !out_hnrm)
+        return set_err(c, MCPT_E_INVALID, "temporal: null argument");
+    if (w == 0 || h == 0 || (uint64_t)w * h >= (1ull << 28)) return set_err(c, MCPT_E_INVALID, "temporal: bad image size");
+    int rc = temporal_check_params(c, *pp);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = (size_t)w * h;
+    free_list(c->tmp_bufs);
+    auto& L = c->tmp_bufs;
+    float *d_rgb, *d_v, *d_x, *d_n, *d_z, *d_hc, *d_hp, *d_hn;
+    uint32_t* d_s;
+    float4 *o_col, *o_hc, *o_hp, *o_hn;
+    float2* o_vl;
+    if ((rc = dupload(c, L, &d_rgb, rgb, 3 * n)) || (rc = dupload(c, L, &d_s, samples, n)) || (rc = dupload(c, L, &d_v, variance, n)) ||
+        (rc = dupload(c, L, &d_x, position, 3 * n)) || (rc = dupload(c, L, &d_n, normal, 3 * n)) ||
+        (rc = dupload(c, L, &d_z, depth, n)) || (rc = dupload(c, L, &d_hc, hcol, 4 * n)) || (rc = dupload(c, L, &d_hp, hpos, 4 * n)) ||
+        (rc = dupload(c, L, &d_hn, hnrm, 4 * n)) || (rc = dalloc(c, L, &o_col, n)) || (rc = dalloc(c, L, &o_vl, n)) ||
+        (rc = dalloc(c, L, &o_hc, n)) || (rc = dalloc(c, L, &o_hp, n)) || (rc = dalloc(c, L, &o_hn, n))) {
+        free_list(L);
+        return rc;
+    }
+    TemporalArgs a{};
+    a.W = (int)w;
+    a.H = (int)h;
+    a.k = temporal_params(*pp);
+    memcpy(a.vp_prev, vp_prev16, sizeof(a.vp_prev));
+    a.samples = d_s;
+    a.rgb = d_rgb;
+    a.variance = d_v;
+    a.position = d_x;
+    a.normal = d_n;
+    a.depth = d_z;
+    a.hcol = (const float4*)d_hc;
+    a.hpos = (const float4*)d_hp;
+    a.hnrm = (const float4*)d_hn;
+    a.col = o_col;
+    a.vl = o_vl;
+    a.out_hcol = o_hc;
+    a.out_hpos = o_hp;
+    a.out_hnrm = o_hn;
+    if ((rc = temporal_launch(c, a))) return rc;
+    HIPCHK(c, hipMemcpy(out_col, o_col, n * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out_vl, o_vl, n * sizeof(float2), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out_hcol, o_hc, n * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out_hpos, o_hp, n * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out_hnrm, o_hn, n * sizeof(float4), hipMemcpyDeviceToHost));
+    free_list(L);
+    return MCPT_OK;
+}
+
+int64_t mcpt_debug_temporal_bytes(const mcpt_ctx* c) { return c ? (int64_t)c->tp_bytes : (int64_t)MCPT_E_INVALID; }
+
+int mcpt_debug_temporal_ms(const mcpt_ctx* c, float* out1) {
+    if (!c || !out1) return MCPT_E_INVALID;
+    out1[0] = c->tp_ms;
     return MCPT_OK;
 }
 

@@ -88,6 +88,10 @@ class SampleBudgetParams(C.Structure):  # mcpt_sample_budget_params
     _fields_ = [("target_rel_err", C.c_float), ("lum_floor", C.c_float), ("min_spp", C.c_uint32), ("max_spp", C.c_uint32)]
 
 
+class TemporalParams(C.Structure):  # mcpt_temporal_params
+    _fields_ = [("pos_tol", C.c_float), ("nrm_tol", C.c_float), ("max_history", C.c_float), ("alpha_min", C.c_float)]
+
+
 class PathView(C.Structure):  # mcpt_path_view: path state at the shading stages' boundary
     _fields_ = [("film_w", C.c_uint32), ("film_h", C.c_uint32), ("flags", _u), ("samples", _u), ("hit_tri", _i),
                 ("ray_o", _f), ("ray_d", _f), ("beta", _f), ("nee0", _f), ("nee1", _f),
@@ -172,6 +176,17 @@ ABI = {
     "mcpt_budget_from_error": (C.c_int, [C.c_void_p, C.POINTER(SampleBudgetParams), C.POINTER(C.c_uint64)]),
     "mcpt_debug_adaptive_bytes": (C.c_int64, [C.c_void_p]),
     "mcpt_debug_adaptive_ms": (C.c_int, [C.c_void_p, _f]),
+    "mcpt_set_seed": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "mcpt_camera_view_proj": (C.c_int, [C.POINTER(Camera), _f]),
+    "mcpt_temporal_default_params": (C.c_int, [C.POINTER(TemporalParams)]),
+    "mcpt_film_temporal": (C.c_int, [C.c_void_p, C.POINTER(TemporalParams)]),
+    "mcpt_temporal_reset": (C.c_int, [C.c_void_p]),
+    "mcpt_temporal_read": (C.c_int, [C.c_void_p, _f, _f, _f, _f]),
+    "mcpt_temporal_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseGuidedParams)]),
+    "mcpt_temporal_run": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _f, _u, _f, _f, _f, _f, _f, _f, _f, _f,
+                                    C.POINTER(TemporalParams), _f, _f, _f, _f, _f]),
+    "mcpt_debug_temporal_bytes": (C.c_int64, [C.c_void_p]),
+    "mcpt_debug_temporal_ms": (C.c_int, [C.c_void_p, _f]),
     "mcpt_sync": (C.c_int, [C.c_void_p]),
     "mcpt_device_name": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
     "mcpt_debug_queue_rays": (C.c_int, [C.c_void_p, C.c_int, _f, _f, _u]),
@@ -636,6 +651,50 @@ class PathTracer:
         self._ck(lib().mcpt_debug_denoise_ms(self.h, v))
         return {"guides": float(v[0]), "prepare": float(v[1]), "passes": [float(x) for x in v[2:]]}
 
+    # ---- temporal accumulation ----
+    def set_seed(self, seed):
+        """Seed of the live context (mcpt_set_seed): clears the film and makes the guides stale; the
+        temporal history stays."""
+        self._ck(lib().mcpt_set_seed(self.h, int(seed)))
+        self.cfg.seed = int(seed)
+
+    def temporal_accumulate(self, **params):
+        """Reproject the previous accumulated frame into the film's and blend the two
+        (mcpt_film_temporal); keyword arguments override the defaults (pos_tol, nrm_tol, max_history,
+        alpha_min).  Needs render_guides() under the current camera."""
+        p = temporal_params(**params) if params else None
+        self._ck(lib().mcpt_film_temporal(self.h, C.byref(p) if p is not None else None))
+
+    def temporal(self) -> dict:
+        """The last accumulated frame (mcpt_temporal_read): rgb / position (H, W, 3), nsamples /
+        variance (H, W; variance -1 where unknown)."""
+        P = self.W * self.H
+        rgb, pos = np.zeros(3 * P, np.float32), np.zeros(3 * P, np.float32)
+        ns, var = np.zeros(P, np.float32), np.zeros(P, np.float32)
+        self._ck(lib().mcpt_temporal_read(self.h, fptr(rgb), fptr(ns), fptr(var), fptr(pos)))
+        return {"rgb": rgb.reshape(self.H, self.W, 3), "nsamples": ns.reshape(self.H, self.W),
+                "variance": var.reshape(self.H, self.W), "position": pos.reshape(self.H, self.W, 3)}
+
+    def temporal_denoise(self, **params):
+        """The guided a-trous passes over the last accumulated frame (mcpt_temporal_denoise); read the
+        result like denoise_guided()'s.  Keyword arguments override the guided defaults."""
+        p = denoise_guided_params(**params) if params else None
+        self._ck(lib().mcpt_temporal_denoise(self.h, C.byref(p) if p is not None else None))
+
+    def temporal_reset(self):
+        """Drop the temporal history (mcpt_temporal_reset): the next temporal_accumulate() starts over."""
+        self._ck(lib().mcpt_temporal_reset(self.h))
+
+    def temporal_bytes(self) -> int:
+        """Device bytes held for the temporal stage (mcpt_debug_temporal_bytes): 0 until it is used."""
+        return int(lib().mcpt_debug_temporal_bytes(self.h))
+
+    def temporal_ms(self) -> float:
+        """Device time of the last k_temporal launch (mcpt_debug_temporal_ms)."""
+        v = (C.c_float * 1)()
+        self._ck(lib().mcpt_debug_temporal_ms(self.h, v))
+        return float(v[0])
+
     # ---- adaptive sampling (DESIGN.md section 11) ----
     def set_sample_budget(self, budget=None):
         """Per-pixel sample budget ((H, W) uint32; mcpt_set_sample_budget) in place of the uniform spp;
@@ -817,6 +876,45 @@ def denoise_guided_params(**kw) -> DenoiseGuidedParams:
             raise TypeError(f"unknown guided denoise parameter {k!r}")
         setattr(p, k, v)
     return p
+
+
+def temporal_params(**kw) -> TemporalParams:
+    """mcpt_temporal_default_params with keyword overrides."""
+    p = TemporalParams()
+    _check(lib().mcpt_temporal_default_params(C.byref(p)))
+    for k, v in kw.items():
+        if k not in dict(TemporalParams._fields_):
+            raise TypeError(f"unknown temporal parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def camera_view_proj(cam: Camera):
+    """proj * view of a Camera as 16 float32, column-major (mcpt_camera_view_proj): the inverse of its
+    inv_view_proj, the matrix the temporal stage projects into the previous frame with."""
+    out = np.zeros(16, np.float32)
+    _check(lib().mcpt_camera_view_proj(C.byref(cam), fptr(out)))
+    return out
+
+
+def temporal_run(pt, rgb, samples, variance, position, normal, depth, hcol, hpos, hnrm, vp_prev, **params):
+    """mcpt_temporal_run on PathTracer pt: the temporal stage over host images of the current frame
+    ((H, W, 3) rgb / position / normal, (H, W) samples / variance / depth), the three (H, W, 4) history
+    planes of the previous call and VP_prev; returns (col (H, W, 4), vl (H, W, 2), hcol, hpos, hnrm)."""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    H, W = rgb.shape[:2]
+    sm = np.ascontiguousarray(samples, np.uint32).reshape(H, W)
+    var = np.ascontiguousarray(variance, np.float32).reshape(H, W)
+    pos = np.ascontiguousarray(position, np.float32).reshape(H, W, 3)
+    nm = np.ascontiguousarray(normal, np.float32).reshape(H, W, 3)
+    z = np.ascontiguousarray(depth, np.float32).reshape(H, W)
+    hist = [np.ascontiguousarray(a, np.float32).reshape(H, W, 4) for a in (hcol, hpos, hnrm)]
+    vp = np.ascontiguousarray(vp_prev, np.float32).reshape(16)
+    out = [np.zeros((H, W, k), np.float32) for k in (4, 2, 4, 4, 4)]
+    p = temporal_params(**params)
+    _check(lib().mcpt_temporal_run(pt.h, W, H, fptr(rgb), sm.ctypes.data_as(_u), fptr(var), fptr(pos), fptr(nm), fptr(z),
+                                   *(fptr(a) for a in hist), fptr(vp), C.byref(p), *(fptr(a) for a in out)), pt.h)
+    return tuple(out)
 
 
 def sample_budget_params(**kw) -> SampleBudgetParams:

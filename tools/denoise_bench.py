@@ -12,6 +12,12 @@ times the passes with strides 1 and 2 moved from the LDS kernel to the direct on
 with 4 path slots, and every repeat runs mcpt_film_denoise_guided and mcpt_film_denoise one after the
 other, so the plain passes of the same run are the yardstick.  A guided pass moves 80 B per pixel
 (the plain pass's 64 B plus the float2 {variance, luminance} plane read and written).
+
+--temporal times the temporal stage (profiles/temporal.json): 4 spp in 4 path slots, two frames one
+degree of yaw apart per repeat, k_temporal's device time on the second (mcpt_debug_temporal_ms), its
+compulsory bytes (220 B per pixel: the film, its error plane, the guide sums and the camera records in,
+48 B of history in, 72 B of planes out) as a share of the same run's mcpt_debug_hbm_copy ceiling, and the
+five guided passes over the accumulated frame measured in the same process.
 """
 import argparse
 import json
@@ -19,6 +25,8 @@ import os
 import statistics
 import sys
 import time
+
+import numpy as np
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "mc-path-tracer_amd"))
@@ -70,6 +78,56 @@ def guided(a, pt, W, H):
             f.write(line + "\n")
 
 
+def temporal(a, pt, W, H):
+    """k_temporal on frame B accumulated onto frame A, the camera yawed by --yaw degrees between the two.
+    Every repeat renders both frames anew (a seed each), so the history the timed launch gathers from is
+    one call old, as in a preview loop; the guided passes then run over the accumulated frame."""
+    rc = mcpt.CONFIGS[2]
+    q = mcpt.denoise_guided_params()
+    aspect = np.float32(W) / np.float32(H)
+    cams = [mcpt.make_camera(rc.position, rc.yaw + y, rc.pitch, rc.fovy, aspect=aspect) for y in (0.0, a.yaw)]
+    rows = []
+    for i in range(a.warmup + a.repeats):
+        pt.temporal_reset()
+        for k, cam in enumerate(cams):
+            pt.set_camera(cam)
+            pt.set_seed((0x9E3779B97F4A7C15 * (2 * i + k + 1)) & (2 ** 64 - 1))
+            pt.render()
+            pt.render_guides(a.guide_samples)
+            t = time.perf_counter()
+            pt.temporal_accumulate()
+            wall = (time.perf_counter() - t) * 1e3
+        ms_t = pt.temporal_ms()
+        pt.temporal_denoise()
+        ms = pt.denoise_ms()
+        if i >= a.warmup:
+            rows.append((wall, ms_t, ms["prepare"], ms["passes"][:q.passes]))
+    copy_gbps = pt.hbm_copy_gbps()
+    px = W * H
+    gained = float((pt.temporal()["nsamples"] > a.spp).mean())
+    bpp = 16 + 4 + 16 + 16 + 16 + 32 + 48 + 72  # Ld, samples, err, two guide sums, camera records; history in; planes out
+    t_ms = med([r[1] for r in rows])
+    passes_ms = [med([r[3][i] for r in rows]) for i in range(q.passes)]
+    res = {"tool": "denoise_bench --temporal", "device": pt.device_name, "config": 2, "width": W, "height": H,
+           "film_spp": a.spp, "slots": a.slots, "yaw_deg": a.yaw, "repeats": a.repeats, "warmup": a.warmup,
+           "hbm_copy_gbps": copy_gbps, "pixels_with_history": gained,
+           "accumulate_wall_ms_median": med([r[0] for r in rows]),
+           "temporal": {"params": {f: getattr(mcpt.temporal_params(), f) for f, _ in mcpt.TemporalParams._fields_},
+                        "k_temporal_ms_median": t_ms, "k_temporal_ms_min": min(r[1] for r in rows),
+                        "bytes_per_pixel": bpp, "gbps": bpp * px / (t_ms * 1e-3) / 1e9,
+                        "share_of_copy": bpp * px / (t_ms * 1e-3) / 1e9 / copy_gbps,
+                        "device_bytes": pt.temporal_bytes()},
+           "guided": {"prepare_ms_median": med([r[2] for r in rows]), "pass_ms_median": passes_ms,
+                      "passes_ms_total_median": med([sum(r[3]) for r in rows]), "bytes_per_pixel_per_pass": 80,
+                      "pass_share_of_copy": [80 * px / (ms * 1e-3) / 1e9 / copy_gbps for ms in passes_ms]}}
+    pt.close()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=15)
@@ -81,6 +139,8 @@ def main():
     ap.add_argument("--ab", action="store_true", help="also time MCPT_DENOISE_LDS_MAX = 0 / 1 / 2")
     ap.add_argument("--guided", action="store_true", help="time the guided passes beside the plain ones")
     ap.add_argument("--slots", type=int, default=4, help="path slots of the film (--guided)")
+    ap.add_argument("--temporal", action="store_true", help="time k_temporal and the guided passes after it")
+    ap.add_argument("--yaw", type=float, default=1.0, help="degrees of yaw between the two frames (--temporal)")
     ap.add_argument("--out", help="also write the JSON here")
     a = ap.parse_args()
     if a.repeats < 10:
@@ -92,8 +152,10 @@ def main():
     pt.upload_scene(scene)
     pt.set_camera(mcpt.config_camera(rc, W, H))
     pt.resize(W, H)
-    if a.guided:
+    if a.guided or a.temporal:
         pt.set_path_slots(a.slots)
+    if a.temporal:
+        return temporal(a, pt, W, H)
     pt.render()
     p = mcpt.denoise_params()
     if a.guided:

@@ -12,6 +12,13 @@ the defaults (mcpt_denoise_default_params) are the best row.  A sigma of 0 turns
 spp and one render_adaptive frame at its defaults each, five passes, the guide sigmas at their current
 defaults, ranked by the geometric mean over the nine frames; the plain filter's row on the same frames
 is printed beside it.  The best row is mcpt_denoise_guided_default_params.
+
+--temporal sweeps the temporal stage's (pos_tol, nrm_tol, max_history, alpha_min)
+(profiles/temporal_defaults.txt): sequences of 8 frames of the same scenes and size at 2 spp in 2 path
+slots, the camera yawed by 0.5 or 2 degrees per frame, a seed per frame; the score is the MSE of the
+last frame after accumulation and the guided passes, relative to the guided passes over the last frame
+alone, both against the 1024-spp frame at the last camera, ranked by the geometric mean over the six
+sequences.  The best row is mcpt_temporal_default_params.
 """
 import argparse
 import itertools
@@ -119,11 +126,115 @@ def guided(out):
     print(f"best: sigma_lum {b[0]:g} lum_eps {b[1]:g}")
 
 
+T_FRAMES, T_SPP, T_SLOTS, T_GUIDES = 8, 2, 2, 2
+T_YAW = (0.5, 2.0)
+POS_TOL = (0.02, 0.05, 0.1, 0.2)
+NRM_TOL = (0.25, 0.5, 1.0)
+MAX_HISTORY = (4.0, 8.0, 16.0, 32.0, 64.0)
+ALPHA_MIN = (0.0, 0.05, 0.1, 0.2, 0.4)
+
+
+def frame_seed(k):
+    """A seed per frame that differs in every bit field (seeds one apart hand a pixel the same samples)."""
+    return (0x9E3779B97F4A7C15 * (k + 1)) & (2 ** 64 - 1)
+
+
+def temporal(out):
+    """Sequences of T_FRAMES frames per scene and yaw step; each frame's film means, variances, guide
+    means and positions are recorded once from the film path, and every candidate replays the sequence
+    through mcpt_temporal_run and filters the last accumulated frame with mcpt_denoise_guided_run."""
+    cands = list(itertools.product(POS_TOL, NRM_TOL, MAX_HISTORY, ALPHA_MIN))
+    run = mcpt.PathTracer(0)
+    names, single_mse, cols = [], [], []
+    for name, scene, cam0, depth in scenes():
+        rc = {"config1": mcpt.CONFIGS[1], "config2": mcpt.CONFIGS[2]}.get(name)
+        pos = rc.position if rc else (0.3, 0.1, 3.0)
+        for step in T_YAW:
+            cams = [mcpt.make_camera(pos, -90.0 + step * f, rc.pitch if rc else 0.0, aspect=np.float32(W) / np.float32(H))
+                    for f in range(T_FRAMES)]
+            rp = tracer(scene, cams[-1], REF_SPP, depth)
+            Lr, sr = rp.film()
+            rp.close()
+            pt = mcpt.PathTracer(0, mcpt.default_config(spp=T_SPP, max_depth=depth, tile=64))
+            pt.upload_scene(scene)
+            pt.set_camera(cams[0])
+            pt.resize(W, H, 64, 64)
+            pt.set_path_slots(T_SLOTS)
+            rec = []
+            for f, cam in enumerate(cams):
+                pt.set_camera(cam)
+                pt.set_seed(frame_seed(f))
+                pt.render()
+                pt.render_guides(T_GUIDES)
+                pt.temporal_accumulate()
+                L, s = pt.film()
+                g = pt.guides()
+                se = pt.film_error()[..., 0]
+                with np.errstate(all="ignore"):
+                    cnt = g["count"].astype(np.float32)
+                    rec.append(dict(rgb=L / s[..., None].astype(np.float32), samples=s,
+                                    variance=np.where(se < 0, np.float32(-1), se * se).astype(np.float32),
+                                    position=pt.temporal()["position"], normal=g["normal"] / cnt[..., None],
+                                    depth=g["depth"] / cnt, albedo=g["albedo"] / cnt[..., None],
+                                    vp=mcpt.camera_view_proj(cam)))
+            pt.denoise_guided()
+            single = pt.denoised()
+            pt.close()
+            with np.errstate(all="ignore"):
+                ref = Lr / sr[..., None].astype(np.float32)
+            keep = (rec[-1]["samples"] > 0) & (sr > 0) & np.isfinite(ref).all(axis=2)
+            r64 = ref[keep].astype(np.float64)
+            m = float(np.mean((single[keep] - r64) ** 2))
+            names.append(f"{name}/{step:g}")
+            single_mse.append(m)
+            col = []
+            for pt_, nt, mh, am in cands:
+                hist, vp_prev = tuple(np.zeros((H, W, 4), np.float32) for _ in range(3)), rec[0]["vp"]
+                for r in rec:
+                    c4, vl, *hist = mcpt.temporal_run(run, r["rgb"], r["samples"], r["variance"], r["position"], r["normal"],
+                                                      r["depth"], *hist, vp_prev, pos_tol=pt_, nrm_tol=nt, max_history=mh,
+                                                      alpha_min=am)
+                    vp_prev = r["vp"]
+                last = rec[-1]
+                den, _ = mcpt.denoise_guided_run(run, c4[..., :3], vl[..., 0], last["albedo"], last["normal"], last["depth"],
+                                                 (c4[..., 3] != 0).astype(np.uint32))
+                col.append(float(np.mean((den[keep] - r64) ** 2)) / m)
+            cols.append(col)
+    run.close()
+    ratios = np.array(cols).T  # candidate x sequence
+    score = np.exp(np.mean(np.log(ratios), axis=1))
+    # (candidates whose alpha never differs, e.g. a short max_history under any alpha_min, replay the same
+    # frames and tie exactly: a stable sort keeps them in grid order)
+    order = np.argsort(score, kind="stable")
+    d = mcpt.temporal_params()
+    cur = (d.pos_tol, d.nrm_tol, d.max_history, d.alpha_min)
+    lines = [f"# temporal defaults: {W}x{H}, sequences of {T_FRAMES} frames, {T_SPP} spp in {T_SLOTS} slots, {T_GUIDES} guide "
+             f"samples, a seed per frame, the guided passes at their defaults, against {REF_SPP} spp at the last camera",
+             "# sequences (scene/yaw step in degrees): " + " ".join(names),
+             "# MSE(denoise_guided of the last frame alone): " + " ".join(f"{m:.6g}" for m in single_mse),
+             "# columns: pos_tol nrm_tol max_history alpha_min | MSE(accumulate + temporal_denoise) / MSE(last frame alone) "
+             "per sequence | geometric mean",
+             f"# built-in defaults: {cur[0]:g} {cur[1]:g} {cur[2]:g} {cur[3]:g}"]
+    for i in order:
+        c = cands[i]
+        mark = "  <- defaults" if all(abs(x - y) < 1e-6 for x, y in zip(c, cur)) else ""
+        lines.append(f"{c[0]:5g} {c[1]:5g} {c[2]:5g} {c[3]:5g} | " + " ".join(f"{r:9.5f}" for r in ratios[i]) +
+                     f" | {score[i]:9.5f}{mark}")
+    with open(out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("\n".join(lines[:17]))
+    b = cands[order[0]]
+    print(f"best: pos_tol {b[0]:g} nrm_tol {b[1]:g} max_history {b[2]:g} alpha_min {b[3]:g}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--guided", action="store_true", help="sweep the variance-guided filter's sigma_lum and lum_eps")
+    ap.add_argument("--temporal", action="store_true", help="sweep the temporal stage's four parameters")
     ap.add_argument("--out")
     a = ap.parse_args()
+    if a.temporal:
+        return temporal(a.out or os.path.join(REPO, "profiles", "temporal_defaults.txt"))
     if a.guided:
         return guided(a.out or os.path.join(REPO, "profiles", "denoise_guided_defaults.txt"))
     a.out = a.out or os.path.join(REPO, "profiles", "denoise_defaults.txt")
