@@ -6,302 +6,12 @@
 // Differences by design: one stream, no host sync or managed-memory counter
 // readback between stages (counts stay on the device and the trace kernels are
 // persistent), a whole tile set per iteration instead of one 256x256 tile, and
-// error codes instead of exit(99).
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
+// error codes instead of exit(99).  The film's post-processing entry points (guides,
+// denoise, adaptive sampling, temporal accumulation) are postprocess.cpp.
 #include <cstdio>
-#include <cstring>
 #include <functional>
-#include <string>
-#include <vector>
 
-#include "kernels.hpp"
-#include "mcpt.h"
-
-using namespace mcpt_dev;
-
-namespace mcpt_host {
-void set_global_error(const std::string& e);
-const char* global_error();
-}  // namespace mcpt_host
-
-struct mcpt_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
-    mcpt_config cfg{};
-    char devname[256] = {0};
-    int num_cu = 0;
-    LaunchGeom geom{};             // persistent grids and k_trace partitions of this device
-    uint32_t trace_parts_default = 1;
-    // scene
-    std::vector<void*> scene_bufs;
-    DevScene scene{};
-    bool has_scene = false;
-    bool has_scene_before = false;  // set at the start of a re-upload
-    int32_t ntri = 0;               // triangles of the uploaded scene
-    size_t occ_entries_n = 0;       // occluder-cache table entries (DevScene::occ; + kOccGateWords gate words)
-    uint32_t* occ_init = nullptr;   // the table as the upload's pre-fill left it (film clears restore it); nullptr: empty
-    int pair_depth = 0;
-    bool cull_ok = true, occ_nest_ok = true;  // last upload: boxes contain their triangles / nest (scene_upload)
-    // traversal work counters (mcpt_set_work_counters): k_trace's counting instantiation, whose six
-    // per-lane counters cost the fast one its spill-free registers -- off by default
-    bool count_work = getenv("MCPT_WORK_COUNTERS") != nullptr;
-    int node_layout = 0;  // pair-node numbering the last upload used (mcpt_debug_node_layout)
-    // mcpt_set_skip_discarded: paths the next logic pass is certain to end make no extension ray
-    // (ShadeArgs::skip); results and ray counts are the same either way
-    bool skip_discarded = true;
-    // camera
-    mcpt::CamView cam{};
-    bool has_cam = false;
-    // per-pixel camera records (cam_table): for the film size and camera they were built for
-    float4* cam_tab = nullptr;
-    size_t cam_tab_cap = 0;  // pixels allocated
-    uint32_t cam_tab_W = 0, cam_tab_H = 0;
-    mcpt::CamView cam_tab_cam{};
-    bool cam_tab_ok = false;
-    // Primary-hit candidate table (prim_table): built for (scene upload, camera, film size); a film
-    // clear keeps it.  Best-effort: any failure leaves it off and the primary rays are traversed.
-    // (MCPT_PRIMARY_HITS=0: off, for A/B runs and tests.  bench.py has no entry for the switch and
-    // stamps a run that sets it as an unknown knob, i.e. not the product.)
-    bool prim_on = [] { const char* e = getenv(kPrimaryHitsEnv); return !(e && e[0] == '0' && e[1] == 0); }();
-    uint8_t* prim_cnt = nullptr;
-    uint32_t* prim_list = nullptr;
-    uint32_t* prim_stats_d = nullptr;  // k_primary_build's two counters
-    size_t prim_cap = 0;               // pixels allocated
-    uint2* prim_q = nullptr;
-    size_t prim_q_cap = 0;             // entries allocated
-    bool prim_ok = false;              // the table is valid for the key below
-    bool prim_failed = false;          // the build for the key below failed: not retried until the key changes
-    uint64_t prim_scene_gen = 0;
-    uint32_t prim_W = 0, prim_H = 0;
-    mcpt::CamView prim_cam{};
-    uint64_t scene_gen = 0;            // scene uploads so far
-    uint64_t prim_builds = 0;          // table builds so far
-    uint32_t prim_lists = 0, prim_over = 0;  // the current table: pixels with a list / overflow pixels
-    float prim_build_ms = 0.f;         // the last build
-    // Film observes camera and scene (Film::update -> clear(), Film.cu:278-281; notified by
-    // Camera::update, Camera.cu:207, and Scene::notify, Scene.cu:534-545): a change marks the
-    // film stale and the next iteration clears it first (unless MCPT_FLAG_NO_AUTO_CLEAR).
-    bool film_stale = false;
-    // film + paths
-    uint32_t W = 0, H = 0, tile_w = 256, tile_h = 256;
-    size_t P = 0;      // pixels (W * H)
-    uint32_t slots = 1;  // path slots per pixel (mcpt_set_path_slots); path state holds slots * npx paths
-    // Path layout (mcpt_set_compact_paths).  Full: npx = P, path index = slot * P + pixel id.  Compact:
-    // the path state covers the tile set only, npx = tile-set tiles x tile pixels (ShadeArgs::npx).
-    bool compact = false;
-    size_t npx = 0;
-    float4* film_Ld = nullptr;     // slots > 1 or compact: the film, W x H (sum of the slot accumulators)
-    uint32_t* film_samples = nullptr;
-    std::vector<void*> film_bufs;
-    uint8_t* blk_done = nullptr;  // k_shade block done flags (ShadeArgs::blk_done), in film_bufs
-    size_t blk_done_n = 0;
-    bool blk_done_off = getenv("MCPT_NO_BLOCK_DONE") != nullptr;  // A/B switch: every block runs
-    DevPaths p{};
-    uint32_t *ext_q = nullptr, *any_q = nullptr, *mat_q = nullptr;
-    float4* any_ray = nullptr;          // any-hit rays at their queue positions: o [2 queue_alloc], then d
-    uint32_t ext_cap = 0, any_cap = 0;  // per-shard capacities
-    size_t queue_alloc = 0;             // entries allocated for ext_q (any_q holds twice)
-    CounterBlock* cnt = nullptr;
-    CounterBlock* cnt_host = nullptr;  // pinned
-    CounterBlock totals{};             // host copy of the counters after the last call (valid: totals_ok)
-    bool totals_ok = false;
-    int2* step_tile = nullptr;         // mcpt_wavefront_step's one-tile set: device + pinned staging (16 B:
-    int2* step_tile_h = nullptr;       // the tile, then its index in the tile set, ShadeArgs::tile_base)
-    int2* tiles = nullptr;
-    std::vector<int2> tiles_h;
-    // tiles holding pixels scattered in from another context (mcpt_film_unpack_tiles, mcpt_gather)
-    // since the last film clear: the full layout's slot 0 holds them, so they may not become own
-    // tiles before a clear (their sample count restarts from the flags word while Ld accumulates)
-    std::vector<int2> unpacked;
-    uint32_t tiles_cap = 0;
-    std::vector<hipEvent_t> events;
-    // stage_run scratch
-    std::vector<void*> tmp_bufs;
-    float last_stage_ms = 0.f;
-    float last_build_ms = 0.f;  // last GPU BVH build (mcpt_scene_upload_gpu_bvh)
-    float last_env_build_ms = 0.f;  // last device build of the HRDI tables (env_build.hip)
-    bool env_device_built = false;  // the uploaded scene's HRDI tables were built on the device
-    bool env_guides = false;        // env_cell uses the search guides
-    int gpu_bvh_builder = MCPT_GPU_BVH_PLOC;  // mcpt_set_gpu_bvh_builder
-    bool tiny_stack = false;  // mcpt_debug_tiny_lds_stack: k_trace with a 2-entry LDS stack (tests)
-    unsigned long long phase_base[kPhaseWords] = {};  // mcpt_debug_trace_profile's reset point
-    // Preview denoiser.  Guide sums of the W x H film: g_alb (albedo rgb, sample
-    // count), g_nz (normal xyz, depth), allocated by the first mcpt_guides_render, valid for the
-    // (scene upload, camera, film size) they were rendered for.  dn_*: the filter's planes of the film
-    // (two colour planes in ping-pong, guides, albedo), allocated by the first mcpt_film_denoise[_guided]
-    // (denoise_planes_ensure); dn_result: the colour plane that holds the last result (-1: none).  All
-    // freed with the film.
-    float4 *g_alb = nullptr, *g_nz = nullptr;
-    bool guides_ok = false;
-    uint64_t guides_scene_gen = 0;
-    mcpt::CamView guides_cam{};
-    float4 *dn_col[2] = {nullptr, nullptr}, *dn_gd = nullptr, *dn_al = nullptr;
-    int dn_result = -1;
-    // Variance-guided form: the {variance, luminance} planes in ping-pong beside
-    // dn_col, allocated by the first mcpt_film_denoise_guided; dn_guided: dn_result is a guided result,
-    // whose variances are dn_vl[dn_result]
-    float2* dn_vl[2] = {nullptr, nullptr};
-    bool dn_guided = false;
-    float guides_ms = 0.f, dn_ms[9] = {};  // device times of the last guide pass / filter set-up and passes
-    // Adaptive sampling, all keyed by film pixel and allocated by the first call
-    // that needs them: budget, the per-pixel sample budget k_shade reads in place of cfg.spp while
-    // budget_on (budget_max: its largest entry, which sizes mcpt_render's batches); err4, the last
-    // mcpt_film_error result {se, mean, K, n} (err_ok); own_map, the film tiles' ownership (OwnMap) as
-    // of the last call that used it; bud_cnt, k_budget's three counters.  Film clears, slot, tile-set
-    // and layout changes keep them; mcpt_film_resize frees them.
-    uint32_t* budget = nullptr;
-    bool budget_on = false;
-    uint32_t budget_max = 0;
-    float4* err4 = nullptr;
-    bool err_ok = false;
-    int32_t* own_map = nullptr;
-    size_t own_map_cap = 0;
-    unsigned long long* bud_cnt = nullptr;
-    size_t adaptive_bytes = 0;     // device bytes held by the above (mcpt_debug_adaptive_bytes)
-    float err_ms = 0.f, budget_ms = 0.f;  // device times of the last k_film_error / k_budget
-    // Temporal accumulation, allocated by the first mcpt_film_temporal: two sets
-    // of history planes {hcol, hpos, hnrm} in ping-pong (a call gathers from one and writes the other;
-    // tp_set: the one that holds the last accumulated frame), that frame's colour and vl planes for
-    // the spatial passes, and its camera (tp_ok: there is such a frame).  Film clears, seed, camera and
-    // slot changes keep them; a scene upload and mcpt_temporal_reset forget the frame, mcpt_film_resize
-    // frees everything.
-    float4* tp_h[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
-    float4* tp_col = nullptr;
-    float2* tp_vl = nullptr;
-    int tp_set = 0;
-    bool tp_ok = false;
-    mcpt::CamView tp_cam{};
-    size_t tp_bytes = 0;  // device bytes held by the above (mcpt_debug_temporal_bytes)
-    float tp_ms = 0.f;    // device time of the last k_temporal
-    uint64_t guides_seed = 0;  // the seed the guides were rendered with (their lens rays are keyed by it)
-};
-
-static int set_err(mcpt_ctx* c, int rc, const std::string& msg) {
-    if (c) c->err = msg;
-    mcpt_host::set_global_error(msg);
-    return rc;
-}
-#define HIPCHK(c, x)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (x);                                                                  \
-        if (e_ != hipSuccess)                                                                 \
-            return set_err((c), MCPT_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_));  \
-    } while (0)
-
-static void prim_free(mcpt_ctx* c) {
-    if (c->prim_cnt) (void)hipFree(c->prim_cnt);
-    if (c->prim_list) (void)hipFree(c->prim_list);
-    if (c->prim_stats_d) (void)hipFree(c->prim_stats_d);
-    if (c->prim_q) (void)hipFree(c->prim_q);
-    c->prim_cnt = nullptr;
-    c->prim_list = nullptr;
-    c->prim_stats_d = nullptr;
-    c->prim_q = nullptr;
-    c->prim_cap = c->prim_q_cap = 0;
-    c->prim_ok = false;
-}
-// The filter's planes of the film: four float4 planes, and the guided form's two float2 planes
-static void denoise_planes_free(mcpt_ctx* c) {
-    for (void** q : {(void**)&c->dn_col[0], (void**)&c->dn_col[1], (void**)&c->dn_gd, (void**)&c->dn_al, (void**)&c->dn_vl[0],
-                     (void**)&c->dn_vl[1]}) {
-        if (*q) (void)hipFree(*q);
-        *q = nullptr;
-    }
-    c->dn_result = -1;
-    c->dn_guided = false;
-}
-// Allocates those that are missing, the float2 planes only with_vl, and forgets the last result.
-// false: an allocation failed and every plane was freed.
-static bool denoise_planes_ensure(mcpt_ctx* c, bool with_vl) {
-    c->dn_result = -1;
-    c->dn_guided = false;
-    bool ok = true;
-    const auto need = [&](void** q, size_t bytes) {
-        if (ok && !*q && hipMalloc(q, bytes) != hipSuccess) {
-            *q = nullptr;
-            ok = false;
-        }
-    };
-    for (float4** q : {&c->dn_col[0], &c->dn_col[1], &c->dn_gd, &c->dn_al}) need((void**)q, c->P * sizeof(float4));
-    if (with_vl)
-        for (float2** q : {&c->dn_vl[0], &c->dn_vl[1]}) need((void**)q, c->P * sizeof(float2));
-    if (!ok) {
-        (void)hipGetLastError();
-        denoise_planes_free(c);
-    }
-    return ok;
-}
-// guide sums and filter planes: they belong to the film size
-static void denoise_free(mcpt_ctx* c) {
-    denoise_planes_free(c);
-    for (float4** q : {&c->g_alb, &c->g_nz}) {
-        if (*q) (void)hipFree(*q);
-        *q = nullptr;
-    }
-    c->guides_ok = false;
-}
-static void adaptive_free(mcpt_ctx* c) {
-    if (c->budget) (void)hipFree(c->budget);
-    if (c->err4) (void)hipFree(c->err4);
-    if (c->own_map) (void)hipFree(c->own_map);
-    if (c->bud_cnt) (void)hipFree(c->bud_cnt);
-    c->budget = nullptr;
-    c->err4 = nullptr;
-    c->own_map = nullptr;
-    c->bud_cnt = nullptr;
-    c->own_map_cap = 0;
-    c->budget_on = c->err_ok = false;
-    c->budget_max = 0;
-    c->adaptive_bytes = 0;
-}
-static void temporal_free(mcpt_ctx* c) {
-    for (void** q : {(void**)&c->tp_h[0][0], (void**)&c->tp_h[0][1], (void**)&c->tp_h[0][2], (void**)&c->tp_h[1][0],
-                     (void**)&c->tp_h[1][1], (void**)&c->tp_h[1][2], (void**)&c->tp_col, (void**)&c->tp_vl}) {
-        if (*q) (void)hipFree(*q);
-        *q = nullptr;
-    }
-    c->tp_ok = false;
-    c->tp_bytes = 0;
-}
-static void free_list(std::vector<void*>& v) {
-    for (void* q : v)
-        if (q) (void)hipFree(q);
-    v.clear();
-}
-template <class T>
-static int dalloc(mcpt_ctx* c, std::vector<void*>& list, T** out, size_t count) {
-    void* q = nullptr;
-    size_t bytes = std::max<size_t>(count * sizeof(T), 16);
-    hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) return set_err(c, MCPT_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    list.push_back(q);
-    *out = (T*)q;
-    return MCPT_OK;
-}
-template <class T>
-static int dupload(mcpt_ctx* c, std::vector<void*>& list, T** out, const T* src, size_t count) {
-    int rc = dalloc(c, list, out, count);
-    if (rc) return rc;
-    if (count) HIPCHK(c, hipMemcpy(*out, src, count * sizeof(T), hipMemcpyHostToDevice));
-    return MCPT_OK;
-}
-
-// device memory of adaptive sampling, counted (mcpt_debug_adaptive_bytes); a buffer that exists is kept
-template <class T>
-static int adaptive_alloc(mcpt_ctx* c, T** out, size_t count) {
-    if (*out) return MCPT_OK;
-    const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
-    hipError_t e = hipMalloc((void**)out, bytes);
-    if (e != hipSuccess) {
-        *out = nullptr;
-        return set_err(c, MCPT_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    }
-    c->adaptive_bytes += bytes;
-    return MCPT_OK;
-}
+#include "runtime_internal.hpp"
 
 extern "C" {
 
@@ -364,14 +74,9 @@ void mcpt_destroy(mcpt_ctx* c) {
     if (c->any_q) (void)hipFree(c->any_q);
     if (c->mat_q) (void)hipFree(c->mat_q);
     if (c->any_ray) (void)hipFree(c->any_ray);
-    if (c->cam_tab) (void)hipFree(c->cam_tab);
-    prim_free(c);
-    denoise_free(c);
-    adaptive_free(c);
-    temporal_free(c);
     for (auto e : c->events) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;  // (every DevBuf of the context goes here)
 }
 
 int mcpt_device_name(mcpt_ctx* c, char* buf, int32_t len) {
@@ -452,7 +157,6 @@ static int pairs_to_quads(const std::vector<float4>& pn, int root_ref, std::vect
     return 0;
 }
 
-static hipEvent_t ev(mcpt_ctx* c, size_t i);
 static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
     if (!c || !d) return set_err(c, MCPT_E_INVALID, "null argument");
     if (d->ntri < 0 || d->nnodes < 0 || d->nmat < 0 || d->ndir < 0) return set_err(c, MCPT_E_INVALID, "negative sizes");
@@ -952,7 +656,7 @@ static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
         // The per-triangle leaf-box records serve the occluder cache and the primary-hit table alike
         // (either switch alone keeps them).  For the table alone they are best-effort.
         float4* lbx = nullptr;
-        if (d->ntri > 0 && c->occ_nest_ok && (occ_want || c->prim_on)) {
+        if (d->ntri > 0 && c->occ_nest_ok && (occ_want || c->prim.on)) {
             void* q = nullptr;
             if (hipMalloc(&q, kOccRecF4 * (size_t)d->ntri * sizeof(float4)) == hipSuccess) {
                 c->scene_bufs.push_back(q);
@@ -990,7 +694,7 @@ static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
     }
     c->scene = s;
     c->scene_gen++;  // with the scene itself: the previous scene's primary-hit table is stale (prim_table)
-    c->tp_ok = false;  // ... and so is the temporal history (no motion vectors for moved geometry)
+    c->tp.ok = false;  // ... and so is the temporal history (no motion vectors for moved geometry)
     c->ntri = d->ntri;
     c->occ_init = nullptr;  // (the previous scene's copy went with scene_bufs)
     if (s.occ) {
@@ -1073,11 +777,11 @@ int mcpt_debug_ray_counts(const mcpt_ctx* c, uint64_t* out) {
 }
 int mcpt_debug_primary_stats(const mcpt_ctx* c, double* out4) {
     if (!c || !out4) return MCPT_E_INVALID;
-    out4[0] = c->prim_ok ? (double)c->prim_lists : 0.0;
-    out4[1] = c->prim_ok ? (double)c->prim_over : 0.0;
+    out4[0] = c->prim.ok ? (double)c->prim.lists : 0.0;
+    out4[1] = c->prim.ok ? (double)c->prim.over : 0.0;
     out4[2] = c->totals_ok ? (double)c->totals.tot_prim : 0.0;
-    out4[3] = (double)c->prim_build_ms;
-    return (int)std::min<uint64_t>(c->prim_builds, 0x7fffffffull);
+    out4[3] = (double)c->prim.build_ms;
+    return (int)std::min<uint64_t>(c->prim.builds, 0x7fffffffull);
 }
 int mcpt_debug_discard_stats(const mcpt_ctx* c, uint64_t* out4) {
     if (!c || !out4) return MCPT_E_INVALID;
@@ -1238,7 +942,8 @@ static int film_resize(mcpt_ctx* c, uint32_t w, uint32_t h, uint32_t tw, uint32_
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     free_list(c->film_bufs);
-    denoise_free(c);
+    c->guides = Guides{};  // guide sums and filter planes: they belong to the film size
+    c->dn = Denoise{};
     c->P = 0;
     c->npx = 0;
     c->p = DevPaths{};  // (set_tiles_internal below re-points the any-hit ray buffers)
@@ -1260,15 +965,11 @@ static int film_resize(mcpt_ctx* c, uint32_t w, uint32_t h, uint32_t tw, uint32_
 }
 int mcpt_film_resize(mcpt_ctx* c, uint32_t w, uint32_t h, uint32_t tw, uint32_t th) {
     if (!c || w == 0 || h == 0 || tw == 0 || th == 0) return set_err(c, MCPT_E_INVALID, "bad film size");
-    if (c->budget || c->err4 || c->own_map || c->bud_cnt) {  // the sample budget and the estimate belong to the film size
+    if (c->ad.bytes() || c->tp.bytes()) {  // the sample budget, the estimate and the temporal history belong to the film size
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        adaptive_free(c);
-    }
-    if (c->tp_bytes) {  // ... and so does the temporal history
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        temporal_free(c);
+        c->ad = Adaptive{};
+        c->tp = Temporal{};
     }
     return film_resize(c, w, h, tw, th);
 }
@@ -1344,7 +1045,7 @@ int mcpt_set_compact_paths(mcpt_ctx* c, int32_t on) {
     return mcpt_film_clear(c);
 }
 
-static hipEvent_t ev(mcpt_ctx* c, size_t i) {
+extern "C++" hipEvent_t ev(mcpt_ctx* c, size_t i) {
     while (c->events.size() <= i) {
         hipEvent_t e;
         if (hipEventCreate(&e) != hipSuccess) return nullptr;
@@ -1355,28 +1056,25 @@ static hipEvent_t ev(mcpt_ctx* c, size_t i) {
 
 // The camera records of a W x H film under the current camera (k_cam_table: gen_ray_pixel of every
 // pixel, 32 B each), rebuilt on the context's stream when the film size or the camera changed.
-static int cam_table(mcpt_ctx* c, uint32_t W, uint32_t H, const float4** px, const float4** dir) {
+extern "C++" int cam_table(mcpt_ctx* c, uint32_t W, uint32_t H, const float4** px, const float4** dir) {
     const size_t n = (size_t)W * H;
-    if (!(c->cam_tab_ok && c->cam_tab_W == W && c->cam_tab_H == H && memcmp(&c->cam_tab_cam, &c->cam, sizeof(c->cam)) == 0)) {
-        if (n > c->cam_tab_cap) {
+    CamTable& t = c->cam_tab;
+    ViewKey key = c->view();
+    key.W = W;
+    key.H = H;
+    if (!(t.ok && t.key.same(key, ViewKey::SIZE | ViewKey::CAM))) {
+        if (2 * n > t.tab.size()) {
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (c->cam_tab) (void)hipFree(c->cam_tab);
-            c->cam_tab = nullptr;
-            c->cam_tab_cap = 0;
-            c->cam_tab_ok = false;
-            if (hipMalloc(&c->cam_tab, 2 * n * sizeof(float4)) != hipSuccess)
-                return set_err(c, MCPT_E_NOMEM, "camera table allocation failed");
-            c->cam_tab_cap = n;
+            t.ok = false;
+            if (!t.tab.ensure(2 * n)) return set_err(c, MCPT_E_NOMEM, "camera table allocation failed");
         }
-        launch_cam_table(c->cam, (int)W, (int)H, c->cam_tab, c->cam_tab + n, c->stream);
+        launch_cam_table(c->cam, (int)W, (int)H, t.tab, t.tab + n, c->stream);
         HIPCHK(c, hipGetLastError());
-        c->cam_tab_W = W;
-        c->cam_tab_H = H;
-        c->cam_tab_cam = c->cam;
-        c->cam_tab_ok = true;
+        t.key = key;
+        t.ok = true;
     }
-    *px = c->cam_tab;
-    *dir = c->cam_tab + n;
+    *px = t.tab;
+    *dir = t.tab + n;
     return MCPT_OK;
 }
 
@@ -1389,37 +1087,31 @@ static void prim_table(mcpt_ctx* c, ShadeArgs& sa) {
     sa.prim_cnt = nullptr;
     sa.prim_list = nullptr;
     sa.prim_q = nullptr;
-    if (!c->prim_on || !c->scene.occ_rec || !c->occ_nest_ok || c->scene.ntri == 0) return;
+    PrimTable& t = c->prim;
+    if (!t.on || !c->scene.occ_rec || !c->occ_nest_ok || c->scene.ntri == 0) return;
     const uint32_t W = c->W, H = c->H;
     const size_t n = (size_t)W * H;
-    const bool same = c->prim_scene_gen == c->scene_gen && c->prim_W == W && c->prim_H == H &&
-                      memcmp(&c->prim_cam, &c->cam, sizeof(c->cam)) == 0;
-    if (same && c->prim_failed) return;
+    const ViewKey key = c->view();
+    const bool same = t.key.same(key, ViewKey::SCENE | ViewKey::SIZE | ViewKey::CAM);
+    if (same && t.failed) return;
     const size_t qn = (size_t)kShards * c->ext_cap;
     auto fail = [&]() {
         (void)hipGetLastError();
         (void)hipStreamSynchronize(c->stream);
-        prim_free(c);
-        c->prim_failed = true;
-        c->prim_lists = c->prim_over = 0;
+        t.release();
+        t.failed = true;
+        t.lists = t.over = 0;
     };
     if (!same) {
-        c->prim_scene_gen = c->scene_gen;
-        c->prim_W = W;
-        c->prim_H = H;
-        c->prim_cam = c->cam;
-        c->prim_failed = false;
-        c->prim_ok = false;
+        t.key = key;
+        t.failed = false;
+        t.ok = false;
     }
-    if (!c->prim_ok) {
-        if (n > c->prim_cap || !c->prim_stats_d) {
+    if (!t.ok) {
+        if (n > t.cnt.size() || !t.stats) {
             (void)hipStreamSynchronize(c->stream);
-            prim_free(c);
-            if (hipMalloc(&c->prim_cnt, std::max<size_t>(n, 16)) != hipSuccess ||
-                hipMalloc(&c->prim_list, n * kPrimLine * sizeof(uint32_t)) != hipSuccess ||
-                hipMalloc(&c->prim_stats_d, 16) != hipSuccess)
-                return fail();
-            c->prim_cap = n;
+            t.release();
+            if (!t.cnt.ensure(n) || !t.list.ensure(n * kPrimLine) || !t.stats.ensure(4)) return fail();
         }
         PrimaryBuildArgs ba{};
         ba.scene = c->scene;
@@ -1428,42 +1120,38 @@ static void prim_table(mcpt_ctx* c, ShadeArgs& sa) {
         ba.H = (int)H;
         ba.cam_px = sa.cam_px;
         ba.cam_dir = sa.cam_dir;
-        ba.cnt = c->prim_cnt;
-        ba.list = c->prim_list;
-        ba.stats = c->prim_stats_d;
+        ba.cnt = t.cnt;
+        ba.list = t.list;
+        ba.stats = t.stats;
         hipEvent_t e0 = nullptr, e1 = nullptr;
         uint32_t st[2] = {0, 0};
         float ms = 0.f;
         const bool ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess &&
-                        hipMemsetAsync(c->prim_stats_d, 0, 16, c->stream) == hipSuccess &&
+                        hipMemsetAsync(t.stats, 0, 16, c->stream) == hipSuccess &&
                         hipEventRecord(e0, c->stream) == hipSuccess &&
                         (launch_primary_build(ba, c->stream), hipGetLastError() == hipSuccess) &&
                         hipEventRecord(e1, c->stream) == hipSuccess &&
-                        hipMemcpyAsync(st, c->prim_stats_d, sizeof(st), hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
+                        hipMemcpyAsync(st, t.stats, sizeof(st), hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
                         hipStreamSynchronize(c->stream) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
         if (e0) (void)hipEventDestroy(e0);
         if (e1) (void)hipEventDestroy(e1);
         if (!ok) return fail();
-        c->prim_ok = true;
-        c->prim_builds++;
-        c->prim_lists = st[0];
-        c->prim_over = st[1];
-        c->prim_build_ms = ms;
+        t.ok = true;
+        t.builds++;
+        t.lists = st[0];
+        t.over = st[1];
+        t.build_ms = ms;
     }
-    if (qn > c->prim_q_cap) {  // the primary queue follows the ray queues' capacity (set_tiles_internal)
+    if (qn > t.q.size()) {  // the primary queue follows the ray queues' capacity (set_tiles_internal)
         (void)hipStreamSynchronize(c->stream);
-        if (c->prim_q) (void)hipFree(c->prim_q);
-        c->prim_q = nullptr;
-        c->prim_q_cap = 0;
-        if (hipMalloc(&c->prim_q, qn * sizeof(uint2)) != hipSuccess) return fail();
-        c->prim_q_cap = qn;
+        if (!t.q.ensure(qn)) return fail();
     }
-    sa.prim_cnt = c->prim_cnt;
-    sa.prim_list = c->prim_list;
-    sa.prim_q = c->prim_q;
+    sa.prim_cnt = t.cnt;
+    sa.prim_list = t.list;
+    sa.prim_q = t.q;
 }
 
-static int check_ready(mcpt_ctx* c) {
+extern "C++" int check_ready(mcpt_ctx* c) {
     if (!c) return MCPT_E_INVALID;
     if (!c->has_scene) return set_err(c, MCPT_E_INVALID, "no scene uploaded");
     if (!c->has_cam) return set_err(c, MCPT_E_INVALID, "no camera set");
@@ -1503,7 +1191,7 @@ static int enqueue_iteration(mcpt_ctx* c, size_t evbase, bool timing, const int2
     sa.cnt = c->cnt;
     sa.blk_done = c->blk_done_off ? nullptr : c->blk_done;
     sa.skip = c->skip_discarded ? 1 : 0;
-    sa.budget = c->budget_on ? c->budget : nullptr;
+    sa.budget = c->ad.budget_on ? c->ad.budget.get() : nullptr;
     if (int rc = cam_table(c, c->W, c->H, &sa.cam_px, &sa.cam_dir)) return rc;
     prim_table(c, sa);
     const int bpt = shade_blocks_per_tile((int)(c->tile_w * c->tile_h), (int)c->slots);
@@ -1656,7 +1344,7 @@ int mcpt_render(mcpt_ctx* c, mcpt_stage_stats* st) {
     if (rc) return rc;
     mcpt_stage_stats acc{}, one{};
     // the largest sample count in force: the budget map's maximum where one is installed
-    const uint64_t spp = c->budget_on ? (uint64_t)c->budget_max : (uint64_t)c->cfg.spp;
+    const uint64_t spp = c->ad.budget_on ? (uint64_t)c->ad.budget_max : (uint64_t)c->cfg.spp;
     const uint64_t cap = (spp + 1) * (uint64_t)(c->cfg.max_depth + 2) + 16;
     uint64_t done = 0;
     // Iterations per batch (one host synchronisation each).  Once the film is done, the rest of a
@@ -2000,7 +1688,7 @@ int mcpt_stage_run(mcpt_ctx* c, int stage, const mcpt_soa_view* in, mcpt_soa_vie
 
 // The film (dFilm.Ld / samples): the path state's accumulators with one slot per pixel,
 // else their per-pixel sum in slot order (k_resolve) -- enqueued on the context stream.
-static int film_view(mcpt_ctx* c, const float4** Ld, const uint32_t** samples) {
+extern "C++" int film_view(mcpt_ctx* c, const float4** Ld, const uint32_t** samples) {
     if (c->slots <= 1 && !c->compact) {
         *Ld = c->p.Ld;
         *samples = c->p.samples;
@@ -2089,11 +1777,7 @@ int mcpt_film_read(mcpt_ctx* c, float* Ld, uint32_t* samples) {
     int rc = film_view(c, &fL, &fs);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (Ld) {
-        std::vector<float4> tmp(c->P);
-        HIPCHK(c, hipMemcpy(tmp.data(), fL, c->P * sizeof(float4), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < c->P; i++) { Ld[3 * i] = tmp[i].x; Ld[3 * i + 1] = tmp[i].y; Ld[3 * i + 2] = tmp[i].z; }
-    }
+    if (Ld && (rc = read_plane(c, fL, c->P, Ld, nullptr))) return rc;
     if (samples) HIPCHK(c, hipMemcpy(samples, fs, c->P * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return MCPT_OK;
 }
@@ -2255,19 +1939,39 @@ int mcpt_film_tonemap_rgba8(mcpt_ctx* c, float exposure, uint8_t* out) {
     const uint32_t* fs;
     int rc = film_view(c, &fL, &fs);
     if (rc) return rc;
-    uchar4* d = nullptr;
-    HIPCHK(c, hipMalloc(&d, c->P * sizeof(uchar4)));
-    TonemapArgs a{fL, fs, d, exposure, (uint32_t)c->P};
-    launch_tonemap(a, c->stream);
-    hipError_t e = hipGetLastError();
+    return tonemap_rgba8(c, fL, fs, exposure, out);
+}
+
+}  // extern "C"
+
+int tonemap_rgba8(mcpt_ctx* c, const float4* col, const uint32_t* samples, float exposure, uint8_t* out) {
+    DevBuf<uchar4> d;
+    DevBuf<uint32_t> ones;
+    if (!d.ensure(c->P) || (!samples && !ones.ensure(c->P))) {
+        (void)hipGetLastError();
+        return set_err(c, MCPT_E_NOMEM, "tonemap buffers");
+    }
+    hipError_t e = samples ? hipSuccess : hipMemsetD32Async((hipDeviceptr_t)ones.get(), 1, c->P, c->stream);
+    if (e == hipSuccess) {
+        TonemapArgs a{col, samples ? samples : ones.get(), d, exposure, (uint32_t)c->P};
+        launch_tonemap(a, c->stream);
+        e = hipGetLastError();
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(out, d, c->P * sizeof(uchar4), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) return set_err(c, MCPT_E_HIP, std::string("tonemap: ") + hipGetErrorString(e));
     return MCPT_OK;
 }
 
-}  // extern "C"
+int read_plane(mcpt_ctx* c, const float4* d, size_t n, float* xyz, float* w) {
+    std::vector<float4> o(n);
+    HIPCHK(c, hipMemcpy(o.data(), d, n * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) {
+        if (xyz) { xyz[3 * i] = o[i].x; xyz[3 * i + 1] = o[i].y; xyz[3 * i + 2] = o[i].z; }
+        if (w) w[i] = o[i].w;
+    }
+    return MCPT_OK;
+}
 
 extern "C" {
 int mcpt_debug_queue_rays(mcpt_ctx* c, int which, float* ro, float* rd, uint32_t* n_inout) {
@@ -2384,879 +2088,3 @@ int mcpt_debug_shade_sections(mcpt_ctx* c, uint64_t* out, int n, int reset) {
 }
 }
 
-// ---------------------------------------------------------------------------
-// Preview denoiser: first-hit guide buffers and the a-trous filter
-// (device/denoise.hpp, denoise.hip) between the film and the display.
-// ---------------------------------------------------------------------------
-static bool guides_valid(const mcpt_ctx* c) {
-    return c->guides_ok && c->g_alb && c->g_nz && c->guides_scene_gen == c->scene_gen && c->guides_seed == c->cfg.seed &&
-           memcmp(&c->guides_cam, &c->cam, sizeof(c->cam)) == 0;
-}
-// One filter request, from either parameter struct: the plain parameters, and with `guided` the
-// variance-guided form's two; `who` heads its error texts
-struct DenoiseRequest {
-    mcpt_denoise_params p;
-    bool guided;
-    float sigma_lum, lum_eps;
-    const char* who;
-};
-static DenoiseRequest denoise_request(const mcpt_denoise_params& p) { return {p, false, 0.f, 0.f, "denoise"}; }
-static DenoiseRequest denoise_request(const mcpt_denoise_guided_params& q) {
-    return {{q.passes, q.sigma_color, q.sigma_normal, q.sigma_albedo, q.sigma_depth}, true, q.sigma_lum, q.lum_eps,
-            "guided denoise"};
-}
-static int denoise_check_params(mcpt_ctx* c, const DenoiseRequest& r) {
-    if (r.p.passes < 1 || r.p.passes > 8) return set_err(c, MCPT_E_INVALID, std::string(r.who) + ": passes must be 1..8");
-    if (!r.guided) return MCPT_OK;
-    if (!(r.sigma_lum > 0.f) || !(r.sigma_lum <= 3.402823466e+38f))
-        return set_err(c, MCPT_E_INVALID, "guided denoise: sigma_lum must be > 0");
-    if (!(r.lum_eps >= 0.f) || !(r.lum_eps <= 3.402823466e+38f))
-        return set_err(c, MCPT_E_INVALID, "guided denoise: lum_eps must be >= 0");
-    return MCPT_OK;
-}
-// The passes over planes of a W x H image: col ping-pongs, and vl with it where the request is guided
-// (vl is not looked at otherwise); *result = the plane that holds the last pass
-static int denoise_passes(mcpt_ctx* c, const DenoiseRequest& r, uint32_t W, uint32_t H, float4* const col[2],
-                          float2* const vl[2], const float4* gd, const float4* al, int* result) {
-    const mcpt_denoise_params& p = r.p;
-    int lds_max = 2;  // MCPT_DENOISE_LDS_MAX: the widest stride that takes the LDS kernel (A/B; same bits)
-    if (const char* e = getenv(kDenoiseLdsEnv))
-        if (e[0] >= '0' && e[0] <= '2' && e[1] == 0) lds_max = e[0] - '0';
-    for (int i = 0; i < 8; i++) c->dn_ms[1 + i] = 0.f;
-    int src = 0;
-    for (int i = 0; i < p.passes; i++) {
-        DenoiseGuidedArgs a{};
-        float sc = p.sigma_color;
-        for (int k = 0; k < i; k++) sc = sc * 0.5f;  // sigma_color 2^-i
-        a.k.kc = mcpt::dn_k(sc);
-        a.k.kn = mcpt::dn_k(p.sigma_normal);
-        a.k.ka = mcpt::dn_k(p.sigma_albedo);
-        a.k.kz = mcpt::dn_k(p.sigma_depth);
-        a.k.stride = 1 << i;
-        a.W = (int)W;
-        a.H = (int)H;
-        a.col = col[src];
-        a.gd = gd;
-        a.al = al;
-        a.out = col[src ^ 1];
-        if (r.guided) a.v = {r.sigma_lum, r.lum_eps, vl[src], vl[src ^ 1]};
-        HIPCHK(c, hipEventRecord(ev(c, 1 + (size_t)i), c->stream));
-        launch_denoise_pass(a, lds_max, c->stream);
-        src ^= 1;
-    }
-    HIPCHK(c, hipEventRecord(ev(c, 1 + (size_t)p.passes), c->stream));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipEventElapsedTime(&c->dn_ms[0], c->events[0], c->events[1]));
-    for (int i = 0; i < p.passes; i++) HIPCHK(c, hipEventElapsedTime(&c->dn_ms[1 + i], c->events[1 + i], c->events[2 + i]));
-    *result = src;
-    return MCPT_OK;
-}
-// Read-back of a device plane: the rgb of n float4 / the first component of n float2
-static int read_rgb(mcpt_ctx* c, const float4* d, size_t n, float* rgb) {
-    std::vector<float4> o(n);
-    HIPCHK(c, hipMemcpy(o.data(), d, n * sizeof(float4), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; i++) { rgb[3 * i] = o[i].x; rgb[3 * i + 1] = o[i].y; rgb[3 * i + 2] = o[i].z; }
-    return MCPT_OK;
-}
-static int read_x(mcpt_ctx* c, const float2* d, size_t n, float* x) {
-    std::vector<float2> o(n);
-    HIPCHK(c, hipMemcpy(o.data(), d, n * sizeof(float2), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; i++) x[i] = o[i].x;
-    return MCPT_OK;
-}
-
-// mcpt_denoise_run / mcpt_denoise_guided_run (whose null checks come first): upload, planes, passes,
-// read-back.  variance and out_variance are the guided form's; out_variance may be nullptr.
-static int denoise_run(mcpt_ctx* c, const DenoiseRequest& r, uint32_t w, uint32_t h, const float* rgb, const uint32_t* samples,
-                       const float* variance, const float* albedo, const float* normal, const float* depth, float* out_rgb,
-                       float* out_variance) {
-    if (w == 0 || h == 0 || (uint64_t)w * h >= (1ull << 28))
-        return set_err(c, MCPT_E_INVALID, std::string(r.who) + ": bad image size");
-    int rc = denoise_check_params(c, r);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t n = (size_t)w * h;
-    free_list(c->tmp_bufs);
-    auto& L = c->tmp_bufs;
-    float *d_rgb, *d_al, *d_n, *d_z, *d_v = nullptr;
-    uint32_t* d_s = nullptr;
-    float4 *col[2], *gd, *al;
-    float2* vl[2] = {nullptr, nullptr};
-    if ((rc = dupload(c, L, &d_rgb, rgb, 3 * n)) || (rc = dupload(c, L, &d_al, albedo, 3 * n)) ||
-        (rc = dupload(c, L, &d_n, normal, 3 * n)) || (rc = dupload(c, L, &d_z, depth, n)) ||
-        (samples && (rc = dupload(c, L, &d_s, samples, n))) || (rc = dalloc(c, L, &col[0], n)) ||
-        (rc = dalloc(c, L, &col[1], n)) || (rc = dalloc(c, L, &gd, n)) || (rc = dalloc(c, L, &al, n)) ||
-        (r.guided && ((rc = dupload(c, L, &d_v, variance, n)) || (rc = dalloc(c, L, &vl[0], n)) || (rc = dalloc(c, L, &vl[1], n))))) {
-        free_list(L);
-        return rc;
-    }
-    DenoiseGuidedPrepArgs pa{};
-    pa.samples = d_s;
-    pa.rgb = d_rgb;
-    pa.normal = d_n;
-    pa.albedo = d_al;
-    pa.depth = d_z;
-    pa.col = col[0];
-    pa.gd = gd;
-    pa.al = al;
-    pa.n = (uint32_t)n;
-    pa.variance = d_v;
-    pa.vl = vl[0];
-    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
-    launch_denoise_prep(pa, c->stream);
-    int res = 0;
-    if ((rc = denoise_passes(c, r, w, h, col, vl, gd, al, &res))) return rc;
-    if ((rc = read_rgb(c, col[res], n, out_rgb))) return rc;
-    if (out_variance && (rc = read_x(c, vl[res], n, out_variance))) return rc;
-    free_list(L);
-    return MCPT_OK;
-}
-
-// mcpt_film_denoise / mcpt_film_denoise_guided: the film and the context's guides through the
-// context's planes.  Guided: the variance is se^2 of a fresh mcpt_film_error estimate, on that
-// call's own path (its checks: >= 2 path slots, no paths in flight).
-static int film_denoise(mcpt_ctx* c, const DenoiseRequest& r) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
-    int rc = denoise_check_params(c, r);
-    if (rc) return rc;
-    if (!guides_valid(c))
-        return set_err(c, MCPT_E_INVALID, "denoise: guide buffers missing or stale (camera, scene or film changed): call mcpt_guides_render first");
-    if (r.guided && (rc = mcpt_film_error(c))) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!denoise_planes_ensure(c, r.guided)) return set_err(c, MCPT_E_NOMEM, std::string(r.who) + ": plane allocation failed");
-    DenoiseGuidedPrepArgs pa{};
-    if ((rc = film_view(c, &pa.Ld, &pa.samples))) return rc;
-    pa.g_alb = c->g_alb;
-    pa.g_nz = c->g_nz;
-    pa.col = c->dn_col[0];
-    pa.gd = c->dn_gd;
-    pa.al = c->dn_al;
-    pa.n = (uint32_t)c->P;
-    if (r.guided) {
-        pa.err = c->err4;
-        pa.vl = c->dn_vl[0];
-    }
-    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
-    launch_denoise_prep(pa, c->stream);
-    int res = 0;
-    if ((rc = denoise_passes(c, r, c->W, c->H, c->dn_col, c->dn_vl, c->dn_gd, c->dn_al, &res))) return rc;
-    c->dn_result = res;
-    c->dn_guided = r.guided;
-    return MCPT_OK;
-}
-
-extern "C" {
-
-int mcpt_denoise_default_params(mcpt_denoise_params* p) {
-    if (!p) return MCPT_E_INVALID;
-    // the best row of profiles/denoise_defaults.txt (4 spp against 1024 spp; configs 1, 2, cube)
-    p->passes = 5;
-    p->sigma_color = 2.0f;
-    p->sigma_normal = 0.3f;
-    p->sigma_albedo = 0.3f;
-    p->sigma_depth = 0.1f;
-    return MCPT_OK;
-}
-
-int mcpt_guides_render(mcpt_ctx* c, uint32_t nsamples) {
-    int rc = check_ready(c);
-    if (rc) return rc;
-    if (nsamples < 1 || nsamples >= kMaxSpp - 256) return set_err(c, MCPT_E_INVALID, "guides: nsamples must be 1 .. 2^19 - 257");
-    HIPCHK(c, hipSetDevice(c->device));
-    c->guides_ok = false;
-    const size_t P = c->P;
-    if (!c->g_alb || !c->g_nz) {
-        denoise_free(c);  // (the filter's planes go too: they are re-made on demand)
-        if (hipMalloc(&c->g_alb, P * sizeof(float4)) != hipSuccess || hipMalloc(&c->g_nz, P * sizeof(float4)) != hipSuccess) {
-            (void)hipGetLastError();
-            denoise_free(c);
-            return set_err(c, MCPT_E_NOMEM, "guides: buffer allocation failed");
-        }
-    }
-    // Chunk: np pixels x ns samples of rays; per ray 2 float4 (ray), 2 float4 (hit record), 1 index
-    constexpr size_t kRayBytes = 4 * sizeof(float4) + sizeof(int32_t);
-    size_t budget = (size_t)64 << 20;
-    if (const char* e = getenv(kGuideChunkEnv)) {
-        const long long v = atoll(e);
-        if (v > 0) budget = (size_t)v;
-    }
-    const size_t R = std::min<size_t>(std::max<size_t>(budget / kRayBytes, 1), (size_t)1 << 24);
-    const uint32_t n_eff = c->cam.lens_radius > 0.f ? nsamples : 1u;  // a pinhole's samples share one ray
-    const uint32_t np_max = (uint32_t)std::min<size_t>(P, R);
-    const uint32_t ns_max = (uint32_t)std::min<size_t>(n_eff, std::max<size_t>(R / np_max, 1));
-    const size_t nr = (size_t)np_max * ns_max;
-    free_list(c->tmp_bufs);
-    float4 *ro, *rd, *hp, *hn;
-    int32_t* ht;
-    if ((rc = dalloc(c, c->tmp_bufs, &ro, nr)) || (rc = dalloc(c, c->tmp_bufs, &rd, nr)) ||
-        (rc = dalloc(c, c->tmp_bufs, &hp, nr)) || (rc = dalloc(c, c->tmp_bufs, &hn, nr)) ||
-        (rc = dalloc(c, c->tmp_bufs, &ht, nr))) {
-        (void)hipGetLastError();
-        free_list(c->tmp_bufs);
-        return rc;
-    }
-    GuideArgs ga{};
-    ga.cam = c->cam;
-    if ((rc = cam_table(c, c->W, c->H, &ga.cam_px, &ga.cam_dir))) return rc;
-    ga.W = (int)c->W;
-    ga.H = (int)c->H;
-    ga.seed = c->cfg.seed;
-    ga.ro = ro;
-    ga.rd = rd;
-    ga.hit_p = hp;
-    ga.hit_n = hn;
-    ga.mats = c->scene.mats;
-    ga.g_alb = c->g_alb;
-    ga.g_nz = c->g_nz;
-    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->g_alb, 0, P * sizeof(float4), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->g_nz, 0, P * sizeof(float4), c->stream));
-    bool drained = true;
-    for (size_t p0 = 0; p0 < P; p0 += np_max) {
-        ga.p0 = (uint32_t)p0;
-        ga.np = (uint32_t)std::min<size_t>(np_max, P - p0);
-        for (uint32_t s0 = 0; s0 < n_eff; s0 += ns_max) {
-            ga.s0 = s0;
-            ga.ns = std::min<uint32_t>(ns_max, n_eff - s0);
-            const uint32_t n = ga.np * ga.ns;
-            launch_guide_rays(ga, c->stream);
-            // closest hits as mcpt_stage_run(EXTEND) traces them: no occluder cache, unfiltered rays
-            TraceArgs ta{};
-            ta.scene = c->scene;
-            ta.scene.occ = nullptr;
-            ta.nshards = 1;
-            TraceSet& ts = ta.set[0];
-            ts.ro = ro;
-            ts.rd = rd;
-            ts.count = n;
-            ts.shard_cap = n;
-            ta.hit_tri = ht;
-            ta.grab = &c->cnt->grab[0][0];
-            ta.tiny_stack = c->tiny_stack ? 1 : 0;
-            launch_trace(ta, c->geom, c->stream);
-            HIPCHK(c, hipMemcpyAsync(&c->cnt_host->grab[0][0], &c->cnt->grab[0][0], sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemsetAsync(c->cnt->grab, 0, sizeof(c->cnt->grab), c->stream));  // hand-out counters back to 0
-            HitRecordArgs ha{c->scene, ro, rd, ht, hp, hn, ht, n};
-            launch_hit_record(ha, c->stream);
-            launch_guide_accum(ga, c->stream);
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipStreamSynchronize(c->stream));  // the next chunk reuses the buffers (and the staging word)
-            if (c->cnt_host->grab[0][0] < n) drained = false;
-        }
-    }
-    HIPCHK(c, hipEventRecord(ev(c, 1), c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipEventElapsedTime(&c->guides_ms, c->events[0], c->events[1]));
-    free_list(c->tmp_bufs);
-    if (!drained) return set_err(c, MCPT_E_HIP, "guides: k_trace left rays untraced");
-    c->guides_scene_gen = c->scene_gen;
-    c->guides_cam = c->cam;
-    c->guides_seed = c->cfg.seed;
-    c->guides_ok = true;
-    return MCPT_OK;
-}
-
-int mcpt_guides_read(mcpt_ctx* c, float* albedo, float* normal, float* depth, uint32_t* count) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
-    if (!guides_valid(c)) return set_err(c, MCPT_E_INVALID, "no valid guide buffers: call mcpt_guides_render first");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::vector<float4> a(c->P), n(c->P);
-    HIPCHK(c, hipMemcpy(a.data(), c->g_alb, c->P * sizeof(float4), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(n.data(), c->g_nz, c->P * sizeof(float4), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < c->P; i++) {
-        if (albedo) { albedo[3 * i] = a[i].x; albedo[3 * i + 1] = a[i].y; albedo[3 * i + 2] = a[i].z; }
-        if (normal) { normal[3 * i] = n[i].x; normal[3 * i + 1] = n[i].y; normal[3 * i + 2] = n[i].z; }
-        if (depth) depth[i] = n[i].w;
-        if (count) count[i] = (uint32_t)a[i].w;
-    }
-    return MCPT_OK;
-}
-
-int mcpt_denoise_run(mcpt_ctx* c, uint32_t w, uint32_t h, const float* rgb, const uint32_t* samples, const float* albedo,
-                     const float* normal, const float* depth, const mcpt_denoise_params* pp, float* out_rgb) {
-    if (!c || !rgb || !albedo || !normal || !depth || !out_rgb || !pp) return set_err(c, MCPT_E_INVALID, "denoise: null argument");
-    return denoise_run(c, denoise_request(*pp), w, h, rgb, samples, nullptr, albedo, normal, depth, out_rgb, nullptr);
-}
-
-int mcpt_film_denoise(mcpt_ctx* c, const mcpt_denoise_params* pp) {
-    mcpt_denoise_params p;
-    if (pp) p = *pp;
-    else (void)mcpt_denoise_default_params(&p);
-    return film_denoise(c, denoise_request(p));
-}
-
-static int denoised_check(mcpt_ctx* c) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
-    if (c->dn_result < 0) return set_err(c, MCPT_E_INVALID, "no denoised frame: call mcpt_film_denoise first");
-    return MCPT_OK;
-}
-
-int mcpt_denoised_read(mcpt_ctx* c, float* rgb) {
-    int rc = denoised_check(c);
-    if (rc) return rc;
-    if (!rgb) return set_err(c, MCPT_E_INVALID, "null argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return read_rgb(c, c->dn_col[c->dn_result], c->P, rgb);
-}
-
-int mcpt_denoised_read_device(mcpt_ctx* c, void* d_rgb) {
-    int rc = denoised_check(c);
-    if (rc) return rc;
-    if (!d_rgb) return set_err(c, MCPT_E_INVALID, "null argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(d_rgb, c->dn_col[c->dn_result], c->P * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return MCPT_OK;
-}
-
-int mcpt_denoised_tonemap_rgba8(mcpt_ctx* c, float exposure, uint8_t* out) {
-    int rc = denoised_check(c);
-    if (rc) return rc;
-    if (!out) return set_err(c, MCPT_E_INVALID, "null argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    // k_tonemap over the denoised means with a sample count of 1 per pixel
-    uchar4* d = nullptr;
-    uint32_t* ones = nullptr;
-    if (hipMalloc(&d, c->P * sizeof(uchar4)) != hipSuccess || hipMalloc(&ones, c->P * sizeof(uint32_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        if (d) (void)hipFree(d);
-        return set_err(c, MCPT_E_NOMEM, "tonemap buffers");
-    }
-    hipError_t e = hipMemsetD32Async((hipDeviceptr_t)ones, 1, c->P, c->stream);
-    if (e == hipSuccess) {
-        TonemapArgs a{c->dn_col[c->dn_result], ones, d, exposure, (uint32_t)c->P};
-        launch_tonemap(a, c->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(out, d, c->P * sizeof(uchar4), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    (void)hipFree(ones);
-    if (e != hipSuccess) return set_err(c, MCPT_E_HIP, std::string("tonemap: ") + hipGetErrorString(e));
-    return MCPT_OK;
-}
-
-// ---- variance-guided form ----
-
-int mcpt_denoise_guided_default_params(mcpt_denoise_guided_params* p) {
-    if (!p) return MCPT_E_INVALID;
-    // sigma_lum / lum_eps: the best row of profiles/denoise_guided_defaults.txt (4 and 16 spp and an
-    // adaptive frame against 1024 spp; configs 1, 2, cube).  The rest: mcpt_denoise_default_params
-    p->passes = 5;
-    p->sigma_lum = 8.0f;
-    p->lum_eps = 0.f;
-    p->sigma_color = 2.0f;
-    p->sigma_normal = 0.3f;
-    p->sigma_albedo = 0.3f;
-    p->sigma_depth = 0.1f;
-    return MCPT_OK;
-}
-
-int mcpt_denoise_guided_run(mcpt_ctx* c, uint32_t w, uint32_t h, const float* rgb, const uint32_t* samples, const float* variance,
-                            const float* albedo, const float* normal, const float* depth, const mcpt_denoise_guided_params* pp,
-                            float* out_rgb, float* out_variance) {
-    if (!c || !rgb || !variance || !albedo || !normal || !depth || !out_rgb || !pp)
-        return set_err(c, MCPT_E_INVALID, "guided denoise: null argument");
-    return denoise_run(c, denoise_request(*pp), w, h, rgb, samples, variance, albedo, normal, depth, out_rgb, out_variance);
-}
-
-int mcpt_film_denoise_guided(mcpt_ctx* c, const mcpt_denoise_guided_params* pp) {
-    mcpt_denoise_guided_params p;
-    if (pp) p = *pp;
-    else (void)mcpt_denoise_guided_default_params(&p);
-    return film_denoise(c, denoise_request(p));
-}
-
-int mcpt_denoised_variance_read(mcpt_ctx* c, float* var) {
-    int rc = denoised_check(c);
-    if (rc) return rc;
-    if (!c->dn_guided) return set_err(c, MCPT_E_INVALID, "no denoised variance: the last denoise was not mcpt_film_denoise_guided");
-    if (!var) return set_err(c, MCPT_E_INVALID, "null argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return read_x(c, c->dn_vl[c->dn_result], c->P, var);
-}
-
-int mcpt_debug_denoise_ms(const mcpt_ctx* c, float* out10) {
-    if (!c || !out10) return MCPT_E_INVALID;
-    out10[0] = c->guides_ms;
-    for (int i = 0; i < 9; i++) out10[1 + i] = c->dn_ms[i];
-    return MCPT_OK;
-}
-
-// ---- adaptive sampling ----
-
-// Whether the last iteration since the film clear left live paths (the counters' host copy)
-static int paths_in_flight(mcpt_ctx* c, bool* live) {
-    if (!c->totals_ok) {
-        HIPCHK(c, hipMemcpyAsync(c->cnt_host, c->cnt, sizeof(CounterBlock), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->totals = *c->cnt_host;
-        c->totals_ok = true;
-    }
-    *live = c->totals.last_live != 0;
-    return MCPT_OK;
-}
-// What a finished frame leaves behind that would keep raised sample counts from being picked up: the
-// k_shade block done flags and the counter block's idle word (run_iterations resets the latter per
-// call too).  The film, the flags words' next sample indices and the ray counters stay.
-static int frame_done_reset(mcpt_ctx* c) {
-    if (c->blk_done) HIPCHK(c, hipMemsetAsync(c->blk_done, 0, c->blk_done_n, c->stream));
-    HIPCHK(c, hipMemsetAsync(&c->cnt->idle, 0, sizeof(uint32_t), c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return MCPT_OK;
-}
-// The film tiles' ownership for the current tile set and layout (OwnMap), uploaded
-static int own_map_build(mcpt_ctx* c, OwnMap* m) {
-    const uint32_t ntx = (c->W + c->tile_w - 1) / c->tile_w, nty = (c->H + c->tile_h - 1) / c->tile_h;
-    std::vector<int32_t> own((size_t)ntx * nty, -1);
-    for (size_t i = 0; i < c->tiles_h.size(); i++) own[(size_t)c->tiles_h[i].y * ntx + (size_t)c->tiles_h[i].x] = (int32_t)i;
-    for (const int2& t : c->unpacked) own[(size_t)t.y * ntx + (size_t)t.x] = -1;  // another context's pixels
-    if (own.size() > c->own_map_cap) {
-        if (c->own_map) {
-            (void)hipFree(c->own_map);
-            c->adaptive_bytes -= std::max<size_t>(c->own_map_cap * sizeof(int32_t), 16);
-            c->own_map = nullptr;
-            c->own_map_cap = 0;
-        }
-        int rc = adaptive_alloc(c, &c->own_map, own.size());
-        if (rc) return rc;
-        c->own_map_cap = own.size();
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(c->own_map, own.data(), own.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    *m = OwnMap{c->own_map, c->compact ? 1 : 0, (int)c->tile_w, (int)c->tile_h, (int)c->W, (int)c->H};
-    return MCPT_OK;
-}
-
-int mcpt_set_sample_budget(mcpt_ctx* c, const uint32_t* budget) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
-    HIPCHK(c, hipSetDevice(c->device));
-    bool live = false;
-    int rc = paths_in_flight(c, &live);
-    if (rc) return rc;
-    if (live) return set_err(c, MCPT_E_INVALID, "sample budget: paths are in flight (finish the render or clear the film)");
-    uint32_t mx = 0;
-    if (budget) {
-        for (size_t i = 0; i < c->P; i++) mx = std::max(mx, budget[i]);
-        if (mx > kMaxSpp - 256) return set_err(c, MCPT_E_INVALID, "sample budget: an entry exceeds 2^19 - 256");
-        if ((rc = adaptive_alloc(c, &c->budget, c->P))) return rc;
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipMemcpy(c->budget, budget, c->P * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    c->budget_on = budget != nullptr;
-    c->budget_max = mx;
-    return frame_done_reset(c);
-}
-
-int mcpt_sample_budget_read(mcpt_ctx* c, uint32_t* out) {
-    if (!c || !out) return set_err(c, MCPT_E_INVALID, "null argument");
-    if (!c->budget_on) return set_err(c, MCPT_E_INVALID, "no sample budget installed");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out, c->budget, c->P * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return MCPT_OK;
-}
-
-int mcpt_set_spp(mcpt_ctx* c, int32_t spp) {
-    if (!c) return MCPT_E_INVALID;
-    if (spp < 0 || (uint32_t)spp > kMaxSpp - 256) return set_err(c, MCPT_E_INVALID, "spp must be 0..2^19-256");
-    if (c->P) {
-        HIPCHK(c, hipSetDevice(c->device));
-        bool live = false;
-        int rc = paths_in_flight(c, &live);
-        if (rc) return rc;
-        if (live) return set_err(c, MCPT_E_INVALID, "set_spp: paths are in flight (finish the render or clear the film)");
-    }
-    c->cfg.spp = spp;
-    return c->P ? frame_done_reset(c) : MCPT_OK;
-}
-
-int mcpt_film_error(mcpt_ctx* c) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
-    if (c->slots < 2) return set_err(c, MCPT_E_INVALID, "film error: needs at least 2 path slots (mcpt_set_path_slots)");
-    HIPCHK(c, hipSetDevice(c->device));
-    bool live = false;
-    int rc = paths_in_flight(c, &live);
-    if (rc) return rc;
-    if (live) return set_err(c, MCPT_E_INVALID, "film error: paths are in flight");
-    if ((rc = adaptive_alloc(c, &c->err4, c->P))) return rc;
-    FilmErrorArgs a{};
-    if ((rc = own_map_build(c, &a.m))) return rc;
-    a.Ld = c->p.Ld;
-    a.samples = c->p.samples;
-    a.stride = c->npx;
-    a.slots = (int)c->slots;
-    a.out = c->err4;
-    c->err_ok = false;
-    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
-    launch_film_error(a, c->stream);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(ev(c, 1), c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipEventElapsedTime(&c->err_ms, c->events[0], c->events[1]));
-    c->err_ok = true;
-    return MCPT_OK;
-}
-
-int mcpt_film_error_read(mcpt_ctx* c, float* out4) {
-    if (!c || !out4) return set_err(c, MCPT_E_INVALID, "null argument");
-    if (!c->err_ok) return set_err(c, MCPT_E_INVALID, "no film error estimate (call mcpt_film_error first)");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out4, c->err4, c->P * sizeof(float4), hipMemcpyDeviceToHost));
-    return MCPT_OK;
-}
-
-int mcpt_error_run(mcpt_ctx* c, uint32_t w, uint32_t h, uint32_t slots, const float* Ld_slots, const uint32_t* samples_slots,
-                   float* out4) {
-    if (!c || !Ld_slots || !samples_slots || !out4) return set_err(c, MCPT_E_INVALID, "error run: null argument");
-    if (w == 0 || h == 0 || slots == 0 || slots > 256 || (uint64_t)w * h * slots >= (1ull << 28))
-        return set_err(c, MCPT_E_INVALID, "error run: bad image size or slot count");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t n = (size_t)w * h;
-    std::vector<float4> L4(n * slots);
-    for (size_t i = 0; i < n * slots; i++) L4[i] = make_float4(Ld_slots[3 * i], Ld_slots[3 * i + 1], Ld_slots[3 * i + 2], 0.f);
-    free_list(c->tmp_bufs);
-    auto& L = c->tmp_bufs;
-    float4 *d_L, *d_out;
-    uint32_t* d_s;
-    int rc;
-    if ((rc = dupload(c, L, &d_L, L4.data(), n * slots)) || (rc = dupload(c, L, &d_s, samples_slots, n * slots)) ||
-        (rc = dalloc(c, L, &d_out, n))) {
-        free_list(L);
-        return rc;
-    }
-    FilmErrorArgs a{};
-    a.m = OwnMap{nullptr, 0, (int)w, (int)h, (int)w, (int)h};
-    a.Ld = d_L;
-    a.samples = d_s;
-    a.stride = n;
-    a.slots = (int)slots;
-    a.out = d_out;
-    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
-    launch_film_error(a, c->stream);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(ev(c, 1), c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipEventElapsedTime(&c->err_ms, c->events[0], c->events[1]));
-    HIPCHK(c, hipMemcpy(out4, d_out, n * sizeof(float4), hipMemcpyDeviceToHost));
-    free_list(L);
-    return MCPT_OK;
-}
-
-int mcpt_debug_film_read_slot(mcpt_ctx* c, uint32_t slot, float* Ld, uint32_t* samples) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
-    if (slot >= c->slots) return set_err(c, MCPT_E_INVALID, "slot out of range");
-    HIPCHK(c, hipSetDevice(c->device));
-    SlotImageArgs a{};
-    int rc = own_map_build(c, &a.m);
-    if (rc) return rc;
-    free_list(c->tmp_bufs);
-    auto& L = c->tmp_bufs;
-    if ((rc = dalloc(c, L, &a.out_Ld, c->P)) || (rc = dalloc(c, L, &a.out_samples, c->P))) {
-        free_list(L);
-        return rc;
-    }
-    a.Ld = c->p.Ld + (size_t)slot * c->npx;
-    a.samples = c->p.samples + (size_t)slot * c->npx;
-    launch_slot_image(a, c->stream);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (Ld) {
-        std::vector<float4> tmp(c->P);
-        HIPCHK(c, hipMemcpy(tmp.data(), a.out_Ld, c->P * sizeof(float4), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < c->P; i++) { Ld[3 * i] = tmp[i].x; Ld[3 * i + 1] = tmp[i].y; Ld[3 * i + 2] = tmp[i].z; }
-    }
-    if (samples) HIPCHK(c, hipMemcpy(samples, a.out_samples, c->P * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    free_list(L);
-    return MCPT_OK;
-}
-
-int mcpt_sample_budget_default_params(mcpt_sample_budget_params* p) {
-    if (!p) return MCPT_E_INVALID;
-    // target_rel_err: see DESIGN.md section 11 for the rows it was chosen from
-    p->target_rel_err = 0.05f;
-    p->lum_floor = 0.01f;
-    p->min_spp = 32;
-    p->max_spp = 256;
-    return MCPT_OK;
-}
-
-int mcpt_budget_from_error(mcpt_ctx* c, const mcpt_sample_budget_params* pp, uint64_t* out3) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
-    mcpt_sample_budget_params p;
-    if (pp) p = *pp;
-    else (void)mcpt_sample_budget_default_params(&p);
-    if (!(p.target_rel_err > 0.f) || !(p.target_rel_err <= 3.402823466e+38f) || !(p.lum_floor >= 0.f) ||
-        !(p.lum_floor <= 3.402823466e+38f) || p.min_spp > p.max_spp || p.max_spp > kMaxSpp - 256)
-        return set_err(c, MCPT_E_INVALID, "budget: bad parameters (target_rel_err > 0, lum_floor >= 0, min_spp <= max_spp <= 2^19-256)");
-    if (!c->err_ok) return set_err(c, MCPT_E_INVALID, "budget: no film error estimate (call mcpt_film_error first)");
-    HIPCHK(c, hipSetDevice(c->device));
-    bool live = false;
-    int rc = paths_in_flight(c, &live);
-    if (rc) return rc;
-    if (live) return set_err(c, MCPT_E_INVALID, "budget: paths are in flight");
-    if ((rc = adaptive_alloc(c, &c->budget, c->P)) || (rc = adaptive_alloc(c, &c->bud_cnt, 4))) return rc;
-    BudgetArgs a{};
-    if ((rc = own_map_build(c, &a.m))) return rc;
-    a.err = c->err4;
-    a.p = mcpt::BudgetParams{p.target_rel_err, p.lum_floor, p.min_spp, p.max_spp};
-    a.budget = c->budget;
-    a.cnt = c->bud_cnt;
-    HIPCHK(c, hipMemsetAsync(c->bud_cnt, 0, 4 * sizeof(unsigned long long), c->stream));
-    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
-    launch_budget(a, c->stream);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(ev(c, 1), c->stream));
-    unsigned long long cnt[4] = {};
-    HIPCHK(c, hipMemcpyAsync(cnt, c->bud_cnt, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipEventElapsedTime(&c->budget_ms, c->events[0], c->events[1]));
-    // (an entry past a pixel's n > max_spp is that n: still a count the film holds, below 2^19)
-    c->budget_on = true;
-    c->budget_max = (uint32_t)cnt[1];
-    if (out3) { out3[0] = cnt[0]; out3[1] = cnt[1]; out3[2] = cnt[2]; }
-    return frame_done_reset(c);
-}
-
-int64_t mcpt_debug_adaptive_bytes(const mcpt_ctx* c) { return c ? (int64_t)c->adaptive_bytes : (int64_t)MCPT_E_INVALID; }
-
-int mcpt_debug_adaptive_ms(const mcpt_ctx* c, float* out2) {
-    if (!c || !out2) return MCPT_E_INVALID;
-    out2[0] = c->err_ms;
-    out2[1] = c->budget_ms;
-    return MCPT_OK;
-}
-
-// ---- temporal accumulation ----
-
-int mcpt_set_seed(mcpt_ctx* c, uint64_t seed) {
-    if (!c) return MCPT_E_INVALID;
-    if (c->P) {
-        HIPCHK(c, hipSetDevice(c->device));
-        bool live = false;
-        int rc = paths_in_flight(c, &live);
-        if (rc) return rc;
-        if (live) return set_err(c, MCPT_E_INVALID, "set_seed: paths are in flight (finish the render or clear the film)");
-    }
-    c->cfg.seed = seed;  // (guides_valid compares it: the guides are stale from here on)
-    return c->P ? mcpt_film_clear(c) : MCPT_OK;
-}
-
-int mcpt_camera_view_proj(const mcpt_camera* cam, float* out16) {
-    if (!cam || !out16) return MCPT_E_INVALID;
-    mcpt::tp_view_proj(cam->inv_view_proj, out16);
-    return MCPT_OK;
-}
-
-int mcpt_temporal_default_params(mcpt_temporal_params* p) {
-    if (!p) return MCPT_E_INVALID;
-    // the best row of profiles/temporal_defaults.txt (8 frames of 2 spp against 1024 spp; configs 1, 2, cube).
-    // With 2-spp frames max_history 8 bounds alpha at 0.2 from below, SVGF's value; the rows that reach
-    // that bound through alpha_min tie with it exactly.
-    p->pos_tol = 0.1f;
-    p->nrm_tol = 1.0f;
-    p->max_history = 8.f;
-    p->alpha_min = 0.f;
-    return MCPT_OK;
-}
-
-static int temporal_check_params(mcpt_ctx* c, const mcpt_temporal_params& p) {
-    const auto bad = [](float v) { return !(v >= 0.f) || !(v <= 3.402823466e+38f); };
-    if (bad(p.pos_tol)) return set_err(c, MCPT_E_INVALID, "temporal: pos_tol must be a finite number >= 0");
-    if (bad(p.nrm_tol)) return set_err(c, MCPT_E_INVALID, "temporal: nrm_tol must be a finite number >= 0");
-    if (bad(p.max_history)) return set_err(c, MCPT_E_INVALID, "temporal: max_history must be a finite number >= 0");
-    if (bad(p.alpha_min) || p.alpha_min > 1.f) return set_err(c, MCPT_E_INVALID, "temporal: alpha_min must be in [0, 1]");
-    return MCPT_OK;
-}
-static mcpt::TemporalParams temporal_params(const mcpt_temporal_params& p) {
-    return mcpt::TemporalParams{p.pos_tol, p.nrm_tol, p.max_history, p.alpha_min};
-}
-// k_temporal between events 0 and 1 of the context's stream; its device time -> tp_ms
-static int temporal_launch(mcpt_ctx* c, const TemporalArgs& a) {
-    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
-    launch_temporal(a, c->stream);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(ev(c, 1), c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipEventElapsedTime(&c->tp_ms, c->events[0], c->events[1]));
-    return MCPT_OK;
-}
-
-int mcpt_film_temporal(mcpt_ctx* c, const mcpt_temporal_params* pp) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
-    mcpt_temporal_params p;
-    if (pp) p = *pp;
-    else (void)mcpt_temporal_default_params(&p);
-    int rc = temporal_check_params(c, p);
-    if (rc) return rc;
-    if (!guides_valid(c))
-        return set_err(c, MCPT_E_INVALID, "temporal: guide buffers missing or stale (camera, scene, seed or film changed): call mcpt_guides_render first");
-    HIPCHK(c, hipSetDevice(c->device));
-    bool live = false;
-    if ((rc = paths_in_flight(c, &live))) return rc;
-    if (live) return set_err(c, MCPT_E_INVALID, "temporal: paths are in flight");
-    if (c->slots >= 2 && (rc = mcpt_film_error(c))) return rc;
-    if (!c->tp_bytes) {
-        bool ok = true;
-        const auto need = [&](void** q, size_t bytes) {
-            if (ok && hipMalloc(q, bytes) != hipSuccess) {
-                *q = nullptr;
-                ok = false;
-            }
-        };
-        for (int s = 0; s < 2; s++)
-            for (int k = 0; k < 3; k++) need((void**)&c->tp_h[s][k], c->P * sizeof(float4));
-        need((void**)&c->tp_col, c->P * sizeof(float4));
-        need((void**)&c->tp_vl, c->P * sizeof(float2));
-        if (!ok) {
-            (void)hipGetLastError();
-            temporal_free(c);
-            return set_err(c, MCPT_E_NOMEM, "temporal: plane allocation failed");
-        }
-        c->tp_bytes = c->P * (7 * sizeof(float4) + sizeof(float2));
-    }
-    const int prev = c->tp_set, next = prev ^ 1;
-    if (!c->tp_ok)  // no history: N = 0 everywhere, and every tap is rejected
-        for (int k = 0; k < 3; k++) HIPCHK(c, hipMemsetAsync(c->tp_h[prev][k], 0, c->P * sizeof(float4), c->stream));
-    TemporalArgs a{};
-    a.W = (int)c->W;
-    a.H = (int)c->H;
-    a.k = temporal_params(p);
-    mcpt::tp_view_proj(c->tp_ok ? c->tp_cam.ivp : c->cam.ivp, a.vp_prev);
-    if ((rc = film_view(c, &a.Ld, &a.samples))) return rc;
-    a.err = c->slots >= 2 ? c->err4 : nullptr;
-    a.g_alb = c->g_alb;
-    a.g_nz = c->g_nz;
-    if ((rc = cam_table(c, c->W, c->H, &a.cam_px, &a.cam_dir))) return rc;
-    a.cam = c->cam;
-    a.hcol = c->tp_h[prev][0];
-    a.hpos = c->tp_h[prev][1];
-    a.hnrm = c->tp_h[prev][2];
-    a.col = c->tp_col;
-    a.vl = c->tp_vl;
-    a.out_hcol = c->tp_h[next][0];
-    a.out_hpos = c->tp_h[next][1];
-    a.out_hnrm = c->tp_h[next][2];
-    c->tp_ok = false;
-    if ((rc = temporal_launch(c, a))) return rc;
-    c->tp_set = next;
-    c->tp_cam = c->cam;
-    c->tp_ok = true;
-    return MCPT_OK;
-}
-
-int mcpt_temporal_reset(mcpt_ctx* c) {
-    if (!c) return MCPT_E_INVALID;
-    c->tp_ok = false;
-    return MCPT_OK;
-}
-
-int mcpt_temporal_read(mcpt_ctx* c, float* rgb, float* nsamples, float* variance, float* position) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
-    if (!c->tp_ok) return set_err(c, MCPT_E_INVALID, "no accumulated frame: call mcpt_film_temporal first");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::vector<float4> hc(c->P), hp(c->P);
-    HIPCHK(c, hipMemcpy(hc.data(), c->tp_h[c->tp_set][0], c->P * sizeof(float4), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(hp.data(), c->tp_h[c->tp_set][1], c->P * sizeof(float4), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < c->P; i++) {
-        if (rgb) { rgb[3 * i] = hc[i].x; rgb[3 * i + 1] = hc[i].y; rgb[3 * i + 2] = hc[i].z; }
-        if (nsamples) nsamples[i] = hc[i].w;
-        if (variance) variance[i] = hp[i].w;
-        if (position) { position[3 * i] = hp[i].x; position[3 * i + 1] = hp[i].y; position[3 * i + 2] = hp[i].z; }
-    }
-    return MCPT_OK;
-}
-
-int mcpt_temporal_denoise(mcpt_ctx* c, const mcpt_denoise_guided_params* pp) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
-    mcpt_denoise_guided_params p;
-    if (pp) p = *pp;
-    else (void)mcpt_denoise_guided_default_params(&p);
-    const DenoiseRequest r = denoise_request(p);
-    int rc = denoise_check_params(c, r);
-    if (rc) return rc;
-    if (!c->tp_ok) return set_err(c, MCPT_E_INVALID, "temporal denoise: no accumulated frame: call mcpt_film_temporal first");
-    if (!guides_valid(c) || memcmp(&c->tp_cam, &c->cam, sizeof(c->cam)) != 0)
-        return set_err(c, MCPT_E_INVALID, "temporal denoise: the camera, scene or seed changed since the frame was accumulated: call mcpt_guides_render and mcpt_film_temporal first");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!denoise_planes_ensure(c, true)) return set_err(c, MCPT_E_NOMEM, "temporal denoise: plane allocation failed");
-    const TemporalPrepArgs pa{c->tp_col, c->tp_vl, c->g_alb, c->g_nz, c->dn_col[0], c->dn_gd, c->dn_al, c->dn_vl[0], (uint32_t)c->P};
-    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
-    launch_temporal_prep(pa, c->stream);
-    int res = 0;
-    if ((rc = denoise_passes(c, r, c->W, c->H, c->dn_col, c->dn_vl, c->dn_gd, c->dn_al, &res))) return rc;
-    c->dn_result = res;
-    c->dn_guided = true;
-    return MCPT_OK;
-}
-
-int mcpt_temporal_run(mcpt_ctx* c, uint32_t w, uint32_t h, const float* rgb, const uint32_t* samples, const float* variance,
-                      const float* position, const float* normal, const float* depth, const float* hcol, const float* hpos,
-                      const float* hnrm, const float* vp_prev16, const mcpt_temporal_params* pp, float* out_col, float* out_vl,
-                      float* out_hcol, float* out_hpos, float* out_hnrm) {
-    if (!c || !rgb || !samples || !variance || !position || !normal || !depth || !hcol || !hpos || !hnrm || !vp_prev16 || !pp ||
-        !out_col || !out_vl || !out_hcol || !out_hpos || !out_hnrm)
-        return set_err(c, MCPT_E_INVALID, "temporal: null argument");
-    if (w == 0 || h == 0 || (uint64_t)w * h >= (1ull << 28)) return set_err(c, MCPT_E_INVALID, "temporal: bad image size");
-    int rc = temporal_check_params(c, *pp);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t n = (size_t)w * h;
-    free_list(c->tmp_bufs);
-    auto& L = c->tmp_bufs;
-    float *d_rgb, *d_v, *d_x, *d_n, *d_z, *d_hc, *d_hp, *d_hn;
-    uint32_t* d_s;
-    float4 *o_col, *o_hc, *o_hp, *o_hn;
-    float2* o_vl;
-    if ((rc = dupload(c, L, &d_rgb, rgb, 3 * n)) || (rc = dupload(c, L, &d_s, samples, n)) || (rc = dupload(c, L, &d_v, variance, n)) ||
-        (rc = dupload(c, L, &d_x, position, 3 * n)) || (rc = dupload(c, L, &d_n, normal, 3 * n)) ||
-        (rc = dupload(c, L, &d_z, depth, n)) || (rc = dupload(c, L, &d_hc, hcol, 4 * n)) || (rc = dupload(c, L, &d_hp, hpos, 4 * n)) ||
-        (rc = dupload(c, L, &d_hn, hnrm, 4 * n)) || (rc = dalloc(c, L, &o_col, n)) || (rc = dalloc(c, L, &o_vl, n)) ||
-        (rc = dalloc(c, L, &o_hc, n)) || (rc = dalloc(c, L, &o_hp, n)) || (rc = dalloc(c, L, &o_hn, n))) {
-        free_list(L);
-        return rc;
-    }
-    TemporalArgs a{};
-    a.W = (int)w;
-    a.H = (int)h;
-    a.k = temporal_params(*pp);
-    memcpy(a.vp_prev, vp_prev16, sizeof(a.vp_prev));
-    a.samples = d_s;
-    a.rgb = d_rgb;
-    a.variance = d_v;
-    a.position = d_x;
-    a.normal = d_n;
-    a.depth = d_z;
-    a.hcol = (const float4*)d_hc;
-    a.hpos = (const float4*)d_hp;
-    a.hnrm = (const float4*)d_hn;
-    a.col = o_col;
-    a.vl = o_vl;
-    a.out_hcol = o_hc;
-    a.out_hpos = o_hp;
-    a.out_hnrm = o_hn;
-    if ((rc = temporal_launch(c, a))) return rc;
-    HIPCHK(c, hipMemcpy(out_col, o_col, n * sizeof(float4), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(out_vl, o_vl, n * sizeof(float2), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(out_hcol, o_hc, n * sizeof(float4), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(out_hpos, o_hp, n * sizeof(float4), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(out_hnrm, o_hn, n * sizeof(float4), hipMemcpyDeviceToHost));
-    free_list(L);
-    return MCPT_OK;
-}
-
-int64_t mcpt_debug_temporal_bytes(const mcpt_ctx* c) { return c ? (int64_t)c->tp_bytes : (int64_t)MCPT_E_INVALID; }
-
-int mcpt_debug_temporal_ms(const mcpt_ctx* c, float* out1) {
-    if (!c || !out1) return MCPT_E_INVALID;
-    out1[0] = c->tp_ms;
-    return MCPT_OK;
-}
-
-}  // extern "C"

@@ -1,0 +1,310 @@
+// runtime_internal.hpp -- what runtime.cpp (context, scene, film, render loop) and postprocess.cpp
+// (guides, denoise, adaptive sampling, temporal accumulation) share: the device context behind the
+// mcpt_* C ABI, its error helpers, the owner of a device buffer and a few host helpers.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "kernels.hpp"
+#include "mcpt.h"
+
+using namespace mcpt_dev;
+
+namespace mcpt_host {
+void set_global_error(const std::string& e);
+const char* global_error();
+}  // namespace mcpt_host
+
+// Owner of one hipMalloc'd array of T: move-only, freed exactly once (reset(), or the destructor).
+template <class T>
+class DevBuf {
+    T* p_ = nullptr;
+    size_t n_ = 0;  // elements
+
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr, o.n_ = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            std::swap(p_, o.p_);
+            std::swap(n_, o.n_);
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    void reset() {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+        n_ = 0;
+    }
+    // A buffer of at least count elements: one that is large enough is kept (contents too), else it is
+    // replaced.  false: the allocation failed and the buffer is empty (hipGetLastError has the cause).
+    bool ensure(size_t count) {
+        if (p_ && n_ >= count) return true;
+        reset();
+        if (hipMalloc((void**)&p_, std::max<size_t>(count * sizeof(T), 16)) != hipSuccess) {
+            p_ = nullptr;
+            return false;
+        }
+        n_ = count;
+        return true;
+    }
+    size_t size() const { return n_; }
+    size_t bytes() const { return p_ ? std::max<size_t>(n_ * sizeof(T), 16) : 0; }  // as allocated
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+};
+
+// What a view-dependent product was built for.  Each product stores the key of its build and names
+// the fields it depends on when it compares that key with the context's current one.
+struct ViewKey {
+    enum : unsigned { SCENE = 1, SEED = 2, SIZE = 4, CAM = 8 };
+    uint64_t scene_gen = 0, seed = 0;
+    uint32_t W = 0, H = 0;
+    mcpt::CamView cam{};
+    bool same(const ViewKey& o, unsigned fields) const {
+        return (!(fields & SCENE) || scene_gen == o.scene_gen) && (!(fields & SEED) || seed == o.seed) &&
+               (!(fields & SIZE) || (W == o.W && H == o.H)) && (!(fields & CAM) || memcmp(&cam, &o.cam, sizeof(cam)) == 0);
+    }
+};
+
+// Per-pixel camera records (cam_table): valid for the film size and camera of `key`
+struct CamTable {
+    DevBuf<float4> tab;  // pixel records, then directions
+    ViewKey key;
+    bool ok = false;
+};
+
+// Primary-hit candidate table (prim_table): built for (scene upload, camera, film size); a film
+// clear keeps it.  Best-effort: any failure leaves it off and the primary rays are traversed.
+// (MCPT_PRIMARY_HITS=0: off, for A/B runs and tests.  bench.py has no entry for the switch and
+// stamps a run that sets it as an unknown knob, i.e. not the product.)
+struct PrimTable {
+    bool on = [] { const char* e = getenv(kPrimaryHitsEnv); return !(e && e[0] == '0' && e[1] == 0); }();
+    DevBuf<uint8_t> cnt;
+    DevBuf<uint32_t> list, stats;  // stats: k_primary_build's two counters
+    DevBuf<uint2> q;
+    bool ok = false;      // the table is valid for `key`
+    bool failed = false;  // the build for `key` failed: not retried until the key changes
+    ViewKey key;
+    uint64_t builds = 0;            // table builds so far
+    uint32_t lists = 0, over = 0;   // the current table: pixels with a list / overflow pixels
+    float build_ms = 0.f;           // the last build
+    void release() {  // the buffers go; key, failed and the counts stay
+        cnt.reset(), list.reset(), stats.reset(), q.reset();
+        ok = false;
+    }
+};
+
+// Preview denoiser.  Guide sums of the W x H film: alb (albedo rgb, sample
+// count), nz (normal xyz, depth), allocated by the first mcpt_guides_render, valid for the (scene
+// upload, seed, camera) of `key`.  Freed with the film.
+struct Guides {
+    DevBuf<float4> alb, nz;
+    bool ok = false;
+    ViewKey key;
+};
+// The filter's planes of the film (two colour planes in ping-pong, guides, albedo), allocated by the
+// first mcpt_film_denoise[_guided] (denoise_planes_ensure); result: the colour plane that holds the
+// last result (-1: none).  Variance-guided form: the {variance, luminance}
+// planes in ping-pong beside col, allocated by the first guided call; guided: result is a guided
+// result, whose variances are vl[result].  Freed with the film.
+struct Denoise {
+    DevBuf<float4> col[2], gd, al;
+    DevBuf<float2> vl[2];
+    int result = -1;
+    bool guided = false;
+};
+// Adaptive sampling, all keyed by film pixel and allocated by the first call
+// that needs them: budget, the per-pixel sample budget k_shade reads in place of cfg.spp while
+// budget_on (budget_max: its largest entry, which sizes mcpt_render's batches); err4, the last
+// mcpt_film_error result {se, mean, K, n} (err_ok); own_map, the film tiles' ownership (OwnMap) as
+// of the last call that used it; bud_cnt, k_budget's three counters.  Film clears, slot, tile-set
+// and layout changes keep them; mcpt_film_resize frees them.
+struct Adaptive {
+    DevBuf<uint32_t> budget;
+    bool budget_on = false;
+    uint32_t budget_max = 0;
+    DevBuf<float4> err4;
+    bool err_ok = false;
+    DevBuf<int32_t> own_map;
+    DevBuf<unsigned long long> bud_cnt;
+    size_t bytes() const { return budget.bytes() + err4.bytes() + own_map.bytes() + bud_cnt.bytes(); }  // mcpt_debug_adaptive_bytes
+};
+// Temporal accumulation, allocated by the first mcpt_film_temporal: two sets
+// of history planes {hcol, hpos, hnrm} in ping-pong (a call gathers from one and writes the other;
+// set: the one that holds the last accumulated frame), that frame's colour and vl planes for the
+// spatial passes, and its camera in `key` (ok: there is such a frame).  Film clears, seed, camera and
+// slot changes keep them; a scene upload and mcpt_temporal_reset forget the frame, mcpt_film_resize
+// frees everything.
+struct Temporal {
+    DevBuf<float4> h[2][3], col;
+    DevBuf<float2> vl;
+    int set = 0;
+    bool ok = false;
+    ViewKey key;
+    size_t bytes() const {  // mcpt_debug_temporal_bytes
+        size_t b = col.bytes() + vl.bytes();
+        for (const auto& s : h)
+            for (const auto& p : s) b += p.bytes();
+        return b;
+    }
+};
+// Device times of the last launches (mcpt_debug_*_ms).  Kept apart from the state above: the *_run
+// entry points time launches over temporaries, and a time outlives the buffers it was measured on.
+struct StageMs {
+    float guides = 0.f, dn[9] = {};    // the last guide pass / filter set-up and passes
+    float err = 0.f, budget = 0.f;     // the last k_film_error / k_budget
+    float tp = 0.f;                    // the last k_temporal
+};
+
+struct mcpt_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::string err;
+    mcpt_config cfg{};
+    char devname[256] = {0};
+    int num_cu = 0;
+    LaunchGeom geom{};             // persistent grids and k_trace partitions of this device
+    uint32_t trace_parts_default = 1;
+    // scene
+    std::vector<void*> scene_bufs;
+    DevScene scene{};
+    bool has_scene = false;
+    bool has_scene_before = false;  // set at the start of a re-upload
+    int32_t ntri = 0;               // triangles of the uploaded scene
+    size_t occ_entries_n = 0;       // occluder-cache table entries (DevScene::occ; + kOccGateWords gate words)
+    uint32_t* occ_init = nullptr;   // the table as the upload's pre-fill left it (film clears restore it); nullptr: empty
+    int pair_depth = 0;
+    bool cull_ok = true, occ_nest_ok = true;  // last upload: boxes contain their triangles / nest (scene_upload)
+    // traversal work counters (mcpt_set_work_counters): k_trace's counting instantiation, whose six
+    // per-lane counters cost the fast one its spill-free registers -- off by default
+    bool count_work = getenv("MCPT_WORK_COUNTERS") != nullptr;
+    int node_layout = 0;  // pair-node numbering the last upload used (mcpt_debug_node_layout)
+    // mcpt_set_skip_discarded: paths the next logic pass is certain to end make no extension ray
+    // (ShadeArgs::skip); results and ray counts are the same either way
+    bool skip_discarded = true;
+    // camera
+    mcpt::CamView cam{};
+    bool has_cam = false;
+    CamTable cam_tab;
+    PrimTable prim;
+    uint64_t scene_gen = 0;  // scene uploads so far
+    // Film observes camera and scene (Film::update -> clear(), Film.cu:278-281; notified by
+    // Camera::update, Camera.cu:207, and Scene::notify, Scene.cu:534-545): a change marks the
+    // film stale and the next iteration clears it first (unless MCPT_FLAG_NO_AUTO_CLEAR).
+    bool film_stale = false;
+    // film + paths
+    uint32_t W = 0, H = 0, tile_w = 256, tile_h = 256;
+    size_t P = 0;      // pixels (W * H)
+    uint32_t slots = 1;  // path slots per pixel (mcpt_set_path_slots); path state holds slots * npx paths
+    // Path layout (mcpt_set_compact_paths).  Full: npx = P, path index = slot * P + pixel id.  Compact:
+    // the path state covers the tile set only, npx = tile-set tiles x tile pixels (ShadeArgs::npx).
+    bool compact = false;
+    size_t npx = 0;
+    float4* film_Ld = nullptr;     // slots > 1 or compact: the film, W x H (sum of the slot accumulators)
+    uint32_t* film_samples = nullptr;
+    std::vector<void*> film_bufs;
+    uint8_t* blk_done = nullptr;  // k_shade block done flags (ShadeArgs::blk_done), in film_bufs
+    size_t blk_done_n = 0;
+    bool blk_done_off = getenv("MCPT_NO_BLOCK_DONE") != nullptr;  // A/B switch: every block runs
+    DevPaths p{};
+    uint32_t *ext_q = nullptr, *any_q = nullptr, *mat_q = nullptr;
+    float4* any_ray = nullptr;          // any-hit rays at their queue positions: o [2 queue_alloc], then d
+    uint32_t ext_cap = 0, any_cap = 0;  // per-shard capacities
+    size_t queue_alloc = 0;             // entries allocated for ext_q (any_q holds twice)
+    CounterBlock* cnt = nullptr;
+    CounterBlock* cnt_host = nullptr;  // pinned
+    CounterBlock totals{};             // host copy of the counters after the last call (valid: totals_ok)
+    bool totals_ok = false;
+    int2* step_tile = nullptr;         // mcpt_wavefront_step's one-tile set: device + pinned staging (16 B:
+    int2* step_tile_h = nullptr;       // the tile, then its index in the tile set, ShadeArgs::tile_base)
+    int2* tiles = nullptr;
+    std::vector<int2> tiles_h;
+    // tiles holding pixels scattered in from another context (mcpt_film_unpack_tiles, mcpt_gather)
+    // since the last film clear: the full layout's slot 0 holds them, so they may not become own
+    // tiles before a clear (their sample count restarts from the flags word while Ld accumulates)
+    std::vector<int2> unpacked;
+    uint32_t tiles_cap = 0;
+    std::vector<hipEvent_t> events;
+    // scratch of one call (TmpScope; the stage runs)
+    std::vector<void*> tmp_bufs;
+    float last_stage_ms = 0.f;
+    float last_build_ms = 0.f;  // last GPU BVH build (mcpt_scene_upload_gpu_bvh)
+    float last_env_build_ms = 0.f;  // last device build of the HRDI tables (env_build.hip)
+    bool env_device_built = false;  // the uploaded scene's HRDI tables were built on the device
+    bool env_guides = false;        // env_cell uses the search guides
+    int gpu_bvh_builder = MCPT_GPU_BVH_PLOC;  // mcpt_set_gpu_bvh_builder
+    bool tiny_stack = false;  // mcpt_debug_tiny_lds_stack: k_trace with a 2-entry LDS stack (tests)
+    unsigned long long phase_base[kPhaseWords] = {};  // mcpt_debug_trace_profile's reset point
+    // film post-processing (postprocess.cpp)
+    Guides guides;
+    Denoise dn;
+    Adaptive ad;
+    Temporal tp;
+    StageMs ms;
+
+    ViewKey view() const { return ViewKey{scene_gen, cfg.seed, W, H, cam}; }
+};
+
+inline int set_err(mcpt_ctx* c, int rc, const std::string& msg) {
+    if (c) c->err = msg;
+    mcpt_host::set_global_error(msg);
+    return rc;
+}
+#define HIPCHK(c, x)                                                                          \
+    do {                                                                                      \
+        hipError_t e_ = (x);                                                                  \
+        if (e_ != hipSuccess)                                                                 \
+            return set_err((c), MCPT_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_));  \
+    } while (0)
+
+inline void free_list(std::vector<void*>& v) {
+    for (void* q : v)
+        if (q) (void)hipFree(q);
+    v.clear();
+}
+template <class T>
+int dalloc(mcpt_ctx* c, std::vector<void*>& list, T** out, size_t count) {
+    void* q = nullptr;
+    size_t bytes = std::max<size_t>(count * sizeof(T), 16);
+    hipError_t e = hipMalloc(&q, bytes);
+    if (e != hipSuccess) return set_err(c, MCPT_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    list.push_back(q);
+    *out = (T*)q;
+    return MCPT_OK;
+}
+template <class T>
+int dupload(mcpt_ctx* c, std::vector<void*>& list, T** out, const T* src, size_t count) {
+    int rc = dalloc(c, list, out, count);
+    if (rc) return rc;
+    if (count) HIPCHK(c, hipMemcpy(*out, src, count * sizeof(T), hipMemcpyHostToDevice));
+    return MCPT_OK;
+}
+// The temporaries of one call (dalloc / dupload into c->tmp_bufs): the list starts empty and is freed
+// on every return.
+struct TmpScope {
+    std::vector<void*>& L;
+    explicit TmpScope(mcpt_ctx* c) : L(c->tmp_bufs) { free_list(L); }
+    ~TmpScope() { free_list(L); }
+    TmpScope(const TmpScope&) = delete;
+    TmpScope& operator=(const TmpScope&) = delete;
+};
+
+// Defined in runtime.cpp (C++ linkage: `extern "C++"` where they stand inside its extern "C" block)
+hipEvent_t ev(mcpt_ctx* c, size_t i);
+int check_ready(mcpt_ctx* c);
+int cam_table(mcpt_ctx* c, uint32_t W, uint32_t H, const float4** px, const float4** dir);
+int film_view(mcpt_ctx* c, const float4** Ld, const uint32_t** samples);
+// n float4 of a device plane to the host: the xyz as 3 floats per element and / or the w (nullptr: not wanted)
+int read_plane(mcpt_ctx* c, const float4* d, size_t n, float* xyz, float* w);
+// k_tonemap over a W x H colour plane and its per-pixel sample counts (nullptr: 1 everywhere) -> out
+int tonemap_rgba8(mcpt_ctx* c, const float4* col, const uint32_t* samples, float exposure, uint8_t* out);
