@@ -3,7 +3,7 @@
 // INTEGRATION.md): build a BASELINE config scene with the host builder, upload it,
 // run the wavefront iterations until every pixel has its samples, write PNG + PFM.
 //
-//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>]
+//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill]
 //
 // --denoise renders the first-hit guide buffers (default 4 guide samples per pixel), filters the film
 // with the default parameters and writes <out_prefix>_denoised.png beside the raw image.
@@ -18,6 +18,9 @@
 // every frame its own seed, accumulates each into the temporal history and filters it (DESIGN.md section
 // 13); it writes the last frame's <out_prefix>_temporal.png beside that frame's single-frame
 // <out_prefix>_denoised.png.  It uses 2 path slots if --slots is not given (the variance).
+// --variance-fill turns the spatial variance estimate on (at its defaults): the
+// variances the path slots do not give are estimated from the frame, so --denoise-guided and --temporal
+// work with --slots 1, which is what they then use if --slots is not given.
 // --tiles-per-call uses the reference orchestration (one 256x256 tile per call,
 // wavefront_kernels.cu:377-442 + Film::update_tile_position) instead of batch mode.
 #include <stdio.h>
@@ -33,7 +36,7 @@ struct Cfg { int w, h, spp, depth; float pos[3], pitch; const char* env; };
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>]\n", argv[0]);
+        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill]\n", argv[0]);
         return 2;
     }
     const Cfg cfgs[6] = {{0, 0, 0, 0, {0, 0, 0}, 0, ""},
@@ -49,7 +52,7 @@ int main(int argc, char** argv) {
     std::string out = (argc > 3 && argv[3][0] != '-') ? argv[3] : "mcpt_render";
     bool gpu_bvh = false, ref_bvh = false, fixed = false, per_tile = false;
     uint32_t slots = 1, guide_samples = 0, guided_samples = 0;  // guide_samples / guided_samples > 0: denoise [guided]
-    bool adaptive = false, slots_given = false;
+    bool adaptive = false, slots_given = false, variance_fill = false;
     mcpt_sample_budget_params ap;
     mcpt_sample_budget_default_params(&ap);
     uint32_t rounds = 2;
@@ -64,6 +67,7 @@ int main(int argc, char** argv) {
         if (!strcmp(argv[i], "--gpu-bvh")) gpu_bvh = true;
         if (!strcmp(argv[i], "--reference-bvh")) ref_bvh = true;
         if (!strcmp(argv[i], "--fixed")) fixed = true;
+        if (!strcmp(argv[i], "--variance-fill")) variance_fill = true;
         if (!strcmp(argv[i], "--tiles-per-call")) per_tile = true;
         if (!strcmp(argv[i], "--slots") && i + 1 < argc) { slots = (uint32_t)atoi(argv[++i]); slots_given = true; }
         if (!strcmp(argv[i], "--adaptive")) {
@@ -83,8 +87,9 @@ int main(int argc, char** argv) {
             if (i + 1 < argc && argv[i + 1][0] >= '1' && argv[i + 1][0] <= '9') guided_samples = (uint32_t)atoi(argv[++i]);
         }
     }
-    if (guided_samples && !slots_given) slots = 4;  // the variance is the spread of the path slots' means
-    if (t_frames && !slots_given) slots = 2;  // the variance is the spread of the path slots' means
+    // the variance is the spread of the path slots' means, or with --variance-fill the frame's own estimate
+    if (guided_samples && !slots_given && !variance_fill) slots = 4;
+    if (t_frames && !slots_given && !variance_fill) slots = 2;
     if (adaptive && !slots_given) slots = 8;  // the estimate is the spread of the path slots' means
     if (adaptive) c.spp = (int)ap.min_spp;    // the first pass
     const char* assets = getenv("MCPT_ASSETS") ? getenv("MCPT_ASSETS") : "assets";
@@ -116,6 +121,8 @@ int main(int argc, char** argv) {
     if (!rc) rc = mcpt_camera_set(ctx, &cam);
     if (!rc) rc = mcpt_set_path_slots(ctx, slots);  // paths in flight per pixel (default 1)
     if (!rc) rc = mcpt_film_resize(ctx, c.w, c.h, 256, 256);
+    mcpt_variance_params vp;
+    if (!rc && variance_fill && !(rc = mcpt_variance_default_params(&vp))) rc = mcpt_set_variance_fill(ctx, &vp);
     if (rc) { fprintf(stderr, "setup: %s\n", mcpt_last_error(ctx)); return 1; }
 
     mcpt_stage_stats st{};

@@ -344,8 +344,9 @@ int mcpt_denoise_guided_run(mcpt_ctx *ctx, uint32_t w, uint32_t h, const float *
 /* Filter the film as mcpt_film_denoise does, with v = se^2 of a fresh mcpt_film_error estimate (which
  * it runs itself and leaves readable through mcpt_film_error_read): needs valid guides, >= 2 path
  * slots and no paths in flight.  Pixels without an estimate (fewer than 2 slots with samples; pixels
- * scattered in from another context) take the plain term.  The result replaces the last denoised
- * frame: the mcpt_denoised_* readers serve it. */
+ * scattered in from another context) take the plain term, unless mcpt_set_variance_fill is on (below),
+ * which also lifts the slot requirement.  The result replaces the last denoised frame: the
+ * mcpt_denoised_* readers serve it. */
 int mcpt_film_denoise_guided(mcpt_ctx *ctx, const mcpt_denoise_guided_params *p);
 /* The filtered variances (W*H floats, -1 where unknown) of the last denoise; MCPT_E_INVALID unless
  * that was mcpt_film_denoise_guided. */
@@ -446,7 +447,7 @@ typedef struct mcpt_temporal_params {
 int mcpt_temporal_default_params(mcpt_temporal_params *p);
 /* Accumulate the film into the history (p == NULL: the defaults): needs valid guides and no paths in
  * flight; with >= 2 path slots v_c = se^2 of a fresh mcpt_film_error estimate, with 1 slot every
- * variance is unknown.  Uses the camera and planes the previous call stored, then stores this call's.
+ * variance is unknown (mcpt_set_variance_fill, below, estimates the unknown ones).  Uses the camera and planes the previous call stored, then stores this call's.
  * The first call, and any call after a reset, accumulates nothing.  mcpt_temporal_reset drops the
  * history, and so do a scene upload and mcpt_film_resize; film clears, mcpt_set_seed, camera changes
  * and mcpt_set_path_slots keep it. */
@@ -473,6 +474,49 @@ int mcpt_temporal_run(mcpt_ctx *ctx, uint32_t w, uint32_t h, const float *rgb, c
  * (ms) of the last k_temporal launch. */
 int64_t mcpt_debug_temporal_bytes(const mcpt_ctx *ctx);
 int mcpt_debug_temporal_ms(const mcpt_ctx *ctx, float *out1);
+/* ---- spatial variance estimate: a variance of the mean luminance for pixels
+ * the path slots give none -- every pixel of a one-slot render, pixels scattered in from another
+ * context, host frames -- from the frame itself, as SVGF's spatial fallback does (Schied et al. 2017,
+ * 4.2).  Opt-in: a context that never calls these launches nothing for them and every entry point above
+ * computes what it always did, the one-slot refusal of mcpt_film_denoise_guided and the one-slot
+ * "variance unknown" of mcpt_film_temporal included.
+ *
+ * Of a valid pixel p without a known variance, over the valid taps q of the (2 radius + 1)^2 window:
+ *   e = 1 at p, else the filter's edge-stopping factor without its colour term (sigma_normal,
+ *   sigma_albedo, sigma_depth);  d = l(q) - l(p)
+ *   m = sum e d / sum e;  var = max(sum e d^2 / sum e - m^2, 0);  neff = (sum e)^2 / sum e^2
+ *   v = var neff / (neff - 1), known if neff >= min_neff and v is a finite number >= 0, else -1
+ * A known variance is kept; an invalid pixel stays at -1.  A constant window gives exactly 0, and
+ * radiance scaled by 2^k scales v by 4^k exactly.  The estimate is the variance among the neighbours'
+ * means: it assumes the window's pixels hold about the centre's sample count. */
+typedef struct mcpt_variance_params {
+    int32_t radius;                                  /* 1..3 */
+    float sigma_normal, sigma_albedo, sigma_depth;   /* <= 0 disables the term */
+    float min_neff;                                  /* >= 1 */
+} mcpt_variance_params;
+int mcpt_variance_default_params(mcpt_variance_params *p);
+/* The estimate over host images as mcpt_denoise_guided_run takes them (needs neither a scene nor a
+ * film): variance (w*h floats, a value outside [0, FLT_MAX] is "unknown") may be NULL (none known);
+ * out_variance: w*h floats, the known inputs unchanged, the estimate elsewhere, -1 where unknown. */
+int mcpt_variance_run(mcpt_ctx *ctx, uint32_t w, uint32_t h, const float *rgb, const uint32_t *samples,
+                      const float *variance, const float *albedo, const float *normal, const float *depth,
+                      const mcpt_variance_params *p, float *out_variance);
+/* p != NULL: mcpt_film_denoise_guided and mcpt_film_temporal fill the variances they do not know with
+ * the estimate over the current film frame (exactly mcpt_variance_run's values for the film's means, the
+ * guides' means and v = se^2 where the slots give one); p == NULL (the default): off.
+ *   mcpt_film_denoise_guided: with >= 2 path slots pixels of fewer than 2 slots with samples and
+ *     scattered-in pixels are filled; with 1 slot it is no longer refused, runs no mcpt_film_error
+ *     (but still needs no paths in flight), and every variance is the estimate.
+ *   mcpt_film_temporal: v_c is se^2 where the slots give one, else the estimate.  It forms them in
+ *     the filter's planes, so the last denoised frame is forgotten (mcpt_denoised_* return
+ *     MCPT_E_INVALID until the next denoise).
+ * mcpt_denoise_guided_run and mcpt_temporal_run are unchanged: compose them with mcpt_variance_run.
+ * The setting survives film clears, resizes, seed and slot changes.  MCPT_E_INVALID (radius outside
+ * 1..3, a sigma that is not finite, min_neff below 1 or not finite) leaves the previous setting. */
+int mcpt_set_variance_fill(mcpt_ctx *ctx, const mcpt_variance_params *p);
+/* Device time (ms) of the last k_variance_spatial launch.  (Where it runs inside a film denoise, the
+ * plane set-up time of mcpt_debug_denoise_ms includes it.) */
+int mcpt_debug_variance_ms(const mcpt_ctx *ctx, float *out1);
 int mcpt_sync(mcpt_ctx *ctx);
 int mcpt_device_name(mcpt_ctx *ctx, char *buf, int32_t len);
 /* diagnostics: rays of the current extension (which=0) or any-hit (which=1) queue, and the

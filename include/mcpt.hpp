@@ -582,6 +582,14 @@ public:
         if (guide_samples) detail::check(mcpt_guides_render(ctx_, guide_samples), ctx_, "guides");
         detail::check(mcpt_film_denoise_guided(ctx_, params), ctx_, "denoise_guided");
     }
+    // The spatial variance estimate (mcpt.h): with it on, denoise_guided() and temporal_accumulate()
+    // estimate the variances the path slots do not give from the frame itself, which makes both usable
+    // with one path slot.  params == nullptr: the defaults; set_variance_fill(false): off.
+    void set_variance_fill(bool on = true, const mcpt_variance_params* params = nullptr) {
+        mcpt_variance_params p;
+        if (on && !params) detail::check(mcpt_variance_default_params(&p), ctx_, "set_variance_fill");
+        detail::check(mcpt_set_variance_fill(ctx_, on ? (params ? params : &p) : nullptr), ctx_, "set_variance_fill");
+    }
     void denoised_variance(std::vector<float>& var) {
         uint32_t w = 0, h = 0;
         detail::check(mcpt_film_size(ctx_, &w, &h), ctx_, "denoised_variance");

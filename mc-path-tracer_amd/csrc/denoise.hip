@@ -211,7 +211,7 @@ __global__ void k_denoise_prep_film(DnPrepArgs<Guided> a) {
     a.gd[i] = gd;
     a.al[i] = al;
     if constexpr (Guided) {
-        const float se = a.err[i].x;
+        const float se = a.err ? a.err[i].x : -1.f;
         a.vl[i] = dn_vl(col, (se >= 0.f && dn_finite(se)) ? se * se : -1.f);
     }
 }
@@ -228,7 +228,7 @@ __global__ void k_denoise_prep_images(DnPrepArgs<Guided> a) {
     a.col[i] = col;
     a.gd[i] = gd;
     a.al[i] = al;
-    if constexpr (Guided) a.vl[i] = dn_vl(col, a.variance[i]);
+    if constexpr (Guided) a.vl[i] = dn_vl(col, a.variance ? a.variance[i] : -1.f);
 }
 template <bool Guided>
 static void launch_prep(const DnPrepArgs<Guided>& a, hipStream_t s) {

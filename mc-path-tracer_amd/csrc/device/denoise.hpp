@@ -89,19 +89,22 @@ MCPT_HD float dn_sq3(float ax, float ay, float az, float bx, float by, float bz)
 MCPT_HD float dn_xc(const DenoisePass& k, const float4& cp, const float4& cq) {
     return k.kc * dn_sq3(cp.x, cp.y, cp.z, cq.x, cq.y, cq.z);
 }
+// Edge-stopping factor of a tap q != p, given its colour term xc: exp(-(xc + the normal, albedo and
+// depth terms)); an exponent that is not a finite number >= 0 gives 0.  (aq.w is not looked at.)
+MCPT_HD float dn_edge(const DenoisePass& k, float xc, const float4& gp, const float4& ap, const float4& gq,
+                      const float4& aq) {
+    const float dn = dn_sq3(gp.x, gp.y, gp.z, gq.x, gq.y, gq.z);
+    const float da = dn_sq3(ap.x, ap.y, ap.z, aq.x, aq.y, aq.z);
+    const float dz = gp.w - gq.w;
+    const float x = ((xc + k.kn * dn) + k.ka * da) + (k.kz * (dz * dz)) * ap.w;
+    return (x >= 0.f && x <= 3.402823466e+38f) ? dexp_neg(x) : 0.f;
+}
 // Weight of tap q = p + stride (dx, dy) of a valid pixel p, given its colour term xc (dn_xc, or the
-// guided form's).  The centre's exponent is 0 by definition (its xc is not looked at); elsewhere an
-// exponent that is not a finite number >= 0 gives weight 0.
+// guided form's).  The centre's exponent is 0 by definition (its xc is not looked at).
 MCPT_HD float dn_weight(const DenoisePass& k, int dx, int dy, float xc, const float4& gp, const float4& ap,
                         const float4& gq, const float4& aq) {
     float e = 1.f;
-    if (dx != 0 || dy != 0) {
-        const float dn = dn_sq3(gp.x, gp.y, gp.z, gq.x, gq.y, gq.z);
-        const float da = dn_sq3(ap.x, ap.y, ap.z, aq.x, aq.y, aq.z);
-        const float dz = gp.w - gq.w;
-        const float x = ((xc + k.kn * dn) + k.ka * da) + (k.kz * (dz * dz)) * ap.w;
-        e = (x >= 0.f && x <= 3.402823466e+38f) ? dexp_neg(x) : 0.f;
-    }
+    if (dx != 0 || dy != 0) e = dn_edge(k, xc, gp, ap, gq, aq);
     return (dn_h(dy) * dn_h(dx)) * e;
 }
 MCPT_HD void dn_add(float w, const float4& cq, DnAcc& acc) {

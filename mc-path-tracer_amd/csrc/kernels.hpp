@@ -28,6 +28,7 @@
 #include "device/denoise.hpp"
 #include "device/mcpt_core.hpp"
 #include "device/temporal.hpp"
+#include "device/variance.hpp"
 
 namespace mcpt_dev {
 
@@ -420,7 +421,8 @@ struct DenoiseGuidedArgs : DenoiseArgs {
     mcpt::DenoiseVar v;
 };
 // Its planes: DenoisePrepArgs' plus vl, from the film's error plane err {se, mean, K, n} (with Ld:
-// variance = se se, unknown where se < 0 or not finite) or from a caller image of variances
+// variance = se se, unknown where se < 0 or not finite, and everywhere where err is nullptr) or from a
+// caller image of variances (nullptr: none is known)
 struct DenoiseGuidedPrepArgs : DenoisePrepArgs {
     const float4* err;
     const float* variance;
@@ -472,7 +474,8 @@ void launch_slot_image(const SlotImageArgs& a, hipStream_t s);
 // the colour and vl planes for the spatial passes and the new history planes out.  The current frame
 // comes from the film (Ld != nullptr: Ld / samples, err {se, ...} or nullptr without an estimate, the
 // guide sums and the camera records) or from caller images of means (rgb / position / normal 3 floats
-// per pixel, variance / depth 1, samples).
+// per pixel, variance / depth 1, samples).  vfill (film form only; nullptr: none): a vl plane of the
+// current film frame whose variance a pixel takes where err gives it none.
 struct TemporalArgs {
     int W, H;
     mcpt::TemporalParams k;
@@ -485,6 +488,7 @@ struct TemporalArgs {
     float4* col;
     float2* vl;
     float4 *out_hcol, *out_hpos, *out_hnrm;
+    const float2* vfill;
 };
 // The spatial passes' planes of n pixels from an accumulated frame: its colour and vl planes copied, the
 // guide and albedo planes from the guide sums as k_denoise_prep_film forms them
@@ -494,5 +498,16 @@ struct TemporalPrepArgs {
 };
 void launch_temporal(const TemporalArgs& a, hipStream_t s);
 void launch_temporal_prep(const TemporalPrepArgs& a, hipStream_t s);
+
+// ---- spatial variance estimate (variance.hip) ----
+// k_variance_spatial over the filter's planes of a W x H image, in place on vl: a valid pixel whose
+// variance is unknown gets the estimate (or stays unknown); col, gd, al and the luminances are read only
+struct VarianceArgs {
+    mcpt::VariancePass k;  // k.radius: 1 .. 3
+    int W, H;
+    const float4 *col, *gd, *al;
+    float2* vl;
+};
+void launch_variance_spatial(const VarianceArgs& a, hipStream_t s);
 
 }  // namespace mcpt_dev

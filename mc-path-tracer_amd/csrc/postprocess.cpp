@@ -1,7 +1,8 @@
 // postprocess.cpp -- film post-processing behind the mcpt_* C ABI (include/mcpt.h): the preview
 // denoiser's guide buffers and a-trous filter (DESIGN.md sections 10 and 12), adaptive sampling
-// (section 11) and temporal accumulation (section 13).  The context, the film and the render loop
-// are runtime.cpp's; runtime_internal.hpp holds what the two share.
+// (section 11), temporal accumulation (section 13) and the spatial variance estimate (section 14).
+// The context, the film and the render loop are runtime.cpp's; runtime_internal.hpp holds what the
+// two share.
 #include <cfloat>
 
 #include "runtime_internal.hpp"
@@ -194,33 +195,83 @@ static int denoise_run(mcpt_ctx* c, const DenoiseRequest& r, uint32_t w, uint32_
     return out_variance ? read_x(c, vl[res], n, out_variance) : MCPT_OK;
 }
 
-// mcpt_film_denoise / mcpt_film_denoise_guided: the film and the context's guides through the
-// context's planes.  Guided: the variance is se^2 of a fresh mcpt_film_error estimate, on that
-// call's own path (its checks: >= 2 path slots, no paths in flight).
-static int film_denoise(mcpt_ctx* c, const DenoiseRequest& r) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
-    int rc = denoise_check_params(c, r);
-    if (rc) return rc;
-    if (!guides_valid(c))
-        return set_err(c, MCPT_E_INVALID, "denoise: guide buffers missing or stale (camera, scene or film changed): call mcpt_guides_render first");
-    if (r.guided && (rc = mcpt_film_error(c))) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!denoise_planes_ensure(c, r.guided)) return set_err(c, MCPT_E_NOMEM, std::string(r.who) + ": plane allocation failed");
+// ---- spatial variance estimate: what the film stages below share ----
+static int variance_check_params(mcpt_ctx* c, const mcpt_variance_params& p) {
+    if (p.radius < 1 || p.radius > 3) return set_err(c, MCPT_E_INVALID, "variance: radius must be 1..3");
+    if (!mcpt::dn_finite(p.sigma_normal)) return set_err(c, MCPT_E_INVALID, "variance: sigma_normal must be a finite number");
+    if (!mcpt::dn_finite(p.sigma_albedo)) return set_err(c, MCPT_E_INVALID, "variance: sigma_albedo must be a finite number");
+    if (!mcpt::dn_finite(p.sigma_depth)) return set_err(c, MCPT_E_INVALID, "variance: sigma_depth must be a finite number");
+    if (!(p.min_neff >= 1.f && p.min_neff <= FLT_MAX)) return set_err(c, MCPT_E_INVALID, "variance: min_neff must be a finite number >= 1");
+    return MCPT_OK;
+}
+// k_variance_spatial over planes of a W x H image, in place on vl, between events 10 and 11 (past the
+// filter's 0 .. 9); variance_time, after the stream is synchronised: its device time -> ms.var
+constexpr size_t kVarianceEv = 10;
+static int variance_launch(mcpt_ctx* c, const mcpt_variance_params& p, uint32_t W, uint32_t H, const float4* col,
+                           const float4* gd, const float4* al, float2* vl) {
+    VarianceArgs a{};
+    a.k = mcpt::VariancePass{mcpt::dn_k(p.sigma_normal), mcpt::dn_k(p.sigma_albedo), mcpt::dn_k(p.sigma_depth), p.min_neff, p.radius};
+    a.W = (int)W;
+    a.H = (int)H;
+    a.col = col;
+    a.gd = gd;
+    a.al = al;
+    a.vl = vl;
+    HIPCHK(c, hipEventRecord(ev(c, kVarianceEv), c->stream));
+    launch_variance_spatial(a, c->stream);
+    HIPCHK(c, hipEventRecord(ev(c, kVarianceEv + 1), c->stream));
+    return MCPT_OK;
+}
+static int variance_time(mcpt_ctx* c) {
+    HIPCHK(c, hipEventElapsedTime(&c->ms.var, c->events[kVarianceEv], c->events[kVarianceEv + 1]));
+    return MCPT_OK;
+}
+// The film's planes into the context's (after denoise_planes_ensure(c, guided)).  Guided: variance =
+// se^2 of the last mcpt_film_error with >= 2 path slots, unknown everywhere with one; then, with the
+// fill on, the estimate where it is unknown.  Launches only; variance_time is the caller's.
+static int film_planes(mcpt_ctx* c, bool guided, const float4* Ld, const uint32_t* samples) {
     DenoiseGuidedPrepArgs pa{};
-    if ((rc = film_view(c, &pa.Ld, &pa.samples))) return rc;
+    pa.Ld = Ld;
+    pa.samples = samples;
     pa.g_alb = c->guides.alb;
     pa.g_nz = c->guides.nz;
     pa.col = c->dn.col[0];
     pa.gd = c->dn.gd;
     pa.al = c->dn.al;
     pa.n = (uint32_t)c->P;
-    if (r.guided) {
-        pa.err = c->ad.err4;
+    if (guided) {
+        pa.err = c->slots >= 2 ? c->ad.err4.get() : nullptr;
         pa.vl = c->dn.vl[0];
     }
-    if ((rc = span_begin(c))) return rc;
     launch_denoise_prep(pa, c->stream);
-    return denoise_film_planes(c, r);
+    if (!guided || !c->vf.on) return MCPT_OK;
+    return variance_launch(c, c->vf.p, c->W, c->H, c->dn.col[0], c->dn.gd, c->dn.al, c->dn.vl[0]);
+}
+
+// mcpt_film_denoise / mcpt_film_denoise_guided: the film and the context's guides through the
+// context's planes.  Guided: the variance is se^2 of a fresh mcpt_film_error estimate, on that
+// call's own path (its checks: >= 2 path slots, no paths in flight); with the variance fill on, one
+// path slot skips that call (no paths in flight all the same) and every variance is the estimate.
+static int film_denoise(mcpt_ctx* c, const DenoiseRequest& r) {
+    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    int rc = denoise_check_params(c, r);
+    if (rc) return rc;
+    if (!guides_valid(c))
+        return set_err(c, MCPT_E_INVALID, "denoise: guide buffers missing or stale (camera, scene or film changed): call mcpt_guides_render first");
+    if (r.guided && c->vf.on && c->slots < 2) {
+        HIPCHK(c, hipSetDevice(c->device));
+        if ((rc = require_idle(c, "guided denoise: paths are in flight"))) return rc;
+    } else if (r.guided && (rc = mcpt_film_error(c))) {
+        return rc;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!denoise_planes_ensure(c, r.guided)) return set_err(c, MCPT_E_NOMEM, std::string(r.who) + ": plane allocation failed");
+    const float4* Ld;
+    const uint32_t* samples;
+    if ((rc = film_view(c, &Ld, &samples)) || (rc = span_begin(c)) || (rc = film_planes(c, r.guided, Ld, samples)) ||
+        (rc = denoise_film_planes(c, r)))
+        return rc;
+    return (r.guided && c->vf.on) ? variance_time(c) : MCPT_OK;
 }
 
 extern "C" {
@@ -692,6 +743,9 @@ int mcpt_film_temporal(mcpt_ctx* c, const mcpt_temporal_params* pp) {
         t = Temporal{};
         return set_err(c, MCPT_E_NOMEM, "temporal: plane allocation failed");
     }
+    // the variance fill forms v_c in the filter's planes (which forgets the last denoised frame)
+    const bool fill = c->vf.on;
+    if (fill && !denoise_planes_ensure(c, true)) return set_err(c, MCPT_E_NOMEM, "temporal: plane allocation failed");
     const int prev = t.set, next = prev ^ 1;
     if (!t.ok)  // no history: N = 0 everywhere, and every tap is rejected
         for (int k = 0; k < 3; k++) HIPCHK(c, hipMemsetAsync(t.h[prev][k], 0, c->P * sizeof(float4), c->stream));
@@ -715,11 +769,15 @@ int mcpt_film_temporal(mcpt_ctx* c, const mcpt_temporal_params* pp) {
     a.out_hpos = t.h[next][1];
     a.out_hnrm = t.h[next][2];
     t.ok = false;
+    if (fill) {
+        if ((rc = film_planes(c, true, a.Ld, a.samples))) return rc;
+        a.vfill = c->dn.vl[0];
+    }
     if ((rc = temporal_launch(c, a))) return rc;
     t.set = next;
     t.key = c->view();
     t.ok = true;
-    return MCPT_OK;
+    return fill ? variance_time(c) : MCPT_OK;
 }
 
 int mcpt_temporal_reset(mcpt_ctx* c) {
@@ -811,6 +869,70 @@ int64_t mcpt_debug_temporal_bytes(const mcpt_ctx* c) { return c ? (int64_t)c->tp
 int mcpt_debug_temporal_ms(const mcpt_ctx* c, float* out1) {
     if (!c || !out1) return MCPT_E_INVALID;
     out1[0] = c->ms.tp;
+    return MCPT_OK;
+}
+
+// ---- spatial variance estimate ----
+
+int mcpt_variance_default_params(mcpt_variance_params* p) {
+    if (!p) return MCPT_E_INVALID;
+    // radius / min_neff: the best row of profiles/variance_defaults.txt (one-slot frames of 2 .. 16 spp
+    // against 1024 spp; configs 1, 2, cube).  The guide sigmas: mcpt_denoise_default_params
+    p->radius = 1;
+    p->sigma_normal = 0.3f;
+    p->sigma_albedo = 0.3f;
+    p->sigma_depth = 0.1f;
+    p->min_neff = 4.f;
+    return MCPT_OK;
+}
+
+int mcpt_variance_run(mcpt_ctx* c, uint32_t w, uint32_t h, const float* rgb, const uint32_t* samples, const float* variance,
+                      const float* albedo, const float* normal, const float* depth, const mcpt_variance_params* pp,
+                      float* out_variance) {
+    if (!c || !rgb || !albedo || !normal || !depth || !pp || !out_variance) return set_err(c, MCPT_E_INVALID, "variance: null argument");
+    if (w == 0 || h == 0 || (uint64_t)w * h >= (1ull << 28)) return set_err(c, MCPT_E_INVALID, "variance: bad image size");
+    int rc = variance_check_params(c, *pp);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = (size_t)w * h;
+    TmpScope tmp(c);
+    auto& L = tmp.L;
+    DenoiseGuidedPrepArgs pa{};
+    float *d_rgb, *d_al, *d_n, *d_z, *d_v = nullptr;
+    uint32_t* d_s = nullptr;
+    if ((rc = dupload(c, L, &d_rgb, rgb, 3 * n)) || (rc = dupload(c, L, &d_al, albedo, 3 * n)) ||
+        (rc = dupload(c, L, &d_n, normal, 3 * n)) || (rc = dupload(c, L, &d_z, depth, n)) ||
+        (samples && (rc = dupload(c, L, &d_s, samples, n))) || (variance && (rc = dupload(c, L, &d_v, variance, n))) ||
+        (rc = dalloc(c, L, &pa.col, n)) || (rc = dalloc(c, L, &pa.gd, n)) || (rc = dalloc(c, L, &pa.al, n)) ||
+        (rc = dalloc(c, L, &pa.vl, n)))
+        return rc;
+    pa.samples = d_s;
+    pa.rgb = d_rgb;
+    pa.normal = d_n;
+    pa.albedo = d_al;
+    pa.depth = d_z;
+    pa.variance = d_v;
+    pa.n = (uint32_t)n;
+    launch_denoise_prep(pa, c->stream);
+    if ((rc = variance_launch(c, *pp, w, h, pa.col, pa.gd, pa.al, pa.vl))) return rc;
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((rc = variance_time(c))) return rc;
+    return read_x(c, pa.vl, n, out_variance);
+}
+
+int mcpt_set_variance_fill(mcpt_ctx* c, const mcpt_variance_params* p) {
+    if (!c) return MCPT_E_INVALID;
+    if (p)
+        if (int rc = variance_check_params(c, *p)) return rc;
+    c->vf.on = p != nullptr;
+    if (p) c->vf.p = *p;
+    return MCPT_OK;
+}
+
+int mcpt_debug_variance_ms(const mcpt_ctx* c, float* out1) {
+    if (!c || !out1) return MCPT_E_INVALID;
+    out1[0] = c->ms.var;
     return MCPT_OK;
 }
 

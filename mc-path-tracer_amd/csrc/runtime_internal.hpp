@@ -164,6 +164,13 @@ struct StageMs {
     float guides = 0.f, dn[9] = {};    // the last guide pass / filter set-up and passes
     float err = 0.f, budget = 0.f;     // the last k_film_error / k_budget
     float tp = 0.f;                    // the last k_temporal
+    float var = 0.f;                   // the last k_variance_spatial
+};
+// Spatial variance estimate: the mcpt_set_variance_fill setting.  It holds no
+// buffer and belongs to no film size, so nothing resets it.
+struct VarianceFill {
+    bool on = false;
+    mcpt_variance_params p{};
 };
 
 struct mcpt_ctx {
@@ -250,6 +257,7 @@ struct mcpt_ctx {
     Denoise dn;
     Adaptive ad;
     Temporal tp;
+    VarianceFill vf;
     StageMs ms;
 
     ViewKey view() const { return ViewKey{scene_gen, cfg.seed, W, H, cam}; }

@@ -35,6 +35,7 @@ __global__ __launch_bounds__(256) void k_temporal(TemporalArgs a) {
             const float se = a.err[i].x;
             var = (se >= 0.f && dn_finite(se)) ? se * se : -1.f;
         }
+        if (a.vfill && !(var >= 0.f)) var = a.vfill[i].x;  // no slot estimate: the spatial one (or -1)
         const float4 cp = a.cam_px[i], cd = a.cam_dir[i];
         // (the camera table holds pFocal for a lens and the pinhole origin otherwise: k_cam_table)
         const V3 X = a.cam.lens_radius > 0.f ? tp_world_focal(a.cam, v3(cp.x, cp.y, cp.z), z)

@@ -92,6 +92,11 @@ class TemporalParams(C.Structure):  # mcpt_temporal_params
     _fields_ = [("pos_tol", C.c_float), ("nrm_tol", C.c_float), ("max_history", C.c_float), ("alpha_min", C.c_float)]
 
 
+class VarianceParams(C.Structure):  # mcpt_variance_params
+    _fields_ = [("radius", C.c_int32), ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float),
+                ("sigma_depth", C.c_float), ("min_neff", C.c_float)]
+
+
 class PathView(C.Structure):  # mcpt_path_view: path state at the shading stages' boundary
     _fields_ = [("film_w", C.c_uint32), ("film_h", C.c_uint32), ("flags", _u), ("samples", _u), ("hit_tri", _i),
                 ("ray_o", _f), ("ray_d", _f), ("beta", _f), ("nee0", _f), ("nee1", _f),
@@ -187,6 +192,10 @@ ABI = {
                                     C.POINTER(TemporalParams), _f, _f, _f, _f, _f]),
     "mcpt_debug_temporal_bytes": (C.c_int64, [C.c_void_p]),
     "mcpt_debug_temporal_ms": (C.c_int, [C.c_void_p, _f]),
+    "mcpt_variance_default_params": (C.c_int, [C.POINTER(VarianceParams)]),
+    "mcpt_variance_run": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _f, _u, _f, _f, _f, _f, C.POINTER(VarianceParams), _f]),
+    "mcpt_set_variance_fill": (C.c_int, [C.c_void_p, C.POINTER(VarianceParams)]),
+    "mcpt_debug_variance_ms": (C.c_int, [C.c_void_p, _f]),
     "mcpt_sync": (C.c_int, [C.c_void_p]),
     "mcpt_device_name": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
     "mcpt_debug_queue_rays": (C.c_int, [C.c_void_p, C.c_int, _f, _f, _u]),
@@ -629,7 +638,8 @@ class PathTracer:
 
     def denoise_guided(self, **params):
         """Variance-guided a-trous filter of the film (mcpt_film_denoise_guided): the variance is the
-        squared standard error of a fresh film error estimate (>= 2 path slots).  The result is read
+        squared standard error of a fresh film error estimate (>= 2 path slots; with
+        set_variance_fill() the spatial estimate fills in, and one slot is enough).  The result is read
         like denoise()'s; keyword arguments override the defaults (passes, sigma_lum, lum_eps, ...)."""
         p = denoise_guided_params(**params) if params else None
         self._ck(lib().mcpt_film_denoise_guided(self.h, C.byref(p) if p is not None else None))
@@ -693,6 +703,26 @@ class PathTracer:
         """Device time of the last k_temporal launch (mcpt_debug_temporal_ms)."""
         v = (C.c_float * 1)()
         self._ck(lib().mcpt_debug_temporal_ms(self.h, v))
+        return float(v[0])
+
+    # ---- spatial variance estimate (DESIGN.md section 14) ----
+    def set_variance_fill(self, *off, **params):
+        """mcpt_set_variance_fill: set_variance_fill(**params) makes denoise_guided() and
+        temporal_accumulate() fill the variances the path slots do not give with the spatial estimate
+        (keyword arguments override the defaults: radius, sigma_normal, sigma_albedo, sigma_depth,
+        min_neff), which makes both usable with one path slot; set_variance_fill(None) turns it off."""
+        if off:
+            if len(off) != 1 or off[0] is not None or params:
+                raise TypeError("set_variance_fill takes keyword parameters, or None alone")
+            self._ck(lib().mcpt_set_variance_fill(self.h, None))
+            return
+        p = variance_params(**params)
+        self._ck(lib().mcpt_set_variance_fill(self.h, C.byref(p)))
+
+    def variance_ms(self) -> float:
+        """Device time of the last k_variance_spatial launch (mcpt_debug_variance_ms)."""
+        v = (C.c_float * 1)()
+        self._ck(lib().mcpt_debug_variance_ms(self.h, v))
         return float(v[0])
 
     # ---- adaptive sampling (DESIGN.md section 11) ----
@@ -972,6 +1002,36 @@ def denoise_guided_run(pt, rgb, variance, albedo, normal, depth, samples=None, *
     _check(lib().mcpt_denoise_guided_run(pt.h, W, H, fptr(rgb), None if sm is None else sm.ctypes.data_as(_u), fptr(var),
                                          fptr(al), fptr(nm), fptr(z), C.byref(p), fptr(out), fptr(out_v)), pt.h)
     return out, out_v
+
+
+def variance_params(**kw) -> VarianceParams:
+    """mcpt_variance_default_params with keyword overrides."""
+    p = VarianceParams()
+    _check(lib().mcpt_variance_default_params(C.byref(p)))
+    for k, v in kw.items():
+        if k not in dict(VarianceParams._fields_):
+            raise TypeError(f"unknown variance parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def variance_run(pt, rgb, albedo, normal, depth, samples=None, variance=None, **params):
+    """mcpt_variance_run on PathTracer pt: the spatial variance estimate over denoise_guided_run's host
+    images; variance (H, W) holds what is already known (None: nothing).  Returns (H, W) float32: the
+    known inputs unchanged, the estimate elsewhere, -1 where unknown."""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    H, W = rgb.shape[:2]
+    al = np.ascontiguousarray(albedo, np.float32).reshape(H, W, 3)
+    nm = np.ascontiguousarray(normal, np.float32).reshape(H, W, 3)
+    z = np.ascontiguousarray(depth, np.float32).reshape(H, W)
+    sm = None if samples is None else np.ascontiguousarray(samples, np.uint32).reshape(H, W)
+    var = None if variance is None else np.ascontiguousarray(variance, np.float32).reshape(H, W)
+    out = np.zeros((H, W), np.float32)
+    p = variance_params(**params)
+    _check(lib().mcpt_variance_run(pt.h, W, H, fptr(rgb), None if sm is None else sm.ctypes.data_as(_u),
+                                   None if var is None else fptr(var), fptr(al), fptr(nm), fptr(z), C.byref(p), fptr(out)),
+           pt.h)
+    return out
 
 
 def gather(tracers, root=0):

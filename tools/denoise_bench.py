@@ -18,6 +18,11 @@ degree of yaw apart per repeat, k_temporal's device time on the second (mcpt_deb
 compulsory bytes (220 B per pixel: the film, its error plane, the guide sums and the camera records in,
 48 B of history in, 72 B of planes out) as a share of the same run's mcpt_debug_hbm_copy ceiling, and the
 five guided passes over the accumulated frame measured in the same process.
+
+--variance times the spatial variance estimate (profiles/variance.json): the film in one path slot,
+every repeat one mcpt_film_denoise_guided with the variance fill at its defaults; k_variance_spatial's
+device time (mcpt_debug_variance_ms) beside the stride-1 guided pass of the same call and the run's
+copy ceiling.
 """
 import argparse
 import json
@@ -128,6 +133,47 @@ def temporal(a, pt, W, H):
             f.write(line + "\n")
 
 
+def variance(a, pt, W, H):
+    """k_variance_spatial inside a one-slot mcpt_film_denoise_guided with the fill at its defaults: its
+    device time beside the stride-1 guided pass of the same call."""
+    q, v = mcpt.denoise_guided_params(), mcpt.variance_params()
+    pt.render_guides(a.guide_samples)
+    pt.set_variance_fill()
+    rows = []
+    for i in range(a.warmup + a.repeats):
+        t = time.perf_counter()
+        pt.denoise_guided()
+        wall = (time.perf_counter() - t) * 1e3
+        ms = pt.denoise_ms()
+        if i >= a.warmup:
+            rows.append((wall, pt.variance_ms(), ms["prepare"], ms["passes"][:q.passes]))
+    known = float((pt.denoised_variance() >= 0).mean())
+    copy_gbps = pt.hbm_copy_gbps()
+    px = W * H
+    # the colour, guide and albedo planes' lines (16 B each; of the colour plane only the valid flag is
+    # used), the vl plane read (8 B) and the variance written (4 B)
+    bpp = 16 + 16 + 16 + 8 + 4
+    v_ms = med([r[1] for r in rows])
+    passes_ms = [med([r[3][i] for r in rows]) for i in range(q.passes)]
+    res = {"tool": "denoise_bench --variance", "device": pt.device_name, "config": 2, "width": W, "height": H,
+           "film_spp": a.spp, "slots": 1, "repeats": a.repeats, "warmup": a.warmup, "hbm_copy_gbps": copy_gbps,
+           "pixels_with_a_variance": known,
+           "variance": {"params": {f: getattr(v, f) for f, _ in mcpt.VarianceParams._fields_},
+                        "k_variance_spatial_ms_median": v_ms, "k_variance_spatial_ms_min": min(r[1] for r in rows),
+                        "bytes_per_pixel": bpp, "gbps": bpp * px / (v_ms * 1e-3) / 1e9,
+                        "share_of_copy": bpp * px / (v_ms * 1e-3) / 1e9 / copy_gbps},
+           "guided": {"wall_ms_median": med([r[0] for r in rows]), "prepare_ms_median_incl_variance": med([r[2] for r in rows]),
+                      "pass_ms_median": passes_ms, "bytes_per_pixel_per_pass": 80,
+                      "pass_share_of_copy": [80 * px / (ms * 1e-3) / 1e9 / copy_gbps for ms in passes_ms]},
+           "variance_over_stride1_pass_ms": v_ms / passes_ms[0]}
+    pt.close()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=15)
@@ -141,6 +187,7 @@ def main():
     ap.add_argument("--slots", type=int, default=4, help="path slots of the film (--guided)")
     ap.add_argument("--temporal", action="store_true", help="time k_temporal and the guided passes after it")
     ap.add_argument("--yaw", type=float, default=1.0, help="degrees of yaw between the two frames (--temporal)")
+    ap.add_argument("--variance", action="store_true", help="time k_variance_spatial on a one-slot film")
     ap.add_argument("--out", help="also write the JSON here")
     a = ap.parse_args()
     if a.repeats < 10:
@@ -158,6 +205,8 @@ def main():
         return temporal(a, pt, W, H)
     pt.render()
     p = mcpt.denoise_params()
+    if a.variance:
+        return variance(a, pt, W, H)
     if a.guided:
         return guided(a, pt, W, H)
 

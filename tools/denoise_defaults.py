@@ -19,6 +19,12 @@ slots, the camera yawed by 0.5 or 2 degrees per frame, a seed per frame; the sco
 last frame after accumulation and the guided passes, relative to the guided passes over the last frame
 alone, both against the 1024-spp frame at the last camera, ranked by the geometric mean over the six
 sequences.  The best row is mcpt_temporal_default_params.
+
+--variance sweeps the spatial variance estimate's (radius, min_neff) and the guided filter's sigma_lum
+over it (profiles/variance_defaults.txt): one-slot frames of the same scenes and size at 2, 4, 8 and 16
+spp, mcpt_film_denoise_guided with the variance fill on, five passes, lum_eps 0, the guide sigmas at
+their defaults, ranked by the geometric mean over the twelve frames; the plain filter's row on the same
+frames is printed beside it.  The best row is mcpt_variance_default_params.
 """
 import argparse
 import itertools
@@ -227,12 +233,74 @@ def temporal(out):
     print(f"best: pos_tol {b[0]:g} nrm_tol {b[1]:g} max_history {b[2]:g} alpha_min {b[3]:g}")
 
 
+V_SPP = (2, 4, 8, 16)
+V_RADIUS = (1, 2, 3)
+V_MIN_NEFF = (1.5, 2.0, 4.0)
+V_SIGMA_LUM = (4.0, 8.0)
+
+
+def variance(out):
+    cands = list(itertools.product(V_RADIUS, V_MIN_NEFF, V_SIGMA_LUM))
+    frames, raw_mse, cols, plain = [], [], [], []
+    for name, scene, cam, depth in scenes():
+        rp = tracer(scene, cam, REF_SPP, depth)
+        Lr, sr = rp.film()
+        rp.close()
+        with np.errstate(all="ignore"):
+            ref = Lr / sr[..., None].astype(np.float32)
+        for spp in V_SPP:
+            pt = tracer(scene, cam, spp, depth)  # one path slot
+            pt.render_guides(GUIDES)
+            Ln, sn = pt.film()
+            with np.errstate(all="ignore"):
+                raw = Ln / sn[..., None].astype(np.float32)
+            keep = (sn > 0) & (sr > 0) & np.isfinite(ref).all(axis=2)
+            r64 = ref[keep].astype(np.float64)
+            m = float(np.mean((raw[keep] - r64) ** 2))
+            frames.append(f"{name}/{spp}")
+            raw_mse.append(m)
+            pt.denoise(passes=PASSES)
+            plain.append(float(np.mean((pt.denoised()[keep] - r64) ** 2)) / m)
+            col = []
+            for radius, neff, sl in cands:
+                pt.set_variance_fill(radius=radius, min_neff=neff)
+                pt.denoise_guided(passes=PASSES, sigma_lum=sl, lum_eps=0.0)
+                col.append(float(np.mean((pt.denoised()[keep] - r64) ** 2)) / m)
+            cols.append(col)
+            pt.close()
+    ratios = np.array(cols).T  # candidate x frame
+    gm = lambda r: float(np.exp(np.mean(np.log(r))))  # noqa: E731
+    score = np.array([gm(r) for r in ratios])
+    order = np.argsort(score, kind="stable")
+    d, g = mcpt.variance_params(), mcpt.denoise_guided_params()
+    lines = [f"# variance estimate defaults: {W}x{H}, one path slot, {GUIDES} guide samples, {PASSES} guided passes with "
+             f"lum_eps 0, against {REF_SPP} spp",
+             "# frames (scene/spp): " + " ".join(frames),
+             "# MSE(raw): " + " ".join(f"{m:.6g}" for m in raw_mse),
+             "# columns: radius min_neff sigma_lum | MSE(denoised) / MSE(raw) per frame | geometric mean",
+             f"# built-in defaults: radius {d.radius}, min_neff {d.min_neff:g}, guide sigmas {d.sigma_normal:g} "
+             f"{d.sigma_albedo:g} {d.sigma_depth:g}; the guided filter's sigma_lum {g.sigma_lum:g}",
+             "plain filter     | " + " ".join(f"{r:8.4f}" for r in plain) + f" | {gm(plain):8.4f}"]
+    for i in order:
+        radius, neff, sl = cands[i]
+        mark = "  <- defaults" if radius == d.radius and abs(neff - d.min_neff) < 1e-6 and abs(sl - g.sigma_lum) < 1e-6 else ""
+        lines.append(f"{radius:3d} {neff:5g} {sl:5g}  | " + " ".join(f"{r:8.4f}" for r in ratios[i]) + f" | {score[i]:8.4f}{mark}")
+    with open(out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+    b = cands[order[0]]
+    print(f"best: radius {b[0]} min_neff {b[1]:g} sigma_lum {b[2]:g}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--guided", action="store_true", help="sweep the variance-guided filter's sigma_lum and lum_eps")
     ap.add_argument("--temporal", action="store_true", help="sweep the temporal stage's four parameters")
+    ap.add_argument("--variance", action="store_true", help="sweep the spatial variance estimate's radius and min_neff")
     ap.add_argument("--out")
     a = ap.parse_args()
+    if a.variance:
+        return variance(a.out or os.path.join(REPO, "profiles", "variance_defaults.txt"))
     if a.temporal:
         return temporal(a.out or os.path.join(REPO, "profiles", "temporal_defaults.txt"))
     if a.guided:
