@@ -41,7 +41,7 @@ tests/native/facade_test: tests/native/facade_test.cpp include/mcpt.hpp include/
 tests/native/primary_beam: tests/native/primary_beam.cpp $(PKG)/csrc/device/primary_beam.hpp $(PKG)/csrc/device/mcpt_core.hpp
 	$(HIPCC) -O2 -std=c++17 -ffp-contract=off -fno-fast-math -Iinclude -I$(PKG)/csrc $< -o $@
 
-oracle/liboracle.so: oracle/mcpt_oracle.c oracle/mcpt_oracle.h
+oracle/liboracle.so: oracle/mcpt_oracle.c oracle/trav_model.c oracle/mcpt_oracle.h
 	$(MAKE) -C oracle
 
 clean:

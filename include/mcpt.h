@@ -540,6 +540,31 @@ int mcpt_debug_env_tables(mcpt_ctx *ctx, float *marginal_y, float *conds_y, floa
  * MCPT_SIBLING_LAYOUT=0/1/2/3 at upload forces one; inputs that are not a tree -- a shared child --
  * always get 0). */
 int mcpt_debug_node_layout(const mcpt_ctx *ctx);
+/* Tests: the child-pair tree of the last upload, read back from the device.
+ *   nodes: 16 floats per pair node, 4 x float4: per axis (min child 0, min child 1, max child 0,
+ *     max child 1), then (ref 0, ref 1, margin 0, margin 1) -- refs as int32 bits: >= 0 a pair
+ *     node, < 0 a leaf (bits 0..23 first triangle record, bits 24..26 count - 1), -1 no child (pad
+ *     nodes of layout 3) -- with the culling margins as the upload left them.  A 4-wide upload
+ *     (MCPT_BVH_WIDTH=4) collapses this array; it is reported unchanged.
+ *   tris: 4 * tri_f4 floats per triangle record in storage order ((v0.xyz, e1.x) (e1.yz, e2.xy)
+ *     (e2.z, id, -, -)): scene order for a host tree, Morton order for a device-built one.
+ * Either may be NULL (sizes only: read info first).  An empty scene reports npairs = ntri = 0 and
+ * root_ref 0; a tree that is one leaf reports npairs = 0 and a negative root_ref. */
+typedef struct mcpt_bvh_info {
+    int32_t npairs;      /* pair nodes in `nodes` (pads of layout 3 included) */
+    int32_t root_ref;    /* ref of the root: a pair node or, for a single-leaf tree, a leaf */
+    int32_t depth;       /* the largest number of pair nodes on a root-to-leaf path as the upload took
+                          * it (the margin passes and the traversal stack are sized by it) */
+    int32_t width;       /* node width the traversal uses (2 or 4) */
+    int32_t layout;      /* mcpt_debug_node_layout (host numbering; 0 for a device-built tree) */
+    int32_t ntri;        /* triangle records */
+    int32_t tri_f4;      /* float4 per triangle record */
+    int32_t gpu_built;   /* 1: built by mcpt_scene_upload_gpu_bvh */
+    int32_t rounds;      /* clustering rounds of a PLOC build, else 0 */
+    float root_mn[3], root_mx[3]; /* the root box */
+    float cull_p;        /* the far coefficient P of the culling bound */
+} mcpt_bvh_info;
+int mcpt_debug_bvh_read(mcpt_ctx *ctx, float *nodes, float *tris, mcpt_bvh_info *info);
 /* any-hit occluder cache: any-hit rays resolved by it since the film was
  * last cleared (counted in shadow_rays / vis_rays as traced rays; they skip the traversal), and
  * whether the uploaded scene has the cache (MCPT_OCC_G=0 at upload turns it off). */

@@ -174,6 +174,8 @@ static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     free_list(c->scene_bufs);
+    c->pair_nodes = nullptr;
+    c->pair_count = 0;
     c->has_scene_before = c->has_scene_before || c->has_scene;
     c->has_scene = false;
     const int N = gpu_bvh ? 0 : d->nnodes;  // gpu_bvh: the desc's BVH arrays are ignored
@@ -330,13 +332,9 @@ static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
         return me;
     };
     std::vector<int> leaf_ref(N, 0);
-    int xdepth = 0;  // extra levels under a desc leaf
     for (int i = 0; i < N; i++) {
         if (d->nprims[i] == 0) continue;
         leaf_ref[i] = expand(d->offset[i], d->nprims[i]);
-        int lv = 0;
-        while ((1 << lv) < d->nprims[i]) lv++;
-        xdepth = std::max(xdepth, lv);
     }
     auto ref_of = [&](int j) -> int { return d->nprims[j] == 0 ? pair_of[j] : leaf_ref[j]; };
     std::vector<float4> pn((size_t)npair * 4);
@@ -363,18 +361,21 @@ static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
         q[3] = make_float4(fr0, fr1, 0.f, 0.f);  // .z / .w: the children's culling margins (launch_cull_margins)
     }
     pn.insert(pn.end(), xn.begin(), xn.end());
-    // depth of the tree = bound on stack pushes
+    // depth of the tree = the most pair nodes on a root-to-leaf path (a bound on stack pushes, and the
+    // passes launch_cull_margins needs): a desc leaf adds the levels of its own expansion (halving, so
+    // ceil(log2 nprims)) to its own depth -- not the deepest expansion anywhere to the deepest leaf
     int depth = 0;
     if (N > 0) {
         std::vector<std::pair<int, int>> st{{0, 0}};
         while (!st.empty()) {
             auto [n, dd] = st.back();
             st.pop_back();
-            depth = std::max(depth, dd);
-            if (d->nprims[n] == 0) { st.push_back({n + 1, dd + 1}); st.push_back({d->offset[n], dd + 1}); }
+            if (d->nprims[n] == 0) { st.push_back({n + 1, dd + 1}); st.push_back({d->offset[n], dd + 1}); continue; }
+            int lv = 0;  // extra levels under this desc leaf
+            while ((1 << lv) < d->nprims[n]) lv++;
+            depth = std::max(depth, dd + lv);
         }
     }
-    depth += xdepth;
     if (depth > kMaxStack) return set_err(c, MCPT_E_INVALID, "BVH deeper than the 64-entry traversal stack");
     c->pair_depth = depth;
     std::vector<float4> tri((size_t)d->ntri * kTriF4, make_float4(0.f, 0.f, 0.f, 0.f)), sh((size_t)d->ntri * 3);
@@ -458,6 +459,11 @@ static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
     {
         const uint32_t npairs = (uint32_t)(gpu_bvh ? lb.nnodes : pn.size() / 4);
         const int proot = gpu_bvh ? lb.root_ref : (N > 0 ? ref_of(0) : 0);
+        c->pair_nodes = npairs ? dn : nullptr;
+        c->pair_count = npairs;
+        c->pair_root = proot;
+        c->pair_gpu_built = gpu_bvh && d->ntri > 0;
+        c->ploc_rounds = c->pair_gpu_built && c->gpu_bvh_builder == MCPT_GPU_BVH_PLOC ? lb.rounds : 0;
         float* tw = nullptr;
         uint32_t* pm = nullptr;
         if (d->ntri > 0) {
@@ -764,6 +770,31 @@ int mcpt_debug_env_tables(mcpt_ctx* c, float* marginal_y, float* conds_y, float*
     return MCPT_OK;
 }
 int mcpt_debug_node_layout(const mcpt_ctx* c) { return c ? c->node_layout : MCPT_E_INVALID; }
+int mcpt_debug_bvh_read(mcpt_ctx* c, float* nodes, float* tris, mcpt_bvh_info* info) {
+    if (!c) return set_err(c, MCPT_E_INVALID, "null context");
+    if (!c->has_scene) return set_err(c, MCPT_E_INVALID, "no scene uploaded");
+    const DevScene& s = c->scene;
+    if (info) {
+        info->npairs = (int32_t)c->pair_count;
+        info->root_ref = c->pair_root;
+        info->depth = c->pair_depth;
+        info->width = s.width;
+        info->layout = c->node_layout;
+        info->ntri = (int32_t)s.ntri;
+        info->tri_f4 = kTriF4;
+        info->gpu_built = c->pair_gpu_built ? 1 : 0;
+        info->rounds = c->ploc_rounds;
+        for (int k = 0; k < 3; k++) { info->root_mn[k] = s.root_mn[k]; info->root_mx[k] = s.root_mx[k]; }
+        info->cull_p = s.cull_p;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (nodes && c->pair_count)
+        HIPCHK(c, hipMemcpy(nodes, c->pair_nodes, (size_t)c->pair_count * 4 * sizeof(float4), hipMemcpyDeviceToHost));
+    if (tris && s.ntri)
+        HIPCHK(c, hipMemcpy(tris, s.tri, (size_t)s.ntri * kTriF4 * sizeof(float4), hipMemcpyDeviceToHost));
+    return MCPT_OK;
+}
 int mcpt_debug_ray_counts(const mcpt_ctx* c, uint64_t* out) {
     if (!c || !out) return MCPT_E_INVALID;
     const CounterBlock& t = c->totals;

@@ -196,6 +196,12 @@ struct mcpt_ctx {
     // per-lane counters cost the fast one its spill-free registers -- off by default
     bool count_work = getenv("MCPT_WORK_COUNTERS") != nullptr;
     int node_layout = 0;  // pair-node numbering the last upload used (mcpt_debug_node_layout)
+    // the last upload's child-pair tree (mcpt_debug_bvh_read): the array launch_cull_margins wrote,
+    // which a 4-wide upload collapses from (owned by scene_bufs either way)
+    const float4* pair_nodes = nullptr;
+    uint32_t pair_count = 0;
+    int pair_root = 0, ploc_rounds = 0;
+    bool pair_gpu_built = false;
     // mcpt_set_skip_discarded: paths the next logic pass is certain to end make no extension ray
     // (ShadeArgs::skip); results and ray counts are the same either way
     bool skip_discarded = true;

@@ -97,6 +97,12 @@ class VarianceParams(C.Structure):  # mcpt_variance_params
                 ("sigma_depth", C.c_float), ("min_neff", C.c_float)]
 
 
+class BvhInfo(C.Structure):  # mcpt_bvh_info
+    _fields_ = [("npairs", C.c_int32), ("root_ref", C.c_int32), ("depth", C.c_int32), ("width", C.c_int32),
+                ("layout", C.c_int32), ("ntri", C.c_int32), ("tri_f4", C.c_int32), ("gpu_built", C.c_int32),
+                ("rounds", C.c_int32), ("root_mn", C.c_float * 3), ("root_mx", C.c_float * 3), ("cull_p", C.c_float)]
+
+
 class PathView(C.Structure):  # mcpt_path_view: path state at the shading stages' boundary
     _fields_ = [("film_w", C.c_uint32), ("film_h", C.c_uint32), ("flags", _u), ("samples", _u), ("hit_tri", _i),
                 ("ray_o", _f), ("ray_d", _f), ("beta", _f), ("nee0", _f), ("nee1", _f),
@@ -204,6 +210,7 @@ ABI = {
     "mcpt_debug_last_env_build_ms": (C.c_float, [C.c_void_p]),
     "mcpt_debug_env_tables": (C.c_int, [C.c_void_p, _f, _f, _f, _i]),
     "mcpt_debug_node_layout": (C.c_int, [C.c_void_p]),
+    "mcpt_debug_bvh_read": (C.c_int, [C.c_void_p, _f, _f, C.POINTER(BvhInfo)]),
     "mcpt_debug_occ_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
     "mcpt_debug_ray_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mcpt_debug_primary_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
@@ -524,6 +531,21 @@ class PathTracer:
     @property
     def last_build_ms(self) -> float:
         return lib().mcpt_debug_last_build_ms(self.h)
+
+    def bvh_read(self):
+        """The last upload's child-pair tree (mcpt_debug_bvh_read): (nodes (npairs, 4, 4) float32 with the
+        culling margins in, triangle records (ntri, tri_f4, 4) float32 in storage order, info dict)."""
+        bi = BvhInfo()
+        self._ck(lib().mcpt_debug_bvh_read(self.h, None, None, C.byref(bi)))
+        nodes = np.zeros((bi.npairs, 4, 4), np.float32)
+        tris = np.zeros((bi.ntri, bi.tri_f4, 4), np.float32)
+        self._ck(lib().mcpt_debug_bvh_read(self.h, fptr(nodes) if nodes.size else None,
+                                           fptr(tris) if tris.size else None, C.byref(bi)))
+        info = {k: getattr(bi, k) for k, _ in BvhInfo._fields_}
+        for k in ("root_mn", "root_mx"):
+            info[k] = np.array(list(info[k]), np.float32)
+        info["cull_p"] = np.float32(info["cull_p"])
+        return nodes, tris, info
 
     @property
     def last_env_build_ms(self) -> float:

@@ -95,7 +95,7 @@ static double plane_b(mv3 e1, mv3 e2) {
  * sqrt3 beta >= 1/2 (a triangle so large against the det threshold that no box holding it is
  * ever culled).  A box's margin is the maximum over the triangles it holds.  *far: the
  * triangle's coefficient of t_best in the far cut (P is their maximum). */
-static float to_f_up(double w) { return isinf(w) ? INFINITY : (float)(w * (1.0 + 1.0 / 1048576.0)) * (1.0f + 1.0f / 1048576.0f); }
+static float to_f_up(double w) { return !(w < 3.0e38) ? INFINITY : (float)(w * (1.0 + 1.0 / 1048576.0)) * (1.0f + 1.0f / 1048576.0f); }
 static double g_safe_c = 0.0; /* or_model_set_safe: 0 = the product's margins */
 void or_model_set_safe(double c) { g_safe_c = c; }
 /* beta of the safe-ray bound: |R_a| / det <= 28.285 u |tvec| |e1| |e2| / K, K = c |m| - 7.0712 u |e1| |e2| */
@@ -109,7 +109,9 @@ static double safe_beta(mv3 e1, mv3 e2, double c) {
 }
 static double tri_w_of(const or_scene *sc, int t, double *far) {
     mv3 a = mld(sc->v0, t), b = mld(sc->v1, t), c = mld(sc->v2, t);
-    mv3 e1 = msub(b, a), e2 = msub(c, a), e3 = msub(c, b);
+    /* the third edge as the product forms it, from the two edges its triangle record stores (the
+     * triangle Moller-Trumbore tests is p0, p0 + e1, p0 + e2; v2 - v1 rounds differently) */
+    mv3 e1 = msub(b, a), e2 = msub(c, a), e3 = msub(e2, e1);
     double be, om;
     tri_beta_omega(e1, e2, &be, &om);
     const double pb = plane_b(e1, e2);
@@ -169,7 +171,7 @@ int32_t or_model_margins(const or_scene *sc, float *node_w, float *tri_w, float 
             if (lo[3 * n + k] < sc->bmin[3 * n + k] || hi[3 * n + k] > sc->bmax[3 * n + k]) contained = 0;
         node_w[n] = to_f_up(nw[n]);
     }
-    *p = (float)pg;
+    *p = pg > 0.0 ? to_f_up(pg) : 0.f; /* rounded up, as k_cull_tri does before its maximum */
     free(nw); free(lo); free(hi);
     return contained;
 }
