@@ -15,10 +15,10 @@ SRCS := $(PKG)/csrc/kernels.hip $(PKG)/csrc/bvh_build.hip $(PKG)/csrc/env_build.
         $(PKG)/csrc/host/image_io.cpp
 OBJS := $(patsubst $(PKG)/csrc/%,$(BUILD)/%.o,$(SRCS))
 HDRS := include/mcpt.h $(PKG)/csrc/kernels.hpp $(PKG)/csrc/device/mcpt_core.hpp \
-        $(PKG)/csrc/device/primary_beam.hpp $(PKG)/csrc/device/denoise.hpp $(PKG)/csrc/device/adaptive.hpp $(PKG)/csrc/device/temporal.hpp $(PKG)/csrc/device/variance.hpp \
+        $(PKG)/csrc/device/primary_beam.hpp $(PKG)/csrc/device/occ_beam.hpp $(PKG)/csrc/device/denoise.hpp $(PKG)/csrc/device/adaptive.hpp $(PKG)/csrc/device/temporal.hpp $(PKG)/csrc/device/variance.hpp \
         $(PKG)/csrc/runtime_internal.hpp $(PKG)/csrc/host/host_internal.hpp
 
-all: $(PKG)/libmcpt.so oracle/liboracle.so examples/mcpt_render tests/native/facade_test tests/native/primary_beam
+all: $(PKG)/libmcpt.so oracle/liboracle.so examples/mcpt_render tests/native/facade_test tests/native/primary_beam tests/native/occ_beam
 
 $(BUILD)/%.o: $(PKG)/csrc/% $(HDRS)
 	@mkdir -p $(dir $@)
@@ -41,11 +41,15 @@ tests/native/facade_test: tests/native/facade_test.cpp include/mcpt.hpp include/
 tests/native/primary_beam: tests/native/primary_beam.cpp $(PKG)/csrc/device/primary_beam.hpp $(PKG)/csrc/device/mcpt_core.hpp
 	$(HIPCC) -O2 -std=c++17 -ffp-contract=off -fno-fast-math -Iinclude -I$(PKG)/csrc $< -o $@
 
+# Host check of the occluder table's complete candidate lists (device/occ_beam.hpp) on the CPU
+tests/native/occ_beam: tests/native/occ_beam.cpp $(PKG)/csrc/device/occ_beam.hpp $(PKG)/csrc/device/primary_beam.hpp $(PKG)/csrc/device/mcpt_core.hpp
+	$(HIPCC) -O2 -std=c++17 -ffp-contract=off -fno-fast-math -Iinclude -I$(PKG)/csrc $< -o $@
+
 oracle/liboracle.so: oracle/mcpt_oracle.c oracle/trav_model.c oracle/mcpt_oracle.h
 	$(MAKE) -C oracle
 
 clean:
-	rm -rf $(BUILD) $(PKG)/libmcpt.so examples/mcpt_render tests/native/facade_test tests/native/primary_beam
+	rm -rf $(BUILD) $(PKG)/libmcpt.so examples/mcpt_render tests/native/facade_test tests/native/primary_beam tests/native/occ_beam
 	$(MAKE) -C oracle clean
 
 .PHONY: all clean

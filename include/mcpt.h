@@ -569,6 +569,12 @@ int mcpt_debug_bvh_read(mcpt_ctx *ctx, float *nodes, float *tris, mcpt_bvh_info 
  * last cleared (counted in shadow_rays / vis_rays as traced rays; they skip the traversal), and
  * whether the uploaded scene has the cache (MCPT_OCC_G=0 at upload turns it off). */
 int mcpt_debug_occ_stats(const mcpt_ctx *ctx, uint64_t *resolved, int32_t *enabled);
+/* Complete keys of the occluder table (MCPT_OCC_COMPLETE=0 at upload turns them
+ * off), 4 values: keys of the uploaded scene whose entry lists every triangle a ray of the key can be
+ * accepted on; since the last film clear, any-hit rays such entries resolved as unoccluded (counted as
+ * any-hit rays, neither as traversed nor in mcpt_debug_occ_stats' count) and as occluded (part of that
+ * count); and the milliseconds the upload spent building the lists. */
+int mcpt_debug_occ_complete_stats(const mcpt_ctx *ctx, double *out4);
 /* Ray counts since the last film clear (5 values): extension rays, of them traversed by k_trace
  * (the rest: NaN / zero directions and root-box misses resolved where the ray was made), any-hit
  * (shadow + BRDF visibility) rays, of them traversed, and of them resolved by the occluder cache. */

@@ -423,14 +423,15 @@ __device__ inline void hit_record(const DevScene& sc, V3 o, V3 d, int tri, V3& p
 // The table's contents (racy plain stores) only decide how much work is skipped, never
 // a result.  Rays with an infinite inverse component (slab(), NaN slabs) are not tested.
 // ---------------------------------------------------------------------------
-__device__ inline uint32_t occ_index(const DevScene& sc, V3 o, V3 d) {
+// (cx, cy, cz): the origin cell; dirbin = (face B + ub) B + vb: the direction bin
+__device__ inline void occ_coords(const DevScene& sc, V3 o, V3 d, uint32_t& cx, uint32_t& cy, uint32_t& cz, uint32_t& face,
+                                  uint32_t& ub, uint32_t& vb) {
     const float gm = (float)(sc.occ_g - 1), bm = (float)(sc.occ_b - 1), hb = 0.5f * (float)sc.occ_b;
     // fmaxf(NaN, 0) = 0: a NaN coordinate falls in cell / bin 0
-    const uint32_t cx = (uint32_t)__builtin_fminf(__builtin_fmaxf((o.x - sc.root_mn[0]) * sc.occ_inv[0], 0.f), gm);
-    const uint32_t cy = (uint32_t)__builtin_fminf(__builtin_fmaxf((o.y - sc.root_mn[1]) * sc.occ_inv[1], 0.f), gm);
-    const uint32_t cz = (uint32_t)__builtin_fminf(__builtin_fmaxf((o.z - sc.root_mn[2]) * sc.occ_inv[2], 0.f), gm);
+    cx = (uint32_t)__builtin_fminf(__builtin_fmaxf((o.x - sc.root_mn[0]) * sc.occ_inv[0], 0.f), gm);
+    cy = (uint32_t)__builtin_fminf(__builtin_fmaxf((o.y - sc.root_mn[1]) * sc.occ_inv[1], 0.f), gm);
+    cz = (uint32_t)__builtin_fminf(__builtin_fmaxf((o.z - sc.root_mn[2]) * sc.occ_inv[2], 0.f), gm);
     const float ax = __builtin_fabsf(d.x), ay = __builtin_fabsf(d.y), az = __builtin_fabsf(d.z);
-    uint32_t face;
     float u, v, m;
     if (ax >= ay && ax >= az) {
         face = d.x < 0.f ? 1u : 0u; u = d.y; v = d.z; m = ax;
@@ -440,9 +441,17 @@ __device__ inline uint32_t occ_index(const DevScene& sc, V3 o, V3 d) {
         face = d.z < 0.f ? 5u : 4u; u = d.x; v = d.y; m = az;
     }
     const float r = hb * __builtin_amdgcn_rcpf(m);  // cube-map coordinates in [-1, 1] -> [0, B)
-    const uint32_t ub = (uint32_t)__builtin_fminf(__builtin_fmaxf(u * r + hb, 0.f), bm);
-    const uint32_t vb = (uint32_t)__builtin_fminf(__builtin_fmaxf(v * r + hb, 0.f), bm);
+    ub = (uint32_t)__builtin_fminf(__builtin_fmaxf(u * r + hb, 0.f), bm);
+    vb = (uint32_t)__builtin_fminf(__builtin_fmaxf(v * r + hb, 0.f), bm);
+}
+// The key's coordinates in one word for k_material's membership test (occ_member2): dirbin | cx << 15 |
+// cy << 20 | cz << 25; dirbin < 6 * 64^2 < 2^15 always, the cells fit for occ_g <= 32 (the upload
+// builds complete keys, the only users, for no larger grid)
+__device__ inline uint32_t occ_index(const DevScene& sc, V3 o, V3 d, uint32_t* packed = nullptr) {
+    uint32_t cx, cy, cz, face, ub, vb;
+    occ_coords(sc, o, d, cx, cy, cz, face, ub, vb);
     const uint32_t G = (uint32_t)sc.occ_g, B = (uint32_t)sc.occ_b;
+    if (packed) *packed = ((face * B + ub) * B + vb) | cx << 15 | cy << 20 | cz << 25;
     // one table cell per key (hashing the keys into a 2^21- or 2^23-cell table measured 43 % / 60 %
     // of config 2's any-hit rays resolved against 72 % direct: the keys that occur collide heavily)
 #if MCPT_OCC_LAYOUT == 1
@@ -475,33 +484,69 @@ __device__ inline bool occ_test(V3 o, V3 d, V3 inv, float io, float4 bmn, float4
 // The cell's entries of (o, d): kOccWays triangle records (k_trace writes way tri mod kOccWays).
 // MCPT_NT bit 16: the table's random 8-B reads and the occluder stores are non-temporal (the 96 MB
 // table cannot stay in L2; its lines would evict the env tables' and occluder records').
-__device__ inline uint2 occ_entry(const DevScene& sc, uint32_t cell) {
-    const uint2* e = reinterpret_cast<const uint2*>(sc.occ) + cell;
-    if constexpr (MCPT_NT & 16) {
-        typedef uint32_t u2v_t __attribute__((ext_vector_type(2)));
-        const u2v_t v = __builtin_nontemporal_load(reinterpret_cast<const u2v_t*>(e));
-        return make_uint2(v.x, v.y);
-    } else {
-        return *e;
-    }
+struct OccEnt { uint32_t w[kOccWays]; };
+__device__ inline OccEnt occ_entry(const DevScene& sc, uint32_t cell) {
+    typedef uint32_t uwv_t __attribute__((ext_vector_type(kOccWays)));
+    const uwv_t* e = reinterpret_cast<const uwv_t*>(sc.occ) + cell;
+    uwv_t v;
+    if constexpr (MCPT_NT & 16) v = __builtin_nontemporal_load(e);
+    else v = *e;
+    OccEnt r;
+#pragma unroll
+    for (uint32_t k = 0; k < kOccWays; k++) r.w[k] = v[k];
+    return r;
 }
 // An any-hit ray against its cell's entries: both candidates' occluder records (leaf box, margin
 // and triangle in one aligned 64-B record: one half line each, where the leaf box and the 48-B
 // triangle record used to cost two or three) are fetched in one round trip (an empty way reads
 // record 0 and is not tested).  k_material calls it for the light ray, then the BRDF ray: 32
 // VGPRs of records at a time, next to the BRDF sample's deferred state.
-__device__ inline bool occ_hit1(const DevScene& sc, V3 o, V3 d, uint2 e) {
-    const bool v0 = e.x < sc.ntri, v1 = e.y < sc.ntri;
-    if (!(v0 || v1)) return false;
-    const float4* p0 = sc.occ_rec + kOccRecF4 * (size_t)(v0 ? e.x : 0u);
-    const float4* p1 = sc.occ_rec + kOccRecF4 * (size_t)(v1 ? e.y : 0u);
-    const float4 bn0 = p0[0], bx0 = p0[1], r20 = p0[2], r30 = p0[3];
-    const float4 bn1 = p1[0], bx1 = p1[1], r21 = p1[2], r31 = p1[3];
+// Returns kOccHit: occluded; kOccOpen: not resolved; kOccMaybe: no listed triangle is hit, the entry is
+// complete (both words marked: it lists every triangle a ray of the key's beam can be accepted on,
+// device/occ_beam.hpp) and the ray's culling scale is positive, so the ray is unoccluded if it lies in
+// the beam of its key (occ_member2).  done: the entry is complete.
+enum : int { kOccOpen = 0, kOccHit = 1, kOccMaybe = 2 };
+__device__ inline int occ_hit1(const DevScene& sc, V3 o, V3 d, OccEnt e, bool& done) {
+    done = sc.occ_dir != nullptr;
+    bool any = false;
+#pragma unroll
+    for (uint32_t k = 0; k < kOccWays; k++) done = done && mcpt::occ_word_done(e.w[k]);
+#pragma unroll
+    for (uint32_t k = 0; k < kOccWays; k++) {
+        if (done) e.w[k] &= mcpt::kOccDoneIndex;  // the marked empty word's index is beyond every record
+        any = any || e.w[k] < sc.ntri;
+    }
+    if (!(any || done)) return kOccOpen;
     const V3 inv = v3(1.f / d.x, 1.f / d.y, 1.f / d.z);  // k_trace's
-    if (!(__builtin_fabsf(inv.x) < K_INF_F && __builtin_fabsf(inv.y) < K_INF_F && __builtin_fabsf(inv.z) < K_INF_F))
-        return false;
+    const bool fin = __builtin_fabsf(inv.x) < K_INF_F && __builtin_fabsf(inv.y) < K_INF_F && __builtin_fabsf(inv.z) < K_INF_F;
     const float io = cull_iota(sc, d, inv);
-    return (v0 && occ_test(o, d, inv, io, bn0, bx0, r20, r30)) || (v1 && occ_test(o, d, inv, io, bn1, bx1, r21, r31));
+#pragma unroll
+    for (uint32_t k = 0; k < kOccWays; k += 2) {  // two records in flight at a time
+        const bool v0 = e.w[k] < sc.ntri, v1 = e.w[k + 1] < sc.ntri;
+        if (kOccWays > 2 && !(v0 || v1)) continue;
+        const float4* p0 = sc.occ_rec + kOccRecF4 * (size_t)(v0 ? e.w[k] : 0u);
+        const float4* p1 = sc.occ_rec + kOccRecF4 * (size_t)(v1 ? e.w[k + 1] : 0u);
+        const float4 bn0 = p0[0], bx0 = p0[1], r20 = p0[2], r30 = p0[3];
+        const float4 bn1 = p1[0], bx1 = p1[1], r21 = p1[2], r31 = p1[3];
+        if (!fin) return kOccOpen;
+        if ((v0 && occ_test(o, d, inv, io, bn0, bx0, r20, r30)) || (v1 && occ_test(o, d, inv, io, bn1, bx1, r21, r31)))
+            return kOccHit;
+    }
+    return done && fin && io > 0.f ? kOccMaybe : kOccOpen;
+}
+// The run-time membership test of k_material's two any-hit rays at once (their bin intervals are fetched
+// in one round trip): m_l / m_b = the ray lies in the beam of the key kl / kb (occ_index's packed
+// coordinates, kept from the entry's fetch; 0 for a ray without one: in range like every packed key, so a
+// ray that is not pending costs only the arithmetic).  (Fetching the intervals ahead of the occluder
+// records, so that the test waits for no load of its own, measured no better: 126 VGPRs for 115.)
+__device__ inline void occ_member2(const DevScene& sc, V3 ol, V3 dl, uint32_t kl, V3 ob, V3 db, uint32_t kb, bool& m_l,
+                                   bool& m_b) {
+    const mcpt::OccGrid g{{sc.root_mn[0], sc.root_mn[1], sc.root_mn[2]}, {sc.occ_cell[0], sc.occ_cell[1], sc.occ_cell[2]},
+                          sc.occ_g, sc.occ_b, sc.occ_dir};
+    const mcpt::Beam bl = mcpt::occ_key_beam(g, (kl >> 15) & 31u, (kl >> 20) & 31u, kl >> 25, kl & 0x7fffu);
+    const mcpt::Beam bb = mcpt::occ_key_beam(g, (kb >> 15) & 31u, (kb >> 20) & 31u, kb >> 25, kb & 0x7fffu);
+    m_l = mcpt::beam_contains(bl, ol, dl);
+    m_b = mcpt::beam_contains(bb, ob, db);
 }
 
 // ---------------------------------------------------------------------------
@@ -523,7 +568,8 @@ struct MatOut {
     bool skip_ext;        // the extension ray is counted, not made: the next logic pass ends the path (ShadeArgs::skip)
     bool doomed_inplace;  // switch off: such a path's extension ray, resolved in place (C_SKIP_INPLACE)
     uint32_t trivial_any;
-    uint2 el, eb;  // occluder-cache entries of the light / BRDF rays (loads issued inside material())
+    OccEnt el, eb;  // occluder-cache entries of the light / BRDF rays (loads issued inside material())
+    uint32_t kl, kb;  // their keys' packed coordinates (occ_index)
     // the BRDF sample's light terms are finished by material_brdf_terms after the occluder cache
     // (a visibility ray it resolves as occluded needs none: k_shade reads nee1.xyz only when
     // vis = 1, wavefront_kernels.cu:336-343)
@@ -544,9 +590,9 @@ template <bool FIXED>
 __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix, uint32_t sidx, uint32_t len,
                                  V3 beta_store, int32_t htri, float4* stage, bool occ_on, bool no_cont) {
     const DevScene& sc = a.scene;
-    const uint2 none = make_uint2(kOccEmpty, kOccEmpty);
     MatOut mo{};
-    mo.el = mo.eb = none;
+#pragma unroll
+    for (uint32_t k = 0; k < kOccWays; k++) mo.el.w[k] = mo.eb.w[k] = kOccEmpty;
     // the pixel and the sample index come with the record (k_shade: slot k of a pixel runs
     // samples k, k + S, k + 2S, ...)
     MCPT_MARK("m_hit");
@@ -657,7 +703,7 @@ __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix
             stage[1 * kBlock + threadIdx.x] = f4(ldir, 0.f);
             mo.want_l = true;
             // the occluder-cache entry, loaded now and used after material()
-            if (occ_on) mo.el = occ_entry(sc, occ_index(sc, so_l, ldir));
+            if (occ_on) mo.el = occ_entry(sc, occ_index(sc, so_l, ldir, &mo.kl));
         }
     }
     // the BRDF sample's direction and visibility ray (its light terms come after the occluder
@@ -674,7 +720,7 @@ __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix
             a.p.vis[2 * pid + 1] = 1;
             mo.trivial_any++;
         } else {
-            if (occ_on) mo.eb = occ_entry(sc, occ_index(sc, so_b, wi_b));
+            if (occ_on) mo.eb = occ_entry(sc, occ_index(sc, so_b, wi_b, &mo.kb));
             stage[2 * kBlock + threadIdx.x] = f4(so_b, __uint_as_float(2 * pid + 1));
             stage[3 * kBlock + threadIdx.x] = f4(wi_b, 0.f);
             mo.want_b = true;
@@ -1089,7 +1135,7 @@ __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_k
     uint32_t* sc_ctr = a.cnt->shard[shard];
     const uint32_t n = sc_ctr[C_MAT];
     const int lane = threadIdx.x & 63;
-    uint32_t n_ext = 0, n_any = 0, n_vis = 0, n_occ = 0, occ_try = 0, n_skip = 0, n_inpl = 0;
+    uint32_t n_ext = 0, n_any = 0, n_vis = 0, n_occ = 0, occ_try = 0, n_skip = 0, n_inpl = 0, n_dvis = 0, n_docc = 0;
     const bool occ_on = a.scene.occ && a.scene.occ_gate[0] == 0 && a.scene.occ_gate[2] != 0;  // see DevScene::occ_gate
     // Any-hit rays are staged here (light ray o/d, BRDF visibility ray o/d) and stored after
     // the block push at their queue positions: the block's rays of one kind land contiguously,
@@ -1102,6 +1148,7 @@ __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_k
         MatOut mo{};
         uint32_t mpid = 0;
         bool occ_l = false, occ_b = false, try_l = false, try_b = false;  // resolved by / tested against the occluder cache
+        bool done_l = false, done_b = false, clr_l = false, clr_b = false;  // ... from a complete entry / as unoccluded
         if (i < n) {
             const uint4 q = ld_s(a.mat_rec + shard * a.ext_cap + i);  // {pid, pixel, sample index | len << 24, hit_tri}
             const float4 b4 = ld_s(a.mat_beta + shard * a.ext_cap + i);
@@ -1116,8 +1163,33 @@ __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_k
                 try_b = mo.want_b;
                 const V3 ol = xyz(s_any[0][threadIdx.x]), dl = xyz(s_any[1][threadIdx.x]);
                 const V3 ob = xyz(s_any[2][threadIdx.x]), db = xyz(s_any[3][threadIdx.x]);
-                if (mo.want_l) occ_l = occ_hit1(a.scene, ol, dl, mo.el);
-                if (mo.want_b) occ_b = occ_hit1(a.scene, ob, db, mo.eb);
+                if (mo.want_l) {
+                    const int r = occ_hit1(a.scene, ol, dl, mo.el, done_l);
+                    occ_l = r == kOccHit;
+                    clr_l = r == kOccMaybe;
+                }
+                if (mo.want_b) {
+                    const int r = occ_hit1(a.scene, ob, db, mo.eb, done_b);
+                    occ_b = r == kOccHit;
+                    clr_b = r == kOccMaybe;
+                }
+                if (clr_l || clr_b) {
+                    bool m_l, m_b;
+                    occ_member2(a.scene, ol, dl, mo.kl, ob, db, mo.kb, m_l, m_b);
+                    clr_l = clr_l && m_l;
+                    clr_b = clr_b && m_b;
+                }
+                // unoccluded by a complete entry: wf_shadow's result for a ray that finds nothing
+                if (clr_l) {
+                    a.p.vis[2 * mpid] = 1;
+                    mo.want_l = false;
+                    mo.trivial_any++;
+                }
+                if (clr_b) {
+                    a.p.vis[2 * mpid + 1] = 1;
+                    mo.want_b = false;
+                    mo.trivial_any++;
+                }
                 if (occ_l) {
                     a.p.vis[2 * mpid] = 0;
                     mo.want_l = false;
@@ -1165,6 +1237,8 @@ __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_k
         // next trip's material())
         n_occ += (uint32_t)(__popcll(__ballot(occ_l)) + __popcll(__ballot(occ_b)));
         occ_try += (uint32_t)(__popcll(__ballot(try_l)) + __popcll(__ballot(try_b)));
+        n_dvis += (uint32_t)(__popcll(__ballot(clr_l)) + __popcll(__ballot(clr_b)));
+        n_docc += (uint32_t)(__popcll(__ballot(occ_l && done_l)) + __popcll(__ballot(occ_b && done_b)));
         // queued + resolved-in-place rays + those the next logic pass would discard (counted, not made)
         n_ext += (uint32_t)__popcll(__ballot(mo.want_ext || mo.trivial_ext || mo.skip_ext));
         n_skip += (uint32_t)__popcll(__ballot(mo.skip_ext));
@@ -1179,6 +1253,8 @@ __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_k
         if (n_vis) atomicAdd(sc_ctr + C_VIS, n_vis);
         if (n_occ) atomicAdd(sc_ctr + C_OCC, n_occ);
         if (occ_try) atomicAdd(sc_ctr + C_OCC_TRY, occ_try);
+        if (n_dvis) atomicAdd(sc_ctr + C_OCC_DONE_VIS, n_dvis);
+        if (n_docc) atomicAdd(sc_ctr + C_OCC_DONE_OCC, n_docc);
         if (n_skip) atomicAdd(sc_ctr + C_SKIP_EXT, n_skip);
         if (n_inpl) atomicAdd(sc_ctr + C_SKIP_INPLACE, n_inpl);
     }
@@ -2214,7 +2290,8 @@ __global__ void k_accumulate(CounterBlock* c, uint32_t nparts, uint32_t* occ_gat
         for (int off = 32; off > 0; off >>= 1) phw[k] += __shfl_xor(phw[k], off);
     }
     uint32_t er = c->shard[t][C_EXT_RAYS], ar = c->shard[t][C_ANY_RAYS], oc = c->shard[t][C_OCC],
-             ot = c->shard[t][C_OCC_TRY], pr = c->shard[t][C_PRIM_RAYS];
+             ot = c->shard[t][C_OCC_TRY], pr = c->shard[t][C_PRIM_RAYS], dv = c->shard[t][C_OCC_DONE_VIS],
+             dc = c->shard[t][C_OCC_DONE_OCC];
     const int skw[4] = {C_SKIP_EXT, C_SKIP_ANY, C_SKIP_MAT, C_SKIP_INPLACE};
     uint32_t sk[4];
 #pragma unroll
@@ -2230,7 +2307,11 @@ __global__ void k_accumulate(CounterBlock* c, uint32_t nparts, uint32_t* occ_gat
     c->shard[t][C_MAT] = 0;
     c->shard[t][C_OCC] = 0;
     c->shard[t][C_OCC_TRY] = 0;
+    if (dv) c->shard[t][C_OCC_DONE_VIS] = 0;
+    if (dc) c->shard[t][C_OCC_DONE_OCC] = 0;
     for (int off = 32; off > 0; off >>= 1) {
+        dv += __shfl_xor(dv, off);
+        dc += __shfl_xor(dc, off);
         er += __shfl_xor(er, off);
         ar += __shfl_xor(ar, off);
         oc += __shfl_xor(oc, off);
@@ -2243,6 +2324,8 @@ __global__ void k_accumulate(CounterBlock* c, uint32_t nparts, uint32_t* occ_gat
         for (int k = 0; k < 4; k++) c->tot_skip[k] += sk[k];
         c->tot_any += ar;
         c->tot_occ += oc;
+        c->tot_done[0] += dv;
+        c->tot_done[1] += dc;
         // occluder-cache gate for the next iterations' k_material (a speed choice only)
         if (occ_gate) {
             if (occ_gate[0]) {
@@ -2252,7 +2335,8 @@ __global__ void k_accumulate(CounterBlock* c, uint32_t nparts, uint32_t* occ_gat
                 // recorded their occluders: k_material starts its lookups after it
                 if (v[C_ANY]) occ_gate[2] = 1;
             } else if (ot >= 4096u) {
-                if ((unsigned long long)oc * kOccMinRate < ot) {
+                // (lookups pay by the rays they resolve either way: occluded, or unoccluded from a complete entry)
+                if (((unsigned long long)oc + dv) * kOccMinRate < ot) {
                     occ_gate[1] = occ_gate[1] ? min(2u * occ_gate[1] + 1u, 255u) : (uint32_t)MCPT_OCC_BACKOFF0;
                     occ_gate[0] = occ_gate[1];
                 } else {
@@ -2594,6 +2678,38 @@ __global__ void k_occ_probes(DevScene sc, float4* ro, float4* rd, uint32_t nkeys
     const float inv_n = 1.f / __builtin_sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
     ro[key] = make_float4(o[0], o[1], o[2], 0.f);
     rd[key] = make_float4(d[0] * inv_n, d[1] * inv_n, d[2] * inv_n, 0.f);
+}
+// Complete keys (device/occ_beam.hpp): one thread per table key walks the child-pair tree with the
+// key's beam; a key with at most kOccWays candidates gets them as marked words (the rest of its ways
+// the marked empty word), every other key keeps what the pre-fill left.
+__global__ void k_occ_complete(DevScene sc, mcpt::OccTree tree, uint32_t nkeys, uint32_t* ndone) {
+    const uint32_t key = blockIdx.x * blockDim.x + threadIdx.x;
+    bool done = false;
+    if (key < nkeys) {
+        const uint32_t G = (uint32_t)sc.occ_g, B = (uint32_t)sc.occ_b;
+        uint32_t t = key, cx, cy, cz, face, ub, vb;
+#if MCPT_OCC_LAYOUT == 1
+        cx = t % G; t /= G; cy = t % G; t /= G; cz = t % G; t /= G; vb = t % B; t /= B; ub = t % B; face = t / B;
+#else
+        vb = t % B; t /= B; ub = t % B; t /= B; face = t % 6u; t /= 6u; cx = t % G; t /= G; cy = t % G; cz = t / G;
+#endif
+        const mcpt::OccGrid g{{sc.root_mn[0], sc.root_mn[1], sc.root_mn[2]}, {sc.occ_cell[0], sc.occ_cell[1], sc.occ_cell[2]},
+                              sc.occ_g, sc.occ_b, sc.occ_dir};
+        const mcpt::Beam b = mcpt::occ_key_beam(g, cx, cy, cz, (face * B + ub) * B + vb);
+        uint32_t list[kOccWays];
+        const int n = mcpt::occ_key_list(tree, b, (int)kOccWays, list);
+        if (n >= 0) {
+            done = true;
+            for (uint32_t w = 0; w < kOccWays; w++)
+                sc.occ[(size_t)key * kOccWays + w] = (int)w < n ? (mcpt::kOccDoneBit | list[w]) : mcpt::kOccDoneNone;
+        }
+    }
+    const uint32_t cnt = (uint32_t)__popcll(__ballot(done));
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(ndone, cnt);
+}
+void launch_occ_complete(const DevScene& sc, const mcpt::OccTree& tree, uint32_t nkeys, uint32_t* ndone, hipStream_t s) {
+    if (nkeys == 0) return;
+    hipLaunchKernelGGL(k_occ_complete, dim3((nkeys + 255) / 256), dim3(256), 0, s, sc, tree, nkeys, ndone);
 }
 void launch_occ_probes(const DevScene& sc, float4* ro, float4* rd, uint32_t nkeys, hipStream_t s) {
     if (nkeys == 0) return;

@@ -27,6 +27,7 @@
 #include "device/adaptive.hpp"
 #include "device/denoise.hpp"
 #include "device/mcpt_core.hpp"
+#include "device/occ_beam.hpp"
 #include "device/temporal.hpp"
 #include "device/variance.hpp"
 
@@ -117,6 +118,12 @@ struct DevScene {
     uint32_t ntri;
     int occ_g, occ_b;       // origin cells per axis, direction bins per face coordinate
     float occ_inv[3];       // occ_g / root box extent, per axis
+    // Complete keys (device/occ_beam.hpp): an entry whose words all carry
+    // kOccDoneBit holds every triangle a ray of the key's beam can be accepted on, so k_material
+    // resolves such a ray either way.  occ_dir: the direction-bin table of the keys' beams (OccGrid::dir;
+    // nullptr: no complete keys, MCPT_OCC_COMPLETE=0), occ_cell the origin cells' extent per axis.
+    const float4* occ_dir;
+    float occ_cell[3];
     // Conservative culling (mcpt_core.hpp "conservative box culling"): every node holds each
     // child's margin W (pair nodes: q3.z / q3.w; 4-wide nodes: float4 7; occ_rec[4t].w), P is the
     // scene's far coefficient, root_w the root box's margin.  cull_ok = 0 (a caller BVH whose boxes
@@ -124,8 +131,15 @@ struct DevScene {
     float cull_p, root_w;
     int cull_ok;
 };
+// "0" at upload: no complete keys (A/B runs, tests).  As with kPrimaryHitsEnv below, bench.py has no entry
+// for it and stamps a run that sets it as an unknown knob, i.e. not the product.
+constexpr char kOccCompleteEnv[] = "MCPT_OCC_COMPLETE";
 constexpr uint32_t kOccEmpty = 0xffffffffu;
-constexpr uint32_t kOccWays = 2;      // entries per cell: k_trace writes way tri mod 2, k_material tests both
+#ifndef MCPT_OCC_WAYS
+#define MCPT_OCC_WAYS 2  // 4: 16-B entries, measured and not kept (tools/experiments/INDEX.md, occ_ways4.patch)
+#endif
+constexpr uint32_t kOccWays = MCPT_OCC_WAYS;  // entries per cell: k_trace writes way tri mod kOccWays, k_material tests all
+static_assert(kOccWays == 2 || kOccWays == 4, "an entry is one 8-B or 16-B load");
                                       // (1 way resolved 52 % of config 2's any-hit rays, 2 ways 64 %)
 constexpr uint32_t kOccGateWords = 3;  // DevScene::occ_gate
 constexpr uint32_t kOccMinRate = 10;  // lookups pay when >= 1 in kOccMinRate resolves a ray (see occ_skip)
@@ -146,13 +160,15 @@ constexpr int kShards = 64;
 constexpr int kMaxParts = kShards;  // k_trace work partitions (at most one per queue shard)
 enum : int { C_EXT = 0, C_ANY = 1, C_VIS = 2, C_STATS = 3, C_EXT_RAYS = 9, C_ANY_RAYS = 10, C_MAT = 11, C_OCC = 12,
               C_OCC_TRY = 13, C_PH = 14, C_SKIP_INPLACE = 25, C_PRIM = 26, C_PRIM_RAYS = 27, C_SKIP_EXT = 28,
-              C_SKIP_ANY = 29, C_SKIP_MAT = 30, C_WORDS = 32 };
+              C_SKIP_ANY = 29, C_SKIP_MAT = 30, C_OCC_DONE_VIS = 31, C_OCC_DONE_OCC = 32, C_WORDS = 64 };
 // C_STATS..+5; C_OCC / C_OCC_TRY: any-hit rays resolved by / tested against the occluder cache;
 // C_PH..+kPhaseWords-1: k_trace's loop-phase counts (counting build, PH_*); C_PRIM: primary-queue
 // pushes (k_shade -> k_primary), C_PRIM_RAYS: primary rays resolved from the candidate table
 // C_SKIP_EXT / C_SKIP_ANY / C_SKIP_MAT: extension rays, any-hit rays and material evaluations of
 // paths the next logic pass discards, counted as rays but not made (ShadeArgs::skip);
 // C_SKIP_INPLACE: with the switch off, such paths' extension rays that were resolved in place
+// C_OCC_DONE_VIS / C_OCC_DONE_OCC: any-hit rays resolved from complete entries of the occluder table as
+// unoccluded (counted as rays only: neither traversed nor in C_OCC) / as occluded (also part of C_OCC)
 // k_trace loop-phase counts of the counting instantiation (mcpt_debug_trace_profile), per wave summed:
 enum : int {
     PH_TRIPS = 0,          // loop trips with a ray in the wave
@@ -183,6 +199,7 @@ struct CounterBlock {
     unsigned long long tot_phase[kPhaseWords];  // k_trace loop-phase counts (PH_*; counting build only)
     unsigned long long tot_prim;  // primary rays resolved from the candidate table (part of tot_ext)
     unsigned long long tot_skip[4];  // C_SKIP_EXT, C_SKIP_ANY, C_SKIP_MAT, C_SKIP_INPLACE
+    unsigned long long tot_done[2];  // C_OCC_DONE_VIS, C_OCC_DONE_OCC
 };
 static_assert(C_PH + kPhaseWords <= C_SKIP_INPLACE, "counter words overlap");
 
@@ -326,6 +343,9 @@ void launch_clear(const ClearArgs& a, hipStream_t s);
 constexpr int kOccRecF4 = 4;
 void launch_occ_records(const DevScene& sc, uint32_t nnodes, float4* rec, hipStream_t s);
 void launch_occ_probes(const DevScene& sc, float4* ro, float4* rd, uint32_t nkeys, hipStream_t s);
+// Complete keys: every key of sc.occ whose candidate list (occ_key_list over the child-pair tree
+// `tree`) has at most kOccWays triangles gets the list, marked (kOccDoneBit); *ndone += their number
+void launch_occ_complete(const DevScene& sc, const mcpt::OccTree& tree, uint32_t nkeys, uint32_t* ndone, hipStream_t s);
 // Culling margins of a child-pair tree (mcpt_core.hpp cull_*): tri_w[t] = W'_T of record t,
 // *pmax = the far coefficient P's bits (max), then `passes` bottom-up passes writing every
 // child's subtree maximum into q3.z / q3.w (passes >= tree depth + 1 reach the fixed point).

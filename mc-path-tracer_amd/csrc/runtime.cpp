@@ -649,6 +649,10 @@ static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
     s.ntri = (uint32_t)d->ntri;
     s.occ = nullptr;
     s.occ_rec = nullptr;
+    s.occ_dir = nullptr;
+    for (int k = 0; k < 3; k++) s.occ_cell[k] = 0.f;
+    c->occ_done_keys = 0;
+    c->occ_done_ms = 0.f;
     {
         // 24^3 cells x 6 x 12^2 bins x 2 ways = 96 MB.  Config 2 with the table emptied at every film
         // clear: 62 % of the any-hit rays resolved (16^3 x 8^2: 60 %, 32^3 x 16^2: 64 %; frame rates
@@ -695,6 +699,19 @@ static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
             for (int k = 0; k < 3; k++) {
                 const float ext = s.root_mx[k] - s.root_mn[k];
                 s.occ_inv[k] = ext > 0.f && ext < 3.4e38f ? (float)G / ext : 0.f;
+                s.occ_cell[k] = s.occ_inv[k] > 0.f ? ext / (float)G : 0.f;
+            }
+            // Complete keys (device/occ_beam.hpp): the direction-bin table of the keys' beams.  They
+            // need the culling bound (a resolved ray's culling scale is positive) and a root box with
+            // an extent on every axis, and at most 32 cells per axis (k_material's packed key coordinates).
+            // MCPT_OCC_COMPLETE=0: none (A/B runs, tests).
+            const char* ce = getenv(kOccCompleteEnv);
+            if (!(ce && ce[0] == '0' && ce[1] == 0) && cull_ok && G <= 32 && s.occ_cell[0] > 0.f && s.occ_cell[1] > 0.f && s.occ_cell[2] > 0.f) {
+                std::vector<float4> dirs((size_t)6 * B * B * mcpt::kOccDirF4);
+                mcpt::occ_dir_table(B, dirs.data());
+                float4* dd2;
+                if ((rc = dupload(c, c->scene_bufs, &dd2, dirs.data(), dirs.size()))) return rc;
+                s.occ_dir = dd2;
             }
         }
     }
@@ -710,13 +727,15 @@ static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
         // clears restore this table, so every frame starts from the same one and no frame depends
         // on another.  MCPT_OCC_PREFILL=0: frames start from an empty table.
         const char* pe = getenv("MCPT_OCC_PREFILL");
-        if (!(pe && pe[0] == '0' && pe[1] == 0)) {
-            const uint32_t nkeys = (uint32_t)(c->occ_entries_n / kOccWays);
+        const bool prefill = !(pe && pe[0] == '0' && pe[1] == 0), complete = s.occ_dir != nullptr;
+        const uint32_t nkeys = (uint32_t)(c->occ_entries_n / kOccWays);
+        if ((prefill || complete) && (rc = dalloc(c, c->scene_bufs, &c->occ_init, c->occ_entries_n))) return rc;
+        if (prefill) {
             float4 *pro, *prd;
             uint8_t* pvis;
             free_list(c->tmp_bufs);
             if ((rc = dalloc(c, c->tmp_bufs, &pro, nkeys)) || (rc = dalloc(c, c->tmp_bufs, &prd, nkeys)) ||
-                (rc = dalloc(c, c->tmp_bufs, &pvis, nkeys)) || (rc = dalloc(c, c->scene_bufs, &c->occ_init, c->occ_entries_n)))
+                (rc = dalloc(c, c->tmp_bufs, &pvis, nkeys)))
                 return rc;
             launch_occ_probes(s, pro, prd, nkeys, c->stream);
             TraceArgs ta{};
@@ -731,6 +750,37 @@ static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
             ta.grab = &c->cnt->grab[0][0];
             launch_trace(ta, c->geom, c->stream);
             HIPCHK(c, hipMemsetAsync(c->cnt->grab, 0, sizeof(c->cnt->grab), c->stream));  // hand-out counters back to 0
+            HIPCHK(c, hipGetLastError());
+        }
+        if (complete) {
+            // Complete keys, over the pre-fill: the candidate lists of the keys that have at most
+            // kOccWays candidates, from the child-pair tree (kept on the device for either node width:
+            // the 4-wide nodes' boxes and margins are copies of its entries).  Like the pre-fill a
+            // property of the scene alone; the snapshot below carries them into every frame.
+            mcpt::OccTree tr{};
+            tr.nodes = c->pair_nodes;
+            tr.tri = s.tri;
+            tr.tri_f4 = kTriF4;
+            tr.ntri = s.ntri;
+            tr.root_ref = c->pair_root;
+            for (int k = 0; k < 3; k++) { tr.root_mn[k] = s.root_mn[k]; tr.root_mx[k] = s.root_mx[k]; }
+            tr.root_w = s.root_w;
+            tr.cull_p = s.cull_p;
+            uint32_t* dn;
+            if ((rc = dalloc(c, c->tmp_bufs, &dn, 1))) return rc;
+            HIPCHK(c, hipMemsetAsync(dn, 0, sizeof(uint32_t), c->stream));
+            HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
+            launch_occ_complete(s, tr, nkeys, dn, c->stream);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipEventRecord(ev(c, 1), c->stream));
+            uint32_t nd = 0;
+            HIPCHK(c, hipMemcpyAsync(&nd, dn, sizeof(nd), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipEventSynchronize(c->events[1]));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            HIPCHK(c, hipEventElapsedTime(&c->occ_done_ms, c->events[0], c->events[1]));
+            c->occ_done_keys = nd;
+        }
+        if (prefill || complete) {
             HIPCHK(c, hipMemcpyAsync(c->occ_init, s.occ, c->occ_entries_n * sizeof(uint32_t), hipMemcpyDeviceToDevice,
                                      c->stream));
             const uint32_t warm[kOccGateWords] = {0u, 0u, 1u};  // the table holds occluders: lookups from the start
@@ -817,6 +867,14 @@ int mcpt_debug_primary_stats(const mcpt_ctx* c, double* out4) {
 int mcpt_debug_discard_stats(const mcpt_ctx* c, uint64_t* out4) {
     if (!c || !out4) return MCPT_E_INVALID;
     for (int k = 0; k < 4; k++) out4[k] = c->totals_ok ? c->totals.tot_skip[k] : 0;
+    return MCPT_OK;
+}
+int mcpt_debug_occ_complete_stats(const mcpt_ctx* c, double* out4) {
+    if (!c || !out4) return MCPT_E_INVALID;
+    out4[0] = (double)c->occ_done_keys;
+    out4[1] = c->totals_ok ? (double)c->totals.tot_done[0] : 0.0;
+    out4[2] = c->totals_ok ? (double)c->totals.tot_done[1] : 0.0;
+    out4[3] = (double)c->occ_done_ms;
     return MCPT_OK;
 }
 int mcpt_debug_occ_stats(const mcpt_ctx* c, uint64_t* resolved, int32_t* enabled) {

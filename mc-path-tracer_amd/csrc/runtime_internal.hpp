@@ -189,7 +189,9 @@ struct mcpt_ctx {
     bool has_scene_before = false;  // set at the start of a re-upload
     int32_t ntri = 0;               // triangles of the uploaded scene
     size_t occ_entries_n = 0;       // occluder-cache table entries (DevScene::occ; + kOccGateWords gate words)
-    uint32_t* occ_init = nullptr;   // the table as the upload's pre-fill left it (film clears restore it); nullptr: empty
+    uint32_t* occ_init = nullptr;   // the table as the upload's pre-fill and complete keys left it (film clears restore it); nullptr: empty
+    uint64_t occ_done_keys = 0;     // complete keys of the last upload (device/occ_beam.hpp) and their build's ms
+    float occ_done_ms = 0.f;
     int pair_depth = 0;
     bool cull_ok = true, occ_nest_ok = true;  // last upload: boxes contain their triangles / nest (scene_upload)
     // traversal work counters (mcpt_set_work_counters): k_trace's counting instantiation, whose six

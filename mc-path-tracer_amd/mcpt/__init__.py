@@ -212,6 +212,7 @@ ABI = {
     "mcpt_debug_node_layout": (C.c_int, [C.c_void_p]),
     "mcpt_debug_bvh_read": (C.c_int, [C.c_void_p, _f, _f, C.POINTER(BvhInfo)]),
     "mcpt_debug_occ_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
+    "mcpt_debug_occ_complete_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "mcpt_debug_ray_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mcpt_debug_primary_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "mcpt_set_work_counters": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -527,6 +528,15 @@ class PathTracer:
         r, e = C.c_uint64(0), C.c_int32(0)
         self._ck(lib().mcpt_debug_occ_stats(self.h, C.byref(r), C.byref(e)))
         return int(r.value), bool(e.value)
+
+    def occ_complete_stats(self) -> dict:
+        """Complete keys of the occluder table (mcpt_debug_occ_complete_stats): keys of the uploaded scene
+        with a complete candidate list, any-hit rays they resolved as unoccluded / as occluded since the
+        last film clear, and the upload's build time of the lists in ms."""
+        v = (C.c_double * 4)()
+        if hasattr(lib(), "mcpt_debug_occ_complete_stats") or not os.environ.get("MCPT_LIB"):
+            self._ck(lib().mcpt_debug_occ_complete_stats(self.h, v))  # (an older variant library: zeros)
+        return dict(keys=int(v[0]), unoccluded=int(v[1]), occluded=int(v[2]), build_ms=float(v[3]))
 
     @property
     def last_build_ms(self) -> float:
