@@ -3,7 +3,7 @@
 // INTEGRATION.md): build a BASELINE config scene with the host builder, upload it,
 // run the wavefront iterations until every pixel has its samples, write PNG + PFM.
 //
-//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill]
+//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>]
 //
 // --denoise renders the first-hit guide buffers (default 4 guide samples per pixel), filters the film
 // with the default parameters and writes <out_prefix>_denoised.png beside the raw image.
@@ -21,8 +21,16 @@
 // --variance-fill turns the spatial variance estimate on (at its defaults): the
 // variances the path slots do not give are estimated from the frame, so --denoise-guided and --temporal
 // work with --slots 1, which is what they then use if --slots is not given.
+// --animate renders <frames> frames at [spp] of the config's mesh under a deterministic sinusoidal warp
+// (a wave along y of <amplitude> times the scene's extent that travels with the frame number): before
+// every frame the moved vertices go to mcpt_scene_update_geometry, which refits the tree on the device
+// (DESIGN.md section 15), and the frame is rendered; the last frame is the one written.  It combines with
+// --temporal (the longer of the two frame counts; an update drops the temporal history, there being no
+// motion vectors for moved geometry) and with --denoise / --denoise-guided (the last frame); not with
+// --tiles-per-call or --adaptive (rejected).
 // --tiles-per-call uses the reference orchestration (one 256x256 tile per call,
 // wavefront_kernels.cu:377-442 + Film::update_tile_position) instead of batch mode.
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -34,9 +42,24 @@
 
 struct Cfg { int w, h, spp, depth; float pos[3], pitch; const char* env; };
 
+// --animate: the desc's vertices under a wave along y, amp x the scene's largest extent high, whose
+// phase advances one turn over `frames` frames; a function of the position, so shared vertices stay shared
+static void warp(const mcpt_scene_desc& d, float amp, uint32_t frame, uint32_t frames, std::vector<float> out[3]) {
+    float ext = 0.f;
+    for (int k = 0; k < 3 && d.nnodes > 0; k++) ext = fmaxf(ext, d.bmax[k] - d.bmin[k]);
+    if (!(ext > 0.f)) ext = 1.f;
+    const float ph = 6.2831853f * (float)frame / (float)frames, kx = 9.f / ext;
+    const float* in[3] = {d.v0, d.v1, d.v2};
+    for (int a = 0; a < 3; a++) {
+        out[a].assign(in[a], in[a] + 3 * (size_t)d.ntri);
+        for (size_t t = 0; t < (size_t)d.ntri; t++)
+            out[a][3 * t + 1] += amp * ext * sinf(ph + kx * (out[a][3 * t] + out[a][3 * t + 2]));
+    }
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill]\n", argv[0]);
+        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>]\n", argv[0]);
         return 2;
     }
     const Cfg cfgs[6] = {{0, 0, 0, 0, {0, 0, 0}, 0, ""},
@@ -58,7 +81,15 @@ int main(int argc, char** argv) {
     uint32_t rounds = 2;
     uint32_t t_frames = 0;  // > 0: --temporal
     float t_yaw = 0.f;
+    uint32_t a_frames = 0;  // > 0: --animate
+    float a_amp = 0.f;
     for (int i = 2; i < argc; i++) {
+        if (!strcmp(argv[i], "--animate")) {
+            if (i + 2 >= argc || atoi(argv[i + 1]) < 1) { fprintf(stderr, "--animate needs <frames> <amplitude>\n"); return 2; }
+            a_frames = (uint32_t)atoi(argv[++i]);
+            a_amp = (float)atof(argv[++i]);
+            continue;
+        }
         if (!strcmp(argv[i], "--temporal")) {
             if (i + 2 >= argc || atoi(argv[i + 1]) < 1) { fprintf(stderr, "--temporal needs <frames> <yaw_step_deg>\n"); return 2; }
             t_frames = (uint32_t)atoi(argv[++i]);
@@ -92,6 +123,7 @@ int main(int argc, char** argv) {
     if (t_frames && !slots_given && !variance_fill) slots = 2;
     if (adaptive && !slots_given) slots = 8;  // the estimate is the spread of the path slots' means
     if (adaptive) c.spp = (int)ap.min_spp;    // the first pass
+    if (a_frames && (per_tile || adaptive)) { fprintf(stderr, "--animate does not combine with --tiles-per-call or --adaptive\n"); return 2; }
     const char* assets = getenv("MCPT_ASSETS") ? getenv("MCPT_ASSETS") : "assets";
 
     // Scene::load + BVHAccel + EnvironmentLight (host builder)
@@ -143,10 +175,35 @@ int main(int argc, char** argv) {
         }
         st.extend_rays = rays;
         st.ms_total = (float)ms;
+    } else if (a_frames && !t_frames) {  // animated geometry: move the mesh, refit, render
+        std::vector<float> w[3];
+        float ums[8] = {0};
+        for (uint32_t f = 0; f < a_frames && !rc; f++) {
+            mcpt_stage_stats one{};
+            warp(d, a_amp, f, a_frames, w);
+            if ((rc = mcpt_scene_update_geometry(ctx, d.ntri, w[0].data(), w[1].data(), w[2].data(), nullptr, nullptr, nullptr,
+                                                 MCPT_GEOM_REFIT)) ||
+                (rc = mcpt_render(ctx, &one)))
+                break;
+            st.extend_rays += one.extend_rays;
+            st.shadow_rays += one.shadow_rays;
+            st.vis_rays += one.vis_rays;
+            st.ms_total += one.ms_total;
+        }
+        if (!rc) rc = mcpt_debug_geometry_update_ms(ctx, ums);
+        if (!rc) printf("animate: %u frames, amplitude %.3f of the extent, last update %.3f ms on the device\n", a_frames, a_amp, ums[6]);
     } else if (t_frames) {  // a preview loop: camera, seed, render, guides, accumulate, filter
-        for (uint32_t f = 0; f < t_frames && !rc; f++) {
+        std::vector<float> w[3];
+        const uint32_t nframes = a_frames > t_frames ? a_frames : t_frames;
+        for (uint32_t f = 0; f < nframes && !rc; f++) {
             cp.yaw_deg = -90.f + (float)f * t_yaw;
             mcpt_stage_stats one{};
+            if (a_frames) {
+                warp(d, a_amp, f, nframes, w);
+                if ((rc = mcpt_scene_update_geometry(ctx, d.ntri, w[0].data(), w[1].data(), w[2].data(), nullptr, nullptr,
+                                                     nullptr, MCPT_GEOM_REFIT)))
+                    break;
+            }
             // (a seed per frame that differs in every bit field: seeds one apart repeat each other's samples)
             if ((rc = mcpt_camera_make(&cp, &cam)) || (rc = mcpt_camera_set(ctx, &cam)) ||
                 (rc = mcpt_set_seed(ctx, 0x9E3779B97F4A7C15ull * (uint64_t)(f + 1))) || (rc = mcpt_render(ctx, &one)) ||

@@ -197,6 +197,44 @@ int mcpt_scene_upload(mcpt_ctx *ctx, const mcpt_scene_desc *desc);
 #define MCPT_GPU_BVH_PLOC 1
 int mcpt_scene_upload_gpu_bvh(mcpt_ctx *ctx, const mcpt_scene_desc *desc);
 int mcpt_set_gpu_bvh_builder(mcpt_ctx *ctx, int32_t builder);
+/* Geometry update: new vertex positions, and optionally normals, for the
+ * triangles of the scene that is already uploaded -- animated geometry without a re-upload.  The arrays
+ * are in the order of the uploaded desc's triangle arrays.  The triangle records are rewritten on the
+ * device and the tree is refitted in place or rebuilt; then exactly the state that depends on geometry
+ * is derived again (culling margins, root box, the 4-wide nodes' boxes, the occluder cache's records,
+ * cells, pre-fill and complete keys).  Triangle and material ids, materials, lights, the environment
+ * with all its tables and the occluder grid's size stay, and so do the upload-time environment knobs
+ * (MCPT_CULL, MCPT_CULL_PLANE, MCPT_BVH_WIDTH, MCPT_SIBLING_LAYOUT, MCPT_OCC_*) as the upload read them.
+ * Hits and films after an update equal, bit for bit, those of a fresh upload of the moved mesh.
+ * The film sees an update as it sees a re-upload: it goes stale (the next iteration clears it unless
+ * MCPT_FLAG_NO_AUTO_CLEAR), the guides go stale, the temporal history is dropped and the primary-hit
+ * table is rebuilt on next use.
+ * MCPT_E_INVALID, with the scene left exactly as it was: no scene; ntri different from the uploaded
+ * count; only some of the three normal arrays; an unknown mode; MCPT_GEOM_REBUILD on a scene uploaded
+ * with a host tree.  A scene without triangles accepts ntri == 0 and does nothing.  Synchronous.
+ * Any other error (MCPT_E_HIP, MCPT_E_NOMEM) does not leave the scene as it was: the records and nodes
+ * are rewritten in place before the occluder state is derived, and a rebuild frees the old tree before
+ * it builds the new one.  After such an error the context has no scene: upload it again.
+ * Normals left NULL keep the current ones: those of the last update that gave normals, else the upload's.
+ * The update keeps device scratch between calls (per triangle 32 B of vertex boxes and 4 B of margins,
+ * and for the host entry 36 B of staged vertices, 72 B with normals); a scene upload frees it. */
+#define MCPT_GEOM_REFIT   0   /* keep the tree's topology, recompute boxes and margins */
+/* Device-built scenes only: run the GPU builder (mcpt_set_gpu_bvh_builder) again.  A scene of 4-wide
+ * nodes (more than 32 MB of pair nodes, or MCPT_BVH_WIDTH=4) is collapsed again on the host as at upload,
+ * which dominates such a rebuild (2 M triangles: 173 of 210 ms); a refit only regathers boxes on the device. */
+#define MCPT_GEOM_REBUILD 1
+int mcpt_scene_update_geometry(mcpt_ctx *ctx, int32_t ntri,
+                               const float *v0, const float *v1, const float *v2,   /* 3*ntri each, host */
+                               const float *n0, const float *n1, const float *n2,   /* all three, or all NULL: keep */
+                               int32_t mode);
+/* The same with device pointers on ctx's GPU (vertices skinned by a torch op, say); the caller has
+ * finished writing them. */
+int mcpt_scene_update_geometry_device(mcpt_ctx *ctx, int32_t ntri, const void *d_v0, const void *d_v1,
+                                      const void *d_v2, const void *d_n0, const void *d_n1, const void *d_n2,
+                                      int32_t mode);
+/* Device ms of the last update: [0] records, [1] refit or rebuild incl. margins, [2] 4-wide regather
+ * (a rebuild: the collapse), [3] occluder records, [4] pre-fill probes, [5] complete keys, [6] total; [7] 0 */
+int mcpt_debug_geometry_update_ms(const mcpt_ctx *ctx, float *out8);
 int mcpt_camera_set(mcpt_ctx *ctx, const mcpt_camera *cam);
 int mcpt_film_resize(mcpt_ctx *ctx, uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h);
 int mcpt_film_clear(mcpt_ctx *ctx);                                          /* == clear_dfilm */

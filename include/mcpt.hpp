@@ -41,6 +41,7 @@
 #define MCPT_HPP
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cmath>
 #include <cstdint>
@@ -631,6 +632,29 @@ public:
         detail::check(mcpt_temporal_denoise(ctx_, params), ctx_, "temporal_denoise");
     }
     void temporal_reset() { detail::check(mcpt_temporal_reset(ctx_), ctx_, "temporal_reset"); }
+    // Geometry update (mcpt.h): new vertex positions (3 floats per triangle each; and normals: all three
+    // arrays or none) for the scene the last render uploaded, in the order of its desc's triangle
+    // arrays.  The tree is refitted in place on the device (MCPT_GEOM_REFIT).  The host Scene is not
+    // touched, so the next render of the same, unedited Scene renders the moved mesh; the device film
+    // clears itself first (the context marks it stale), as after a re-upload.
+    void update_geometry(const std::vector<float>& v0, const std::vector<float>& v1, const std::vector<float>& v2,
+                         const std::vector<float>* n0 = nullptr, const std::vector<float>* n1 = nullptr,
+                         const std::vector<float>* n2 = nullptr, int32_t mode = MCPT_GEOM_REFIT) {
+        if (v0.size() % 3 || v1.size() != v0.size() || v2.size() != v0.size() || (n0 && n0->size() != v0.size()) ||
+            (n1 && n1->size() != v0.size()) || (n2 && n2->size() != v0.size()))
+            throw Error(MCPT_E_INVALID, "update_geometry: arrays of 3 floats per triangle, all of one size");
+        detail::check(mcpt_scene_update_geometry(ctx_, (int32_t)(v0.size() / 3), v0.data(), v1.data(), v2.data(),
+                                                 n0 ? n0->data() : nullptr, n1 ? n1->data() : nullptr,
+                                                 n2 ? n2->data() : nullptr, mode),
+                      ctx_, "update_geometry");
+    }
+    // Device ms of the last update_geometry: records, tree, 4-wide regather, occluder records, pre-fill
+    // probes, complete keys, total, 0
+    std::array<float, 8> geometry_update_ms() const {
+        std::array<float, 8> ms{};
+        detail::check(mcpt_debug_geometry_update_ms(ctx_, ms.data()), ctx_, "geometry_update_ms");
+        return ms;
+    }
     // Adaptive sampling (mcpt.h): a per-pixel sample budget (W*H entries; empty: remove it) in place of
     // the uniform spp, and the uniform spp of the live context.  Neither clears the film: the next
     // render_frame renders on.  Call them once the film's size is the context's (after a render).

@@ -374,7 +374,17 @@ struct Bufs {
 static int sort_prims(const LbvhInput& in, LbvhOutput& out, Bufs& tmp, hipStream_t s, float4*& pmn, float4*& pmx,
                       uint32_t*& code_s, uint32_t*& idx_s) {
     const int n = in.ntri;
-    float *dv0 = tmp.get<float>(3 * (size_t)n), *dv1 = tmp.get<float>(3 * (size_t)n), *dv2 = tmp.get<float>(3 * (size_t)n);
+    const float *dv0 = in.v0, *dv1 = in.v1, *dv2 = in.v2;
+    if (!in.verts_on_device) {
+        float *u0 = tmp.get<float>(3 * (size_t)n), *u1 = tmp.get<float>(3 * (size_t)n), *u2 = tmp.get<float>(3 * (size_t)n);
+        if (!u0 || !u1 || !u2) return -2;
+        const size_t vb = 3 * (size_t)n * sizeof(float);
+        if (hipMemcpyAsync(u0, in.v0, vb, hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(u1, in.v1, vb, hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(u2, in.v2, vb, hipMemcpyHostToDevice, s) != hipSuccess)
+            return -3;
+        dv0 = u0, dv1 = u1, dv2 = u2;
+    }
     pmn = tmp.get<float4>(n);
     pmx = tmp.get<float4>(n);
     float4* cen = tmp.get<float4>(n);
@@ -382,13 +392,12 @@ static int sort_prims(const LbvhInput& in, LbvhOutput& out, Bufs& tmp, hipStream
     float4* partial = tmp.get<float4>(2 * nparts);
     uint32_t *code = tmp.get<uint32_t>(n), *idx = tmp.get<uint32_t>(n);
     code_s = tmp.get<uint32_t>(n);
-    idx_s = tmp.get<uint32_t>(n);
-    if (!dv0 || !dv1 || !dv2 || !pmn || !pmx || !cen || !partial || !code || !idx || !code_s || !idx_s) return -2;
-    const size_t vb = 3 * (size_t)n * sizeof(float);
-    if (hipMemcpyAsync(dv0, in.v0, vb, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(dv1, in.v1, vb, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(dv2, in.v2, vb, hipMemcpyHostToDevice, s) != hipSuccess)
-        return -3;
+    // the sorted order outlives the build (owned by the caller): a geometry update writes the new
+    // records through it
+    out.order = nullptr;
+    if (hipMalloc(&out.order, std::max<size_t>((size_t)n * sizeof(uint32_t), 16)) != hipSuccess) return -2;
+    idx_s = out.order;
+    if (!pmn || !pmx || !cen || !partial || !code || !idx || !code_s) return -2;
     const int g = (n + kB - 1) / kB;
     hipLaunchKernelGGL(k_prim_boxes, dim3(g), dim3(kB), 0, s, n, dv0, dv1, dv2, pmn, pmx, cen);
     hipLaunchKernelGGL(k_cen_bounds, dim3(nparts), dim3(kB), 0, s, n, cen, partial);

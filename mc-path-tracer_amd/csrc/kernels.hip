@@ -2642,9 +2642,12 @@ __global__ void k_cull_zero(float4* nodes, uint32_t npairs) {
     q3.z = q3.w = 0.f;
     nodes[4 * (size_t)i + 3] = q3;
 }
+void launch_cull_tri(const float4* tri, uint32_t ntri, float* tri_w, uint32_t* pmax, bool plane, hipStream_t s) {
+    if (ntri) hipLaunchKernelGGL(k_cull_tri, dim3((ntri + 255) / 256), dim3(256), 0, s, tri, ntri, tri_w, pmax, plane ? 1 : 0);
+}
 void launch_cull_margins(float4* nodes, uint32_t npairs, const float4* tri, uint32_t ntri, float* tri_w,
                          uint32_t* pmax, int passes, bool plane, hipStream_t s) {
-    if (ntri) hipLaunchKernelGGL(k_cull_tri, dim3((ntri + 255) / 256), dim3(256), 0, s, tri, ntri, tri_w, pmax, plane ? 1 : 0);
+    launch_cull_tri(tri, ntri, tri_w, pmax, plane, s);
     if (!npairs) return;
     hipLaunchKernelGGL(k_cull_zero, dim3((npairs + 255) / 256), dim3(256), 0, s, nodes, npairs);
     for (int p = 0; p < passes; p++)

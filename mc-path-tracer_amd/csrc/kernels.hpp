@@ -352,6 +352,32 @@ void launch_occ_complete(const DevScene& sc, const mcpt::OccTree& tree, uint32_t
 // plane: the axis-plane bound (cull_plane_b) where it applies (false: the general bound only).
 void launch_cull_margins(float4* nodes, uint32_t npairs, const float4* tri, uint32_t ntri, float* tri_w,
                          uint32_t* pmax, int passes, bool plane, hipStream_t s);
+// Its first step alone: tri_w and *pmax (max) from the records (the refit fuses the passes with its boxes)
+void launch_cull_tri(const float4* tri, uint32_t ntri, float* tri_w, uint32_t* pmax, bool plane, hipStream_t s);
+
+// ---- geometry update (refit.hip) ----
+// k_geom_records: record i of tri (and of sh where n0 is given) from vertices order[i] (nullptr: i) of
+// the v / n arrays (device, 3 floats per triangle); the id and material words stay.  box (or nullptr):
+// 2 x float4 per record, its vertices' exact min / max.
+struct GeomRecordsArgs {
+    uint32_t ntri;
+    const uint32_t* order;
+    const float *v0, *v1, *v2, *n0, *n1, *n2;
+    float4 *tri, *sh, *box;
+};
+void launch_geom_records(const GeomRecordsArgs& a, hipStream_t s);
+// Boxes and margins of the child-pair tree `nodes` for new records, topology kept: leaf children from
+// box / tri_w (k_geom_records, launch_cull_tri), interior children in `passes` bottom-up passes
+// (passes >= tree depth + 1 reach the fixed point; pad nodes stay).  out7 (device): the root box's
+// min, max and margin.
+void launch_refit(float4* nodes, uint32_t npairs, int root_ref, int passes, const float4* box, const float* tri_w,
+                  uint32_t ntri, float* out7, hipStream_t s);
+// The boxes and margins of nquads 4-wide nodes again from the pair tree: slot k of node i copies child
+// (src[4 i + k] & 1) of pair node (src[4 i + k] >> 1); kQuadNoSrc: an empty slot.  Refs stay.
+constexpr uint32_t kQuadNoSrc = 0xffffffffu;
+void launch_quad_regather(float4* quads, uint32_t nquads, const uint32_t* src, const float4* pairs, uint32_t npairs,
+                          hipStream_t s);
+
 // tex[i].w = pdf[i], i < n (EnvView::tex: the pdf in the texture's alpha plane)
 void launch_env_pack(float4* tex, const float* pdf, size_t n, hipStream_t s);
 void launch_env_table(const mcpt::EnvView& e, bool fixed_mode, float4* out, float2* row, float2* col, hipStream_t s);
@@ -366,9 +392,11 @@ void launch_env_guides(const float* marginal_y, const float* conds_y, int W, int
 
 // GPU linear BVH (bvh_build.hip).  Inputs: host vertex arrays (3 floats per
 // triangle each) and the device triangle / shading records in scene order.
-struct LbvhInput { int ntri; const float *v0, *v1, *v2; const float4 *d_tri, *d_sh; };
+// verts_on_device: v0 / v1 / v2 are device arrays (a geometry update's rebuild), used in place.
+struct LbvhInput { int ntri; const float *v0, *v1, *v2; const float4 *d_tri, *d_sh; bool verts_on_device = false; };
 struct LbvhOutput {
     float4 *nodes = nullptr, *tri = nullptr, *tri_sh = nullptr;  // hipMalloc'ed, owned by the caller
+    uint32_t* order = nullptr;  // likewise: order[p] = the input triangle stored at record p (Morton order)
     int nnodes = 0, root_ref = 0, depth = 0, rounds = 0;
     float root_mn[3], root_mx[3];
 };

@@ -94,9 +94,12 @@ int mcpt_device_name(mcpt_ctx* c, char* buf, int32_t len) {
 // every leaf box is the pair tree's (and the reference builder's) exact box.
 // Breadth-first numbering keeps the top levels together.  Returns the new root
 // ref and the largest number of stack pushes along any root-to-leaf path.
+// src: per slot the (pair node, child) it copies, 2 * node + child (kQuadNoSrc: an empty slot) -- the
+// map a geometry update regathers the boxes and margins through (k_quad_regather).
 static int pairs_to_quads(const std::vector<float4>& pn, int root_ref, std::vector<float4>& qn, int& new_root,
-                          int& max_push) {
+                          int& max_push, std::vector<uint32_t>& src) {
     qn.clear();
+    src.clear();
     max_push = 0;
     if (root_ref < 0) { new_root = root_ref; return 0; }
     auto ref_at = [&](int p, int k) { int r; memcpy(&r, k ? &pn[4 * p + 3].y : &pn[4 * p + 3].x, 4); return r; };
@@ -108,7 +111,7 @@ static int pairs_to_quads(const std::vector<float4>& pn, int root_ref, std::vect
     push_depth.push_back(0);
     for (size_t h = 0; h < order.size(); h++) {
         const int p = order[h];
-        struct Slot { float mn[3], mx[3], w; int ref; };  // w: the child's culling margin (q3.z / q3.w)
+        struct Slot { float mn[3], mx[3], w; int ref; uint32_t src; };  // w: the child's culling margin (q3.z / q3.w)
         Slot sl[4];
         int n = 0;
         for (int k = 0; k < 2; k++) {
@@ -116,11 +119,13 @@ static int pairs_to_quads(const std::vector<float4>& pn, int root_ref, std::vect
             if (r < 0) {  // leaf child of the pair node: its box is in p
                 for (int a = 0; a < 3; a++) { sl[n].mn[a] = comp(pn[4 * p + a], k); sl[n].mx[a] = comp(pn[4 * p + a], 2 + k); }
                 sl[n].w = comp(pn[4 * p + 3], 2 + k);
+                sl[n].src = 2u * (uint32_t)p + (uint32_t)k;
                 sl[n++].ref = r;
             } else {      // interior child: take its two children
                 for (int j = 0; j < 2; j++) {
                     for (int a = 0; a < 3; a++) { sl[n].mn[a] = comp(pn[4 * r + a], j); sl[n].mx[a] = comp(pn[4 * r + a], 2 + j); }
                     sl[n].w = comp(pn[4 * r + 3], 2 + j);
+                    sl[n].src = 2u * (uint32_t)r + (uint32_t)j;
                     sl[n++].ref = ref_at(r, j);
                 }
             }
@@ -152,9 +157,280 @@ static int pairs_to_quads(const std::vector<float4>& pn, int root_ref, std::vect
             f[7 * 4 + k] = used ? sl[k].w : 0.f;  // margins (float4 7)
         }
         qn.insert(qn.end(), q, q + 8);
+        for (int k = 0; k < 4; k++) src.push_back(k < n ? sl[k].src : kQuadNoSrc);
     }
     new_root = 0;
     return 0;
+}
+
+// ---- the geometry half of an upload: what a geometry update (mcpt_scene_update_geometry) runs again ----
+
+// The upload-time environment knobs, read once per upload; an update takes them from the context.
+static void read_upload_env(GeomUpdate& g) {
+    auto is0 = [](const char* e) { return e && e[0] == '0' && e[1] == 0; };
+    g.cull_off = is0(getenv("MCPT_CULL"));  // 0: no culling at all (A/B, and a reference-order traversal)
+    // MCPT_CULL_PLANE=0: the general bound for axis-plane triangles too (A/B; the host
+    // builder's isolation of unbounded triangles reads the same variable)
+    g.plane = !is0(std::getenv("MCPT_CULL_PLANE"));
+    g.width = 0;
+    if (const char* we = getenv("MCPT_BVH_WIDTH"))
+        if ((we[0] == '2' || we[0] == '4') && we[1] == 0) g.width = we[0] - '0';
+    g.occ_g = 24, g.occ_b = 12;
+    if (const char* e = getenv("MCPT_OCC_G")) g.occ_g = atoi(e);
+    if (const char* e = getenv("MCPT_OCC_B")) g.occ_b = atoi(e);
+    g.occ_complete = !is0(getenv(kOccCompleteEnv));
+    g.occ_prefill = !is0(getenv("MCPT_OCC_PREFILL"));
+}
+
+// hipFree one array of the scene and drop it from scene_bufs
+static void scene_buf_free(mcpt_ctx* c, const void* p) {
+    if (!p) return;
+    auto it = std::find(c->scene_bufs.begin(), c->scene_bufs.end(), p);
+    if (it != c->scene_bufs.end()) c->scene_bufs.erase(it);
+    (void)hipFree(const_cast<void*>(p));
+}
+
+// The device build of the pair tree over the desc-order records li.d_tri / li.d_sh: the context's
+// builder, its arrays into scene_bufs, last_build_ms, pair_depth.
+static int gpu_tree_build(mcpt_ctx* c, const LbvhInput& li, LbvhOutput& lb) {
+    HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
+    const int brc = c->gpu_bvh_builder == MCPT_GPU_BVH_LBVH ? build_lbvh(li, lb, c->stream) : build_ploc(li, lb, c->stream);
+    for (void* q : {(void*)lb.nodes, (void*)lb.tri, (void*)lb.tri_sh, (void*)lb.order})
+        if (q) c->scene_bufs.push_back(q);
+    if (brc) return set_err(c, MCPT_E_HIP, "GPU BVH build failed (" + std::to_string(brc) + ")");
+    HIPCHK(c, hipEventRecord(ev(c, 1), c->stream));
+    HIPCHK(c, hipEventSynchronize(c->events[1]));
+    HIPCHK(c, hipEventElapsedTime(&c->last_build_ms, c->events[0], c->events[1]));
+    if (lb.depth > kMaxStack) return set_err(c, MCPT_E_INVALID, "GPU BVH deeper than the 64-entry traversal stack");
+    c->pair_depth = lb.depth;
+    c->gu.bvh_nodes = lb.nodes;
+    c->gu.order = lb.order;
+    return MCPT_OK;
+}
+
+// Culling margins of the pair tree dn (launch_cull_margins), the far coefficient P and the root's margin
+static int pair_margins(mcpt_ctx* c, float4* dn, uint32_t npairs, int proot, const float4* dt, int32_t ntri,
+                        float* cull_p, float* root_w) {
+    int rc;
+    float* tw = nullptr;
+    uint32_t* pm = nullptr;
+    if ((rc = dalloc(c, c->tmp_bufs, &tw, (size_t)ntri)) || (rc = dalloc(c, c->tmp_bufs, &pm, 1))) return rc;
+    HIPCHK(c, hipMemsetAsync(pm, 0, sizeof(uint32_t), c->stream));
+    mcpt_dev::launch_cull_margins(dn, npairs, dt, (uint32_t)ntri, tw, pm, c->pair_depth + 2, c->gu.plane, c->stream);
+    HIPCHK(c, hipGetLastError());
+    uint32_t pb = 0;
+    HIPCHK(c, hipMemcpyAsync(&pb, pm, sizeof(pb), hipMemcpyDeviceToHost, c->stream));
+    float4 rq = make_float4(0.f, 0.f, 0.f, 0.f);
+    std::vector<float> leaf_w;
+    if (proot >= 0 && npairs > 0) {
+        HIPCHK(c, hipMemcpyAsync(&rq, dn + 4 * (size_t)proot + 3, sizeof(rq), hipMemcpyDeviceToHost, c->stream));
+    } else if (proot < 0) {  // the whole tree is one leaf
+        const uint32_t off = (uint32_t)proot & 0xffffffu, cnt = (((uint32_t)proot >> 24) & 7u) + 1u;
+        leaf_w.resize(cnt);
+        HIPCHK(c, hipMemcpyAsync(leaf_w.data(), tw + off, cnt * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(cull_p, &pb, 4);
+    *root_w = proot >= 0 ? std::fmax(rq.z, rq.w) : 0.f;
+    for (float w : leaf_w) *root_w = std::fmax(*root_w, w);
+    free_list(c->tmp_bufs);
+    return MCPT_OK;
+}
+
+// Node width of a tree of tree_pairs pair nodes: 4-wide nodes (one 128-B line tests four boxes, half
+// the levels) for trees of more than 32 MB of pair nodes, child pairs otherwise.  Per launch,
+// interleaved on one box: config 5 (2 M tris, 128 MB) 16.7 -> 15.6 ms and config 3 (871K, 55 MB)
+// 1.154 -> 1.148 ms with quads; config 4 (252K, 16 MB) 7.69 -> 7.79 ms and config 2 (4.8K) 0.783 ->
+// 0.848 ms, so those keep pairs.  MCPT_BVH_WIDTH=2/4 forces a width.
+static int node_width(const mcpt_ctx* c, size_t tree_pairs) {
+    return c->gu.width ? c->gu.width : tree_pairs * 64 > ((size_t)32 << 20) ? 4 : 2;
+}
+
+// 4-wide traversal: collapse the pair tree on the device (host SAH or GPU-built, with the margins
+// launch_cull_margins wrote) into 4-wide nodes; s.nodes, the slot source map for later refits.
+static int quads_upload(mcpt_ctx* c, const float4* d_pairs, size_t npairs, int proot, DevScene& s, uint32_t& nnodes,
+                        int& quad_root, int& quad_push) {
+    std::vector<float4> pairs(npairs * 4);
+    if (npairs) HIPCHK(c, hipMemcpy(pairs.data(), d_pairs, pairs.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    std::vector<float4> quads;
+    std::vector<uint32_t> src;
+    int max_push = 0, rc;
+    pairs_to_quads(pairs, proot, quads, quad_root, max_push, src);
+    if (max_push > kMaxStack) return set_err(c, MCPT_E_INVALID, "4-wide BVH needs more than 64 stack entries");
+    quad_push = max_push;
+    float4* dq;
+    uint32_t* dsrc;
+    if ((rc = dupload(c, c->scene_bufs, &dq, quads.data(), quads.size()))) return rc;
+    if ((rc = dupload(c, c->scene_bufs, &dsrc, src.data(), src.size()))) return rc;
+    s.nodes = dq;
+    nnodes = (uint32_t)(quads.size() / 8);
+    c->gu.quads = dq;
+    c->gu.quad_src = dsrc;
+    c->gu.nquads = nnodes;
+    return MCPT_OK;
+}
+
+// Any-hit occluder cache (kernels.hip occ_hit1) and everything else that follows from the finished
+// tree of s: every triangle record's leaf box, the (origin cell x direction bin) table with its cell
+// sizes from the root box, the pre-fill probes, the complete keys, the occ_init snapshot film clears
+// restore and the gate words.  Run by an upload and by a geometry update alike; arrays the context
+// already holds are reused (an upload starts without any).  MCPT_OCC_G=0 turns the cache off;
+// MCPT_OCC_G / MCPT_OCC_B set the cells per axis / bins per face coordinate.  ms (or nullptr): device
+// ms of the leaf-box records, the pre-fill probes and the complete keys.
+static int occ_state(mcpt_ctx* c, DevScene& s, uint32_t nnodes, float* ms) {
+    int rc;
+    const bool cull_ok = s.cull_ok != 0;
+    s.occ = nullptr;
+    s.occ_gate = nullptr;
+    s.occ_rec = nullptr;
+    s.occ_dir = nullptr;
+    for (int k = 0; k < 3; k++) s.occ_cell[k] = 0.f;
+    c->occ_done_keys = 0;
+    c->occ_done_ms = 0.f;
+    if (ms) ms[0] = ms[1] = ms[2] = 0.f;
+    uint32_t* const occ_have = c->scene.occ;  // the table of the scene this one replaces in place (an update)
+    {
+        // 24^3 cells x 6 x 12^2 bins x 2 ways = 96 MB.  Config 2 with the table emptied at every film
+        // clear: 62 % of the any-hit rays resolved (16^3 x 8^2: 60 %, 32^3 x 16^2: 64 %; frame rates
+        // within 1 %: the bigger tables resolve more but warm up more slowly and miss L2 more)
+        const int G = c->gu.occ_g, B = c->gu.occ_b;
+        // the index G^3 * 6 * B^2 must fit 32 bits
+        // (off unless every box nests in its parent's: occ_test relies on it, see cull_ok above)
+        const bool occ_want = G > 0 && G <= 64 && B > 0 && B <= 64 && (uint64_t)G * G * G * 6 * B * B <= 0xffffffffull;
+        // The per-triangle leaf-box records serve the occluder cache and the primary-hit table alike
+        // (either switch alone keeps them).  For the table alone they are best-effort.
+        float4* lbx = c->gu.occ_rec;
+        if (!lbx && s.ntri > 0 && c->occ_nest_ok && (occ_want || c->prim.on)) {
+            void* q = nullptr;
+            if (hipMalloc(&q, kOccRecF4 * (size_t)s.ntri * sizeof(float4)) == hipSuccess) {
+                c->scene_bufs.push_back(q);
+                lbx = (float4*)q;
+            } else {
+                (void)hipGetLastError();
+                if (occ_want) return set_err(c, MCPT_E_NOMEM, "hipMalloc: occluder records");
+            }
+        }
+        c->gu.occ_rec = lbx;
+        if (lbx && !(s.ntri > 0 && c->occ_nest_ok)) lbx = nullptr;
+        if (lbx) {
+            // NaN boxes (all-ones bytes) for a record no leaf holds: occ_test's slab then fails
+            HIPCHK(c, hipEventRecord(ev(c, 2), c->stream));
+            HIPCHK(c, hipMemsetAsync(lbx, 0xff, kOccRecF4 * (size_t)s.ntri * sizeof(float4), c->stream));
+            launch_occ_records(s, nnodes, lbx, c->stream);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipEventRecord(ev(c, 3), c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (ms) HIPCHK(c, hipEventElapsedTime(&ms[0], ev(c, 2), ev(c, 3)));
+            s.occ_rec = lbx;
+        }
+        if (occ_want && lbx) {
+            uint32_t* occ = occ_have;
+            const size_t ne = occ_entries(G, B);
+            if (!occ && (rc = dalloc(c, c->scene_bufs, &occ, ne + kOccGateWords))) return rc;
+            HIPCHK(c, hipMemsetAsync(occ, 0xff, ne * sizeof(uint32_t), c->stream));
+            HIPCHK(c, hipMemsetAsync(occ + ne, 0, kOccGateWords * sizeof(uint32_t), c->stream));  // the lookup gate: on
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            s.occ = occ;
+            s.occ_gate = occ + ne;
+            c->occ_entries_n = ne;
+            s.occ_g = G;
+            s.occ_b = B;
+            for (int k = 0; k < 3; k++) {
+                const float ext = s.root_mx[k] - s.root_mn[k];
+                s.occ_inv[k] = ext > 0.f && ext < 3.4e38f ? (float)G / ext : 0.f;
+                s.occ_cell[k] = s.occ_inv[k] > 0.f ? ext / (float)G : 0.f;
+            }
+            // Complete keys (device/occ_beam.hpp): the direction-bin table of the keys' beams.  They
+            // need the culling bound (a resolved ray's culling scale is positive) and a root box with
+            // an extent on every axis, and at most 32 cells per axis (k_material's packed key coordinates).
+            // MCPT_OCC_COMPLETE=0: none (A/B runs, tests).
+            if (c->gu.occ_complete && cull_ok && G <= 32 && s.occ_cell[0] > 0.f && s.occ_cell[1] > 0.f && s.occ_cell[2] > 0.f) {
+                if (!c->gu.occ_dir) {
+                    std::vector<float4> dirs((size_t)6 * B * B * mcpt::kOccDirF4);
+                    mcpt::occ_dir_table(B, dirs.data());
+                    if ((rc = dupload(c, c->scene_bufs, &c->gu.occ_dir, dirs.data(), dirs.size()))) return rc;
+                }
+                s.occ_dir = c->gu.occ_dir;
+            }
+        }
+    }
+    if (s.occ) {
+        // Occluder-table pre-fill: one any-hit probe ray per table key (origin cell centre, direction
+        // bin centre; k_occ_probes) traced with occluder recording on, so every key whose probe is
+        // occluded starts with a triangle -- derived from the scene alone, like the BVH.  Film
+        // clears restore this table, so every frame starts from the same one and no frame depends
+        // on another.  MCPT_OCC_PREFILL=0: frames start from an empty table.
+        const bool prefill = c->gu.occ_prefill, complete = s.occ_dir != nullptr;
+        const uint32_t nkeys = (uint32_t)(c->occ_entries_n / kOccWays);
+        if ((prefill || complete) && !c->occ_init && (rc = dalloc(c, c->scene_bufs, &c->occ_init, c->occ_entries_n))) return rc;
+        if (prefill) {
+            float4 *pro, *prd;
+            uint8_t* pvis;
+            free_list(c->tmp_bufs);
+            if ((rc = dalloc(c, c->tmp_bufs, &pro, nkeys)) || (rc = dalloc(c, c->tmp_bufs, &prd, nkeys)) ||
+                (rc = dalloc(c, c->tmp_bufs, &pvis, nkeys)))
+                return rc;
+            HIPCHK(c, hipEventRecord(ev(c, 2), c->stream));
+            launch_occ_probes(s, pro, prd, nkeys, c->stream);
+            TraceArgs ta{};
+            ta.scene = s;  // occ on, gate words 0: the finish records the occluder of every occluded probe
+            ta.nshards = 1;
+            TraceSet& ts = ta.set[1];
+            ts.ro = pro;
+            ts.rd = prd;
+            ts.count = nkeys;
+            ts.shard_cap = nkeys;
+            ta.vis = pvis;
+            ta.grab = &c->cnt->grab[0][0];
+            launch_trace(ta, c->geom, c->stream);
+            HIPCHK(c, hipMemsetAsync(c->cnt->grab, 0, sizeof(c->cnt->grab), c->stream));  // hand-out counters back to 0
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipEventRecord(ev(c, 3), c->stream));
+            if (ms) {
+                HIPCHK(c, hipEventSynchronize(ev(c, 3)));
+                HIPCHK(c, hipEventElapsedTime(&ms[1], ev(c, 2), ev(c, 3)));
+            }
+        }
+        if (complete) {
+            // Complete keys, over the pre-fill: the candidate lists of the keys that have at most
+            // kOccWays candidates, from the child-pair tree (kept on the device for either node width:
+            // the 4-wide nodes' boxes and margins are copies of its entries).  Like the pre-fill a
+            // property of the scene alone; the snapshot below carries them into every frame.
+            mcpt::OccTree tr{};
+            tr.nodes = c->pair_nodes;
+            tr.tri = s.tri;
+            tr.tri_f4 = kTriF4;
+            tr.ntri = s.ntri;
+            tr.root_ref = c->pair_root;
+            for (int k = 0; k < 3; k++) { tr.root_mn[k] = s.root_mn[k]; tr.root_mx[k] = s.root_mx[k]; }
+            tr.root_w = s.root_w;
+            tr.cull_p = s.cull_p;
+            uint32_t* dn;
+            if ((rc = dalloc(c, c->tmp_bufs, &dn, 1))) return rc;
+            HIPCHK(c, hipMemsetAsync(dn, 0, sizeof(uint32_t), c->stream));
+            HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
+            launch_occ_complete(s, tr, nkeys, dn, c->stream);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipEventRecord(ev(c, 1), c->stream));
+            uint32_t nd = 0;
+            HIPCHK(c, hipMemcpyAsync(&nd, dn, sizeof(nd), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipEventSynchronize(c->events[1]));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            HIPCHK(c, hipEventElapsedTime(&c->occ_done_ms, c->events[0], c->events[1]));
+            c->occ_done_keys = nd;
+            if (ms) ms[2] = c->occ_done_ms;
+        }
+        if (prefill || complete) {
+            HIPCHK(c, hipMemcpyAsync(c->occ_init, s.occ, c->occ_entries_n * sizeof(uint32_t), hipMemcpyDeviceToDevice,
+                                     c->stream));
+            const uint32_t warm[kOccGateWords] = {0u, 0u, 1u};  // the table holds occluders: lookups from the start
+            HIPCHK(c, hipMemcpyAsync(s.occ_gate, warm, sizeof(warm), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            free_list(c->tmp_bufs);
+        }
+    }
+    return MCPT_OK;
 }
 
 static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
@@ -176,6 +452,12 @@ static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
     free_list(c->scene_bufs);
     c->pair_nodes = nullptr;
     c->pair_count = 0;
+    c->gu.forget();
+    c->gu.stage.reset(), c->gu.box.reset(), c->gu.tri_w.reset();  // the update scratch is sized by the scene
+    c->scene.occ = nullptr;  // (with scene_bufs; occ_state allocates the new scene's)
+    c->occ_init = nullptr;
+    read_upload_env(c->gu);
+    c->gu.gpu_upload = gpu_bvh;
     c->has_scene_before = c->has_scene_before || c->has_scene;
     c->has_scene = false;
     const int N = gpu_bvh ? 0 : d->nnodes;  // gpu_bvh: the desc's BVH arrays are ignored
@@ -406,20 +688,13 @@ static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
     LbvhOutput lb;
     c->last_build_ms = 0.f;
     if (gpu_bvh && d->ntri > 0) {
-        HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
+        c->gu.desc_tri = dt;  // the builders' input: kept for mcpt_scene_update_geometry's rebuild
+        c->gu.desc_sh = dsh;
         LbvhInput li{d->ntri, d->v0, d->v1, d->v2, dt, dsh};
-        const int brc = c->gpu_bvh_builder == MCPT_GPU_BVH_LBVH ? build_lbvh(li, lb, c->stream) : build_ploc(li, lb, c->stream);
-        for (void* q : {(void*)lb.nodes, (void*)lb.tri, (void*)lb.tri_sh})
-            if (q) c->scene_bufs.push_back(q);
-        if (brc) return set_err(c, MCPT_E_HIP, "GPU BVH build failed (" + std::to_string(brc) + ")");
-        HIPCHK(c, hipEventRecord(ev(c, 1), c->stream));
-        HIPCHK(c, hipEventSynchronize(c->events[1]));
-        HIPCHK(c, hipEventElapsedTime(&c->last_build_ms, c->events[0], c->events[1]));
-        if (lb.depth > kMaxStack) return set_err(c, MCPT_E_INVALID, "GPU BVH deeper than the 64-entry traversal stack");
+        if ((rc = gpu_tree_build(c, li, lb))) return rc;
         dn = lb.nodes;
         dt = lb.tri;
         dsh = lb.tri_sh;
-        c->pair_depth = lb.depth;
     }
     // Conservative culling (mcpt_core.hpp "conservative box culling").  The bound holds for a box
     // that contains its triangles: a caller BVH whose node boxes miss some of their subtree's
@@ -451,8 +726,7 @@ static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
         }
         nest_ok = nest_ok && cull_ok;
     }
-    if (const char* e = getenv("MCPT_CULL"))  // 0: no culling at all (A/B, and a reference-order traversal)
-        if (e[0] == '0' && e[1] == 0) cull_ok = false;
+    if (c->gu.cull_off) cull_ok = false;  // MCPT_CULL=0
     c->cull_ok = cull_ok;
     c->occ_nest_ok = nest_ok;
     float cull_p = 0.f, root_w = __builtin_huge_valf();
@@ -464,74 +738,18 @@ static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
         c->pair_root = proot;
         c->pair_gpu_built = gpu_bvh && d->ntri > 0;
         c->ploc_rounds = c->pair_gpu_built && c->gpu_bvh_builder == MCPT_GPU_BVH_PLOC ? lb.rounds : 0;
-        float* tw = nullptr;
-        uint32_t* pm = nullptr;
-        if (d->ntri > 0) {
-            if ((rc = dalloc(c, c->tmp_bufs, &tw, (size_t)d->ntri)) || (rc = dalloc(c, c->tmp_bufs, &pm, 1))) return rc;
-            HIPCHK(c, hipMemsetAsync(pm, 0, sizeof(uint32_t), c->stream));
-            // MCPT_CULL_PLANE=0: the general bound for axis-plane triangles too (A/B; the host
-            // builder's isolation of unbounded triangles reads the same variable)
-            const char* pl = std::getenv("MCPT_CULL_PLANE");
-            const bool plane = !(pl && pl[0] == '0' && pl[1] == 0);
-            mcpt_dev::launch_cull_margins(dn, npairs, dt, (uint32_t)d->ntri, tw, pm, c->pair_depth + 2, plane, c->stream);
-            HIPCHK(c, hipGetLastError());
-            uint32_t pb = 0;
-            HIPCHK(c, hipMemcpyAsync(&pb, pm, sizeof(pb), hipMemcpyDeviceToHost, c->stream));
-            float4 rq = make_float4(0.f, 0.f, 0.f, 0.f);
-            std::vector<float> leaf_w;
-            if (proot >= 0 && npairs > 0) {
-                HIPCHK(c, hipMemcpyAsync(&rq, dn + 4 * (size_t)proot + 3, sizeof(rq), hipMemcpyDeviceToHost, c->stream));
-            } else if (proot < 0) {  // the whole tree is one leaf
-                const uint32_t off = (uint32_t)proot & 0xffffffu, cnt = (((uint32_t)proot >> 24) & 7u) + 1u;
-                leaf_w.resize(cnt);
-                HIPCHK(c, hipMemcpyAsync(leaf_w.data(), tw + off, cnt * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-            }
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            memcpy(&cull_p, &pb, 4);
-            root_w = proot >= 0 ? std::fmax(rq.z, rq.w) : 0.f;
-            for (float w : leaf_w) root_w = std::fmax(root_w, w);
-            free_list(c->tmp_bufs);
-        }
+        if (d->ntri > 0 && (rc = pair_margins(c, dn, npairs, proot, dt, d->ntri, &cull_p, &root_w))) return rc;
     }
     if ((rc = dupload(c, c->scene_bufs, &dm, d->mat_params, (size_t)d->nmat * 8))) return rc;
     if ((rc = dupload(c, c->scene_bufs, &dd, d->dir_params, (size_t)d->ndir * 7))) return rc;
     s.nodes = dn; s.tri = dt; s.tri_sh = dsh; s.mats = dm; s.dirs = dd;
-    // Node width: 4-wide nodes (one 128-B line tests four boxes, half the levels) for trees
-    // of more than 32 MB of pair nodes, child pairs otherwise.  Per launch, interleaved on one
-    // box: config 5 (2 M tris, 128 MB) 16.7 -> 15.6 ms and config 3 (871K, 55 MB) 1.154 ->
-    // 1.148 ms with quads; config 4 (252K, 16 MB) 7.69 -> 7.79 ms and config 2 (4.8K) 0.783 ->
-    // 0.848 ms, so those keep pairs.  MCPT_BVH_WIDTH=2/4 forces a width.
     const size_t tree_pairs = gpu_bvh ? (size_t)lb.nnodes : pn.size() / 4;
     uint32_t nnodes = (uint32_t)tree_pairs;  // nodes of the uploaded width (the leaf-box pass)
-    int width = tree_pairs * 64 > ((size_t)32 << 20) ? 4 : 2;
-    if (const char* we = getenv("MCPT_BVH_WIDTH"))
-        if ((we[0] == '2' || we[0] == '4') && we[1] == 0) width = we[0] - '0';
+    const int width = node_width(c, tree_pairs);
     int quad_root = 0, quad_push = 0;
-    if (width == 4) {
-        // 4-wide traversal: collapse the pair tree (host SAH or GPU LBVH) into 4-wide nodes
-        std::vector<float4> pairs;
-        int proot;
-        if (gpu_bvh && d->ntri > 0) {
-            pairs.resize((size_t)lb.nnodes * 4);
-            if (lb.nnodes) HIPCHK(c, hipMemcpy(pairs.data(), lb.nodes, pairs.size() * sizeof(float4), hipMemcpyDeviceToHost));
-            proot = lb.root_ref;
-        } else {  // the uploaded pairs, with the margins launch_cull_margins wrote
-            pairs.resize(pn.size());
-            if (!pn.empty()) HIPCHK(c, hipMemcpy(pairs.data(), dn, pairs.size() * sizeof(float4), hipMemcpyDeviceToHost));
-            proot = N > 0 ? ref_of(0) : 0;
-        }
-        std::vector<float4> quads;
-        int max_push = 0;
-        if (d->ntri > 0) {
-            pairs_to_quads(pairs, proot, quads, quad_root, max_push);
-            if (max_push > kMaxStack) return set_err(c, MCPT_E_INVALID, "4-wide BVH needs more than 64 stack entries");
-            quad_push = max_push;
-            float4* dq;
-            if ((rc = dupload(c, c->scene_bufs, &dq, quads.data(), quads.size()))) return rc;
-            s.nodes = dq;
-            nnodes = (uint32_t)(quads.size() / 8);
-        }
-    }
+    if (width == 4 && d->ntri > 0 &&
+        (rc = quads_upload(c, dn, tree_pairs, c->pair_root, s, nnodes, quad_root, quad_push)))
+        return rc;
     s.nlights = 1 + d->ndir;
     if (gpu_bvh && d->ntri > 0) {
         for (int k = 0; k < 3; k++) { s.root_mn[k] = lb.root_mn[k]; s.root_mx[k] = lb.root_mx[k]; }
@@ -643,153 +861,12 @@ static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
     s.cull_p = cull_p;
     s.root_w = root_w;
     s.cull_ok = cull_ok ? 1 : 0;
-    // Any-hit occluder cache (kernels.hip occ_hit1): every triangle record's leaf box and the
-    // (origin cell x direction bin) table, empty at upload.  MCPT_OCC_G=0 turns it off;
-    // MCPT_OCC_G / MCPT_OCC_B set the cells per axis / bins per face coordinate.
     s.ntri = (uint32_t)d->ntri;
-    s.occ = nullptr;
-    s.occ_rec = nullptr;
-    s.occ_dir = nullptr;
-    for (int k = 0; k < 3; k++) s.occ_cell[k] = 0.f;
-    c->occ_done_keys = 0;
-    c->occ_done_ms = 0.f;
-    {
-        // 24^3 cells x 6 x 12^2 bins x 2 ways = 96 MB.  Config 2 with the table emptied at every film
-        // clear: 62 % of the any-hit rays resolved (16^3 x 8^2: 60 %, 32^3 x 16^2: 64 %; frame rates
-        // within 1 %: the bigger tables resolve more but warm up more slowly and miss L2 more)
-        int G = 24, B = 12;
-        if (const char* e = getenv("MCPT_OCC_G")) G = atoi(e);
-        if (const char* e = getenv("MCPT_OCC_B")) B = atoi(e);
-        // the index G^3 * 6 * B^2 must fit 32 bits
-        // (off unless every box nests in its parent's: occ_test relies on it, see cull_ok above)
-        const bool occ_want = G > 0 && G <= 64 && B > 0 && B <= 64 && (uint64_t)G * G * G * 6 * B * B <= 0xffffffffull;
-        // The per-triangle leaf-box records serve the occluder cache and the primary-hit table alike
-        // (either switch alone keeps them).  For the table alone they are best-effort.
-        float4* lbx = nullptr;
-        if (d->ntri > 0 && c->occ_nest_ok && (occ_want || c->prim.on)) {
-            void* q = nullptr;
-            if (hipMalloc(&q, kOccRecF4 * (size_t)d->ntri * sizeof(float4)) == hipSuccess) {
-                c->scene_bufs.push_back(q);
-                lbx = (float4*)q;
-            } else {
-                (void)hipGetLastError();
-                if (occ_want) return set_err(c, MCPT_E_NOMEM, "hipMalloc: occluder records");
-            }
-        }
-        if (lbx) {
-            // NaN boxes (all-ones bytes) for a record no leaf holds: occ_test's slab then fails
-            HIPCHK(c, hipMemsetAsync(lbx, 0xff, kOccRecF4 * (size_t)d->ntri * sizeof(float4), c->stream));
-            launch_occ_records(s, nnodes, lbx, c->stream);
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            s.occ_rec = lbx;
-        }
-        if (occ_want && lbx) {
-            uint32_t* occ;
-            const size_t ne = occ_entries(G, B);
-            if ((rc = dalloc(c, c->scene_bufs, &occ, ne + kOccGateWords))) return rc;
-            HIPCHK(c, hipMemsetAsync(occ, 0xff, ne * sizeof(uint32_t), c->stream));
-            HIPCHK(c, hipMemsetAsync(occ + ne, 0, kOccGateWords * sizeof(uint32_t), c->stream));  // the lookup gate: on
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            s.occ = occ;
-            s.occ_gate = occ + ne;
-            c->occ_entries_n = ne;
-            s.occ_g = G;
-            s.occ_b = B;
-            for (int k = 0; k < 3; k++) {
-                const float ext = s.root_mx[k] - s.root_mn[k];
-                s.occ_inv[k] = ext > 0.f && ext < 3.4e38f ? (float)G / ext : 0.f;
-                s.occ_cell[k] = s.occ_inv[k] > 0.f ? ext / (float)G : 0.f;
-            }
-            // Complete keys (device/occ_beam.hpp): the direction-bin table of the keys' beams.  They
-            // need the culling bound (a resolved ray's culling scale is positive) and a root box with
-            // an extent on every axis, and at most 32 cells per axis (k_material's packed key coordinates).
-            // MCPT_OCC_COMPLETE=0: none (A/B runs, tests).
-            const char* ce = getenv(kOccCompleteEnv);
-            if (!(ce && ce[0] == '0' && ce[1] == 0) && cull_ok && G <= 32 && s.occ_cell[0] > 0.f && s.occ_cell[1] > 0.f && s.occ_cell[2] > 0.f) {
-                std::vector<float4> dirs((size_t)6 * B * B * mcpt::kOccDirF4);
-                mcpt::occ_dir_table(B, dirs.data());
-                float4* dd2;
-                if ((rc = dupload(c, c->scene_bufs, &dd2, dirs.data(), dirs.size()))) return rc;
-                s.occ_dir = dd2;
-            }
-        }
-    }
+    if ((rc = occ_state(c, s, nnodes, nullptr))) return rc;
     c->scene = s;
     c->scene_gen++;  // with the scene itself: the previous scene's primary-hit table is stale (prim_table)
     c->tp.ok = false;  // ... and so is the temporal history (no motion vectors for moved geometry)
     c->ntri = d->ntri;
-    c->occ_init = nullptr;  // (the previous scene's copy went with scene_bufs)
-    if (s.occ) {
-        // Occluder-table pre-fill: one any-hit probe ray per table key (origin cell centre, direction
-        // bin centre; k_occ_probes) traced with occluder recording on, so every key whose probe is
-        // occluded starts with a triangle -- derived from the scene alone, like the BVH.  Film
-        // clears restore this table, so every frame starts from the same one and no frame depends
-        // on another.  MCPT_OCC_PREFILL=0: frames start from an empty table.
-        const char* pe = getenv("MCPT_OCC_PREFILL");
-        const bool prefill = !(pe && pe[0] == '0' && pe[1] == 0), complete = s.occ_dir != nullptr;
-        const uint32_t nkeys = (uint32_t)(c->occ_entries_n / kOccWays);
-        if ((prefill || complete) && (rc = dalloc(c, c->scene_bufs, &c->occ_init, c->occ_entries_n))) return rc;
-        if (prefill) {
-            float4 *pro, *prd;
-            uint8_t* pvis;
-            free_list(c->tmp_bufs);
-            if ((rc = dalloc(c, c->tmp_bufs, &pro, nkeys)) || (rc = dalloc(c, c->tmp_bufs, &prd, nkeys)) ||
-                (rc = dalloc(c, c->tmp_bufs, &pvis, nkeys)))
-                return rc;
-            launch_occ_probes(s, pro, prd, nkeys, c->stream);
-            TraceArgs ta{};
-            ta.scene = s;  // occ on, gate words 0: the finish records the occluder of every occluded probe
-            ta.nshards = 1;
-            TraceSet& ts = ta.set[1];
-            ts.ro = pro;
-            ts.rd = prd;
-            ts.count = nkeys;
-            ts.shard_cap = nkeys;
-            ta.vis = pvis;
-            ta.grab = &c->cnt->grab[0][0];
-            launch_trace(ta, c->geom, c->stream);
-            HIPCHK(c, hipMemsetAsync(c->cnt->grab, 0, sizeof(c->cnt->grab), c->stream));  // hand-out counters back to 0
-            HIPCHK(c, hipGetLastError());
-        }
-        if (complete) {
-            // Complete keys, over the pre-fill: the candidate lists of the keys that have at most
-            // kOccWays candidates, from the child-pair tree (kept on the device for either node width:
-            // the 4-wide nodes' boxes and margins are copies of its entries).  Like the pre-fill a
-            // property of the scene alone; the snapshot below carries them into every frame.
-            mcpt::OccTree tr{};
-            tr.nodes = c->pair_nodes;
-            tr.tri = s.tri;
-            tr.tri_f4 = kTriF4;
-            tr.ntri = s.ntri;
-            tr.root_ref = c->pair_root;
-            for (int k = 0; k < 3; k++) { tr.root_mn[k] = s.root_mn[k]; tr.root_mx[k] = s.root_mx[k]; }
-            tr.root_w = s.root_w;
-            tr.cull_p = s.cull_p;
-            uint32_t* dn;
-            if ((rc = dalloc(c, c->tmp_bufs, &dn, 1))) return rc;
-            HIPCHK(c, hipMemsetAsync(dn, 0, sizeof(uint32_t), c->stream));
-            HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
-            launch_occ_complete(s, tr, nkeys, dn, c->stream);
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipEventRecord(ev(c, 1), c->stream));
-            uint32_t nd = 0;
-            HIPCHK(c, hipMemcpyAsync(&nd, dn, sizeof(nd), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipEventSynchronize(c->events[1]));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            HIPCHK(c, hipEventElapsedTime(&c->occ_done_ms, c->events[0], c->events[1]));
-            c->occ_done_keys = nd;
-        }
-        if (prefill || complete) {
-            HIPCHK(c, hipMemcpyAsync(c->occ_init, s.occ, c->occ_entries_n * sizeof(uint32_t), hipMemcpyDeviceToDevice,
-                                     c->stream));
-            const uint32_t warm[kOccGateWords] = {0u, 0u, 1u};  // the table holds occluders: lookups from the start
-            HIPCHK(c, hipMemcpyAsync(s.occ_gate, warm, sizeof(warm), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            free_list(c->tmp_bufs);
-        }
-    }
     if (c->has_scene_before) c->film_stale = true;  // a re-upload notifies the film
     c->has_scene = true;
     return MCPT_OK;
@@ -801,6 +878,158 @@ int mcpt_set_gpu_bvh_builder(mcpt_ctx* c, int32_t builder) {
     if (!c || (builder != MCPT_GPU_BVH_LBVH && builder != MCPT_GPU_BVH_PLOC))
         return set_err(c, MCPT_E_INVALID, "unknown GPU BVH builder");
     c->gpu_bvh_builder = builder;
+    return MCPT_OK;
+}
+
+// ---- geometry update ----
+// New vertex positions (and optionally normals) for the uploaded scene's triangles, in the order of
+// the desc's arrays: the records are rewritten in place and the tree is refitted (topology kept) or,
+// for a device-built scene, built again; then exactly the state that depends on geometry is derived
+// again -- margins, P, the root box, the 4-wide nodes' boxes, the occluder state -- and nothing else:
+// materials, lights, the environment and its tables, ids and the occluder grid's size stay.
+static int geometry_check(mcpt_ctx* c, int32_t ntri, const void* v0, const void* v1, const void* v2, const void* n0,
+                          const void* n1, const void* n2, int32_t mode) {
+    if (!c) return set_err(c, MCPT_E_INVALID, "null context");
+    if (!c->has_scene) return set_err(c, MCPT_E_INVALID, "no scene uploaded");
+    if (ntri != c->ntri) return set_err(c, MCPT_E_INVALID, "ntri differs from the uploaded scene's (topology changes need an upload)");
+    const int given = !!n0 + !!n1 + !!n2;
+    if (given != 0 && given != 3) return set_err(c, MCPT_E_INVALID, "normals: all three arrays or none");
+    if (mode != MCPT_GEOM_REFIT && mode != MCPT_GEOM_REBUILD) return set_err(c, MCPT_E_INVALID, "unknown geometry update mode");
+    if (mode == MCPT_GEOM_REBUILD && !c->gu.gpu_upload)
+        return set_err(c, MCPT_E_INVALID, "MCPT_GEOM_REBUILD needs a scene uploaded by mcpt_scene_upload_gpu_bvh");
+    if (ntri > 0 && (!v0 || !v1 || !v2)) return set_err(c, MCPT_E_INVALID, "null vertex array");
+    return MCPT_OK;
+}
+
+// The arguments are checked, the arrays on the device and complete.
+static int geometry_update_device(mcpt_ctx* c, int32_t ntri, const float* v0, const float* v1, const float* v2,
+                                  const float* n0, const float* n1, const float* n2, int32_t mode) {
+    if (ntri == 0) return MCPT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    GeomUpdate& g = c->gu;
+    const uint32_t n = (uint32_t)ntri;
+    int rc;
+    DevScene s = c->scene;
+    for (float& m : g.ms) m = 0.f;
+    enum { E_START = 4, E_REC, E_TREE, E_QUAD, E_END };  // (occ_state and gpu_tree_build use events 0-3)
+    if (!g.out.ensure(8) || (mode == MCPT_GEOM_REFIT && (!g.box.ensure(2 * (size_t)n) || !g.tri_w.ensure(n))))
+        return set_err(c, MCPT_E_NOMEM, "hipMalloc: geometry update");  // (nothing is rewritten yet)
+    uint32_t nnodes = 0;
+    // From here the scene is rewritten in place: until the update stands the context has no scene, so
+    // an error on the way (MCPT_E_HIP, MCPT_E_NOMEM) cannot leave a half-updated one to be rendered.
+    c->has_scene = false;
+    HIPCHK(c, hipEventRecord(ev(c, E_START), c->stream));
+    if (mode == MCPT_GEOM_REFIT) {
+        float4* pairs = const_cast<float4*>(c->pair_nodes);
+        launch_geom_records(GeomRecordsArgs{n, g.order, v0, v1, v2, n0, n1, n2, const_cast<float4*>(s.tri),
+                                            const_cast<float4*>(s.tri_sh), g.box},
+                            c->stream);
+        // New normals also go into the desc-order records a later rebuild permutes from: a rebuild
+        // without normals keeps the current ones, not the upload's.  (Positions need no such copy: a
+        // rebuild always rewrites them.)
+        if (n0 && g.desc_tri && g.desc_sh)
+            launch_geom_records(GeomRecordsArgs{n, nullptr, v0, v1, v2, n0, n1, n2, g.desc_tri, g.desc_sh, nullptr}, c->stream);
+        HIPCHK(c, hipEventRecord(ev(c, E_REC), c->stream));
+        HIPCHK(c, hipMemsetAsync(g.out, 0, 8 * sizeof(float), c->stream));
+        launch_cull_tri(s.tri, n, g.tri_w, reinterpret_cast<uint32_t*>(g.out.get() + 7), g.plane, c->stream);
+        launch_refit(pairs, c->pair_count, c->pair_root, c->pair_depth + 2, g.box, g.tri_w, n, g.out, c->stream);
+        float out[8] = {};
+        HIPCHK(c, hipMemcpyAsync(out, g.out, sizeof(out), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipEventRecord(ev(c, E_TREE), c->stream));
+        // the 4-wide nodes' boxes and margins are copies of the pair tree's: gather them again
+        if (s.width == 4 && g.quads && g.nquads)
+            launch_quad_regather(g.quads, g.nquads, g.quad_src, pairs, c->pair_count, c->stream);
+        HIPCHK(c, hipEventRecord(ev(c, E_QUAD), c->stream));
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (int k = 0; k < 3; k++) { s.root_mn[k] = out[k]; s.root_mx[k] = out[3 + k]; }
+        s.root_w = out[6];
+        memcpy(&s.cull_p, &out[7], 4);
+        // the refitted boxes contain their triangles and nest, whatever the uploaded ones did
+        c->cull_ok = !g.cull_off;
+        c->occ_nest_ok = true;
+        nnodes = s.width == 4 ? g.nquads : c->pair_count;
+    } else {
+        launch_geom_records(GeomRecordsArgs{n, nullptr, v0, v1, v2, n0, n1, n2, g.desc_tri, g.desc_sh, nullptr}, c->stream);
+        HIPCHK(c, hipEventRecord(ev(c, E_REC), c->stream));
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        // the old tree goes
+        for (const void* q : {(const void*)g.bvh_nodes, (const void*)s.tri, (const void*)s.tri_sh, (const void*)g.order,
+                              (const void*)g.quads, (const void*)g.quad_src})
+            scene_buf_free(c, q);
+        g.bvh_nodes = g.quads = nullptr;
+        g.order = g.quad_src = nullptr;
+        g.nquads = 0;
+        c->pair_nodes = nullptr;
+        c->pair_count = 0;
+        LbvhOutput lb;
+        LbvhInput li{ntri, v0, v1, v2, g.desc_tri, g.desc_sh, true};
+        if ((rc = gpu_tree_build(c, li, lb))) return rc;
+        c->pair_nodes = lb.nnodes ? lb.nodes : nullptr;
+        c->pair_count = (uint32_t)lb.nnodes;
+        c->pair_root = lb.root_ref;
+        c->ploc_rounds = c->gpu_bvh_builder == MCPT_GPU_BVH_PLOC ? lb.rounds : 0;
+        c->cull_ok = !g.cull_off;
+        c->occ_nest_ok = true;
+        if ((rc = pair_margins(c, lb.nodes, (uint32_t)lb.nnodes, lb.root_ref, lb.tri, ntri, &s.cull_p, &s.root_w))) return rc;
+        HIPCHK(c, hipEventRecord(ev(c, E_TREE), c->stream));
+        s.nodes = lb.nodes;
+        s.tri = lb.tri;
+        s.tri_sh = lb.tri_sh;
+        nnodes = (uint32_t)lb.nnodes;
+        s.width = node_width(c, (size_t)lb.nnodes);
+        int quad_root = 0, quad_push = 0;
+        if (s.width == 4 && (rc = quads_upload(c, lb.nodes, (size_t)lb.nnodes, lb.root_ref, s, nnodes, quad_root, quad_push)))
+            return rc;
+        HIPCHK(c, hipEventRecord(ev(c, E_QUAD), c->stream));
+        for (int k = 0; k < 3; k++) { s.root_mn[k] = lb.root_mn[k]; s.root_mx[k] = lb.root_mx[k]; }
+        s.root_ref = s.width == 4 ? (lb.root_ref < 0 ? lb.root_ref : quad_root) : lb.root_ref;
+        s.depth = s.width == 4 ? quad_push : c->pair_depth;
+    }
+    s.cull_ok = c->cull_ok ? 1 : 0;
+    if ((rc = occ_state(c, s, nnodes, g.ms + 3))) return rc;
+    HIPCHK(c, hipEventRecord(ev(c, E_END), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipEventElapsedTime(&g.ms[0], ev(c, E_START), ev(c, E_REC)));
+    HIPCHK(c, hipEventElapsedTime(&g.ms[1], ev(c, E_REC), ev(c, E_TREE)));
+    HIPCHK(c, hipEventElapsedTime(&g.ms[2], ev(c, E_TREE), ev(c, E_QUAD)));
+    HIPCHK(c, hipEventElapsedTime(&g.ms[6], ev(c, E_START), ev(c, E_END)));
+    // the film sees an update as it sees a re-upload
+    c->scene = s;
+    c->scene_gen++;   // the primary-hit table and the guides are stale
+    c->tp.ok = false;  // no motion vectors for moved geometry: the temporal history goes
+    c->film_stale = true;
+    c->has_scene = true;
+    return MCPT_OK;
+}
+
+int mcpt_scene_update_geometry(mcpt_ctx* c, int32_t ntri, const float* v0, const float* v1, const float* v2,
+                               const float* n0, const float* n1, const float* n2, int32_t mode) {
+    int rc = geometry_check(c, ntri, v0, v1, v2, n0, n1, n2, mode);
+    if (rc || ntri == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t m = 3 * (size_t)ntri;
+    const float* src[6] = {v0, v1, v2, n0, n1, n2};
+    const int arrays = n0 ? 6 : 3;
+    if (!c->gu.stage.ensure(arrays * m)) return set_err(c, MCPT_E_NOMEM, "hipMalloc: geometry staging");
+    float* st = c->gu.stage;
+    for (int k = 0; k < arrays; k++) HIPCHK(c, hipMemcpy(st + k * m, src[k], m * sizeof(float), hipMemcpyHostToDevice));
+    return geometry_update_device(c, ntri, st, st + m, st + 2 * m, n0 ? st + 3 * m : nullptr, n0 ? st + 4 * m : nullptr,
+                                  n0 ? st + 5 * m : nullptr, mode);
+}
+int mcpt_scene_update_geometry_device(mcpt_ctx* c, int32_t ntri, const void* d_v0, const void* d_v1, const void* d_v2,
+                                      const void* d_n0, const void* d_n1, const void* d_n2, int32_t mode) {
+    int rc = geometry_check(c, ntri, d_v0, d_v1, d_v2, d_n0, d_n1, d_n2, mode);
+    if (rc) return rc;
+    return geometry_update_device(c, ntri, (const float*)d_v0, (const float*)d_v1, (const float*)d_v2, (const float*)d_n0,
+                                  (const float*)d_n1, (const float*)d_n2, mode);
+}
+int mcpt_debug_geometry_update_ms(const mcpt_ctx* c, float* out8) {
+    if (!c || !out8) return MCPT_E_INVALID;
+    for (int k = 0; k < 8; k++) out8[k] = c->gu.ms[k];
     return MCPT_OK;
 }
 float mcpt_debug_last_build_ms(const mcpt_ctx* c) { return c ? c->last_build_ms : -1.f; }

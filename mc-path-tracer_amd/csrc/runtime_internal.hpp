@@ -173,6 +173,33 @@ struct VarianceFill {
     mcpt_variance_params p{};
 };
 
+// Geometry update (mcpt_scene_update_geometry).  The upload-time environment
+// knobs as the last upload read them (an update never calls getenv), the upload's device arrays an
+// update writes or reuses (all owned by scene_bufs, so a re-upload frees them; nullptr: none), and
+// the update's own scratch, kept between updates.
+struct GeomUpdate {
+    // MCPT_CULL=0, MCPT_CULL_PLANE, MCPT_BVH_WIDTH (0: by tree size), MCPT_OCC_G / _B, MCPT_OCC_COMPLETE, MCPT_OCC_PREFILL
+    bool cull_off = false, plane = true;
+    int width = 0, occ_g = 24, occ_b = 12;
+    bool occ_complete = true, occ_prefill = true;
+    bool gpu_upload = false;              // uploaded by mcpt_scene_upload_gpu_bvh
+    float4* bvh_nodes = nullptr;          // the device builder's node array (also when it holds no node)
+    uint32_t* order = nullptr;            // record p holds desc triangle order[p] (nullptr: identity)
+    float4 *desc_tri = nullptr, *desc_sh = nullptr;  // records in desc order (device-built scenes: the builders' input)
+    float4* quads = nullptr;              // the 4-wide nodes (DevScene::nodes of a width-4 scene)
+    uint32_t* quad_src = nullptr;         // per 4-wide slot the (pair node, child) it copies (kQuadNoSrc: empty)
+    uint32_t nquads = 0;
+    float4* occ_rec = nullptr;            // DevScene::occ_rec
+    float4* occ_dir = nullptr;            // the complete keys' direction-bin table
+    DevBuf<float> stage;                  // the host entry's vertex (and normal) arrays
+    DevBuf<float4> box;                   // per record its vertex box
+    DevBuf<float> tri_w, out;             // per record W'_T; {root box, root margin, P bits}
+    float ms[8] = {};                     // mcpt_debug_geometry_update_ms
+    void forget() {  // the arrays went with scene_bufs
+        order = nullptr, bvh_nodes = desc_tri = desc_sh = quads = occ_rec = occ_dir = nullptr, quad_src = nullptr, nquads = 0;
+    }
+};
+
 struct mcpt_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -204,6 +231,7 @@ struct mcpt_ctx {
     uint32_t pair_count = 0;
     int pair_root = 0, ploc_rounds = 0;
     bool pair_gpu_built = false;
+    GeomUpdate gu;  // what mcpt_scene_update_geometry needs of the last upload
     // mcpt_set_skip_discarded: paths the next logic pass is certain to end make no extension ray
     // (ShadeArgs::skip); results and ray counts are the same either way
     bool skip_discarded = true;

@@ -220,6 +220,9 @@ ABI = {
     "mcpt_debug_discard_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mcpt_scene_upload_gpu_bvh": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mcpt_set_gpu_bvh_builder": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mcpt_scene_update_geometry": (C.c_int, [C.c_void_p, C.c_int32, _f, _f, _f, _f, _f, _f, C.c_int32]),
+    "mcpt_scene_update_geometry_device": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32]),
+    "mcpt_debug_geometry_update_ms": (C.c_int, [C.c_void_p, _f]),
     "mcpt_film_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "mcpt_film_write_png": (C.c_int, [C.c_void_p, C.c_float, C.c_char_p]),
     "mcpt_film_write_pfm": (C.c_int, [C.c_void_p, C.c_char_p]),
@@ -291,6 +294,7 @@ BVH_REFERENCE, BVH_SAH3 = 0, 1
 FLAG_FIXED = 1  # MCPT_FLAG_FIXED: quality-mode integrator
 FLAG_NO_AUTO_CLEAR = 2  # MCPT_FLAG_NO_AUTO_CLEAR: camera / scene changes do not clear the film
 ENV_DEVICE_TABLES = 1  # MCPT_ENV_DEVICE_TABLES: HRDI tables built on the device at upload
+GEOM_MODES = {"refit": 0, "rebuild": 1}  # MCPT_GEOM_REFIT / MCPT_GEOM_REBUILD
 
 
 def default_config(spp=16, max_depth=5, rr_depth=3, seed=0x5EED2026, tile=256, fixed=False,
@@ -455,6 +459,7 @@ class PathTracer:
         h = C.c_void_p()
         _check(lib().mcpt_create(device, C.byref(self.cfg), C.byref(h)))
         self.h = h
+        self.device = device
         self.W = self.H = 0
 
     def close(self):
@@ -489,6 +494,47 @@ class PathTracer:
             self._ck(lib().mcpt_scene_upload_gpu_bvh(self.h, C.byref(d)))
         else:
             self._ck(lib().mcpt_scene_upload(self.h, C.byref(d)))
+
+    def update_geometry(self, v0, v1, v2, n0=None, n1=None, n2=None, mode="refit"):
+        """New vertex positions (and normals: all three or none) for the uploaded scene's triangles, in
+        the order of the uploaded desc's arrays (mcpt_scene_update_geometry).  mode "refit" keeps the
+        tree's topology; "rebuild" (device-built scenes) runs the GPU builder again.  numpy arrays go
+        through the host entry; torch tensors on the context's device go to the _device entry as they
+        are (float32, contiguous).  The film goes stale, as after a re-upload."""
+        if mode not in GEOM_MODES:
+            raise ValueError(f"unknown geometry update mode {mode!r}")
+        arrs = [v0, v1, v2, n0, n1, n2]
+        if all(hasattr(a, "data_ptr") for a in arrs if a is not None) and v0 is not None:
+            import torch
+
+            keep = []
+            for a in arrs:
+                if a is not None:
+                    if not a.is_cuda or a.dtype != torch.float32:
+                        raise ValueError("device arrays must be float32 tensors on the GPU")
+                    if a.device.index != self.device:
+                        raise ValueError(f"device arrays must be on the context's GPU {self.device}, not {a.device}")
+                    a = a.contiguous()
+                keep.append(a)
+            n = keep[0].numel() // 3
+            if any(a is not None and a.numel() != 3 * n for a in keep):
+                raise ValueError("vertex arrays differ in size")
+            torch.cuda.synchronize(keep[0].device)  # the tensors are complete before the context's stream reads them
+            ptrs = [C.c_void_p(a.data_ptr()) if a is not None and a.numel() else None for a in keep]
+            self._ck(lib().mcpt_scene_update_geometry_device(self.h, n, *ptrs, GEOM_MODES[mode]))
+            return
+        keep = [None if a is None else np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in arrs]
+        n = len(keep[0])
+        if any(a is not None and len(a) != n for a in keep):
+            raise ValueError("vertex arrays differ in size")
+        self._ck(lib().mcpt_scene_update_geometry(self.h, n, *[None if a is None else fptr(a) for a in keep],
+                                                  GEOM_MODES[mode]))
+
+    def geometry_update_ms(self) -> dict:
+        """Device times of the last update_geometry() in ms (mcpt_debug_geometry_update_ms)."""
+        v = (C.c_float * 8)()
+        self._ck(lib().mcpt_debug_geometry_update_ms(self.h, v))
+        return dict(zip(("records", "tree", "quads", "occ_records", "prefill", "complete_keys", "total"), [float(x) for x in v[:7]]))
 
     def ray_counts(self) -> dict:
         """Ray counts since the last film clear (mcpt_debug_ray_counts)."""
