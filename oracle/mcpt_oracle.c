@@ -572,6 +572,21 @@ void or_brdf_eval(const float *params, const float *n, const float *wi, const fl
     out[6] = spec_get_pdf(&m, N, WI, WO);
     out[7] = diff_get_pdf();
 }
+/* One lobe draw at the vertex (seed, pixel, sample, len): spec_get_wi (spec != 0) or diff_get_wi
+ * with its draws at slot0.. (e0, e1, then gram_schmidt's three); fixed != 0: the quality mode's
+ * orthonormal frame in place of the reference's gram_schmidt quirk. */
+void or_brdf_sample(const float *params, const float *n, const float *wo, uint64_t seed, uint32_t pixel,
+                    uint32_t sample, uint32_t len, uint32_t slot0, int spec, float *out_wi, int fixed) {
+    mat_t m;
+    m.base = V(params[0], params[1], params[2]);
+    m.fresnel = V(params[3], params[4], params[5]);
+    m.rough = fmx(params[6], BRDF_EPS);
+    m.metal = params[7];
+    rng_t r = {rng_key(seed, pixel, sample), len};
+    v3 N = V(n[0], n[1], n[2]), WO = V(wo[0], wo[1], wo[2]);
+    v3 wi = spec ? spec_get_wi(&m, N, WO, &r, slot0, fixed) : diff_get_wi(N, &r, slot0, fixed);
+    out_wi[0] = wi.x; out_wi[1] = wi.y; out_wi[2] = wi.z;
+}
 
 /* ------------------------------------------------------------------------- */
 /* Geometry: Triangle.cu:9-117, Bounds3f.h:121-153, Triangle.cu:144-243.     */

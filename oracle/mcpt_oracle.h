@@ -109,6 +109,10 @@ void or_env_dir(const or_scene *sc, float ex, float ey, float *wi);
 /* BRDF hooks: params = base rgb, fresnel rgb, roughness, metallic.
  * out: f_spec rgb, f_diff rgb, pdf_spec, pdf_diff. */
 void or_brdf_eval(const float *params, const float *n, const float *wi, const float *wo, float *out);
+/* One lobe sample: spec_get_wi (spec != 0) or diff_get_wi at the vertex (seed, pixel, sample, len),
+ * draws from slot0 on; fixed != 0: quality mode (orthonormal sampling frame). */
+void or_brdf_sample(const float *params, const float *n, const float *wo, uint64_t seed, uint32_t pixel,
+                    uint32_t sample, uint32_t len, uint32_t slot0, int spec, float *out_wi, int fixed);
 float or_power_heuristic(float f, float g);
 int32_t or_upper_bound(const float *list, int32_t size, float val);
 /* Per-stage restatements at the product's shading-stage boundary (include/mcpt.h mcpt_path_view;

@@ -64,6 +64,8 @@ def lib():
             "or_env_pdf": (C.c_float, [C.POINTER(OrScene), C.c_float, C.c_float, C.c_float]),
             "or_env_dir": (None, [C.POINTER(OrScene), C.c_float, C.c_float, _f]),
             "or_brdf_eval": (None, [_f, _f, _f, _f, _f]),
+            "or_brdf_sample": (None, [_f, _f, _f, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                      _f, C.c_int]),
             "or_power_heuristic": (C.c_float, [C.c_float, C.c_float]),
             "or_upper_bound": (C.c_int32, [_f, C.c_int32, C.c_float]),
             "or_gen_ray": (None, [C.POINTER(OrCamera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64,
@@ -317,6 +319,16 @@ def env_build(tex: np.ndarray):
     den = np.zeros(1, np.float32)
     lib().or_env_build(W, H, fptr(tex), fptr(my), fptr(mp), fptr(cy), fptr(pdf), fptr(den))
     return {"marginal_y": my, "marginal_p": mp, "conds_y": cy, "pdf": pdf, "denom": float(den[0])}
+
+
+def brdf_sample(params, n, wo, seed, pixel, sample, ln, slot0, spec, fixed=False):
+    """or_brdf_sample: the oracle's spec_get_wi (spec) or diff_get_wi direction at the vertex
+    (seed, pixel, sample, ln), draws from slot0 on; fixed: the quality mode's orthonormal frame."""
+    p, n, wo = (np.ascontiguousarray(v, np.float32) for v in (params, n, wo))
+    out = np.zeros(3, np.float32)
+    lib().or_brdf_sample(fptr(p), fptr(n), fptr(wo), int(seed), int(pixel), int(sample), int(ln), int(slot0),
+                         int(bool(spec)), fptr(out), int(bool(fixed)))
+    return out
 
 
 def _stage_cfg(spp, max_depth, rr_depth, seed, fixed):

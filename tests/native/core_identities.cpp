@@ -7,7 +7,9 @@
 //   fp32 replacement of the reference's fp64 island);
 //   quot_fp64(a, y) == a / b whenever it reports success, for y = 1/b off by up to 8 ulp of
 //   fp64 (the device's Newton-refined reciprocal is within ~1 ulp), over the full exponent
-//   range including overflow to inf and quotients at the subnormal boundary.
+//   range including overflow to inf and quotients at the subnormal boundary;
+//   brdf_sample_wi == spec_get_wi / diff_get_wi and brdf_f_pdf == (brdf_f, brdf_pdf) over glossy
+//   and metallic materials (merged_brdf_identities).
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -21,6 +23,110 @@
 using namespace mcpt;
 
 static uint32_t bits(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
+
+// k_material's lobe-merged brdf_sample_wi and shared-term brdf_f_pdf against the separate
+// functions the oracle restates (spec_get_wi / diff_get_wi, brdf_f / brdf_pdf): bit for bit, NaN
+// for NaN, over the 19 materials of tests/material_fixtures.py's PALETTE (restated below) and,
+// per material, random unit (n, wo, wi) with random RNG keys, wo grazing the surface, wo below
+// it (the n.wo clamps), wi == -wo (the half vector is normalize(0) == 0) and axis-aligned n
+// (gram_schmidt's divide by zero: NaN frames).  The sampler in both FIXED instantiations.
+struct BrdfCase { V3 n, wo, wi; Rng r; uint32_t s0; };
+
+static int brdf_reports = 0;  // mismatches printed, over all materials
+static bool same_f(float a, float b) { return bits(a) == bits(b) || (a != a && b != b); }
+static bool same_v(V3 a, V3 b) { return same_f(a.x, b.x) && same_f(a.y, b.y) && same_f(a.z, b.z); }
+
+template <bool FIXED>
+static long sampler_identity(const Mat& m, int row, const std::vector<BrdfCase>& cases, long& nan_dirs) {
+    long bad = 0;
+    for (const BrdfCase& c : cases) {
+        V3 ms = brdf_sample_wi<FIXED>(m, c.n, c.wo, c.r, c.s0, true), ss = spec_get_wi<FIXED>(m, c.n, c.wo, c.r, c.s0);
+        V3 md = brdf_sample_wi<FIXED>(m, c.n, c.wo, c.r, c.s0, false), sd = diff_get_wi<FIXED>(c.n, c.r, c.s0);
+        nan_dirs += (ss.x != ss.x) + (sd.x != sd.x);
+        if ((!same_v(ms, ss) || !same_v(md, sd)) && ++bad && brdf_reports++ < 8)
+            std::printf("brdf_sample_wi<%d> row %d key %u len %u: spec %a %a %a vs %a %a %a, diff %a %a %a vs %a %a %a\n",
+                        (int)FIXED, row, c.r.key, c.r.len, ms.x, ms.y, ms.z, ss.x, ss.y, ss.z, md.x, md.y, md.z, sd.x,
+                        sd.y, sd.z);
+    }
+    return bad;
+}
+
+static long merged_brdf_identities() {
+    std::vector<std::vector<float>> palette;
+    for (float r : {1.0f, 0.73f, 0.37f, 0.11f, 0.01f})
+        for (float m : {0.0f, 0.37f, 1.0f}) palette.push_back({0.8f, 0.6f, 0.2f, 0.04f, 0.04f, 0.04f, r, m});
+    palette.push_back({0.f, 0.f, 0.f, 0.04f, 0.5f, 0.9f, 0.3f, 0.f});
+    palette.push_back({0.9f, 0.f, 0.4f, 0.f, 0.f, 0.f, 0.3f, 1.f});
+    palette.push_back({0.5f, 0.5f, 0.5f, 0.04f, 0.04f, 0.04f, 0.0f, 0.f});
+    palette.push_back({0.5f, 0.5f, 0.5f, 0.04f, 0.04f, 0.04f, 1.5f, 0.3f});
+
+    std::mt19937_64 g(19);
+    std::normal_distribution<float> N(0.f, 1.f);
+    std::uniform_real_distribution<float> U(0.f, 1.f);
+    auto unit = [&]() {
+        V3 v;
+        do v = v3(N(g), N(g), N(g)); while (dot(v, v) < 1e-6f);
+        return normalize(v);
+    };
+    auto tangent = [&](V3 n) {  // a unit vector orthogonal to n
+        V3 t;
+        do t = cross(n, unit()); while (dot(t, t) < 1e-4f);
+        return normalize(t);
+    };
+    auto rng = [&]() { return Rng{(uint32_t)g(), 1u + (uint32_t)(g() % 5)}; };
+    auto slot = [&]() { return (g() & 1) ? (uint32_t)SL_MAT_E0 : (uint32_t)SL_CONT_E0; };
+    std::vector<BrdfCase> cases;
+    for (int i = 0; i < 100000; i++) cases.push_back({unit(), unit(), unit(), rng(), slot()});
+    for (int i = 0; i < 4000; i++) {  // grazing wo: |n.wo| up to 0.03, both signs, and exactly in the plane
+        V3 n = unit(), t = tangent(n);
+        float d = (i % 8 == 0) ? 0.f : (U(g) * 2.f - 1.f) * 0.03f;
+        cases.push_back({n, normalize(t + n * d), unit(), rng(), slot()});
+    }
+    for (int i = 0; i < 4000; i++) {  // wo below the surface; wi above, below or along it
+        V3 n = unit(), wo = unit();
+        if (dot(n, wo) > 0.f) wo = -wo;
+        V3 wi = (i % 3 == 0) ? reflect(-wo, n) : unit();
+        cases.push_back({n, wo, wi, rng(), slot()});
+    }
+    for (int i = 0; i < 4000; i++) {  // wi == -wo
+        V3 wo = unit();
+        cases.push_back({unit(), wo, -wo, rng(), slot()});
+    }
+    for (int i = 0; i < 4000; i++) {  // axis-aligned n (either sign), wo on its side / grazing / below
+        V3 n = v3(0.f, 0.f, 0.f);
+        float s = (g() & 1) ? 1.f : -1.f;
+        int ax = (int)(g() % 3);
+        (ax == 0 ? n.x : ax == 1 ? n.y : n.z) = s;
+        V3 wo = unit();
+        if (i % 4 != 3 && dot(n, wo) < 0.f) wo = -wo;
+        if (i % 4 == 2) wo = normalize(tangent(n) + n * (U(g) * 0.02f));
+        cases.push_back({n, wo, unit(), rng(), slot()});
+    }
+
+    long bad = 0, nan_dirs = 0, nan_f = 0, clamped = 0;
+    for (size_t row = 0; row < palette.size(); row++) {
+        const Mat m = load_mat(palette[row].data());
+        bad += sampler_identity<false>(m, (int)row, cases, nan_dirs);
+        bad += sampler_identity<true>(m, (int)row, cases, nan_dirs);
+        for (const BrdfCase& c : cases) {
+            V3 f;
+            float pdf;
+            brdf_f_pdf(m, c.n, c.wi, c.wo, f, pdf);
+            V3 f1 = brdf_f(m, c.n, c.wi, c.wo);
+            float pdf1 = brdf_pdf(m, c.n, c.wi, c.wo);
+            nan_f += (f1.x != f1.x) + (pdf1 != pdf1);
+            clamped += dot(c.n, c.wo) < BRDF_EPS;
+            if ((!same_v(f, f1) || !same_f(pdf, pdf1)) && ++bad && brdf_reports++ < 8)
+                std::printf("brdf_f_pdf row %zu: f %a %a %a vs %a %a %a, pdf %a vs %a\n", row, f.x, f.y, f.z, f1.x, f1.y,
+                            f1.z, pdf, pdf1);
+        }
+    }
+    std::printf("merged brdf identities: %zu materials x %zu inputs; NaN sample directions %ld, NaN f / pdf %ld, "
+                "n.wo clamped %ld\n", palette.size(), cases.size(), nan_dirs, nan_f, clamped);
+    // the NaN-frame and clamp cases must really occur, or the inputs above lost their point
+    if (palette.size() != 19 || nan_dirs == 0 || clamped < 19 * 4000) { std::printf("brdf inputs ineffective\n"); bad++; }
+    return bad;
+}
 
 int main() {
     std::mt19937_64 g(7);
@@ -184,6 +290,7 @@ int main() {
         if ((ploc_count(m) != nmax || ploc_height(m) != 41u) && bad++ < 5)
             std::printf("ploc_merge: %u %u\n", ploc_height(m), ploc_count(m));
     }
+    bad += merged_brdf_identities();
     std::printf("bad=%ld\n", bad);
     return bad != 0;
 }

@@ -6,7 +6,8 @@ Scenes (SCENES: fixture suffix -> BASELINE config): sphere.glb + HDR_029 (config
 proxy (Cornell-style room, spheres of several materials, night_free_Env.hdr), each plus one
 directional light, so the light choice picks the env light (HRDI sampling) or the delta light
 about half the time each.  Config 2's walls give axis-aligned normals (Appendix A's gram_schmidt
-quirk) and its rays start inside the room."""
+quirk) and its rays start inside the room.  "c2pal" is config 2's scene wearing
+material_fixtures.PALETTE (glossy and metallic materials), with a material-stage vector only."""
 import numpy as np
 
 SPP, DEPTH, RR = 16, 5, 3
@@ -14,7 +15,8 @@ FILM = (17, 17)  # 289 paths, 256 processed (the last row / column never are: :1
 N_MAT = 256
 
 
-SCENES = {"c1dir": 1, "c2": 2}
+SCENES = {"c1dir": 1, "c2": 2, "c2pal": 2}
+PALETTE_SCENES = ("c2pal",)  # material stage only, wearing material_fixtures.PALETTE
 
 
 def stage_scene(mcpt, cid=1):
@@ -29,15 +31,15 @@ def stage_camera(mcpt, cid=1):
     return mcpt.config_camera(mcpt.CONFIGS[cid], *FILM)
 
 
-def material_state(a, trace_closest, cid=1):
-    """256 continuing paths at their closest hits (hit_tri = index into the scene arrays), len 1..5,
+def material_state(a, trace_closest, cid=1, n=N_MAT):
+    """n (256) continuing paths at their closest hits (hit_tri = index into the scene arrays), len 1..5,
     random sample indices and throughputs.  Config 1: rays from a shell aimed into the unit sphere;
     config 2: rays from points inside the room (0.8 of its box) in random directions."""
     rng = np.random.default_rng(2026)
     ro_l, rd_l, tri_l = [], [], []
     inv = np.argsort(a["tri_id"])  # scene triangle id -> array index
     mn, mx = np.asarray(a["bmin"][0], np.float64), np.asarray(a["bmax"][0], np.float64)
-    while sum(len(t) for t in tri_l) < N_MAT:
+    while sum(len(t) for t in tri_l) < n:
         if cid == 1:
             o = rng.normal(size=(512, 3))
             o = (o / np.linalg.norm(o, axis=1, keepdims=True) * rng.uniform(1.5, 4.0, (512, 1))).astype(np.float32)
@@ -51,13 +53,13 @@ def material_state(a, trace_closest, cid=1):
         _, _, tri = trace_closest(a, o, d)
         k = tri >= 0
         ro_l.append(o[k]), rd_l.append(d[k]), tri_l.append(inv[tri[k]])
-    ro = np.concatenate(ro_l)[:N_MAT]
-    rd = np.concatenate(rd_l)[:N_MAT]
-    tri = np.concatenate(tri_l)[:N_MAT].astype(np.int32)
-    ln = rng.integers(1, DEPTH + 1, N_MAT).astype(np.uint32)
-    sidx = rng.integers(0, SPP, N_MAT).astype(np.uint32)
-    beta = np.zeros((N_MAT, 4), np.float32)
-    beta[:, :3] = rng.uniform(0.05, 1.0, (N_MAT, 3))
+    ro = np.concatenate(ro_l)[:n]
+    rd = np.concatenate(rd_l)[:n]
+    tri = np.concatenate(tri_l)[:n].astype(np.int32)
+    ln = rng.integers(1, DEPTH + 1, n).astype(np.uint32)
+    sidx = rng.integers(0, SPP, n).astype(np.uint32)
+    beta = np.zeros((n, 4), np.float32)
+    beta[:, :3] = rng.uniform(0.05, 1.0, (n, 3))
     return {"flags": (ln << 1) | (sidx << 13), "hit_tri": tri, "ray_o": ro, "ray_d": rd, "beta": beta}
 
 

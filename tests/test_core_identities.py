@@ -1,5 +1,6 @@
 """Host build of the shared numeric core: the exactness identities the GPU fast paths rely on
-(dsincos == dsin/dcos, the cheap texel wrap, guided CDF search == upper_bound)."""
+(dsincos == dsin/dcos, the cheap texel wrap, guided CDF search == upper_bound, k_material's merged
+BRDF functions == the separate ones over glossy and metallic materials)."""
 import os
 import subprocess
 

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from stage_checks import _check_stage, _same
 
 pytestmark = pytest.mark.gpu
 RTOL = 1e-4
@@ -1122,25 +1123,19 @@ def test_env_device_tables_same_film(mcpt_mod, scene_c2):
     assert np.array_equal(s0, s1) and np.array_equal(L0.view(np.uint32), L1.view(np.uint32))
 
 
-def _same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    if a.dtype.kind == "f":
-        return bool(np.array_equal(a.view(np.uint32), b.view(np.uint32)) or
-                    np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(a[~np.isnan(a)], b[~np.isnan(b)]))
-    return bool(np.array_equal(a, b))
-
-
-@pytest.mark.parametrize("scene", ["c1dir", "c2"])
-@pytest.mark.parametrize("stage", ["logic", "generate", "material"])
+@pytest.mark.parametrize("stage,scene", [(st, sc) for sc in ("c1dir", "c2") for st in ("logic", "generate", "material")]
+                         + [("material", "c2pal")])
 def test_stage_golden_vectors(mcpt_mod, oracle, stage, scene):
     """Per-stage golden vectors: mcpt_stage_run runs the product's
     k_shade (LOGIC / GENERATE: wf_logic + wf_generate, wavefront_kernels.cu:90-251) or k_material
     (MATERIAL: light choice + wf_mat_mix, :207-213, 295-375) on the fixture's path state; every
     output field equals the oracle's stage restatement (tools/make_golden.py) bit for bit, on two
-    fixture scenes (config 1's sphere, config 2's room; stage_fixtures.SCENES).  Rays the kernels
-    resolve in place because they cannot hit the scene are checked against the oracle's traversal
-    instead of a queue entry."""
+    fixture scenes (config 1's sphere, config 2's room; stage_fixtures.SCENES), and for the material
+    stage on config 2's room wearing the glossy / metallic palette (c2pal; material_fixtures.PALETTE).
+    Rays the kernels resolve in place because they cannot hit the scene are checked against the
+    oracle's traversal instead of a queue entry."""
     import stage_fixtures as sf
+    from material_fixtures import with_palette
 
     cid = sf.SCENES[scene]
     g = np.load(os.path.join(GOLDEN, f"stage_{stage}_{scene}.npz"))
@@ -1148,6 +1143,9 @@ def test_stage_golden_vectors(mcpt_mod, oracle, stage, scene):
     ref = {k[4:]: g[k] for k in g.files if k.startswith("out_")}
     s = sf.stage_scene(mcpt_mod, cid)
     a = s.arrays()
+    if scene in sf.PALETTE_SCENES:
+        a = with_palette(a)
+        s = mcpt_mod.desc_from_arrays(a)
     pt = mcpt_mod.PathTracer(0, mcpt_mod.default_config(spp=sf.SPP, max_depth=sf.DEPTH, rr_depth=sf.RR))
     pt.upload_scene(s)
     pt.set_camera(sf.stage_camera(mcpt_mod, cid))
@@ -1180,43 +1178,6 @@ def test_stage_logic_rejects_inconsistent_sample_index(mcpt_mod):
     dead = (got["flags"] & 1) == 1
     assert dead.any() and np.all(got["flags"][dead] == 1)
     pt.close()
-
-
-def _check_stage(stage, got, ref, a, oracle):
-    """mcpt_stage_run outputs against the oracle's stage restatement, field by field, bit for bit."""
-    if stage in ("logic", "generate"):
-        for k in ("flags", "samples", "Ld"):
-            assert _same(got[k], ref[k]), k
-        cont = (ref["queued"] & 2) > 0
-        assert np.array_equal((got["queued"] & 2) > 0, cont)
-        assert _same(got["beta"][cont, :3], ref["beta"][cont, :3])
-        gen = (ref["queued"] & 1) > 0
-        assert gen.sum() > 50 and (stage == "generate" or cont.sum() > 50)
-        assert _same(got["ray_o"][gen], ref["ray_o"][gen]) and _same(got["ray_d"][gen], ref["ray_d"][gen])
-        queued = (got["queued"] & 1) > 0
-        assert not queued[~gen].any()
-        resolved = gen & ~queued  # camera rays missing the scene: resolved in place, never queued
-        assert np.all(got["hit_tri"][resolved] == -1)
-        if resolved.any():
-            assert np.all(oracle.trace_closest(a, ref["ray_o"][resolved], ref["ray_d"][resolved])[2] == -1)
-    else:
-        for k in ("flags", "ray_o", "ray_d", "beta", "nee0", "nee1"):
-            assert _same(got[k], ref[k]), k
-        q = got["queued"]
-        ext_resolved = (q & 1) == 0
-        if ext_resolved.any():
-            assert np.all(got["hit_tri"][ext_resolved] == -1)
-            assert np.all(oracle.trace_closest(a, ref["ray_o"][ext_resolved], ref["ray_d"][ext_resolved])[2] == -1)
-        for bit, vk, o_k, d_k in ((4, 0, "light_o", "light_d"), (8, 1, "bvis_o", "bvis_d")):
-            drawn = ~np.isnan(ref[o_k][:, 0])
-            qd = (q & bit) > 0
-            assert not qd[~drawn].any()
-            assert _same(got[o_k][qd], ref[o_k][qd]) and _same(got[d_k][qd], ref[d_k][qd])
-            res = drawn & ~qd  # resolved in place: visible
-            assert np.all(got["vis"][res, vk] == 1)
-            if res.any():
-                assert np.all(oracle.trace_any(a, ref[o_k][res], ref[d_k][res]) == 1)
-        assert (q & 4).sum() > 50 and (q & 8).sum() > 20 and np.isnan(ref["bvis_o"][:, 0]).sum() > 50
 
 
 @pytest.mark.parametrize("stage", ["logic", "generate", "material"])

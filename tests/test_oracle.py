@@ -139,6 +139,75 @@ def test_brdf_matches_readme(oracle, rough, metal):
         np.testing.assert_allclose(out[7], pd, rtol=1e-6)
 
 
+SAMPLING_DEV_SPEC = 4.51e-5  # measured on the unmodified oracle: see test_lobe_sampling_matches_formulas
+SAMPLING_DEV_DIFF = 2.93e-6
+
+
+def test_lobe_sampling_matches_formulas(oracle):
+    """The oracle's lobe sampling over material_fixtures.PALETTE, 2000 draws per row with random unit
+    n, wo (n.wo > 0) and random RNG keys.  Spec lobe (dMaterial.cu:278-307): the half vector of the
+    returned direction, h = normalize(wo + wi), is the sampled microfacet normal up to sign, so n.h
+    must equal cos(theta_h) = sqrt((1 - e0) / (e0 (a2 - 1) + 1)), recomputed here in float64 from the
+    same draw e0 = or_rand(slot) and a2 = max(roughness, eps)^4.  The sign: wo + wi = 2 (m.wo) m, so
+    h = m whenever the facet normal m faces wo, which theta_h + theta_wo < 90 degrees guarantees; for
+    those draws n.h itself is compared, for the rest |n.h| (h = -m is then legitimate).  Diffuse lobe
+    (dMaterial.cu:232-254): n.wi == e0.
+
+    The identity holds for an orthonormal sampling frame, i.e. with the quality mode's gram_schmidt;
+    the reference's component-wise divide (Vector.h:1128-1139, kept in reference mode) returns a
+    tangent that is not orthogonal to n, and n.h then differs from cos(theta_h) by up to ~0.8 (n.wi
+    from e0 by up to ~1.4) whatever the roughness -- measured with this test's draws -- so the
+    reference frame would make the bound vacuous.  The e0 -> theta_h arithmetic under test is the
+    same code in both modes; reference-mode directions are pinned bit for bit by the c2pal golden
+    vector and the device parity tests.
+
+    Tolerance: 8 x the largest deviation of the unmodified oracle from the float64 formula over
+    these draws (fp32 acos / sincos / normalize noise, growing as cos(theta_h) -> 1 at roughness
+    0.01): measured 4.505e-5 (spec, SAMPLING_DEV_SPEC) and 2.929e-6 (diffuse, SAMPLING_DEV_DIFF).  A formula error (a2 = r^2, 1 + e0,
+    a missing sqrt) moves n.h by 1e-2 and more.  Draws with |wo + wi| < 1e-3 are left out; at most
+    2 % may be."""
+    from material_fixtures import PALETTE
+
+    rng = np.random.default_rng(5)
+    seed = 0x5EED2026
+    eps = np.float64(np.float32(1e-5))
+    dev_s = dev_d = 0.0
+    left_out = signed = total = 0
+    for p in PALETTE:
+        a2 = max(np.float64(p[6]), eps) ** 4
+        for _ in range(2000):
+            n = rng.normal(size=3)
+            n = (n / np.linalg.norm(n)).astype(np.float32)
+            wo = rng.normal(size=3)
+            wo = (wo / np.linalg.norm(wo)).astype(np.float32)
+            if n @ wo < 0:
+                wo = -wo
+            px, sm, ln = int(rng.integers(0, 2**31)), int(rng.integers(0, 256)), int(rng.integers(1, 6))
+            slot = (5, 11)[int(rng.integers(0, 2))]  # SL_MAT_E0 / SL_CONT_E0
+            e0 = np.float64(oracle.lib().or_rand(seed, px, sm, ln, slot))
+            n64, wo64 = n.astype(np.float64), wo.astype(np.float64)
+            total += 1
+            wd = oracle.brdf_sample(p, n, wo, seed, px, sm, ln, slot, False, fixed=True).astype(np.float64)
+            dev_d = max(dev_d, abs(n64 @ wd - e0))
+            wi = oracle.brdf_sample(p, n, wo, seed, px, sm, ln, slot, True, fixed=True).astype(np.float64)
+            s = wo64 + wi
+            if np.linalg.norm(s) < 1e-3:
+                left_out += 1
+                continue
+            ndh = n64 @ (s / np.linalg.norm(s))
+            c = np.sqrt((1.0 - e0) / (e0 * (a2 - 1.0) + 1.0))
+            if np.arccos(min(c, 1.0)) + np.arccos(min(n64 @ wo64, 1.0)) < np.pi / 2 - 1e-3:
+                signed += 1
+            else:
+                ndh = abs(ndh)
+            dev_s = max(dev_s, abs(ndh - c))
+    print(f"lobe sampling: max |n.h - cos(theta_h)| {dev_s:.3e}, max |n.wi - e0| {dev_d:.3e}; "
+          f"{signed} of {total} draws compared with their sign, {left_out} left out")
+    assert left_out <= 0.02 * total and signed > 0.3 * total
+    assert dev_s <= 8 * SAMPLING_DEV_SPEC
+    assert dev_d <= 8 * SAMPLING_DEV_DIFF
+
+
 def test_power_heuristic(oracle):
     ph = oracle.lib().or_power_heuristic
     assert ph(1.0, 1.0) == np.float32(0.5)
@@ -434,18 +503,22 @@ def test_literal_leaf_rule_deviation(mcpt_mod, oracle, scene_c1, scene_cube, sce
         assert n <= 0.01 * tot, (name, n, tot)
 
 
-@pytest.mark.parametrize("scene", ["c1dir", "c2"])
-@pytest.mark.parametrize("stage", ["logic", "generate", "material"])
+@pytest.mark.parametrize("stage,scene", [(st, sc) for sc in ("c1dir", "c2") for st in ("logic", "generate", "material")]
+                         + [("material", "c2pal")])
 def test_stage_golden_vectors_oracle(mcpt_mod, oracle, stage, scene):
     """The oracle's stage restatements (or_stage_logic / or_stage_material, sharing logic_core,
     mis_terms, pick_light and mat_mix_core with the full render) reproduce the committed per-stage
-    golden vectors bit for bit (regression pin; the GPU side is tests/test_gpu.py)."""
+    golden vectors bit for bit (regression pin; the GPU side is tests/test_gpu.py).  c2pal: config
+    2's room wearing material_fixtures.PALETTE, material stage only."""
     import stage_fixtures as sf
+    from material_fixtures import with_palette
 
     cid = sf.SCENES[scene]
     g = np.load(os.path.join(GOLDEN, f"stage_{stage}_{scene}.npz"))
     inp = {k[3:]: g[k] for k in g.files if k.startswith("in_")}
     a = sf.stage_scene(mcpt_mod, cid).arrays()
+    if scene in sf.PALETTE_SCENES:
+        a = with_palette(a)
     kw = dict(max_depth=sf.DEPTH, rr_depth=sf.RR)
     if stage == "material":
         out = oracle.stage_material(a, inp, **kw)

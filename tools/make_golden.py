@@ -16,6 +16,7 @@ sys.path[:0] = [os.path.join(REPO, "mc-path-tracer_amd"), os.path.join(REPO, "or
 import mcpt  # noqa: E402
 import oracle_py as op  # noqa: E402
 import stage_fixtures as sf  # noqa: E402
+from material_fixtures import with_palette  # noqa: E402
 
 OUT = os.environ.get("GOLDEN_OUT", os.path.join(REPO, "tests", "golden"))
 
@@ -68,15 +69,20 @@ def stage_vectors(suffix):
     """Per-stage golden vectors of one fixture scene
     (stage_fixtures.SCENES; round 6 added config 2's proxy): inputs from tests/stage_fixtures.py,
     outputs from the oracle's stage restatements, diffed field by field against mcpt_stage_run by
-    tests/test_gpu.py::test_stage_golden_vectors.  `python tools/make_golden.py --stages c2` writes
-    one scene's vectors only."""
+    tests/test_gpu.py::test_stage_golden_vectors.  A scene of stage_fixtures.PALETTE_SCENES wears
+    material_fixtures.PALETTE (glossy and metallic materials) and has a material vector only.
+    `python tools/make_golden.py --stages c2` writes one scene's vectors only."""
     cid = sf.SCENES[suffix]
     s = sf.stage_scene(mcpt, cid)
     a = s.arrays()
     cam = sf.stage_camera(mcpt, cid)
     W, H = sf.FILM
     kw = dict(max_depth=sf.DEPTH, rr_depth=sf.RR)
-    for name, st in (("logic", sf.logic_state(len(a["mat"]))), ("generate", sf.logic_state(len(a["mat"]), True))):
+    palette = suffix in sf.PALETTE_SCENES
+    if palette:
+        a = with_palette(a)
+    for name, st in (() if palette else (("logic", sf.logic_state(len(a["mat"]))),
+                                         ("generate", sf.logic_state(len(a["mat"]), True)))):
         out = op.stage_logic(a, cam, W, H, st, sf.SPP, **kw)
         np.savez_compressed(os.path.join(OUT, f"stage_{name}_{suffix}.npz"), **{"in_" + k: v for k, v in st.items()},
                             **{"out_" + k: v for k, v in out.items()})
