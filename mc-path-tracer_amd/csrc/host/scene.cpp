@@ -857,7 +857,7 @@ int Scene::build(const mcpt_bvh_params& prm, std::string& err) {
         int nbig = 0;
         if (bld.mode == 1) {
             const char* iso = std::getenv("MCPT_BVH_ISOLATE");
-            const char* pl = std::getenv("MCPT_CULL_PLANE");  // as runtime.cpp's margins
+            const char* pl = std::getenv("MCPT_CULL_PLANE");  // as scene_upload.cpp's margins
             const bool plane = !(pl && pl[0] == '0' && pl[1] == 0);
             if (!(iso && iso[0] == '0' && iso[1] == 0)) {
                 auto unbounded = [&](const PrimInfo& p) {

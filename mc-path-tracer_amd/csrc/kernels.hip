@@ -2653,7 +2653,7 @@ void launch_cull_margins(float4* nodes, uint32_t npairs, const float4* tri, uint
     for (int p = 0; p < passes; p++)
         hipLaunchKernelGGL(k_cull_pairs, dim3((npairs + 255) / 256), dim3(256), 0, s, nodes, npairs, tri_w, ntri);
 }
-// One probe ray per occluder-table key (the pre-fill at upload, runtime.cpp): from the centre of
+// One probe ray per occluder-table key (the pre-fill at upload, scene_upload.cpp): from the centre of
 // the key's origin cell along the centre of its direction bin, so that occ_index maps the probe back
 // to its own key.  Tracing the probes as any-hit rays records an occluder in every key whose probe
 // is occluded -- a property of the scene alone, like the BVH.

@@ -334,7 +334,7 @@ int mcpt_guides_render(mcpt_ctx* c, uint32_t nsamples) {
     ga.rd = rd;
     ga.hit_p = hp;
     ga.hit_n = hn;
-    ga.mats = c->scene.mats;
+    ga.mats = c->scene.dev.mats;
     ga.g_alb = g.alb;
     ga.g_nz = g.nz;
     if ((rc = span_begin(c))) return rc;
@@ -351,7 +351,7 @@ int mcpt_guides_render(mcpt_ctx* c, uint32_t nsamples) {
             launch_guide_rays(ga, c->stream);
             // closest hits as mcpt_stage_run(EXTEND) traces them: no occluder cache, unfiltered rays
             TraceArgs ta{};
-            ta.scene = c->scene;
+            ta.scene = c->scene.dev;
             ta.scene.occ = nullptr;
             ta.nshards = 1;
             TraceSet& ts = ta.set[0];
@@ -365,7 +365,7 @@ int mcpt_guides_render(mcpt_ctx* c, uint32_t nsamples) {
             launch_trace(ta, c->geom, c->stream);
             HIPCHK(c, hipMemcpyAsync(&c->cnt_host->grab[0][0], &c->cnt->grab[0][0], sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipMemsetAsync(c->cnt->grab, 0, sizeof(c->cnt->grab), c->stream));  // hand-out counters back to 0
-            HitRecordArgs ha{c->scene, ro, rd, ht, hp, hn, ht, n};
+            HitRecordArgs ha{c->scene.dev, ro, rd, ht, hp, hn, ht, n};
             launch_hit_record(ha, c->stream);
             launch_guide_accum(ga, c->stream);
             HIPCHK(c, hipGetLastError());

@@ -1,6 +1,7 @@
-// runtime_internal.hpp -- what runtime.cpp (context, scene, film, render loop) and postprocess.cpp
-// (guides, denoise, adaptive sampling, temporal accumulation) share: the device context behind the
-// mcpt_* C ABI, its error helpers, the owner of a device buffer and a few host helpers.
+// runtime_internal.hpp -- what runtime.cpp (context, film, render loop), scene_upload.cpp (scene upload
+// and geometry update) and postprocess.cpp (guides, denoise, adaptive sampling, temporal accumulation)
+// share: the device context behind the mcpt_* C ABI, its error helpers, the owner of a device buffer
+// and a few host helpers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -173,30 +174,80 @@ struct VarianceFill {
     mcpt_variance_params p{};
 };
 
-// Geometry update (mcpt_scene_update_geometry).  The upload-time environment
-// knobs as the last upload read them (an update never calls getenv), the upload's device arrays an
-// update writes or reuses (all owned by scene_bufs, so a re-upload frees them; nullptr: none), and
-// the update's own scratch, kept between updates.
-struct GeomUpdate {
-    // MCPT_CULL=0, MCPT_CULL_PLANE, MCPT_BVH_WIDTH (0: by tree size), MCPT_OCC_G / _B, MCPT_OCC_COMPLETE, MCPT_OCC_PREFILL
-    bool cull_off = false, plane = true;
-    int width = 0, occ_g = 24, occ_b = 12;
-    bool occ_complete = true, occ_prefill = true;
-    bool gpu_upload = false;              // uploaded by mcpt_scene_upload_gpu_bvh
+// The upload-time environment knobs as the last upload read them (read_upload_env, scene_upload.cpp;
+// a geometry update takes them from here and never calls getenv)
+struct UploadKnobs {
+    bool cull_off = false;     // MCPT_CULL=0
+    bool plane = true;         // MCPT_CULL_PLANE
+    int width = 0;             // MCPT_BVH_WIDTH (0: by tree size)
+    int layout = -1;           // MCPT_SIBLING_LAYOUT (-1: by tree size)
+    int occ_g = 24, occ_b = 12;                     // MCPT_OCC_G / MCPT_OCC_B
+    bool occ_complete = true, occ_prefill = true;   // MCPT_OCC_COMPLETE / MCPT_OCC_PREFILL
+    bool env_guides = true;    // MCPT_ENV_GUIDES
+};
+
+inline void free_list(std::vector<void*>& v) {
+    for (void* q : v)
+        if (q) (void)hipFree(q);
+    v.clear();
+}
+
+// The uploaded scene (scene_upload.cpp): every device array of it, what the kernels see of it, and what
+// the last upload or geometry update (mcpt_scene_update_geometry) found out about
+// it.  bufs owns every array below and in dev, so the pointers live exactly as long as their arrays:
+// reset() frees all of them and value-initialises every field.
+struct SceneState {
+    std::vector<void*> bufs;
+    DevScene dev{};
+    bool ok = false;       // dev is complete: false during an upload or update and after a failed one
+    int32_t ntri = 0;      // triangles of the uploaded scene
+    UploadKnobs knobs;
+    bool gpu_upload = false;  // uploaded by mcpt_scene_upload_gpu_bvh
+    // the child-pair tree (mcpt_debug_bvh_read): the array launch_cull_margins wrote, which a 4-wide
+    // upload collapses from
+    const float4* pair_nodes = nullptr;
+    uint32_t pair_count = 0;
+    int pair_root = 0, pair_depth = 0, ploc_rounds = 0;
+    int node_layout = 0;   // pair-node numbering the upload used (mcpt_debug_node_layout)
+    bool pair_gpu_built = false;
+    bool cull_ok = true, nest_ok = true;  // boxes contain their triangles / nest (PairTree)
     float4* bvh_nodes = nullptr;          // the device builder's node array (also when it holds no node)
     uint32_t* order = nullptr;            // record p holds desc triangle order[p] (nullptr: identity)
     float4 *desc_tri = nullptr, *desc_sh = nullptr;  // records in desc order (device-built scenes: the builders' input)
     float4* quads = nullptr;              // the 4-wide nodes (DevScene::nodes of a width-4 scene)
     uint32_t* quad_src = nullptr;         // per 4-wide slot the (pair node, child) it copies (kQuadNoSrc: empty)
     uint32_t nquads = 0;
-    float4* occ_rec = nullptr;            // DevScene::occ_rec
-    float4* occ_dir = nullptr;            // the complete keys' direction-bin table
-    DevBuf<float> stage;                  // the host entry's vertex (and normal) arrays
-    DevBuf<float4> box;                   // per record its vertex box
-    DevBuf<float> tri_w, out;             // per record W'_T; {root box, root margin, P bits}
-    float ms[8] = {};                     // mcpt_debug_geometry_update_ms
-    void forget() {  // the arrays went with scene_bufs
-        order = nullptr, bvh_nodes = desc_tri = desc_sh = quads = occ_rec = occ_dir = nullptr, quad_src = nullptr, nquads = 0;
+    // occluder cache
+    size_t occ_entries_n = 0;       // table entries (DevScene::occ; + kOccGateWords gate words)
+    uint32_t* occ_init = nullptr;   // the table as the pre-fill and complete keys left it (film clears restore it); nullptr: empty
+    uint64_t occ_done_keys = 0;     // complete keys (device/occ_beam.hpp) and their build's ms
+    float occ_done_ms = 0.f;
+    float4* occ_rec = nullptr;      // DevScene::occ_rec
+    float4* occ_dir = nullptr;      // the complete keys' direction-bin table
+    // environment light
+    bool env_device_built = false;  // the HRDI tables were built on the device (env_build.hip)
+    bool env_guides = false;        // env_cell uses the search guides
+    float build_ms = 0.f;           // the GPU BVH build (mcpt_scene_upload_gpu_bvh, MCPT_GEOM_REBUILD)
+    float env_build_ms = 0.f;       // the device build of the HRDI tables
+    // a geometry update's scratch, kept between updates
+    DevBuf<float> stage;            // the host entry's vertex (and normal) arrays
+    DevBuf<float4> box;             // per record its vertex box
+    DevBuf<float> tri_w, out;       // per record W'_T; {root box, root margin, P bits}
+    float update_ms[8] = {};        // mcpt_debug_geometry_update_ms
+
+    void reset() {
+        free_list(bufs);
+        *this = SceneState{};
+    }
+    // hipFree one array of the scene, drop it from bufs and null the pointer
+    template <class T>
+    void release(T*& p) {
+        auto it = std::find(bufs.begin(), bufs.end(), (const void*)p);
+        if (it != bufs.end()) {
+            (void)hipFree(*it);
+            bufs.erase(it);
+        }
+        p = nullptr;
     }
 };
 
@@ -209,29 +260,11 @@ struct mcpt_ctx {
     int num_cu = 0;
     LaunchGeom geom{};             // persistent grids and k_trace partitions of this device
     uint32_t trace_parts_default = 1;
-    // scene
-    std::vector<void*> scene_bufs;
-    DevScene scene{};
-    bool has_scene = false;
+    SceneState scene;
     bool has_scene_before = false;  // set at the start of a re-upload
-    int32_t ntri = 0;               // triangles of the uploaded scene
-    size_t occ_entries_n = 0;       // occluder-cache table entries (DevScene::occ; + kOccGateWords gate words)
-    uint32_t* occ_init = nullptr;   // the table as the upload's pre-fill and complete keys left it (film clears restore it); nullptr: empty
-    uint64_t occ_done_keys = 0;     // complete keys of the last upload (device/occ_beam.hpp) and their build's ms
-    float occ_done_ms = 0.f;
-    int pair_depth = 0;
-    bool cull_ok = true, occ_nest_ok = true;  // last upload: boxes contain their triangles / nest (scene_upload)
     // traversal work counters (mcpt_set_work_counters): k_trace's counting instantiation, whose six
     // per-lane counters cost the fast one its spill-free registers -- off by default
     bool count_work = getenv("MCPT_WORK_COUNTERS") != nullptr;
-    int node_layout = 0;  // pair-node numbering the last upload used (mcpt_debug_node_layout)
-    // the last upload's child-pair tree (mcpt_debug_bvh_read): the array launch_cull_margins wrote,
-    // which a 4-wide upload collapses from (owned by scene_bufs either way)
-    const float4* pair_nodes = nullptr;
-    uint32_t pair_count = 0;
-    int pair_root = 0, ploc_rounds = 0;
-    bool pair_gpu_built = false;
-    GeomUpdate gu;  // what mcpt_scene_update_geometry needs of the last upload
     // mcpt_set_skip_discarded: paths the next logic pass is certain to end make no extension ray
     // (ShadeArgs::skip); results and ray counts are the same either way
     bool skip_discarded = true;
@@ -281,10 +314,6 @@ struct mcpt_ctx {
     // scratch of one call (TmpScope; the stage runs)
     std::vector<void*> tmp_bufs;
     float last_stage_ms = 0.f;
-    float last_build_ms = 0.f;  // last GPU BVH build (mcpt_scene_upload_gpu_bvh)
-    float last_env_build_ms = 0.f;  // last device build of the HRDI tables (env_build.hip)
-    bool env_device_built = false;  // the uploaded scene's HRDI tables were built on the device
-    bool env_guides = false;        // env_cell uses the search guides
     int gpu_bvh_builder = MCPT_GPU_BVH_PLOC;  // mcpt_set_gpu_bvh_builder
     bool tiny_stack = false;  // mcpt_debug_tiny_lds_stack: k_trace with a 2-entry LDS stack (tests)
     unsigned long long phase_base[kPhaseWords] = {};  // mcpt_debug_trace_profile's reset point
@@ -311,11 +340,6 @@ inline int set_err(mcpt_ctx* c, int rc, const std::string& msg) {
             return set_err((c), MCPT_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_));  \
     } while (0)
 
-inline void free_list(std::vector<void*>& v) {
-    for (void* q : v)
-        if (q) (void)hipFree(q);
-    v.clear();
-}
 template <class T>
 int dalloc(mcpt_ctx* c, std::vector<void*>& list, T** out, size_t count) {
     void* q = nullptr;

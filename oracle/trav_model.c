@@ -26,7 +26,7 @@
  * Visit order: both children of an interior node are tested, the nearer (entry t) is visited
  * first -- the product's order; a sound rule gives the reference's answer in any order.
  * Leaves of several primitives test each triangle under its own box (the product's expansion
- * into one-triangle leaves, runtime.cpp scene_upload), with the triangle's own margin.
+ * into one-triangle leaves, host/pair_tree.cpp expand_leaf), with the triangle's own margin.
  */
 #include "mcpt_oracle.h"
 

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import bvh_ref as R
+from test_pair_tree_host import host_tree, pair_tree_exe  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -123,10 +124,11 @@ def test_device_pairs_unchanged_by_the_4_wide_collapse(mcpt_mod, oracle, pt):
 
 
 @pytest.mark.parametrize("which", ["scene_c2", "scene_cube"])
-def test_host_trees_in_every_numbering(request, oracle, pt, which):
-    """The host path's pair conversion (runtime.cpp): four numberings, pad nodes in layout 3, leaves
-    expanded to one triangle each -- every one a valid tree, and all the same tree: equal (box, margin)
-    per leaf range, equal interior (box, margin) multisets, equal depth."""
+def test_host_trees_in_every_numbering(request, oracle, pt, pair_tree_exe, tmp_path, which):
+    """The host path's pair conversion (csrc/host/pair_tree.cpp): four numberings, pad nodes in layout 3,
+    leaves expanded to one triangle each -- every one a valid tree, and all the same tree: equal (box,
+    margin) per leaf range, equal interior (box, margin) multisets, equal depth.  What is on the device is
+    what the stand-alone host program (tests/test_pair_tree_host.py) computes, margins apart."""
     s, a = request.getfixturevalue(which)
     m = oracle.model_margins(a)
     assert m["contained"]
@@ -138,6 +140,10 @@ def test_host_trees_in_every_numbering(request, oracle, pt, which):
         assert np.array_equal(u32(tris), u32(R.tri_records(a, info["tri_f4"])))
         assert np.array_equal(u32(info["root_mn"]), u32(a["bmin"][0])) and np.array_equal(u32(info["root_mx"]), u32(a["bmax"][0]))
         R.check_tree(nodes, tris, info, a, m)
+        host_nodes, host_tris, *_ = host_tree(pair_tree_exe, str(tmp_path), a, layout)
+        no_margins = nodes.copy()
+        no_margins[:, 3, 2:] = 0
+        assert np.array_equal(u32(no_margins), u32(host_nodes)) and np.array_equal(u32(tris), u32(host_tris))
         tables.append(R.leaf_table(nodes, info))
         depths.append(info["depth"])
     assert len(set(depths)) == 1

@@ -3,7 +3,7 @@
 #   * pair steps per ray split by outcome (occluded / unoccluded) and the steps whose node box holds
 #     the ray's origin;
 #   * the 128-B lines the steps fetch under each node numbering (layouts 0 / 1 / 2 of
-#     runtime.cpp scene_upload and the candidates below), distinct lines per ray and the misses of a
+#     host/pair_tree.cpp build_pair_tree and the candidates below), distinct lines per ray and the misses of a
 #     4-MB 16-way LRU (one XCD's L2) over the rays interleaved 16 K at a time.
 # Rays: camera rays of the config to first hits, then from those surface points (offset along the
 # normal) hemisphere directions (any hit: shadow / visibility rays; closest: the next bounce).
@@ -126,7 +126,7 @@ def pair_line_of(a, po):
     pl = np.zeros(len(nprims), np.int64)
     interior = nprims == 0
     pl[interior] = po[interior] >> 1
-    # expansion blocks in desc order of the leaves (runtime.cpp expand): n - 1 pairs each
+    # expansion blocks in desc order of the leaves (host/pair_tree.cpp expand_leaf): n - 1 pairs each
     multi = nprims > 1
     sizes = np.where(multi, nprims - 1, 0)
     starts = base + np.concatenate([[0], np.cumsum(sizes)[:-1]])
