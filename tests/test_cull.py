@@ -32,9 +32,10 @@ def scaled_scene(mcpt, cid, scale=1.0):
     return s
 
 
-def floor_scene(mcpt):
+def floor_scene(mcpt, env=(0.8, 0.8, 0.8), light=None):
     """An exactly axis-aligned 10 x 10 floor at y = 0 (no proxy rotation) with a sphere and a cube
-    resting on it: the contact lines are where a grazing ray meets two surfaces at nearly one t."""
+    resting on it: the contact lines are where a grazing ray meets two surfaces at nearly one t.
+    env: the constant environment colour; light: the direction of one white directional light."""
     s = mcpt.Scene()
     v = np.array([[-5, 0, -5], [5, 0, -5], [5, 0, 5], [-5, 0, 5]], np.float32)
     # wound so that e1 x e2 = +y: rays coming down are front-facing (d . (e1 x e2) < 0, Triangle.cu:20)
@@ -45,7 +46,9 @@ def floor_scene(mcpt):
         m = np.diag([sc, sc, sc, 1.0]).astype(np.float32)
         m[:3, 3] = t
         s.load_glb(os.path.join(mcpt.ASSET_DIR, name), m.T.reshape(16))
-    s.set_env_color((0.8, 0.8, 0.8))
+    s.set_env_color(env)
+    if light is not None:
+        s.add_dir_light(light, (1.0, 1.0, 1.0), 3.0)
     s.build(**mcpt.DEFAULT_BVH)
     return s
 
@@ -406,6 +409,16 @@ def _gpu_scene(mcpt_mod, request, name, scale):
     return s, s.arrays()
 
 
+def same_as_oracle(got, ref):
+    """(pos_t, normal, triangle, visibility) of the product against the oracle's: triangle index and
+    visibility equal, position, t and normal words bit for bit."""
+    (gp, gn, gt, gv), (op_, on, ot, ov) = got, ref
+    bad = np.nonzero((gt != ot) | (gv != ov))[0]
+    assert len(bad) == 0, f"{len(bad)} of {len(gt)} rays differ, first {bad[:5]}"
+    assert np.array_equal(gp.view(np.uint32), op_.view(np.uint32))
+    assert np.array_equal(gn.view(np.uint32), on.view(np.uint32))
+
+
 def _gpu_vs_oracle(mcpt_mod, oracle, s, a, ro, rd, tiny=False):
     pt = mcpt_mod.PathTracer(0)
     pt.upload_scene(s)
@@ -417,10 +430,7 @@ def _gpu_vs_oracle(mcpt_mod, oracle, s, a, ro, rd, tiny=False):
     th = max(1, min(8, os.cpu_count() or 1))
     op_, on, ot = oracle.trace_closest(a, ro, rd, nthreads=th)
     ov = oracle.trace_any(a, ro, rd, nthreads=th)
-    bad = np.nonzero((gt != ot) | (gv != ov))[0]
-    assert len(bad) == 0, f"{len(bad)} of {len(ro)} rays differ, first {bad[:5]}"
-    assert np.array_equal(gp.view(np.uint32), op_.view(np.uint32))
-    assert np.array_equal(gn.view(np.uint32), on.view(np.uint32))
+    same_as_oracle((gp, gn, gt, gv), (op_, on, ot, ov))
     return ot, ov
 
 
