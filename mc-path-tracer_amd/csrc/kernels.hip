@@ -1,4 +1,6 @@
-// kernels.hip -- gfx950 kernels of the wavefront path tracer.
+// kernels.hip -- the gfx950 kernels of one wavefront iteration, their launchers and nothing else.
+// (Tables built at upload, camera change or film resize: scene_tables.hip; film and debug utilities:
+// film.hip; the helpers they share with this file: device/scene_dev.hpp.)
 //
 // One wavefront iteration (= one reference wavefront_pathtrace call,
 // wavefront_kernels.cu:377-442, widened from one 256x256 tile to a tile set):
@@ -21,7 +23,7 @@
 #include <algorithm>
 
 #include "device/mcpt_core.hpp"
-#include "device/primary_beam.hpp"
+#include "device/scene_dev.hpp"
 #include "kernels.hpp"
 
 using namespace mcpt;
@@ -61,8 +63,6 @@ __device__ inline void block_push(const bool (&want)[NQ], uint32_t* const (&coun
         total[q] = s_tot[q];
     }
 }
-
-__device__ inline V3 xyz(float4 a) { return v3(a.x, a.y, a.z); }
 
 // The kernel's by-value argument struct read through an opaque copy of the kernarg segment
 // pointer.  Kernel arguments are invariant loads, so the compiler hoists every field a persistent
@@ -134,12 +134,6 @@ __device__ inline void st_s(uint4* p, uint4 v) {
     if constexpr (MCPT_NT & 2) __builtin_nontemporal_store(u4v_t{v.x, v.y, v.z, v.w}, reinterpret_cast<u4v_t*>(p));
     else *p = v;
 }
-// the xyz of a float4 element with one dwordx3 load (one VGPR fewer than the float4)
-__device__ inline V3 ld3f4(const float4* p) {
-    const float* f = reinterpret_cast<const float*>(p);
-    return v3(f[0], f[1], f[2]);
-}
-__device__ inline float4 f4(V3 v, float w) { return make_float4(v.x, v.y, v.z, w); }
 
 // Diagnostics of the shading kernels' instruction attribution, off in the product:
 //  * -DMCPT_ISA_MARKERS: assembly comments at the section boundaries (MCPT_MARK, mcpt_core.hpp;
@@ -224,10 +218,6 @@ __device__ inline bool slab(float mnx, float mny, float mnz, float mxx, float mx
     return !miss;
 }
 constexpr float K_INF_F = __builtin_huge_valf();
-#ifndef MCPT_OCC_LAYOUT
-#define MCPT_OCC_LAYOUT 0  // occluder-table key order (occ_index): 0 origin-cell major, 1 direction-bin major
-#endif
-constexpr int kEnd = -1;  // not a valid leaf: offset + count <= ntri < 2^24
 
 // Culling scale of a ray (mcpt_core.hpp "conservative box culling"): iota = max_a |1/d_a| (1 + 2^-18)
 // for the rays the bound covers -- finite inverse, |d| <= 1 + 2^-10, a scene whose boxes contain
@@ -382,31 +372,6 @@ __device__ inline bool ray_misses_scene(const DevScene& sc, V3 o, V3 d) {
              keep_box(t0, t1, m, K_INF_F, key));
 }
 
-// Hit record of ray (o, d) on triangle tri, as dTriangle::hit builds it
-// (Triangle.cu:66-92): Moller-Trumbore t/u/v, the interpolated normal
-// normalised twice (identity transform), position o + t d, material id.
-__device__ inline void hit_record(const DevScene& sc, V3 o, V3 d, int tri, V3& pos, V3& nrm, int& mat, float& t_out) {
-    const float4* tp = sc.tri + kTriF4 * tri;
-    const float4 w0 = tp[0], w1 = tp[1], w2 = tp[2];
-    const float4* sp4 = sc.tri_sh + 3 * tri;
-    const float4 s0 = sp4[0], s1 = sp4[1], s2 = sp4[2];
-    // All six loads in one round trip: the compiler otherwise issues the vertex load after
-    // the determinant test and the shading record after the whole test (three serialised
-    // fetches; the hit is known to exist, so every value is used).
-    __asm__ volatile("" ::"v"(w0.x), "v"(w0.y), "v"(w0.z), "v"(w0.w), "v"(w1.x), "v"(w1.y), "v"(w1.z), "v"(w1.w),
-                     "v"(w2.x), "v"(s0.x), "v"(s0.y), "v"(s0.z), "v"(s0.w), "v"(s1.x), "v"(s1.y), "v"(s1.z),
-                     "v"(s1.w), "v"(s2.x), "v"(s2.y));
-    float t, u, v;
-    tri_test(o, d, v3(w0.x, w0.y, w0.z), v3(w0.w, w1.x, w1.y), v3(w1.z, w1.w, w2.x), t, u, v);
-    const V3 n0 = v3(s0.x, s0.y, s0.z), n1 = v3(s0.w, s1.x, s1.y), n2 = v3(s1.z, s1.w, s2.x);
-    const float w = (1.f - u) - v;
-    nrm = normalize((n1 * u + n2 * v) + n0 * w);  // Triangle.cu:76
-    nrm = normalize(nrm);                          // identity transform, :82
-    pos = o + d * t;                               // :86
-    mat = __float_as_int(s2.y);                    // material id bits
-    t_out = t;
-}
-
 // ---------------------------------------------------------------------------
 // Any-hit occluder cache.  An any-hit ray's outcome is one bit (wf_shadow,
 // wavefront_kernels.cu:274-293): occluded iff some triangle passes the traversal's
@@ -423,46 +388,6 @@ __device__ inline void hit_record(const DevScene& sc, V3 o, V3 d, int tri, V3& p
 // The table's contents (racy plain stores) only decide how much work is skipped, never
 // a result.  Rays with an infinite inverse component (slab(), NaN slabs) are not tested.
 // ---------------------------------------------------------------------------
-// (cx, cy, cz): the origin cell; dirbin = (face B + ub) B + vb: the direction bin
-__device__ inline void occ_coords(const DevScene& sc, V3 o, V3 d, uint32_t& cx, uint32_t& cy, uint32_t& cz, uint32_t& face,
-                                  uint32_t& ub, uint32_t& vb) {
-    const float gm = (float)(sc.occ_g - 1), bm = (float)(sc.occ_b - 1), hb = 0.5f * (float)sc.occ_b;
-    // fmaxf(NaN, 0) = 0: a NaN coordinate falls in cell / bin 0
-    cx = (uint32_t)__builtin_fminf(__builtin_fmaxf((o.x - sc.root_mn[0]) * sc.occ_inv[0], 0.f), gm);
-    cy = (uint32_t)__builtin_fminf(__builtin_fmaxf((o.y - sc.root_mn[1]) * sc.occ_inv[1], 0.f), gm);
-    cz = (uint32_t)__builtin_fminf(__builtin_fmaxf((o.z - sc.root_mn[2]) * sc.occ_inv[2], 0.f), gm);
-    const float ax = __builtin_fabsf(d.x), ay = __builtin_fabsf(d.y), az = __builtin_fabsf(d.z);
-    float u, v, m;
-    if (ax >= ay && ax >= az) {
-        face = d.x < 0.f ? 1u : 0u; u = d.y; v = d.z; m = ax;
-    } else if (ay >= az) {
-        face = d.y < 0.f ? 3u : 2u; u = d.x; v = d.z; m = ay;
-    } else {
-        face = d.z < 0.f ? 5u : 4u; u = d.x; v = d.y; m = az;
-    }
-    const float r = hb * __builtin_amdgcn_rcpf(m);  // cube-map coordinates in [-1, 1] -> [0, B)
-    ub = (uint32_t)__builtin_fminf(__builtin_fmaxf(u * r + hb, 0.f), bm);
-    vb = (uint32_t)__builtin_fminf(__builtin_fmaxf(v * r + hb, 0.f), bm);
-}
-// The key's coordinates in one word for k_material's membership test (occ_member2): dirbin | cx << 15 |
-// cy << 20 | cz << 25; dirbin < 6 * 64^2 < 2^15 always, the cells fit for occ_g <= 32 (the upload
-// builds complete keys, the only users, for no larger grid)
-__device__ inline uint32_t occ_index(const DevScene& sc, V3 o, V3 d, uint32_t* packed = nullptr) {
-    uint32_t cx, cy, cz, face, ub, vb;
-    occ_coords(sc, o, d, cx, cy, cz, face, ub, vb);
-    const uint32_t G = (uint32_t)sc.occ_g, B = (uint32_t)sc.occ_b;
-    if (packed) *packed = ((face * B + ub) * B + vb) | cx << 15 | cy << 20 | cz << 25;
-    // one table cell per key (hashing the keys into a 2^21- or 2^23-cell table measured 43 % / 60 %
-    // of config 2's any-hit rays resolved against 72 % direct: the keys that occur collide heavily)
-#if MCPT_OCC_LAYOUT == 1
-    // direction major: lanes whose rays share a direction bin and lie in neighbouring origin cells
-    // (along x) read one 128-B line (A/B knob)
-    return (((face * B + ub) * B + vb) * G + cz) * G * G + cy * G + cx;
-#else
-    return ((((cz * G + cy) * G + cx) * 6u + face) * B + ub) * B + vb;
-#endif
-}
-
 // true: (o, d) (reciprocal inv, all finite; signed culling scale io) is occluded by the triangle of
 // occluder record r0..r3 (kOccRecF4: {leaf box mn, margin} {leaf box mx, v0.x} {v0.yz, e1.xy}
 // {e1.z, e2}) under its leaf box
@@ -1991,8 +1916,8 @@ __global__ __launch_bounds__(kTraceBlock) MCPT_TRACE_ATTR void k_trace(TraceArgs
 // scene id) among those whose own leaf box passes the slab test and that Moller-Trumbore accepts
 // with 0 <= t < K_HUGE -- every ancestor box passes whenever the leaf box does (boxes nest, the
 // rounded slab products are monotone in the box), and the culls skip no triangle that can be
-// accepted.  k_primary_build lists, per pixel, every triangle whose leaf box the pixel's rays do
-// not provably all fail (primary_beam.hpp); k_primary runs that acceptance over the list with the
+// accepted.  k_primary_build (scene_tables.hip) lists, per pixel, every triangle whose leaf box the
+// pixel's rays do not provably all fail (primary_beam.hpp); k_primary runs that acceptance over the list with the
 // traversal's arithmetic: pair_slab's products (finite inverse; k_shade queues only such rays),
 // tri_test_t, !(t < 0), t < best.  The list is in ascending scene-id order, so a tie keeps the
 // earlier candidate.  Dense over the primary queue like k_material: block b serves shard b mod
@@ -2039,216 +1964,8 @@ __global__ __launch_bounds__(kBlock) void k_primary(ShadeArgs a_kernarg) {
         a.p.hit_tri[q.x] = tri;
     }
 }
-
-// The candidate list of every pixel: a beam traversal of the BVH, one thread per pixel.  A subtree
-// is skipped when the beam provably fails its box (each ancestor box contains its leaf boxes); a
-// leaf's triangles are listed unless the whole beam sees them back-facing.  More than kPrimK
-// candidates, or no bound: the pixel gets no list.
-__global__ __launch_bounds__(64) void k_primary_build(PrimaryBuildArgs a) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (uint32_t)a.W * (uint32_t)a.H) return;
-    const DevScene& sc = a.scene;
-    const V3 cp = ld3f4(a.cam_px + i);
-    const Beam b = a.cam.lens_radius > 0.f ? beam_lens(a.cam, cp) : beam_point(cp, ld3f4(a.cam_dir + i));
-    uint32_t ids[kPrimK];
-    int sid[kPrimK];
-    int n = 0;
-    bool over = !b.ok;
-    if (!over) {
-        const BeamInv iv = beam_inv(b);
-        int stack[kMaxStack];
-        int sp = 0;
-        if (!beam_misses_box(b, iv, sc.root_mn[0], sc.root_mn[1], sc.root_mn[2], sc.root_mx[0], sc.root_mx[1], sc.root_mx[2]))
-            stack[sp++] = sc.root_ref;
-        while (sp > 0 && !over) {
-            const int ref = stack[--sp];
-            if (ref == kEnd) continue;
-            if (ref < 0) {  // leaf: 0x80000000 | (count - 1) << 24 | offset
-                const uint32_t off = (uint32_t)ref & 0xffffffu, cnt = (((uint32_t)ref >> 24) & 7u) + 1u;
-                for (uint32_t k = off; k < off + cnt && k < sc.ntri && !over; k++) {
-                    const float4* tr = sc.tri + kTriF4 * (size_t)k;
-                    const float4 w0 = tr[0], w1 = tr[1], w2 = tr[2];
-                    if (beam_backfacing(b, v3(w0.w, w1.x, w1.y), v3(w1.z, w1.w, w2.x))) continue;
-                    if (n == kPrimK) { over = true; break; }
-                    const int s = __float_as_int(w2.y);  // scene id: the list is kept in its order
-                    int j = n++;
-                    for (; j > 0 && sid[j - 1] > s; j--) { sid[j] = sid[j - 1]; ids[j] = ids[j - 1]; }
-                    sid[j] = s;
-                    ids[j] = k;
-                }
-                continue;
-            }
-            float mn[3][4], mx[3][4];
-            int rf[4];
-            int nch;
-            if (sc.width == 4) {
-                const float4* nd = sc.nodes + 8 * (size_t)ref;
-                const float4 q[7] = {nd[0], nd[1], nd[2], nd[3], nd[4], nd[5], nd[6]};
-                for (int ax = 0; ax < 3; ax++) {
-                    mn[ax][0] = q[2 * ax].x; mn[ax][1] = q[2 * ax].y; mn[ax][2] = q[2 * ax].z; mn[ax][3] = q[2 * ax].w;
-                    mx[ax][0] = q[2 * ax + 1].x; mx[ax][1] = q[2 * ax + 1].y; mx[ax][2] = q[2 * ax + 1].z; mx[ax][3] = q[2 * ax + 1].w;
-                }
-                rf[0] = __float_as_int(q[6].x); rf[1] = __float_as_int(q[6].y);
-                rf[2] = __float_as_int(q[6].z); rf[3] = __float_as_int(q[6].w);
-                nch = 4;
-            } else {
-                const float4* nd = sc.nodes + 4 * (size_t)ref;
-                const float4 q[4] = {nd[0], nd[1], nd[2], nd[3]};
-                for (int ax = 0; ax < 3; ax++) {
-                    mn[ax][0] = q[ax].x; mn[ax][1] = q[ax].y; mx[ax][0] = q[ax].z; mx[ax][1] = q[ax].w;
-                }
-                rf[0] = __float_as_int(q[3].x); rf[1] = __float_as_int(q[3].y);
-                nch = 2;
-            }
-            for (int k = 0; k < nch; k++) {
-                if (rf[k] == kEnd) continue;
-                if (beam_misses_box(b, iv, mn[0][k], mn[1][k], mn[2][k], mx[0][k], mx[1][k], mx[2][k])) continue;
-                if (sp == kMaxStack) { over = true; break; }
-                stack[sp++] = rf[k];
-            }
-        }
-    }
-    uint32_t* lp = a.list + (size_t)kPrimLine * i;
-    for (int k = 0; k < kPrimK; k++) lp[k] = (!over && k < n) ? ids[k] : 0u;
-    a.cnt[i] = over ? (uint8_t)0 : (uint8_t)(n + 1);
-    const uint64_t mo = __ballot(over), ml = __ballot(!over);
-    if ((threadIdx.x & 63) == 0) {
-        if (ml) atomicAdd(a.stats + 0, (uint32_t)__popcll(ml));
-        if (mo) atomicAdd(a.stats + 1, (uint32_t)__popcll(mo));
-    }
-}
-void launch_primary_build(const PrimaryBuildArgs& a, hipStream_t s) {
-    const uint32_t n = (uint32_t)a.W * (uint32_t)a.H;
-    if (n) hipLaunchKernelGGL(k_primary_build, dim3((n + 63) / 64), dim3(64), 0, s, a);
-}
 void launch_primary(const ShadeArgs& a, const LaunchGeom& g, hipStream_t s) {
     if (a.prim_cnt) hipLaunchKernelGGL(k_primary, dim3(g.prim_blocks), dim3(kBlock), 0, s, a);
-}
-
-// Camera records of a W x H film: gen_ray_pixel of every pixel (ShadeArgs::cam_px / cam_dir)
-__global__ void k_cam_table(mcpt::CamView cam, int W, int H, float4* px, float4* dir) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (uint32_t)W * (uint32_t)H) return;
-    const int x = (int)(i % (uint32_t)W), y = (int)(i / (uint32_t)W);
-    V3 o, d;
-    gen_ray_pixel(cam, W, H, x, y, o, d);
-    px[i] = f4(cam.lens_radius > 0.f ? gen_ray_focal(cam, o, d) : o, 0.f);
-    dir[i] = f4(d, 0.f);
-}
-void launch_cam_table(const mcpt::CamView& cam, int W, int H, float4* px, float4* dir, hipStream_t s) {
-    const uint32_t n = (uint32_t)W * (uint32_t)H;
-    if (n) hipLaunchKernelGGL(k_cam_table, dim3((n + 255) / 256), dim3(256), 0, s, cam, W, H, px, dir);
-}
-
-// The env texture's device copy takes the pdf table into its alpha plane (EnvView::tex)
-__global__ void k_env_pack(float4* tex, const float* __restrict__ pdf, size_t n) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) tex[i].w = pdf[i];
-}
-void launch_env_pack(float4* tex, const float* pdf, size_t n, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_env_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, tex, pdf, n);
-}
-
-// Light-sample table of an HRDI env light (EnvView::ltab / lrow / lcol): entry (y, x + 1)
-// holds env_L / env_pdf at the direction env_dir returns for cell (x, y) -- computed by the
-// very functions the per-sample path calls, so the values are the same -- and the row /
-// column tables the direction's two factors (spherical_theta / spherical_phi of the cell's
-// v / u, the arithmetic of spherical_direction).
-template <bool FIXED>
-__global__ void k_env_table(EnvView e, float4* out, float2* row, float2* col) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int W1 = e.w + 1;
-    if (i < e.h) {
-        float st, ct;
-        spherical_theta(env_cell_v<FIXED>(e, i), st, ct);
-        row[i] = make_float2(st, ct);
-    }
-    if (i < W1) {
-        const int x = i - 1;
-        float sp, cp;
-        spherical_phi(env_cell_u<FIXED>(e, FIXED && x < 0 ? 0 : x), sp, cp);
-        col[i] = make_float2(sp, cp);
-    }
-    if (i >= W1 * e.h) return;
-    const int y = i / W1, x = i - y * W1 - 1;
-    const V3 d = env_cell_dir<FIXED>(e, FIXED && x < 0 ? 0 : x, y);
-    V3 L;
-    float pdf;
-    env_L_pdf<FIXED>(e, d, L, pdf);
-    out[i] = make_float4(L.x, L.y, L.z, pdf);
-}
-void launch_env_table(const EnvView& e, bool fixed_mode, float4* out, float2* row, float2* col, hipStream_t s) {
-    const int n = (e.w + 1) * e.h;
-    if (fixed_mode) hipLaunchKernelGGL(k_env_table<true>, dim3((n + 255) / 256), dim3(256), 0, s, e, out, row, col);
-    else hipLaunchKernelGGL(k_env_table<false>, dim3((n + 255) / 256), dim3(256), 0, s, e, out, row, col);
-}
-
-__global__ void k_hit_record(HitRecordArgs a) {  // stage_run(EXTEND) outputs
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.n) return;
-    const int tri = a.tri[i];
-    if (tri < 0) {
-        a.hit_p[i] = make_float4(0.f, 0.f, 0.f, K_HUGE);
-        a.hit_n[i] = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
-        a.scene_tri[i] = -1;
-        return;
-    }
-    a.scene_tri[i] = __float_as_int(a.scene.tri[kTriF4 * tri + 2].y);  // storage position -> scene index
-    V3 pos, nrm;
-    int mat;
-    float t;
-    hit_record(a.scene, xyz(a.ro[i]), xyz(a.rd[i]), tri, pos, nrm, mat, t);
-    a.hit_p[i] = make_float4(pos.x, pos.y, pos.z, t);
-    a.hit_n[i] = make_float4(nrm.x, nrm.y, nrm.z, __int_as_float(mat));
-}
-
-__global__ void k_clear(ClearArgs a) {  // g_clear_dfilm (wavefront_kernels.cu:55-66)
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.n) return;
-    a.flags[i] = F_DEAD | ((i / a.npx) << F_SIDX_SHIFT);  // dead, next sample: the slot's first
-    a.samples[i] = 0;
-    a.Ld[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
-__global__ void k_resolve(ResolveArgs a) {  // film = sum of the path slots' accumulators, in slot order
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.n) return;
-    uint32_t o = i;  // the pixel
-    if (a.tiles) {   // compact layout: accumulator i is pixel li of tile-set tile ti
-        const uint32_t tpx = (uint32_t)(a.tile_w * a.tile_h), ti = i / tpx, li = i - ti * tpx;
-        const int2 t = a.tiles[ti];
-        const uint32_t x = (uint32_t)t.x * a.tile_w + li % (uint32_t)a.tile_w, y = (uint32_t)t.y * a.tile_h + li / (uint32_t)a.tile_w;
-        if (x >= (uint32_t)a.W || y >= (uint32_t)a.H) return;
-        o = y * (uint32_t)a.W + x;
-    }
-    float4 L = a.Ld[i];
-    uint32_t n = a.samples[i];
-    for (int k = 1; k < a.slots; k++) {
-        const float4 l = a.Ld[(size_t)k * a.n + i];
-        L = make_float4(L.x + l.x, L.y + l.y, L.z + l.z, 0.f);
-        n += a.samples[(size_t)k * a.n + i];
-    }
-    a.out_Ld[o] = L;
-    a.out_samples[o] = n;
-}
-
-__global__ void k_tonemap(TonemapArgs a) {  // draw_to_surface (wavefront_kernels.cu:6-40)
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.n) return;
-    float4 L = a.Ld[i];
-    float s = (float)a.samples[i];
-    V3 c = v3(L.x / s, L.y / s, L.z / s);
-    c = c * a.exposure;
-    c = v3(c.x / (c.x + 1.0f), c.y / (c.y + 1.0f), c.z / (c.z + 1.0f));
-    float cc[3] = {255 * c.x, 255 * c.y, 255 * c.z};
-    uchar4 o;
-    unsigned char b[3];
-    for (int k = 0; k < 3; k++) {
-        float v = cc[k];
-        b[k] = (v == v && v >= 0.f && v < 4294967296.f) ? (unsigned char)(unsigned int)v : (unsigned char)0;
-    }
-    o.x = b[0]; o.y = b[1]; o.z = b[2]; o.w = 255;
-    a.out[i] = o;
 }
 
 // the occluder gate's first backoff (iterations without lookups after the first that did not pay):
@@ -2354,35 +2071,9 @@ __global__ void k_accumulate(CounterBlock* c, uint32_t nparts, uint32_t* occ_gat
         for (int k = 0; k < kPhaseWords; k++) c->tot_phase[k] += phw[k];
     }
 }
-
-__global__ void k_pack(PackArgs a) {  // tile-set pixels -> packed 16 B/px (for the RCCL gather)
-    const int tile_px = a.tile_w * a.tile_h;
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (uint32_t)(a.ntiles * tile_px)) return;
-    const int tile = i / tile_px, li = i % tile_px;
-    int2 t = a.tiles[tile];
-    int x = t.x * a.tile_w + li % a.tile_w, y = t.y * a.tile_h + li / a.tile_w;
-    float4 o = make_float4(0.f, 0.f, 0.f, __uint_as_float(0u));
-    if (x < a.W && y < a.H) {
-        uint32_t pid = (uint32_t)y * a.W + x;
-        float4 L = a.Ld[pid];
-        o = make_float4(L.x, L.y, L.z, __uint_as_float(a.samples[pid]));
-    }
-    a.out[i] = o;
-}
-
-__global__ void k_unpack(UnpackArgs a) {  // packed 16 B/px of a tile set -> film accumulators (mcpt_gather)
-    const int tile_px = a.tile_w * a.tile_h;
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (uint32_t)(a.ntiles * tile_px)) return;
-    const int tile = i / tile_px, li = i % tile_px;
-    const int2 t = a.tiles[tile];
-    const int x = t.x * a.tile_w + li % a.tile_w, y = t.y * a.tile_h + li / a.tile_w;
-    if (x >= a.W || y >= a.H) return;
-    const uint32_t pid = (uint32_t)y * a.W + x;
-    const float4 v = a.in[i];
-    a.Ld[pid] = make_float4(v.x, v.y, v.z, 0.f);
-    a.samples[pid] = __float_as_uint(v.w);
+void launch_accumulate(CounterBlock* c, uint32_t nparts, uint32_t* occ_gate, hipStream_t s) {
+    hipLaunchKernelGGL(k_accumulate, dim3(1), dim3(kShards), 0, s, c, std::min<uint32_t>(kMaxParts, std::max<uint32_t>(1, nparts)),
+                       occ_gate);
 }
 
 // ---------------------------------------------------------------------------
@@ -2528,227 +2219,6 @@ void launch_trace(const TraceArgs& args, const LaunchGeom& g, hipStream_t s) {
     else if (w == 0) hipLaunchKernelGGL((k_trace<2, kLdsStackDeep, false>), grid, block, 0, s, a);
     else if (k == 0) hipLaunchKernelGGL((k_trace<4, kLdsStack, false>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((k_trace<4, kLdsStackDeep, false>), grid, block, 0, s, a);
-}
-__global__ void k_quot(const float* a, const float* b, float* out, uint32_t n) {  // mcpt_debug_quot
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float q0, q1, q2;
-    quot3(a[i], 1.0f, -a[i], b[i], q0, q1, q2);
-    out[i] = q0;
-}
-void launch_quot(const float* a, const float* b, float* out, uint32_t n, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_quot, dim3((n + 255) / 256), dim3(256), 0, s, a, b, out, n);
-}
-
-// HBM copy ceiling (mcpt_debug_hbm_copy; SURVEY.md 8(d) "re-measure a STREAM-copy ceiling"): one
-// dwordx4 per lane, one pass (a block per 256 float4).  tools/hbm/copy_sweep.hip measured the
-// variants: one-pass grids reach 6.25-6.39 TB/s on 1-4 GiB, persistent grid-stride loops
-// 4.5-5.0 TB/s whatever the unroll or cache policy.
-__global__ __launch_bounds__(256) void k_copy(const float4* __restrict__ src, float4* __restrict__ dst, size_t n) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = src[i];
-}
-void launch_copy(const float4* src, float4* dst, size_t n, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_copy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, dst, n);
-}
-
-// The round-2/3 diagnostics builds (per-section wave clocks of k_shade / k_material, k_trace loop
-// profiles, wave lifetimes, per-ray step counts) are gone from the kernels (they are in git
-// history); rocprofv3 counter passes (tools/gpu/run.sh pmc) replace them.  The ABI entries stay
-// and report that nothing was collected.
-int wave_times(unsigned long long* out, int n) {
-    (void)out;
-    (void)n;
-    return 0;
-}
-int trace_profile(unsigned long long* out, int reset) {  // (replaced by the counting build's phase counts)
-    (void)out;
-    (void)reset;
-    return 0;
-}
-__global__ void k_occ_records(DevScene sc, uint32_t nnodes, float4* out) {  // see launch_occ_records
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    auto put = [&](int ref, float mnx, float mny, float mnz, float mxx, float mxy, float mxz, float w) {
-        if (ref >= 0 || ref == kEnd) return;
-        const uint32_t off = (uint32_t)ref & 0xffffffu, cnt = (((uint32_t)ref >> 24) & 7u) + 1u;
-        for (uint32_t k = off; k < off + cnt && k < sc.ntri; k++) {
-            const float4* tr = sc.tri + kTriF4 * (size_t)k;  // (v0.xyz, e1.x) (e1.yz, e2.xy) (e2.z, ...)
-            const float4 a = tr[0], b = tr[1], c = tr[2];
-            float4* o = out + kOccRecF4 * (size_t)k;
-            o[0] = make_float4(mnx, mny, mnz, w);  // .w: the leaf's culling margin
-            o[1] = make_float4(mxx, mxy, mxz, a.x);
-            o[2] = make_float4(a.y, a.z, a.w, b.x);
-            o[3] = make_float4(b.y, b.z, b.w, c.x);
-        }
-    };
-    if (i == 0 && sc.root_ref < 0)  // the whole tree is one leaf: its box is the root box
-        put(sc.root_ref, sc.root_mn[0], sc.root_mn[1], sc.root_mn[2], sc.root_mx[0], sc.root_mx[1], sc.root_mx[2],
-            sc.root_w);
-    if (i >= nnodes) return;
-    if (sc.width == 4) {  // mn.x[4], mx.x[4], mn.y[4], mx.y[4], mn.z[4], mx.z[4], refs[4], margins[4]
-        const float4* nd = sc.nodes + 8 * (size_t)i;
-        const float4 mnx = nd[0], mxx = nd[1], mny = nd[2], mxy = nd[3], mnz = nd[4], mxz = nd[5], rf = nd[6], wq = nd[7];
-        const float* a0 = &mnx.x; const float* a1 = &mxx.x; const float* b0 = &mny.x;
-        const float* b1 = &mxy.x; const float* c0 = &mnz.x; const float* c1 = &mxz.x; const float* r = &rf.x;
-        const float* w = &wq.x;
-        for (int k = 0; k < 4; k++) put(__float_as_int(r[k]), a0[k], b0[k], c0[k], a1[k], b1[k], c1[k], w[k]);
-    } else {  // per axis (mn0, mn1, mx0, mx1), then (ref0, ref1, margin0, margin1)
-        const float4* nd = sc.nodes + 4 * (size_t)i;
-        const float4 q0 = nd[0], q1 = nd[1], q2 = nd[2], q3 = nd[3];
-        put(__float_as_int(q3.x), q0.x, q1.x, q2.x, q0.z, q1.z, q2.z, q3.z);
-        put(__float_as_int(q3.y), q0.y, q1.y, q2.y, q0.w, q1.w, q2.w, q3.w);
-    }
-}
-
-// Culling margins (mcpt_core.hpp "conservative box culling").  k_cull_tri: W'_T of every triangle
-// record (float, rounded up) and the far coefficient P (positive floats order as their bits).
-__global__ void k_cull_tri(const float4* tri, uint32_t ntri, float* tw, uint32_t* pmax, int plane) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= ntri) return;
-    const float4* r = tri + kTriF4 * (size_t)i;
-    const float4 r0 = r[0], r1 = r[1], r2 = r[2];
-    double far;
-    tw[i] = cull_to_float_up(cull_tri_margin(v3(r0.w, r1.x, r1.y), v3(r1.z, r1.w, r2.x), &far, plane != 0));
-    if (far > 0.0) atomicMax(pmax, __float_as_uint(cull_to_float_up(far)));
-}
-// One bottom-up pass over child-pair nodes: each child's word (q3.z / q3.w) = the largest W'_T
-// under it -- its triangles for a leaf, the child node's two words for an interior child.  Words
-// start at 0 and only grow toward the subtree maxima, so a word read before or after its own
-// update in the same pass is either way a lower bound, and depth + 1 passes reach the fixed point.
-__global__ void k_cull_pairs(float4* nodes, uint32_t npairs, const float* tw, uint32_t ntri) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= npairs) return;
-    const float4 q3 = nodes[4 * (size_t)i + 3];
-    float w[2];
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        const int ref = __float_as_int(k ? q3.y : q3.x);
-        float v = 0.f;
-        if (ref >= 0) {
-            const float4 c = nodes[4 * (size_t)ref + 3];
-            v = __builtin_fmaxf(c.z, c.w);
-        } else if (ref != kEnd) {
-            const uint32_t off = (uint32_t)ref & 0xffffffu, cnt = (((uint32_t)ref >> 24) & 7u) + 1u;
-            for (uint32_t t = off; t < off + cnt && t < ntri; t++) v = __builtin_fmaxf(v, tw[t]);
-        }
-        w[k] = v;
-    }
-    nodes[4 * (size_t)i + 3] = make_float4(q3.x, q3.y, w[0], w[1]);
-}
-__global__ void k_cull_zero(float4* nodes, uint32_t npairs) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= npairs) return;
-    float4 q3 = nodes[4 * (size_t)i + 3];
-    q3.z = q3.w = 0.f;
-    nodes[4 * (size_t)i + 3] = q3;
-}
-void launch_cull_tri(const float4* tri, uint32_t ntri, float* tri_w, uint32_t* pmax, bool plane, hipStream_t s) {
-    if (ntri) hipLaunchKernelGGL(k_cull_tri, dim3((ntri + 255) / 256), dim3(256), 0, s, tri, ntri, tri_w, pmax, plane ? 1 : 0);
-}
-void launch_cull_margins(float4* nodes, uint32_t npairs, const float4* tri, uint32_t ntri, float* tri_w,
-                         uint32_t* pmax, int passes, bool plane, hipStream_t s) {
-    launch_cull_tri(tri, ntri, tri_w, pmax, plane, s);
-    if (!npairs) return;
-    hipLaunchKernelGGL(k_cull_zero, dim3((npairs + 255) / 256), dim3(256), 0, s, nodes, npairs);
-    for (int p = 0; p < passes; p++)
-        hipLaunchKernelGGL(k_cull_pairs, dim3((npairs + 255) / 256), dim3(256), 0, s, nodes, npairs, tri_w, ntri);
-}
-// One probe ray per occluder-table key (the pre-fill at upload, scene_upload.cpp): from the centre of
-// the key's origin cell along the centre of its direction bin, so that occ_index maps the probe back
-// to its own key.  Tracing the probes as any-hit rays records an occluder in every key whose probe
-// is occluded -- a property of the scene alone, like the BVH.
-__global__ void k_occ_probes(DevScene sc, float4* ro, float4* rd, uint32_t nkeys) {
-    const uint32_t key = blockIdx.x * blockDim.x + threadIdx.x;
-    if (key >= nkeys) return;
-    const uint32_t G = (uint32_t)sc.occ_g, B = (uint32_t)sc.occ_b;
-    uint32_t t = key, cx, cy, cz, face, ub, vb;
-#if MCPT_OCC_LAYOUT == 1
-    cx = t % G; t /= G; cy = t % G; t /= G; cz = t % G; t /= G; vb = t % B; t /= B; ub = t % B; face = t / B;
-#else
-    vb = t % B; t /= B; ub = t % B; t /= B; face = t % 6u; t /= 6u; cx = t % G; t /= G; cy = t % G; cz = t / G;
-#endif
-    const uint32_t c[3] = {cx, cy, cz};
-    float o[3];
-    for (int k = 0; k < 3; k++)
-        o[k] = sc.occ_inv[k] > 0.f ? sc.root_mn[k] + ((float)c[k] + 0.5f) / sc.occ_inv[k] : sc.root_mn[k];
-    const float hb = 0.5f * (float)B;
-    const float u = ((float)ub + 0.5f) / hb - 1.f, v = ((float)vb + 0.5f) / hb - 1.f;
-    const float sg = (face & 1u) ? -1.f : 1.f;
-    float d[3];
-    if (face < 2u) { d[0] = sg; d[1] = u; d[2] = v; }
-    else if (face < 4u) { d[0] = u; d[1] = sg; d[2] = v; }
-    else { d[0] = u; d[1] = v; d[2] = sg; }
-    const float inv_n = 1.f / __builtin_sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    ro[key] = make_float4(o[0], o[1], o[2], 0.f);
-    rd[key] = make_float4(d[0] * inv_n, d[1] * inv_n, d[2] * inv_n, 0.f);
-}
-// Complete keys (device/occ_beam.hpp): one thread per table key walks the child-pair tree with the
-// key's beam; a key with at most kOccWays candidates gets them as marked words (the rest of its ways
-// the marked empty word), every other key keeps what the pre-fill left.
-__global__ void k_occ_complete(DevScene sc, mcpt::OccTree tree, uint32_t nkeys, uint32_t* ndone) {
-    const uint32_t key = blockIdx.x * blockDim.x + threadIdx.x;
-    bool done = false;
-    if (key < nkeys) {
-        const uint32_t G = (uint32_t)sc.occ_g, B = (uint32_t)sc.occ_b;
-        uint32_t t = key, cx, cy, cz, face, ub, vb;
-#if MCPT_OCC_LAYOUT == 1
-        cx = t % G; t /= G; cy = t % G; t /= G; cz = t % G; t /= G; vb = t % B; t /= B; ub = t % B; face = t / B;
-#else
-        vb = t % B; t /= B; ub = t % B; t /= B; face = t % 6u; t /= 6u; cx = t % G; t /= G; cy = t % G; cz = t / G;
-#endif
-        const mcpt::OccGrid g{{sc.root_mn[0], sc.root_mn[1], sc.root_mn[2]}, {sc.occ_cell[0], sc.occ_cell[1], sc.occ_cell[2]},
-                              sc.occ_g, sc.occ_b, sc.occ_dir};
-        const mcpt::Beam b = mcpt::occ_key_beam(g, cx, cy, cz, (face * B + ub) * B + vb);
-        uint32_t list[kOccWays];
-        const int n = mcpt::occ_key_list(tree, b, (int)kOccWays, list);
-        if (n >= 0) {
-            done = true;
-            for (uint32_t w = 0; w < kOccWays; w++)
-                sc.occ[(size_t)key * kOccWays + w] = (int)w < n ? (mcpt::kOccDoneBit | list[w]) : mcpt::kOccDoneNone;
-        }
-    }
-    const uint32_t cnt = (uint32_t)__popcll(__ballot(done));
-    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(ndone, cnt);
-}
-void launch_occ_complete(const DevScene& sc, const mcpt::OccTree& tree, uint32_t nkeys, uint32_t* ndone, hipStream_t s) {
-    if (nkeys == 0) return;
-    hipLaunchKernelGGL(k_occ_complete, dim3((nkeys + 255) / 256), dim3(256), 0, s, sc, tree, nkeys, ndone);
-}
-void launch_occ_probes(const DevScene& sc, float4* ro, float4* rd, uint32_t nkeys, hipStream_t s) {
-    if (nkeys == 0) return;
-    hipLaunchKernelGGL(k_occ_probes, dim3((nkeys + 255) / 256), dim3(256), 0, s, sc, ro, rd, nkeys);
-}
-void launch_occ_records(const DevScene& sc, uint32_t nnodes, float4* rec, hipStream_t s) {
-    hipLaunchKernelGGL(k_occ_records, dim3(nnodes / 256 + 1), dim3(256), 0, s, sc, nnodes, rec);
-}
-void launch_clear(const ClearArgs& a, hipStream_t s) {
-    if (a.n == 0) return;  // an empty tile set (compact layout): nothing to launch, no zero-sized grid
-    hipLaunchKernelGGL(k_clear, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
-}
-void launch_hit_record(const HitRecordArgs& a, hipStream_t s) {
-    if (a.n == 0) return;
-    hipLaunchKernelGGL(k_hit_record, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
-}
-void launch_resolve(const ResolveArgs& a, hipStream_t s) {
-    if (a.n == 0) return;
-    hipLaunchKernelGGL(k_resolve, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
-}
-void launch_tonemap(const TonemapArgs& a, hipStream_t s) {
-    if (a.n == 0) return;
-    hipLaunchKernelGGL(k_tonemap, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
-}
-void launch_accumulate(CounterBlock* c, uint32_t nparts, uint32_t* occ_gate, hipStream_t s) {
-    hipLaunchKernelGGL(k_accumulate, dim3(1), dim3(kShards), 0, s, c, std::min<uint32_t>(kMaxParts, std::max<uint32_t>(1, nparts)),
-                       occ_gate);
-}
-void launch_unpack(const UnpackArgs& a, hipStream_t s) {
-    const uint32_t n = (uint32_t)(a.ntiles * a.tile_w * a.tile_h);
-    if (n) hipLaunchKernelGGL(k_unpack, dim3((n + 255) / 256), dim3(256), 0, s, a);
-}
-void launch_pack(const PackArgs& a, hipStream_t s) {
-    uint32_t n = (uint32_t)(a.ntiles * a.tile_w * a.tile_h);
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_pack, dim3((n + 255) / 256), dim3(256), 0, s, a);
 }
 
 }  // namespace mcpt_dev

@@ -1,4 +1,4 @@
-// kernels.hpp -- device data layout shared by kernels.hip and runtime.hip.
+// kernels.hpp -- device data layout shared by the .hip files and the host runtime (runtime.cpp).
 //
 // HBM layout (P = slots * W*H paths; slot 0 is the reference's one path per pixel, path_id ==
 // pixel_id, wavefront_kernels.cu:108,114).  The reference's Paths is an array-of-structs with a
@@ -329,14 +329,18 @@ struct LaunchGeom {
     uint32_t shade_grid;     // k_shade grid cap (resident blocks x MCPT_SHADE_GRID; 0: one block per shading block)
     uint32_t refill_min, tri_min;  // MCPT_REFILL_MIN, MCPT_TRI_MIN
 };
+
+// ---- wavefront iteration (kernels.hip) ----
 int launch_geometry(int device, LaunchGeom& g);  // device must be current
 void launch_shade(const ShadeArgs& a, int nblocks, const LaunchGeom& g, bool fixed_mode, hipStream_t s);
 void launch_shade_stage(bool material_stage, const ShadeArgs& a, int nblocks, const LaunchGeom& g, bool fixed_mode,
                         hipStream_t s);
-void launch_trace(const TraceArgs& a, const LaunchGeom& g, hipStream_t s);
 void launch_primary(const ShadeArgs& a, const LaunchGeom& g, hipStream_t s);  // k_primary: after k_shade, before k_trace
-void launch_primary_build(const PrimaryBuildArgs& a, hipStream_t s);
-void launch_clear(const ClearArgs& a, hipStream_t s);
+void launch_trace(const TraceArgs& a, const LaunchGeom& g, hipStream_t s);
+void launch_accumulate(CounterBlock* c, uint32_t nparts, uint32_t* occ_gate, hipStream_t s);
+int shade_sections(unsigned long long* out, int n, int reset);  // -DMCPT_DIAG_SHADE builds (else 0)
+
+// ---- scene tables (scene_tables.hip) ----
 // Occluder records (DevScene::occ_rec): for each triangle record t, {leaf mn, margin} {leaf mx,
 // v0.x} {v0.yz, e1.xy} {e1.z, e2} of the leaf that holds it (nodes: nnodes nodes of the given
 // width; a root that is itself a leaf gets the root box)
@@ -354,6 +358,21 @@ void launch_cull_margins(float4* nodes, uint32_t npairs, const float4* tri, uint
                          uint32_t* pmax, int passes, bool plane, hipStream_t s);
 // Its first step alone: tri_w and *pmax (max) from the records (the refit fuses the passes with its boxes)
 void launch_cull_tri(const float4* tri, uint32_t ntri, float* tri_w, uint32_t* pmax, bool plane, hipStream_t s);
+void launch_primary_build(const PrimaryBuildArgs& a, hipStream_t s);
+void launch_cam_table(const mcpt::CamView& cam, int W, int H, float4* px, float4* dir, hipStream_t s);
+// tex[i].w = pdf[i], i < n (EnvView::tex: the pdf in the texture's alpha plane)
+void launch_env_pack(float4* tex, const float* pdf, size_t n, hipStream_t s);
+void launch_env_table(const mcpt::EnvView& e, bool fixed_mode, float4* out, float2* row, float2* col, hipStream_t s);
+
+// ---- film (film.hip) ----
+void launch_clear(const ClearArgs& a, hipStream_t s);
+void launch_resolve(const ResolveArgs& a, hipStream_t s);
+void launch_tonemap(const TonemapArgs& a, hipStream_t s);
+void launch_pack(const PackArgs& a, hipStream_t s);
+void launch_unpack(const UnpackArgs& a, hipStream_t s);
+void launch_hit_record(const HitRecordArgs& a, hipStream_t s);
+void launch_quot(const float* a, const float* b, float* out, uint32_t n, hipStream_t s);
+void launch_copy(const float4* src, float4* dst, size_t n, hipStream_t s);
 
 // ---- geometry update (refit.hip) ----
 // k_geom_records: record i of tri (and of sh where n0 is given) from vertices order[i] (nullptr: i) of
@@ -378,9 +397,6 @@ constexpr uint32_t kQuadNoSrc = 0xffffffffu;
 void launch_quad_regather(float4* quads, uint32_t nquads, const uint32_t* src, const float4* pairs, uint32_t npairs,
                           hipStream_t s);
 
-// tex[i].w = pdf[i], i < n (EnvView::tex: the pdf in the texture's alpha plane)
-void launch_env_pack(float4* tex, const float* pdf, size_t n, hipStream_t s);
-void launch_env_table(const mcpt::EnvView& e, bool fixed_mode, float4* out, float2* row, float2* col, hipStream_t s);
 // HRDI tables on the device (env_build.hip), bit-identical to the host build: scratch holds
 // env_build_scratch_floats(W, H) floats; W * H < 2^31.
 size_t env_build_scratch_floats(int W, int H);
@@ -415,18 +431,6 @@ __host__ __device__ constexpr uint32_t ploc_merge(uint32_t a, uint32_t b) {
 }
 int build_lbvh(const LbvhInput& in, LbvhOutput& out, hipStream_t s);
 int build_ploc(const LbvhInput& in, LbvhOutput& out, hipStream_t s);
-int trace_profile(unsigned long long* out, int reset);
-int wave_times(unsigned long long* out, int n);
-int shade_sections(unsigned long long* out, int n, int reset);  // -DMCPT_DIAG_SHADE builds (else 0)
-void launch_cam_table(const mcpt::CamView& cam, int W, int H, float4* px, float4* dir, hipStream_t s);
-void launch_quot(const float* a, const float* b, float* out, uint32_t n, hipStream_t s);
-void launch_copy(const float4* src, float4* dst, size_t n, hipStream_t s);
-void launch_hit_record(const HitRecordArgs& a, hipStream_t s);
-void launch_tonemap(const TonemapArgs& a, hipStream_t s);
-void launch_resolve(const ResolveArgs& a, hipStream_t s);
-void launch_accumulate(CounterBlock* c, uint32_t nparts, uint32_t* occ_gate, hipStream_t s);
-void launch_pack(const PackArgs& a, hipStream_t s);
-void launch_unpack(const UnpackArgs& a, hipStream_t s);
 
 // ---- preview denoiser (denoise.hip) ----
 // Its two switches, for A/B runs and tests; neither changes a result.  (As with kPrimaryHitsEnv, bench.py

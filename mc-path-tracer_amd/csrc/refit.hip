@@ -5,7 +5,7 @@
 // tree that is already there gets new boxes and culling margins without a change of topology:
 //   1. k_geom_records: records (v0, e1 = v1 - v0, e2 = v2 - v0; the same float32 operations as the
 //      upload's host loop) and each record's vertex box (exact min / max, as k_prim_boxes);
-//   2. k_cull_tri (kernels.hip) gives every record its margin W'_T and the far coefficient P;
+//   2. k_cull_tri (scene_tables.hip) gives every record its margin W'_T and the far coefficient P;
 //   3. k_refit_reset: every leaf child's box (the union of its records' boxes) and margin; every
 //      interior child's words start empty (box +inf / -inf, margin 0);
 //   4. k_refit_pass x (depth + 2): an interior child's box and margin are the union / maximum of

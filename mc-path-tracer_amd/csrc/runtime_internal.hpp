@@ -1,7 +1,7 @@
 // runtime_internal.hpp -- what runtime.cpp (context, film, render loop), scene_upload.cpp (scene upload
-// and geometry update) and postprocess.cpp (guides, denoise, adaptive sampling, temporal accumulation)
-// share: the device context behind the mcpt_* C ABI, its error helpers, the owner of a device buffer
-// and a few host helpers.
+// and geometry update), postprocess.cpp (guides, denoise, adaptive sampling, temporal accumulation) and
+// stage_run.cpp (per-stage parity harness, debug entries) share: the device context behind the mcpt_* C
+// ABI, its error helpers, the owner of a device buffer and a few host helpers.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,5 +1,5 @@
-"""Complete keys of the any-hit occluder table (device/occ_beam.hpp, kernels.hip
-k_occ_complete, occ_hit1): an entry that lists every triangle a ray of its key can be accepted on resolves
+"""Complete keys of the any-hit occluder table (device/occ_beam.hpp, scene_tables.hip
+k_occ_complete, kernels.hip occ_hit1): an entry that lists every triangle a ray of its key can be accepted on resolves
 such a ray either way, so films, sample counts and ray totals with the lists and with MCPT_OCC_COMPLETE=0
 are bit-identical, and the rays the lists resolve are exactly the rays that leave the traversal.
 

@@ -1,5 +1,5 @@
 """Primary hits from the per-pixel candidate table (kernels.hip k_primary,
-k_primary_build): the table decides only which primary rays skip the traversal, never a hit, so films,
+scene_tables.hip k_primary_build): the table decides only which primary rays skip the traversal, never a hit, so films,
 sample counts and ray counts with it and with MCPT_PRIMARY_HITS=0 are bit-identical."""
 import os
 import subprocess

@@ -102,7 +102,7 @@ int main(int argc, char** argv) {
     const float gm = (float)(in.G - 1), bm = (float)(in.B - 1), hb = 0.5f * (float)in.B;
     for (int r = 0; r < in.nrays; r++) {
         const V3 o = v3(in.ro[3 * r], in.ro[3 * r + 1], in.ro[3 * r + 2]), d = v3(in.rd[3 * r], in.rd[3 * r + 1], in.rd[3 * r + 2]);
-        // kernels.hip occ_coords (an exact reciprocal for the device's rcp: the membership test decides)
+        // device/scene_dev.hpp occ_coords (an exact reciprocal for the device's rcp: the membership test decides)
         uint32_t c[3];
         const float oo[3] = {o.x, o.y, o.z};
         for (int k = 0; k < 3; k++) c[k] = (uint32_t)std::fmin(std::fmax((oo[k] - g.mn[k]) * inv[k], 0.f), gm);
