@@ -3,7 +3,7 @@
 // INTEGRATION.md): build a BASELINE config scene with the host builder, upload it,
 // run the wavefront iterations until every pixel has its samples, write PNG + PFM.
 //
-//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>]
+//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>] [--emissive <mat> <r> <g> <b>]... [--env-color <r> <g> <b>]
 //
 // --denoise renders the first-hit guide buffers (default 4 guide samples per pixel), filters the film
 // with the default parameters and writes <out_prefix>_denoised.png beside the raw image.
@@ -28,6 +28,11 @@
 // --temporal (the longer of the two frame counts; an update drops the temporal history, there being no
 // motion vectors for moved geometry) and with --denoise / --denoise-guided (the last frame); not with
 // --tiles-per-call or --adaptive (rejected).
+// --emissive makes material <mat> of the config's scene emit the radiance <r> <g> <b> (DESIGN.md section
+// 16; repeatable; the ids are the scene's materials in the order its meshes were added: in config 2 the
+// back wall, floor, ceiling, left and right wall are 0..4 and the spheres 5..9).  --env-color replaces the
+// config's environment map with a constant colour: `mcpt_render 2 64 --emissive 2 8 8 8 --env-color 0 0 0`
+// is a Cornell box lit by its ceiling alone.  Emitters are not sampled as lights, so small ones are noisy.
 // --tiles-per-call uses the reference orchestration (one 256x256 tile per call,
 // wavefront_kernels.cu:377-442 + Film::update_tile_position) instead of batch mode.
 #include <math.h>
@@ -59,7 +64,7 @@ static void warp(const mcpt_scene_desc& d, float amp, uint32_t frame, uint32_t f
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>]\n", argv[0]);
+        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>] [--emissive <mat> <r> <g> <b>]... [--env-color <r> <g> <b>]\n", argv[0]);
         return 2;
     }
     const Cfg cfgs[6] = {{0, 0, 0, 0, {0, 0, 0}, 0, ""},
@@ -83,11 +88,25 @@ int main(int argc, char** argv) {
     float t_yaw = 0.f;
     uint32_t a_frames = 0;  // > 0: --animate
     float a_amp = 0.f;
+    std::vector<float> emissive;  // --emissive: {mat, r, g, b} per use
+    float env_rgb[3] = {0.f, 0.f, 0.f};
+    bool env_given = false;
     for (int i = 2; i < argc; i++) {
         if (!strcmp(argv[i], "--animate")) {
             if (i + 2 >= argc || atoi(argv[i + 1]) < 1) { fprintf(stderr, "--animate needs <frames> <amplitude>\n"); return 2; }
             a_frames = (uint32_t)atoi(argv[++i]);
             a_amp = (float)atof(argv[++i]);
+            continue;
+        }
+        if (!strcmp(argv[i], "--emissive")) {
+            if (i + 4 >= argc) { fprintf(stderr, "--emissive needs <mat> <r> <g> <b>\n"); return 2; }
+            for (int k = 0; k < 4; k++) emissive.push_back((float)atof(argv[++i]));
+            continue;
+        }
+        if (!strcmp(argv[i], "--env-color")) {
+            if (i + 3 >= argc) { fprintf(stderr, "--env-color needs <r> <g> <b>\n"); return 2; }
+            for (int k = 0; k < 3; k++) env_rgb[k] = (float)atof(argv[++i]);
+            env_given = true;
             continue;
         }
         if (!strcmp(argv[i], "--temporal")) {
@@ -130,12 +149,18 @@ int main(int argc, char** argv) {
     mcpt_scene* s = mcpt_scene_new();
     // host BVH: binned 3-axis SAH (default) or BVHAccel's builder; films are identical either way
     mcpt_bvh_params bp = {MCPT_BVH_SAH3, 8, 128, 0.5f, 1.0f};
-    if (!s || mcpt_scene_make_proxy(s, id, assets) || (ref_bvh ? mcpt_scene_build(s, 8) : mcpt_scene_build_ex(s, &bp))) {
+    int src = !s || mcpt_scene_make_proxy(s, id, assets);
+    if (!src && env_given) src = mcpt_scene_set_env_color(s, env_rgb, 1.f);
+    for (size_t k = 0; !src && k < emissive.size(); k += 4) src = mcpt_scene_set_material_emission(s, (int32_t)emissive[k], &emissive[k + 1]);
+    if (src || (ref_bvh ? mcpt_scene_build(s, 8) : mcpt_scene_build_ex(s, &bp))) {
         fprintf(stderr, "scene: %s\n", mcpt_last_error(nullptr));
         return 1;
     }
     mcpt_scene_desc d;
     mcpt_scene_get_desc(s, &d);
+    const float* em_rgb = nullptr;  // the scene's emission table travels beside the desc
+    int32_t em_nmat = 0;
+    mcpt_scene_get_emission(s, &em_rgb, &em_nmat);
 
     // PathTracer::PathTracer
     mcpt_config cfg{0x5EED2026ull, c.spp, c.depth, 3, 256, 256, fixed ? MCPT_FLAG_FIXED : 0};
@@ -145,6 +170,7 @@ int main(int argc, char** argv) {
         return 1;
     }
     int rc = gpu_bvh ? mcpt_scene_upload_gpu_bvh(ctx, &d) : mcpt_scene_upload(ctx, &d);
+    if (!rc && em_rgb) rc = mcpt_set_material_emission(ctx, em_nmat, em_rgb);
     // Camera::update
     mcpt_camera_params cp{{c.pos[0], c.pos[1], c.pos[2]}, -90.f, c.pitch, 0.785398163f, (float)c.w / (float)c.h,
                           0.01f, 1e4f, 1e-4f, 35.f};

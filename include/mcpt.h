@@ -555,6 +555,27 @@ int mcpt_set_variance_fill(mcpt_ctx *ctx, const mcpt_variance_params *p);
 /* Device time (ms) of the last k_variance_spatial launch.  (Where it runs inside a film denoise, the
  * plane set-up time of mcpt_debug_denoise_ms includes it.) */
 int mcpt_debug_variance_ms(const mcpt_ctx *ctx, float *out1);
+/* ---- emissive materials: a per-material table of emitted radiance.  A path
+ * collects the emission of the surface it hit exactly when the logic stage lets it continue into the
+ * material stage from that hit (a hit, len <= max_depth, a non-zero sample, the roulette survived):
+ *   film += Le[material of the hit] * beta, beta the throughput the logic stage stores for the path
+ * after the vertex's MIS terms and the roulette.  len 1 is the primary hit (beta = 1): the term the
+ * reference leaves at zero (wavefront_kernels.cu:132).  Two-sided (emissive_L has no normal test).
+ * Emitters are not sampled as lights: paths, random draws and ray counts are those of the same
+ * scene without emission, and only the film differs.  Opt-in: a context without a table, or with an
+ * all-zero one, launches the kernels it launched before.
+ *
+ * mcpt_set_material_emission installs rgb (3 * nmat floats of radiance, copied); NULL removes the
+ * table.  MCPT_E_INVALID, the installed table staying: no scene, nmat different from the uploaded
+ * scene's, an entry that is negative or not finite.  Values that differ bitwise from the installed
+ * ones mark the film stale as mcpt_camera_set with a different camera does (cleared by the next
+ * iteration unless MCPT_FLAG_NO_AUTO_CLEAR) and drop the temporal history; the guide buffers stay
+ * valid.  Identical values do nothing.  mcpt_scene_update_geometry* keeps the table (it is keyed by
+ * material id, not by triangle); a scene upload drops it.  mcpt_stage_run(MCPT_STAGE_LOGIC) applies it.
+ * mcpt_material_emission_read copies the table (rgb may be NULL) and its size; it returns the number
+ * of materials with a non-zero entry, 0 with *nmat = 0 when no table is installed, or an error code. */
+int mcpt_set_material_emission(mcpt_ctx *ctx, int32_t nmat, const float *rgb);
+int mcpt_material_emission_read(mcpt_ctx *ctx, float *rgb, int32_t *nmat);
 int mcpt_sync(mcpt_ctx *ctx);
 int mcpt_device_name(mcpt_ctx *ctx, char *buf, int32_t len);
 /* diagnostics: rays of the current extension (which=0) or any-hit (which=1) queue, and the
@@ -657,6 +678,14 @@ void mcpt_scene_free(mcpt_scene *s);
 int mcpt_scene_load_glb(mcpt_scene *s, const char *path, const float *xform16);  /* xform may be NULL */
 int mcpt_scene_add_mesh(mcpt_scene *s, int32_t ntri, const float *v0, const float *v1, const float *v2,
                         const float *n0, const float *n1, const float *n2, const float *base_rgb);
+/* Emitted radiance per material (mcpt_set_material_emission takes the array as it is).  mat: a material
+ * id as in mcpt_scene_get_desc's mat array, one material per added mesh (glb primitive) in add order;
+ * a glb material's is emissiveFactor x KHR_materials_emissive_strength.emissiveStrength (defaults 0, 1).
+ * MCPT_E_INVALID: mat out of range, an entry that is negative or not finite.  get: the 3 * nmat floats,
+ * owned by the scene (valid until the next mesh is added); *rgb = NULL when every entry is zero.  The
+ * scene desc does not carry the table. */
+int mcpt_scene_set_material_emission(mcpt_scene *s, int32_t mat, const float *rgb);
+int mcpt_scene_get_emission(const mcpt_scene *s, const float **rgb, int32_t *nmat);
 int mcpt_scene_set_env_hdr(mcpt_scene *s, const char *path, int32_t mode);
 /* flags MCPT_ENV_DEVICE_TABLES: keep the texture only; mcpt_scene_upload then builds the tables on
  * the device (for large maps: the host build is several serial passes over every texel). */

@@ -230,6 +230,21 @@ public:
         detail::check(mcpt_scene_add_mesh(s_, ntri, v0, v1, v2, n0, n1, n2, rgb), nullptr, "Scene::add_mesh");
         geometry_changed();
     }
+    // MI355X extension: emitted radiance of material `mat` (one material per added mesh or glb
+    // primitive, in add order; a glb's emissiveFactor x emissive strength is read by load).  PathTracer
+    // installs the scene's table after it uploads the scene (mcpt.h, mcpt_set_material_emission).
+    void set_material_emission(int32_t mat, vec3 radiance) {
+        const float rgb[3] = {radiance.x, radiance.y, radiance.z};
+        detail::check(mcpt_scene_set_material_emission(s_, mat, rgb), nullptr, "Scene::set_material_emission");
+        notify();
+    }
+    // 3 floats per material; empty when no material emits
+    std::vector<float> material_emission() const {
+        const float* rgb = nullptr;
+        int32_t nmat = 0;
+        detail::check(mcpt_scene_get_emission(s_, &rgb, &nmat), nullptr, "Scene::material_emission");
+        return rgb ? std::vector<float>(rgb, rgb + 3 * (size_t)nmat) : std::vector<float>();
+    }
     // MI355X extension: the BASELINE config proxies of SURVEY.md 8(d) (geometry + environment).
     void make_proxy(int config_id, const std::string& asset_dir) {
         detail::check(mcpt_scene_make_proxy(s_, config_id, asset_dir.c_str()), nullptr, "Scene::make_proxy");
@@ -655,6 +670,25 @@ public:
         detail::check(mcpt_debug_geometry_update_ms(ctx_, ms.data()), ctx_, "geometry_update_ms");
         return ms;
     }
+    // Emissive materials (mcpt.h): the emission table of the scene the last render uploaded, 3 floats of
+    // radiance per material (empty: remove it).  A path collects the emission of every surface it
+    // continues from; emitters are not sampled as lights.  A change clears the device film at the next
+    // render (the context marks it stale); the next upload of an edited Scene installs that Scene's table.
+    void set_material_emission(const std::vector<float>& rgb) {
+        if (rgb.size() % 3) throw Error(MCPT_E_INVALID, "set_material_emission: 3 floats per material");
+        detail::check(mcpt_set_material_emission(ctx_, (int32_t)(rgb.size() / 3), rgb.empty() ? nullptr : rgb.data()), ctx_,
+                      "set_material_emission");
+    }
+    // Returns the number of materials with a non-zero entry; rgb is empty when no table is installed
+    int material_emission(std::vector<float>& rgb) {
+        int32_t nmat = 0;
+        int lit = mcpt_material_emission_read(ctx_, nullptr, &nmat);
+        if (lit < 0) detail::check(lit, ctx_, "material_emission");
+        rgb.resize(3 * (size_t)nmat);
+        if (nmat) lit = mcpt_material_emission_read(ctx_, rgb.data(), &nmat);
+        if (lit < 0) detail::check(lit, ctx_, "material_emission");
+        return lit;
+    }
     // Adaptive sampling (mcpt.h): a per-pixel sample budget (W*H entries; empty: remove it) in place of
     // the uniform spp, and the uniform spp of the live context.  Neither clears the film: the next
     // render_frame renders on.  Call them once the film's size is the context's (after a render).
@@ -716,6 +750,8 @@ private:
             std::vector<float> dir_params;
             const mcpt_scene_desc d = scene.desc(dir_params);
             detail::check(mcpt_scene_upload(ctx_, &d), ctx_, "scene upload");
+            const std::vector<float> em = scene.material_emission();  // the upload dropped the previous table
+            if (!em.empty()) detail::check(mcpt_set_material_emission(ctx_, d.nmat, em.data()), ctx_, "scene emission");
             scene_ = &scene;
             scene_state_ = st;
             edited = true;

@@ -1,4 +1,5 @@
 // capi_host.cpp -- extern "C" entry points of the host scene builder (mcpt_scene_*).
+#include <cmath>
 #include <cstring>
 #include <new>
 
@@ -114,6 +115,22 @@ int mcpt_scene_get_desc(const mcpt_scene* s, mcpt_scene_desc* out) {
     if (!s || !out) return MCPT_E_INVALID;
     if (!s->s.built) return fail(const_cast<mcpt_scene*>(s), MCPT_E_INVALID, "scene not built");
     s->s.desc(out);
+    return MCPT_OK;
+}
+
+int mcpt_scene_set_material_emission(mcpt_scene* s, int32_t mat, const float* rgb) {
+    if (!s || !rgb) return fail(s, MCPT_E_INVALID, "null argument");
+    if (mat < 0 || (size_t)mat >= s->s.emission.size() / 3) return fail(s, MCPT_E_INVALID, "material id out of range");
+    for (int k = 0; k < 3; k++)
+        if (!(rgb[k] >= 0.f) || !std::isfinite(rgb[k])) return fail(s, MCPT_E_INVALID, "emission must be finite and >= 0");
+    for (int k = 0; k < 3; k++) s->s.emission[3 * (size_t)mat + k] = rgb[k];
+    return MCPT_OK;
+}
+
+int mcpt_scene_get_emission(const mcpt_scene* s, const float** rgb, int32_t* nmat) {
+    if (!s || !rgb || !nmat) return MCPT_E_INVALID;
+    *nmat = (int32_t)(s->s.emission.size() / 3);
+    *rgb = s->s.has_emission() ? s->s.emission.data() : nullptr;
     return MCPT_OK;
 }
 

@@ -20,6 +20,7 @@ struct Scene {
     // meshes (Scene::render_objects, Mesh.cu:35-60), world space
     std::vector<Tri> tris;
     std::vector<float> materials;   // 8 floats per material (dMaterial.cuh:11-33)
+    std::vector<float> emission;    // 3 floats per material: emitted radiance (dMaterial.cuh:14-24, emissive_L)
     std::vector<float> dir_lights;  // 7 floats per light (DirectionalLight.h)
     // environment light (EnvironmentLight.h:17-40); default Color 0.8 (Scene.cu:21)
     int env_mode = 0;
@@ -39,7 +40,8 @@ struct Scene {
     std::string err;
 
     void add_mesh(const std::vector<mcpt::V3>& pos, const std::vector<mcpt::V3>& nrm,
-                  const std::vector<uint32_t>& idx, mcpt::V3 base);
+                  const std::vector<uint32_t>& idx, mcpt::V3 base, mcpt::V3 emit = mcpt::v3(0.f, 0.f, 0.f));
+    bool has_emission() const;  // some material emits
     void transform(const float* xf16);
     int load_glb(const char* path, const float* xf16, std::string& err);
     int set_env_hdr(const char* path, int mode, std::string& err, bool host_tables = true);

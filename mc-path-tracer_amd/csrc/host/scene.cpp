@@ -199,10 +199,12 @@ static M4 trs_matrix(const float* t, const float* q, const float* s) {  // glTF 
 // Scene
 // ---------------------------------------------------------------------------
 void Scene::add_mesh(const std::vector<V3>& pos, const std::vector<V3>& nrm, const std::vector<uint32_t>& idx,
-                     V3 base) {
+                     V3 base, V3 emit) {
     int mat_id = (int)(materials.size() / 8);
     float mp[8] = {base.x, base.y, base.z, 0.04f, 0.04f, 0.04f, 1.f, 0.f};  // dMaterial.cuh:13-18, Scene.cu:306-307
     materials.insert(materials.end(), mp, mp + 8);
+    const float em[3] = {emit.x, emit.y, emit.z};
+    emission.insert(emission.end(), em, em + 3);
     for (size_t i = 0; i + 2 < idx.size(); i += 3) {
         Tri t;
         for (int k = 0; k < 3; k++) { t.p[k] = pos[idx[i + k]]; t.n[k] = nrm[idx[i + k]]; }
@@ -361,14 +363,24 @@ int Scene::load_glb(const char* path, const float* xf16, std::string& err) {
                     for (uint32_t ix : idx)
                         if (ix >= nv) { err = "glb: index out of range"; status = MCPT_E_IO; return; }
                     V3 bc = mcpt::v3(1.f, 1.f, 1.f);
+                    V3 em = mcpt::v3(0.f, 0.f, 0.f);
                     int mati = (int)pr.numv("material", -1);
                     if (mats && mati >= 0 && mati < (int)mats->arr.size()) {
                         const Json* pbr = mats->arr[mati].get("pbrMetallicRoughness");
                         const Json* bcf = pbr ? pbr->get("baseColorFactor") : nullptr;
                         if (bcf && bcf->arr.size() >= 3)
                             bc = mcpt::v3((float)bcf->arr[0].num, (float)bcf->arr[1].num, (float)bcf->arr[2].num);
+                        // emitted radiance: emissiveFactor (default 0) x KHR_materials_emissive_strength's
+                        // emissiveStrength (default 1), as Scene.cu:299-304 reads the two
+                        const Json* ef = mats->arr[mati].get("emissiveFactor");
+                        const Json* ext = mats->arr[mati].get("extensions");
+                        const Json* es = ext ? ext->get("KHR_materials_emissive_strength") : nullptr;
+                        const float strength = es ? (float)es->numv("emissiveStrength", 1.0) : 1.f;
+                        if (ef && ef->arr.size() >= 3)
+                            em = mcpt::v3((float)ef->arr[0].num * strength, (float)ef->arr[1].num * strength,
+                                          (float)ef->arr[2].num * strength);
                     }
-                    add_mesh(pos, nrm, idx, bc);
+                    add_mesh(pos, nrm, idx, bc, em);
                 }
             }
         }
@@ -951,6 +963,12 @@ void Scene::desc(mcpt_scene_desc* d) const {
     d->env_conds_y = env_conds_y.empty() ? nullptr : env_conds_y.data();
     d->env_pdf = env_pdf.empty() ? nullptr : env_pdf.data();
     d->tri_id = f_id.empty() ? nullptr : f_id.data();
+}
+
+bool Scene::has_emission() const {
+    for (float e : emission)
+        if (e != 0.f) return true;
+    return false;
 }
 
 // ---------------------------------------------------------------------------

@@ -753,7 +753,10 @@ __device__ inline uint32_t udiv_small(uint32_t n, uint32_t d, float rcp) {
 // One shading block: logic + generate for kBlock pixels of a path slot, then the block's pushes.
 // MAP: the pixel's sample budget (ShadeArgs::budget) stands in for spp.  An instantiation of its own,
 // so the no-map kernel is the code it was.
-template <bool FIXED, bool MAP>
+// EMIT: a path that continues into the material stage collects the emission of the surface it hit
+// (ShadeArgs::emis).  Instantiations of their own again: without a table the
+// kernels are the code they were.
+template <bool FIXED, bool MAP, bool EMIT>
 __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeArgs& a, int vb, const VBlk& v) {
     const DevScene& sc = a.scene;
     const int slot = (int)(v.sr & 0xffu);
@@ -789,8 +792,13 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
     // temporaries on top of the logic's live values set the kernel's register peak (81 VGPRs,
     // 5 waves per SIMD, against 48 without it).  Nothing else touches such a path's film in
     // this iteration, so the order of the two film updates does not change a bit.
+    // Emission is added there too, for the same reason: its two dependent lookups (the hit's shading
+    // record for the material id, then the table) would otherwise sit on top of the logic's live
+    // values.  A path with a hit has no background, so bg_film carries the film of either; the
+    // triangle travels in cont_htri and the weight in beta_store, both live across the pushes anyway.
     bool bg = false;
     V3 bg_film = v3(0.f, 0.f, 0.f), bg_dir = bg_film;
+    bool em = false, em_dirty = false;  // collects emission; its film already differs from the stored one
     bool finished = true;  // dead with its last sample done (or no pixel): see blk_done
     if (valid) {
         // Every load the logic may need is issued up front, in one round: the
@@ -807,7 +815,8 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
         // or a vertex with MIS terms.  Elsewhere the update is film + 0 * beta, which leaves
         // the film's bits unchanged (Ld is never -0: it starts at +0 and every update adds to
         // it), so neither the load nor the store is needed.
-        const bool need_ld = !(fl & F_DEAD) && (need_rd || need_nee);
+        // (EMIT: also at a primary hit, whose emission is the term the reference leaves at zero)
+        const bool need_ld = !(fl & F_DEAD) && (need_rd || need_nee || (EMIT && len == 1 && htri >= 0));
         const V3 ld4 = ld3f4(a.p.Ld + (need_ld ? pid : 0u));  // .w is always 0 (k_clear, k_resolve): xyz only
         const V3 rd = ld3f4(a.p.ray_d + (need_rd ? pid : 0u));
         const float4 n0 = ld_s(a.p.nee0 + (need_nee ? pid : 0u)), n1 = ld_s(a.p.nee1 + (need_nee ? pid : 0u));
@@ -870,10 +879,22 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
                 }
             }
             // film unchanged bit for bit (a zero contribution): the store would rewrite the same bytes
-            if (need_ld && (__float_as_uint(film.x) != __float_as_uint(ld4.x) ||
-                            __float_as_uint(film.y) != __float_as_uint(ld4.y) ||
-                            __float_as_uint(film.z) != __float_as_uint(ld4.z)))
-                st_s(a.p.Ld + pid, f4(film, 0.f));
+            const bool film_dirty = need_ld && (__float_as_uint(film.x) != __float_as_uint(ld4.x) ||
+                                                __float_as_uint(film.y) != __float_as_uint(ld4.y) ||
+                                                __float_as_uint(film.z) != __float_as_uint(ld4.z));
+            if constexpr (EMIT) {
+                // The logic lets the path continue into the material stage from this hit: found,
+                // len <= max_depth, a non-zero sample, the roulette survived (beta_store is final).
+                // The skip switch's early end below (dd) is such a path too: the reference runs its
+                // material stage.  Its film is written once, after the pushes, with the emission.
+                em = !terminate;
+                if (em) {
+                    em_dirty = film_dirty;
+                    bg_film = film;
+                    cont_htri = htri;
+                }
+            }
+            if (film_dirty && !(EMIT && em)) st_s(a.p.Ld + pid, f4(film, 0.f));
             // A continuing path the next logic pass (vertex len + 1) is certain to end (ShadeArgs::skip).
             if (a.skip && !terminate) {
                 if (len + 1u > (uint32_t)a.max_depth) {
@@ -1007,6 +1028,16 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
             __float_as_uint(film.z) != __float_as_uint(bg_film.z))
             a.p.Ld[pid] = f4(film, 0.f);
     }
+    if constexpr (EMIT) {
+        MCPT_MARK("emission");
+        if (em) {  // film += Le[mat(hit_tri)] * beta_store, two-sided (emissive_L: no normal test)
+            const int mat = __float_as_int(sc.tri_sh[3 * cont_htri + 2].y);  // the word k_material reads (hit_record)
+            const V3 film = bg_film + ld3f4(a.emis + mat) * beta_store;
+            if (em_dirty || __float_as_uint(film.x) != __float_as_uint(bg_film.x) ||
+                __float_as_uint(film.y) != __float_as_uint(bg_film.y) || __float_as_uint(film.z) != __float_as_uint(bg_film.z))
+                a.p.Ld[pid] = f4(film, 0.f);
+        }
+    }
     MCPT_MARK("done");
     if (a.blk_done && __syncthreads_and(finished ? 1 : 0) && threadIdx.x == 0) a.blk_done[v.done] = 1;
     MCPT_MARK("end");
@@ -1019,7 +1050,7 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
 // (one workgroup per shading block, G = the block count) paid ~0.2 ms per launch just to dispatch
 // and retire config 2's 246K workgroups once they had all finished (the frame's last ~20
 // iterations; 64 iterations per frame).
-template <bool FIXED, bool MAP>
+template <bool FIXED, bool MAP, bool EMIT>
 __global__ __launch_bounds__(kBlock) MCPT_SHADE_ATTR void k_shade(ShadeArgs a) {
     if (a.cnt->idle) return;  // the tile set is complete (an earlier iteration of the call traced no ray)
     __shared__ uint64_t s_live[kBlock / 64];
@@ -1040,7 +1071,7 @@ __global__ __launch_bounds__(kBlock) MCPT_SHADE_ATTR void k_shade(ShadeArgs a) {
         if (!((s_live[j >> 6] >> (j & 63)) & 1ull)) continue;
         // the arguments re-read per shading block (kernarg_fresh): hoisted out of the loop, the
         // struct's fields took the SGPR file and spilled (89 SGPRs, 54 -> 86 VGPRs)
-        shade_vblock<FIXED, MAP>(kernarg_fresh<ShadeArgs>(), (int)(blockIdx.x + j * G), s_vb[j]);
+        shade_vblock<FIXED, MAP, EMIT>(kernarg_fresh<ShadeArgs>(), (int)(blockIdx.x + j * G), s_vb[j]);
     }
 }
 
@@ -2107,7 +2138,7 @@ int launch_geometry(int dev, LaunchGeom& g) {
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ[1][1], k_trace<4, kLdsStackDeep, false>, kTraceBlock, 0) != hipSuccess ||
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&mat0, k_material<false>, kBlock, 0) != hipSuccess ||
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&mat1, k_material<true>, kBlock, 0) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&sh0, k_shade<false, false>, kBlock, 0) != hipSuccess)
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&sh0, k_shade<false, false, false>, kBlock, 0) != hipSuccess)
         return -1;
     if (cus <= 0) cus = 256;
     per_cu = 32;
@@ -2146,13 +2177,21 @@ void launch_shade(const ShadeArgs& args, int nblocks, const LaunchGeom& g, bool 
     ShadeArgs a = args;
     a.shade_vblocks = (uint32_t)nblocks;
     const uint32_t G = shade_grid((uint32_t)nblocks, g);
+    // (a.emis is set only for a table with a non-zero entry: a context without emission launches
+    // the instantiations it always launched)
     if (fixed_mode) {
-        if (a.budget) hipLaunchKernelGGL((k_shade<true, true>), dim3(G), dim3(kBlock), 0, s, a);
-        else hipLaunchKernelGGL((k_shade<true, false>), dim3(G), dim3(kBlock), 0, s, a);
+        if (a.emis) {
+            if (a.budget) hipLaunchKernelGGL((k_shade<true, true, true>), dim3(G), dim3(kBlock), 0, s, a);
+            else hipLaunchKernelGGL((k_shade<true, false, true>), dim3(G), dim3(kBlock), 0, s, a);
+        } else if (a.budget) hipLaunchKernelGGL((k_shade<true, true, false>), dim3(G), dim3(kBlock), 0, s, a);
+        else hipLaunchKernelGGL((k_shade<true, false, false>), dim3(G), dim3(kBlock), 0, s, a);
         hipLaunchKernelGGL(k_material<true>, dim3(g.mat_blocks[1]), dim3(kBlock), 0, s, a);
     } else {
-        if (a.budget) hipLaunchKernelGGL((k_shade<false, true>), dim3(G), dim3(kBlock), 0, s, a);
-        else hipLaunchKernelGGL((k_shade<false, false>), dim3(G), dim3(kBlock), 0, s, a);
+        if (a.emis) {
+            if (a.budget) hipLaunchKernelGGL((k_shade<false, true, true>), dim3(G), dim3(kBlock), 0, s, a);
+            else hipLaunchKernelGGL((k_shade<false, false, true>), dim3(G), dim3(kBlock), 0, s, a);
+        } else if (a.budget) hipLaunchKernelGGL((k_shade<false, true, false>), dim3(G), dim3(kBlock), 0, s, a);
+        else hipLaunchKernelGGL((k_shade<false, false, false>), dim3(G), dim3(kBlock), 0, s, a);
         hipLaunchKernelGGL(k_material<false>, dim3(g.mat_blocks[0]), dim3(kBlock), 0, s, a);
     }
 }
@@ -2163,8 +2202,11 @@ void launch_shade_stage(bool material_stage, const ShadeArgs& args, int nblocks,
     a.shade_vblocks = (uint32_t)nblocks;
     if (!material_stage) {
         const uint32_t G = shade_grid((uint32_t)nblocks, g);
-        if (fixed_mode) hipLaunchKernelGGL((k_shade<true, false>), dim3(G), dim3(kBlock), 0, s, a);
-        else hipLaunchKernelGGL((k_shade<false, false>), dim3(G), dim3(kBlock), 0, s, a);
+        if (a.emis) {
+            if (fixed_mode) hipLaunchKernelGGL((k_shade<true, false, true>), dim3(G), dim3(kBlock), 0, s, a);
+            else hipLaunchKernelGGL((k_shade<false, false, true>), dim3(G), dim3(kBlock), 0, s, a);
+        } else if (fixed_mode) hipLaunchKernelGGL((k_shade<true, false, false>), dim3(G), dim3(kBlock), 0, s, a);
+        else hipLaunchKernelGGL((k_shade<false, false, false>), dim3(G), dim3(kBlock), 0, s, a);
     } else {
         if (fixed_mode) hipLaunchKernelGGL(k_material<true>, dim3(g.mat_blocks[1]), dim3(kBlock), 0, s, a);
         else hipLaunchKernelGGL(k_material<false>, dim3(g.mat_blocks[0]), dim3(kBlock), 0, s, a);

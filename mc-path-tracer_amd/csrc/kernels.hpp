@@ -262,6 +262,10 @@ struct ShadeArgs {
     // installed, launch_shade runs k_shade's map instantiation, which reads budget[pixel] in place of
     // spp; the no-map instantiation never looks at this field.
     const uint32_t* budget;
+    // Emitted radiance per material id (mcpt_set_material_emission), xyz of a
+    // float4 each; nullptr: no table, or one without a non-zero entry.  Where it is set, launch_shade
+    // runs k_shade's emission instantiation; the others never look at this field.
+    const float4* emis;
 };
 // k_primary_build: the table of a W x H film.  stats: [0] pixels with a list, [1] overflow pixels.
 struct PrimaryBuildArgs {

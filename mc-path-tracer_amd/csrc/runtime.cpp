@@ -138,6 +138,59 @@ int mcpt_camera_set(mcpt_ctx* c, const mcpt_camera* cam) {
     return MCPT_OK;
 }
 
+// The emission table of the uploaded scene's materials.  What the film depends on
+// is the table's values, an absent table counting as zeros: a call that changes them is a change of the
+// lighting, seen by the film as a camera change is, and by the temporal history as a scene change.
+int mcpt_set_material_emission(mcpt_ctx* c, int32_t nmat, const float* rgb) {
+    if (!c) return MCPT_E_INVALID;
+    if (!c->scene.ok) return set_err(c, MCPT_E_INVALID, "no scene uploaded");
+    Emission& em = c->em;
+    const size_t n = 3 * (size_t)c->scene.nmat;
+    std::vector<float> now(n, 0.f);
+    if (rgb) {
+        if (nmat != c->scene.nmat) return set_err(c, MCPT_E_INVALID, "nmat differs from the uploaded scene's");
+        for (size_t i = 0; i < n; i++)
+            if (!(rgb[i] >= 0.f) || !(rgb[i] <= 3.402823466e+38f))
+                return set_err(c, MCPT_E_INVALID, "emission must be finite and >= 0");
+        now.assign(rgb, rgb + n);
+    }
+    const std::vector<float> was = em.rgb.empty() ? std::vector<float>(n, 0.f) : em.rgb;
+    const bool changed = n && memcmp(was.data(), now.data(), n * sizeof(float)) != 0;
+    if (changed || (rgb && em.rgb.empty())) {
+        std::vector<float4> t4(c->scene.nmat);
+        int32_t lit = 0;
+        for (int32_t m = 0; m < c->scene.nmat; m++) {
+            t4[m] = make_float4(now[3 * m], now[3 * m + 1], now[3 * m + 2], 0.f);
+            lit += now[3 * m] != 0.f || now[3 * m + 1] != 0.f || now[3 * m + 2] != 0.f;
+        }
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // no launch in flight reads the old table
+        if (!em.tab.ensure(t4.size())) {
+            em.drop();
+            return set_err(c, MCPT_E_NOMEM, "hipMalloc: emission table");
+        }
+        em.lit = 0;  // (a failed copy leaves a table the kernels never read)
+        if (!t4.empty()) HIPCHK(c, hipMemcpy(em.tab, t4.data(), t4.size() * sizeof(float4), hipMemcpyHostToDevice));
+        em.lit = lit;
+    }
+    if (rgb) em.rgb = now;
+    else em.drop();
+    if (changed) {
+        c->film_stale = true;
+        c->tp.ok = false;  // the history's colours belong to the old lighting
+    }
+    return MCPT_OK;
+}
+
+int mcpt_material_emission_read(mcpt_ctx* c, float* rgb, int32_t* nmat) {
+    if (!c || !nmat) return set_err(c, MCPT_E_INVALID, "null argument");
+    const Emission& em = c->em;
+    *nmat = (int32_t)(em.rgb.size() / 3);
+    if (em.rgb.empty()) return 0;
+    if (rgb) memcpy(rgb, em.rgb.data(), em.rgb.size() * sizeof(float));
+    return em.lit;
+}
+
 static int set_tiles_internal(mcpt_ctx* c, const std::vector<int2>& t) {
     // per-shard queue capacity: shard = k_shade block mod kShards (a block pushes <= one ray per thread)
     const uint32_t nblocks = (uint32_t)t.size() * (uint32_t)shade_blocks_per_tile((int)(c->tile_w * c->tile_h), (int)c->slots);
@@ -522,6 +575,7 @@ static int enqueue_iteration(mcpt_ctx* c, size_t evbase, bool timing, const int2
     sa.blk_done = c->blk_done_off ? nullptr : c->blk_done;
     sa.skip = c->skip_discarded ? 1 : 0;
     sa.budget = c->ad.budget_on ? c->ad.budget.get() : nullptr;
+    sa.emis = c->em.dev_table();
     if (int rc = cam_table(c, c->W, c->H, &sa.cam_px, &sa.cam_dir)) return rc;
     prim_table(c, sa);
     const int bpt = shade_blocks_per_tile((int)(c->tile_w * c->tile_h), (int)c->slots);

@@ -174,6 +174,22 @@ struct VarianceFill {
     mcpt_variance_params p{};
 };
 
+// Emissive materials (mcpt_set_material_emission): the installed table, 3 floats
+// per material of the uploaded scene on the host (empty: none installed) and a float4 per material on
+// the device, and how many materials have a non-zero entry.  Only a table with one reaches the kernels
+// (dev_table()): without, the context launches what it launched before.  Keyed by material id, so a
+// geometry update keeps it; a scene upload drops it.
+struct Emission {
+    std::vector<float> rgb;
+    DevBuf<float4> tab;
+    int32_t lit = 0;
+    const float4* dev_table() const { return lit > 0 ? tab.get() : nullptr; }
+    void drop() {
+        rgb.clear();
+        lit = 0;
+    }
+};
+
 // The upload-time environment knobs as the last upload read them (read_upload_env, scene_upload.cpp;
 // a geometry update takes them from here and never calls getenv)
 struct UploadKnobs {
@@ -201,6 +217,7 @@ struct SceneState {
     DevScene dev{};
     bool ok = false;       // dev is complete: false during an upload or update and after a failed one
     int32_t ntri = 0;      // triangles of the uploaded scene
+    int32_t nmat = 0;      // ... and its materials
     UploadKnobs knobs;
     bool gpu_upload = false;  // uploaded by mcpt_scene_upload_gpu_bvh
     // the child-pair tree (mcpt_debug_bvh_read): the array launch_cull_margins wrote, which a 4-wide
@@ -261,6 +278,7 @@ struct mcpt_ctx {
     LaunchGeom geom{};             // persistent grids and k_trace partitions of this device
     uint32_t trace_parts_default = 1;
     SceneState scene;
+    Emission em;
     bool has_scene_before = false;  // set at the start of a re-upload
     // traversal work counters (mcpt_set_work_counters): k_trace's counting instantiation, whose six
     // per-lane counters cost the fast one its spill-free registers -- off by default

@@ -470,9 +470,11 @@ static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
     SceneState& sc = c->scene;
     c->has_scene_before = c->has_scene_before || sc.ok;
     sc.reset();
+    c->em.drop();  // the emission table belongs to the scene that goes
     read_upload_env(sc.knobs);
     sc.gpu_upload = gpu_bvh;
     sc.ntri = d->ntri;
+    sc.nmat = d->nmat;
     PairTree pt;  // gpu_bvh: the desc's BVH arrays are ignored
     if (!gpu_bvh && !mcpt_host::build_pair_tree(*d, sc.knobs.layout, pt, err)) return set_err(c, MCPT_E_INVALID, err);
     DevScene s{};

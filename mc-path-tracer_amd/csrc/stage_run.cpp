@@ -22,6 +22,10 @@ static int stage_run_paths(mcpt_ctx* c, int stage, const mcpt_path_view* in, mcp
         for (uint32_t i = 0; i < n; i++)
             if (in->hit_tri[i] < 0 || in->hit_tri[i] >= c->scene.ntri)
                 return set_err(c, MCPT_E_INVALID, "MATERIAL: every path needs a hit (0 <= hit_tri < ntri)");
+    if (stage == MCPT_STAGE_LOGIC && in->hit_tri && c->em.dev_table())  // the emission lookup reads the hit's record
+        for (uint32_t i = 0; i < n; i++)
+            if (in->hit_tri[i] >= c->scene.ntri)
+                return set_err(c, MCPT_E_INVALID, "LOGIC with emission: hit_tri must be < ntri");
     if (!in->hit_tri || !in->flags || (!gen && (!in->ray_d || !in->beta)) || (!mat && !in->samples) ||
         (mat && !in->ray_o) || (stage == MCPT_STAGE_LOGIC && (!in->nee0 || !in->nee1 || !in->vis || !in->Ld)))
         return set_err(c, MCPT_E_INVALID, "missing path-state input");
@@ -137,6 +141,7 @@ static int stage_run_paths(mcpt_ctx* c, int stage, const mcpt_path_view* in, mcp
     sa.ext_cap = ext_cap;
     sa.any_cap = any_cap;
     sa.cnt = cnt;
+    if (stage == MCPT_STAGE_LOGIC) sa.emis = c->em.dev_table();  // the context's emission
     HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
     launch_shade_stage(mat, sa, (int)nblocks, c->geom, (c->cfg.flags & MCPT_FLAG_FIXED) != 0, c->stream);
     HIPCHK(c, hipGetLastError());

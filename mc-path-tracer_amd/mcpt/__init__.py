@@ -202,6 +202,10 @@ ABI = {
     "mcpt_variance_run": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _f, _u, _f, _f, _f, _f, C.POINTER(VarianceParams), _f]),
     "mcpt_set_variance_fill": (C.c_int, [C.c_void_p, C.POINTER(VarianceParams)]),
     "mcpt_debug_variance_ms": (C.c_int, [C.c_void_p, _f]),
+    "mcpt_set_material_emission": (C.c_int, [C.c_void_p, C.c_int32, _f]),
+    "mcpt_material_emission_read": (C.c_int, [C.c_void_p, _f, _i]),
+    "mcpt_scene_set_material_emission": (C.c_int, [C.c_void_p, C.c_int32, _f]),
+    "mcpt_scene_get_emission": (C.c_int, [C.c_void_p, C.POINTER(_f), _i]),
     "mcpt_sync": (C.c_int, [C.c_void_p]),
     "mcpt_device_name": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
     "mcpt_debug_queue_rays": (C.c_int, [C.c_void_p, C.c_int, _f, _f, _u]),
@@ -349,6 +353,20 @@ class Scene:
         bc = np.asarray(base_rgb, np.float32)
         return self._ck(lib().mcpt_scene_add_mesh(self.h, len(arrs[0]), *[fptr(a) for a in arrs], fptr(bc)))
 
+    def set_emission(self, mat, rgb):
+        """Emitted radiance of material ``mat`` (one material per added mesh, in add order: the ids of
+        arrays()["mat"]).  PathTracer.upload_scene installs the scene's table after the upload."""
+        e = np.ascontiguousarray(rgb, np.float32).reshape(3)
+        return self._ck(lib().mcpt_scene_set_material_emission(self.h, int(mat), fptr(e)))
+
+    def emission(self):
+        """The per-material emission as an (nmat, 3) array, or None when no material emits."""
+        p, n = _f(), C.c_int32(0)
+        if not hasattr(lib(), "mcpt_scene_get_emission") and os.environ.get("MCPT_LIB"):
+            return None  # (an older variant library: no emission)
+        _check(lib().mcpt_scene_get_emission(self.h, C.byref(p), C.byref(n)))
+        return _arr(p, 3 * n.value, np.float32).reshape(n.value, 3) if p else None
+
     def set_env_hdr(self, path, mode=1, device_tables=False):
         """EnvironmentLight from an .hdr.  device_tables=True keeps the texture only; the
         light tables are then built on the device at upload (MCPT_ENV_DEVICE_TABLES)."""
@@ -494,6 +512,36 @@ class PathTracer:
             self._ck(lib().mcpt_scene_upload_gpu_bvh(self.h, C.byref(d)))
         else:
             self._ck(lib().mcpt_scene_upload(self.h, C.byref(d)))
+        # the desc carries no emission: a Scene's table is installed after the upload (which dropped
+        # the previous scene's), so every rank of mcpt.parallel renders under the same one
+        e = scene.emission() if isinstance(scene, Scene) else None
+        if e is not None:
+            self.set_emission(e)
+
+    def set_emission(self, rgb=None):
+        """Per-material emitted radiance, (nmat, 3) for the uploaded scene's materials, or None to
+        remove the table (mcpt_set_material_emission).  A change clears the film at the next render."""
+        if rgb is None:
+            self._ck(lib().mcpt_set_material_emission(self.h, 0, None))
+            return
+        e = np.ascontiguousarray(rgb, np.float32)
+        if e.ndim != 2 or e.shape[1] != 3:
+            raise ValueError("emission must be an (nmat, 3) array")
+        self._ck(lib().mcpt_set_material_emission(self.h, e.shape[0], fptr(e)))
+
+    def emission(self):
+        """The installed table as an (nmat, 3) array, or None when none is installed."""
+        n = C.c_int32(0)
+        rc = lib().mcpt_material_emission_read(self.h, None, C.byref(n))
+        if rc < 0:
+            self._ck(rc)
+        if n.value == 0:
+            return None
+        e = np.zeros((n.value, 3), np.float32)
+        rc = lib().mcpt_material_emission_read(self.h, fptr(e), C.byref(n))
+        if rc < 0:
+            self._ck(rc)
+        return e
 
     def update_geometry(self, v0, v1, v2, n0=None, n1=None, n2=None, mode="refit"):
         """New vertex positions (and normals: all three or none) for the uploaded scene's triangles, in

@@ -9,6 +9,11 @@ all_gather payload).  Rank 0 receives every buffer into device memory and scatte
 device film with mcpt_film_unpack_tiles, so its film readers return the whole frame.  The film's
 home stays device memory, as in the reference (Film.cu:121-172).  Buffer sizes follow from the
 deterministic tile partition, so no size exchange is needed.  No exchange happens while rendering.
+
+Emissive materials need nothing here: a pixel's film is a function of the scene,
+the emission table and its keyed samples, and every rank installs the same table, which
+PathTracer.upload_scene does from the Scene it uploads (a rank that uploads a bare desc calls
+PathTracer.set_emission with the same array).
 """
 from __future__ import annotations
 
