@@ -10,15 +10,16 @@ LIB     ?= mcpt
 EXTRA_HIPFLAGS ?=
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math \
             -fhip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-function -Iinclude -I$(PKG)/csrc $(EXTRA_HIPFLAGS)
-SRCS := $(PKG)/csrc/kernels.hip $(PKG)/csrc/scene_tables.hip $(PKG)/csrc/film.hip $(PKG)/csrc/bvh_build.hip $(PKG)/csrc/env_build.hip $(PKG)/csrc/denoise.hip $(PKG)/csrc/adaptive.hip $(PKG)/csrc/temporal.hip $(PKG)/csrc/variance.hip $(PKG)/csrc/refit.hip $(PKG)/csrc/runtime.cpp $(PKG)/csrc/stage_run.cpp $(PKG)/csrc/scene_upload.cpp $(PKG)/csrc/postprocess.cpp \
+SRCS := $(PKG)/csrc/kernels.hip $(PKG)/csrc/scene_tables.hip $(PKG)/csrc/film.hip $(PKG)/csrc/bvh_build.hip $(PKG)/csrc/env_build.hip $(PKG)/csrc/denoise.hip $(PKG)/csrc/adaptive.hip $(PKG)/csrc/temporal.hip $(PKG)/csrc/variance.hip $(PKG)/csrc/refit.hip $(PKG)/csrc/emitter.hip $(PKG)/csrc/runtime.cpp $(PKG)/csrc/stage_run.cpp $(PKG)/csrc/scene_upload.cpp $(PKG)/csrc/postprocess.cpp \
         $(PKG)/csrc/host/scene.cpp $(PKG)/csrc/host/proxies.cpp $(PKG)/csrc/host/capi_host.cpp $(PKG)/csrc/host/pair_tree.cpp \
-        $(PKG)/csrc/host/image_io.cpp
+        $(PKG)/csrc/host/image_io.cpp $(PKG)/csrc/host/emitter_table.cpp
 OBJS := $(patsubst $(PKG)/csrc/%,$(BUILD)/%.o,$(SRCS))
 HDRS := include/mcpt.h $(PKG)/csrc/kernels.hpp $(PKG)/csrc/device/mcpt_core.hpp $(PKG)/csrc/device/scene_dev.hpp \
         $(PKG)/csrc/device/primary_beam.hpp $(PKG)/csrc/device/occ_beam.hpp $(PKG)/csrc/device/denoise.hpp $(PKG)/csrc/device/adaptive.hpp $(PKG)/csrc/device/temporal.hpp $(PKG)/csrc/device/variance.hpp \
-        $(PKG)/csrc/runtime_internal.hpp $(PKG)/csrc/host/host_internal.hpp $(PKG)/csrc/host/pair_tree.hpp
+        $(PKG)/csrc/runtime_internal.hpp $(PKG)/csrc/host/host_internal.hpp $(PKG)/csrc/host/pair_tree.hpp \
+        $(PKG)/csrc/host/emitter_table.hpp
 
-all: $(PKG)/libmcpt.so oracle/liboracle.so examples/mcpt_render tests/native/facade_test tests/native/primary_beam tests/native/occ_beam
+all: $(PKG)/libmcpt.so oracle/liboracle.so examples/mcpt_render tests/native/facade_test tests/native/primary_beam tests/native/occ_beam tests/native/emitter_table_host
 
 $(BUILD)/%.o: $(PKG)/csrc/% $(HDRS)
 	@mkdir -p $(dir $@)
@@ -45,11 +46,15 @@ tests/native/primary_beam: tests/native/primary_beam.cpp $(PKG)/csrc/device/prim
 tests/native/occ_beam: tests/native/occ_beam.cpp $(PKG)/csrc/device/occ_beam.hpp $(PKG)/csrc/device/primary_beam.hpp $(PKG)/csrc/device/mcpt_core.hpp
 	$(HIPCC) -O2 -std=c++17 -ffp-contract=off -fno-fast-math -Iinclude -I$(PKG)/csrc $< -o $@
 
+# Host check of the emitter table builder (host/emitter_table.cpp) as a stand-alone CPU program
+tests/native/emitter_table_host: tests/native/emitter_table_host.cpp $(PKG)/csrc/host/emitter_table.cpp $(PKG)/csrc/host/emitter_table.hpp
+	g++ -O2 -std=c++17 -Wall -Wextra -ffp-contract=off -I$(PKG)/csrc $< $(PKG)/csrc/host/emitter_table.cpp -o $@
+
 oracle/liboracle.so: oracle/mcpt_oracle.c oracle/trav_model.c oracle/mcpt_oracle.h
 	$(MAKE) -C oracle
 
 clean:
-	rm -rf $(BUILD) $(PKG)/libmcpt.so examples/mcpt_render tests/native/facade_test tests/native/primary_beam tests/native/occ_beam
+	rm -rf $(BUILD) $(PKG)/libmcpt.so examples/mcpt_render tests/native/facade_test tests/native/primary_beam tests/native/occ_beam tests/native/emitter_table_host
 	$(MAKE) -C oracle clean
 
 .PHONY: all clean

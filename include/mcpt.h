@@ -576,6 +576,30 @@ int mcpt_debug_variance_ms(const mcpt_ctx *ctx, float *out1);
  * of materials with a non-zero entry, 0 with *nmat = 0 when no table is installed, or an error code. */
 int mcpt_set_material_emission(mcpt_ctx *ctx, int32_t nmat, const float *rgb);
 int mcpt_material_emission_read(mcpt_ctx *ctx, float *rgb, int32_t *nmat);
+/* ---- emitter sampling: emissive triangles sampled as lights.  Off by default.
+ * Active = switched on and a non-empty emitter table (some triangle of non-zero area has an emissive
+ * material); otherwise the context launches the kernels and renders the films it did before.  While
+ * active, every material evaluation draws one emitter sample (a triangle by its share of area x
+ * luminance(Le), a uniform point on it) and traces a shadow ray that ends just short of that point;
+ * the logic stage adds the sample's term where it adds the light sample's, and collects emission
+ * (section 16) at the primary hit only.  No MIS between the two: a clean split.  Paths, the other
+ * random draws and the five counts of mcpt_debug_ray_counts are those of the same scene without
+ * sampling.  mcpt_stage_run always runs with sampling off.
+ *
+ * mcpt_set_emitter_sampling: on != 0 builds the emitter table of the uploaded scene (none: when one is
+ * uploaded and its emission installed) and rebuilds it when mcpt_set_material_emission changes the
+ * emission or mcpt_scene_update_geometry* moves the triangles; a scene upload drops it.  Turning the
+ * switch on or off, and a rebuild that changes the table bitwise, mark the film stale and drop the
+ * temporal history as mcpt_set_material_emission does; the same value again does nothing.  Turning it
+ * on without an emissive triangle is no error: sampling is then inactive.
+ * mcpt_emitter_table_read: the table's entries in ascending scene triangle id; cdf, pick and tri_id
+ * (each *n entries; any may be NULL) and *n (0: no table).  pick[k] = cdf[k] - cdf[k-1] in fp32.
+ * mcpt_debug_emitter_stats: out4 = entries, total weight (sum of area x luminance), emitter rays made
+ * since the last film clear, the last table build's milliseconds; returns 1 while sampling is active,
+ * 0 while it is not, or an error code. */
+int mcpt_set_emitter_sampling(mcpt_ctx *ctx, int32_t on);
+int mcpt_emitter_table_read(mcpt_ctx *ctx, float *cdf, float *pick, uint32_t *tri_id, int32_t *n);
+int mcpt_debug_emitter_stats(const mcpt_ctx *ctx, double *out4);
 int mcpt_sync(mcpt_ctx *ctx);
 int mcpt_device_name(mcpt_ctx *ctx, char *buf, int32_t len);
 /* diagnostics: rays of the current extension (which=0) or any-hit (which=1) queue, and the

@@ -689,6 +689,26 @@ public:
         if (lit < 0) detail::check(lit, ctx_, "material_emission");
         return lit;
     }
+    // Emitter sampling (mcpt.h): emissive triangles sampled as lights, off by
+    // default and inactive while nothing emits.  Toggling clears the device film at the next render.
+    void set_emitter_sampling(bool on) {
+        detail::check(mcpt_set_emitter_sampling(ctx_, on ? 1 : 0), ctx_, "set_emitter_sampling");
+    }
+    // The emitter table in ascending scene triangle id; returns the entry count (0: off, or nothing emits)
+    int emitter_table(std::vector<float>& cdf, std::vector<float>& pick, std::vector<uint32_t>& tri_id) {
+        int32_t n = 0;
+        detail::check(mcpt_emitter_table_read(ctx_, nullptr, nullptr, nullptr, &n), ctx_, "emitter_table");
+        cdf.resize((size_t)n), pick.resize((size_t)n), tri_id.resize((size_t)n);
+        if (n) detail::check(mcpt_emitter_table_read(ctx_, cdf.data(), pick.data(), tri_id.data(), &n), ctx_, "emitter_table");
+        return n;
+    }
+    // Entries, total weight, emitter rays made since the last film clear, the last table build's ms
+    std::array<double, 4> emitter_stats() const {
+        std::array<double, 4> s{};
+        const int rc = mcpt_debug_emitter_stats(ctx_, s.data());
+        if (rc < 0) detail::check(rc, ctx_, "emitter_stats");
+        return s;
+    }
     // Adaptive sampling (mcpt.h): a per-pixel sample budget (W*H entries; empty: remove it) in place of
     // the uniform spp, and the uniform spp of the live context.  Neither clears the film: the next
     // render_frame renders on.  Call them once the film's size is the context's (after a render).

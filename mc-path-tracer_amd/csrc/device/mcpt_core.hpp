@@ -228,7 +228,12 @@ enum : uint32_t {
     SL_GEN_U = 0, SL_GEN_V = 1,
     SL_RR = 0, SL_LIGHT = 1, SL_ENV_U = 2, SL_ENV_V = 3,
     SL_MAT_LOBE = 4, SL_MAT_E0 = 5,
-    SL_CONT_LOBE = 10, SL_CONT_E0 = 11
+    SL_CONT_LOBE = 10, SL_CONT_E0 = 11,
+    // Emitter sampling.  brdf_sample_wi draws E0, E0 + 1 and, through
+    // gram_schmidt, E0 + 2 .. E0 + 4: SL_CONT_E0 reaches slot 15, and rngf keys a draw by len * 16 +
+    // slot, so slots 16 .. 18 of a vertex would be slots 0 .. 2 (roulette, light choice, env u) of the
+    // next one.  len has 8 bits, so slots from 16 * 256 on alias no vertex's draws.
+    SL_EMIT_PICK = 4096, SL_EMIT_U = 4097, SL_EMIT_V = 4098
 };
 struct Rng {
     uint32_t key, len;

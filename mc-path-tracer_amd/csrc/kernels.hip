@@ -511,9 +511,12 @@ struct MatOut {
 // a reference quirk of Appendix A: light-selection pdf 1/N folded into both light pdfs
 // (A.6), delta lights get MIS weight 1 (pdf_brdf.y = 0 instead of 1, A.7), textbook
 // Gram-Schmidt (A.9), env sampling/pdf on matched, clamped cells (A.11).
-template <bool FIXED>
+//
+// SAMP (emitter sampling active): one emitter sample beside everything else, from
+// RNG slots of its own, so the other draws, rays and terms are those of the plain instantiation.
+template <bool FIXED, bool SAMP = false>
 __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix, uint32_t sidx, uint32_t len,
-                                 V3 beta_store, int32_t htri, float4* stage, bool occ_on, bool no_cont) {
+                                 V3 beta_store, int32_t htri, float4* stage, bool occ_on, bool no_cont, bool& want_e) {
     const DevScene& sc = a.scene;
     MatOut mo{};
 #pragma unroll
@@ -630,6 +633,47 @@ __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix
             // the occluder-cache entry, loaded now and used after material()
             if (occ_on) mo.el = occ_entry(sc, occ_index(sc, so_l, ldir, &mo.kl));
         }
+    }
+    if constexpr (SAMP) {
+        // The emitter sample: entry k of the emitter table by its cdf, a point uniform on the triangle
+        // (as stored in its record), and the term cE = f Le / pdf with the solid-angle pdf
+        // pick / area * dist^2 / cos at the light, two-sided as the emission itself.  A sample that is
+        // not valid stores cE = 0, makes no ray and leaves its visibility byte 0.  The ray ends just
+        // short of the sampled point (tmax in d.w), is not looked up in the occluder cache and is not
+        // one of the rays "as the reference traces them" (counted on its own, k_material).
+        MCPT_MARK("m_emit");
+        int k = upper_bound(a.emit_cdf, a.emit_n, r(SL_EMIT_PICK));
+        k = k < a.emit_n - 1 ? k : a.emit_n - 1;
+        const uint2 ent = a.emit_ent[k];
+        const float4* tp = sc.tri + (size_t)kTriF4 * ent.x;
+        const float4 w0 = tp[0], w1 = tp[1], w2 = tp[2];
+        const V3 ev0 = v3(w0.x, w0.y, w0.z), e1 = v3(w0.w, w1.x, w1.y), e2 = v3(w1.z, w1.w, w2.x);
+        const float u1 = r(SL_EMIT_U), u2 = r(SL_EMIT_V), su = __builtin_sqrtf(u1);
+        const V3 pe = (ev0 + e1 * (su * (1.f - u2))) + e2 * (su * u2);
+        const V3 so_e = pos + n * 0.01f;  // the light ray's origin
+        const V3 dv = pe - so_e;
+        const float d2 = dot(dv, dv), dist = __builtin_sqrtf(d2);
+        const V3 edir = dv / dist;
+        const V3 c = cross(e1, e2);
+        const float area = 0.5f * __builtin_sqrtf(dot(c, c));
+        const float cosl = __builtin_fabsf(dot(normalize(c), edir));
+        const float pdf_e = ((__uint_as_float(ent.y) / area) * d2) / cosl;
+        V3 f_e;
+        float pdf_be;
+        brdf_f_pdf(m, n, edir, wo, f_e, pdf_be);
+        const int mat_e = __float_as_int(sc.tri_sh[3 * (size_t)ent.x + 2].y);
+        V3 cE = (f_e * ld3f4(a.emis + mat_e)) / pdf_e;
+        const bool ok = dist > 0.f && cosl > 0.f && pdf_e > 0.f && pdf_e < K_INF_F && __builtin_fabsf(cE.x) < K_INF_F &&
+                        __builtin_fabsf(cE.y) < K_INF_F && __builtin_fabsf(cE.z) < K_INF_F;
+        if (ok) {
+            stage[4 * kBlock + threadIdx.x] = f4(so_e, __uint_as_float(a.emit_vis0 + pid));
+            stage[5 * kBlock + threadIdx.x] = f4(edir, dist * 0.999f);
+            want_e = true;  // (SAMP only: the emitter ray is staged)
+        } else {
+            cE = v3(0.f, 0.f, 0.f);
+            a.p.vis[a.emit_vis0 + pid] = 0;
+        }
+        st_s(a.nee2 + pid, f4(cE, 0.f));
     }
     // the BRDF sample's direction and visibility ray (its light terms come after the occluder
     // cache, material_brdf_terms)
@@ -756,7 +800,11 @@ __device__ inline uint32_t udiv_small(uint32_t n, uint32_t d, float rcp) {
 // EMIT: a path that continues into the material stage collects the emission of the surface it hit
 // (ShadeArgs::emis).  Instantiations of their own again: without a table the
 // kernels are the code they were.
-template <bool FIXED, bool MAP, bool EMIT>
+// SAMP (with EMIT): emitter sampling is active.  The logic adds the emitter
+// sample's term of the previous vertex (ShadeArgs::nee2, its visibility byte at emit_vis0 + path) where
+// it adds the light sample's, and collects emission at the primary hit only: at len >= 2 the previous
+// vertex's emitter sample stands for that light.
+template <bool FIXED, bool MAP, bool EMIT, bool SAMP = false>
 __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeArgs& a, int vb, const VBlk& v) {
     const DevScene& sc = a.scene;
     const int slot = (int)(v.sr & 0xffu);
@@ -821,6 +869,12 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
         const V3 rd = ld3f4(a.p.ray_d + (need_rd ? pid : 0u));
         const float4 n0 = ld_s(a.p.nee0 + (need_nee ? pid : 0u)), n1 = ld_s(a.p.nee1 + (need_nee ? pid : 0u));
         const uchar2 vv = reinterpret_cast<const uchar2*>(a.p.vis)[need_nee ? pid : 0u];
+        float4 n2 = make_float4(0.f, 0.f, 0.f, 0.f);
+        uint8_t ve = 0;
+        if constexpr (SAMP) {  // the emitter sample's term and visibility join the load round
+            n2 = ld_s(a.nee2 + (need_nee ? pid : 0u));
+            ve = a.p.vis[a.emit_vis0 + (need_nee ? pid : 0u)];
+        }
         bool dead = (fl & F_DEAD) != 0;
         // the sample count the pixel renders to: the budget map's entry joins the load round above
         uint32_t spp;
@@ -862,6 +916,8 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
                 } else {
                     acc = acc + v3(0.f, 0.f, 0.f);  // delta light: f_brdf = 0, weights 0.5
                 }
+                if constexpr (SAMP)
+                    if (ve) acc = acc + xyz(n2);  // the previous vertex's emitter sample, unoccluded
                 film = film + acc * B;
                 if (fl & F_FZERO) {
                     terminate = true;
@@ -887,7 +943,7 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
                 // len <= max_depth, a non-zero sample, the roulette survived (beta_store is final).
                 // The skip switch's early end below (dd) is such a path too: the reference runs its
                 // material stage.  Its film is written once, after the pushes, with the emission.
-                em = !terminate;
+                em = !terminate && (!SAMP || len == 1);
                 if (em) {
                     em_dirty = film_dirty;
                     bg_film = film;
@@ -1050,7 +1106,7 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
 // (one workgroup per shading block, G = the block count) paid ~0.2 ms per launch just to dispatch
 // and retire config 2's 246K workgroups once they had all finished (the frame's last ~20
 // iterations; 64 iterations per frame).
-template <bool FIXED, bool MAP, bool EMIT>
+template <bool FIXED, bool MAP, bool EMIT, bool SAMP = false>
 __global__ __launch_bounds__(kBlock) MCPT_SHADE_ATTR void k_shade(ShadeArgs a) {
     if (a.cnt->idle) return;  // the tile set is complete (an earlier iteration of the call traced no ray)
     __shared__ uint64_t s_live[kBlock / 64];
@@ -1071,7 +1127,7 @@ __global__ __launch_bounds__(kBlock) MCPT_SHADE_ATTR void k_shade(ShadeArgs a) {
         if (!((s_live[j >> 6] >> (j & 63)) & 1ull)) continue;
         // the arguments re-read per shading block (kernarg_fresh): hoisted out of the loop, the
         // struct's fields took the SGPR file and spilled (89 SGPRs, 54 -> 86 VGPRs)
-        shade_vblock<FIXED, MAP, EMIT>(kernarg_fresh<ShadeArgs>(), (int)(blockIdx.x + j * G), s_vb[j]);
+        shade_vblock<FIXED, MAP, EMIT, SAMP>(kernarg_fresh<ShadeArgs>(), (int)(blockIdx.x + j * G), s_vb[j]);
     }
 }
 
@@ -1082,7 +1138,10 @@ __global__ __launch_bounds__(kBlock) MCPT_SHADE_ATTR void k_shade(ShadeArgs a) {
 // pushes meet at the barrier together.  Block b serves shard b mod kShards, chunks
 // b / kShards, + gridDim.x / kShards, ... of it (grid from the occupancy calculator).
 // ---------------------------------------------------------------------------
-template <bool FIXED>
+// SAMP: the emitter-sampling instantiation, launched only while sampling is
+// active: a third staged ray (six LDS slabs, 24 KiB per block: 96 KiB per CU at 4 waves per SIMD, of 160)
+// pushed onto the any-hit queue with the result index 2P + path.
+template <bool FIXED, bool SAMP = false>
 __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_kernarg) {
     (void)a_kernarg;  // read through kernarg_fresh (the same bytes: it is the kernel's only argument)
     const ShadeArgs& a = kernarg_fresh<ShadeArgs>();
@@ -1092,16 +1151,19 @@ __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_k
     const uint32_t n = sc_ctr[C_MAT];
     const int lane = threadIdx.x & 63;
     uint32_t n_ext = 0, n_any = 0, n_vis = 0, n_occ = 0, occ_try = 0, n_skip = 0, n_inpl = 0, n_dvis = 0, n_docc = 0;
+    uint32_t n_emit = 0;  // SAMP: emitter rays made
+    (void)n_emit;
     const bool occ_on = a.scene.occ && a.scene.occ_gate[0] == 0 && a.scene.occ_gate[2] != 0;  // see DevScene::occ_gate
     // Any-hit rays are staged here (light ray o/d, BRDF visibility ray o/d) and stored after
     // the block push at their queue positions: the block's rays of one kind land contiguously,
     // so k_trace reads them densely and without the queue-entry hop (the pid-indexed layout
     // wrote and read 32-B pieces of partly used lines).
-    __shared__ float4 s_any[4][kBlock];
+    __shared__ float4 s_any[SAMP ? 6 : 4][kBlock];
     for (uint32_t base = w_in * kBlock; base < n; base += bps * kBlock) {  // block-uniform trip count
         const ShadeArgs& a = kernarg_fresh<ShadeArgs>();  // this trip's loads (see kernarg_fresh)
         const uint32_t i = base + threadIdx.x;
         MatOut mo{};
+        bool want_e = false;  // SAMP: the emitter ray
         uint32_t mpid = 0;
         bool occ_l = false, occ_b = false, try_l = false, try_b = false;  // resolved by / tested against the occluder cache
         bool done_l = false, done_b = false, clr_l = false, clr_b = false;  // ... from a complete entry / as unoccluded
@@ -1109,8 +1171,8 @@ __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_k
             const uint4 q = ld_s(a.mat_rec + shard * a.ext_cap + i);  // {pid, pixel, sample index | len << 24, hit_tri}
             const float4 b4 = ld_s(a.mat_beta + shard * a.ext_cap + i);
             mpid = q.x;
-            mo = material<FIXED>(a, mpid, q.y, q.z & (kRecNoCont - 1u), q.z >> kRecLenShift, xyz(b4), (int32_t)q.w,
-                                 &s_any[0][0], occ_on, (q.z & kRecNoCont) != 0u);
+            mo = material<FIXED, SAMP>(a, mpid, q.y, q.z & (kRecNoCont - 1u), q.z >> kRecLenShift, xyz(b4), (int32_t)q.w,
+                                 &s_any[0][0], occ_on, (q.z & kRecNoCont) != 0u, want_e);
             // the occluder cache (see occ_hit1), before the BRDF sample's light terms: a ray it
             // resolves gets its wf_shadow result here and is not queued
             MCPT_MARK("m_occ");
@@ -1162,10 +1224,16 @@ __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_k
             material_brdf_terms<FIXED>(a, mpid, mo);
         }
         MCPT_MARK("m_push");
-        bool want[3] = {mo.want_ext, mo.want_l, mo.want_b};
-        uint32_t* ctr[3] = {sc_ctr + C_EXT, sc_ctr + C_ANY, sc_ctr + C_ANY};
-        uint32_t slot[3], total[3];
-        block_push<3>(want, ctr, slot, total);
+        uint32_t slot[SAMP ? 4 : 3], total[SAMP ? 4 : 3];
+        if constexpr (SAMP) {
+            bool want[4] = {mo.want_ext, mo.want_l, mo.want_b, want_e};
+            uint32_t* ctr[4] = {sc_ctr + C_EXT, sc_ctr + C_ANY, sc_ctr + C_ANY, sc_ctr + C_ANY};
+            block_push<4>(want, ctr, slot, total);
+        } else {
+            bool want[3] = {mo.want_ext, mo.want_l, mo.want_b};
+            uint32_t* ctr[3] = {sc_ctr + C_EXT, sc_ctr + C_ANY, sc_ctr + C_ANY};
+            block_push<3>(want, ctr, slot, total);
+        }
         if (mo.want_ext) st_q(a.ext_q + shard * a.ext_cap + slot[0], mpid);
         // (the any-hit rays carry their result index in o.w: no queue entries)
         if (mo.want_l) {
@@ -1187,6 +1255,19 @@ __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_k
                 a.p.sray_o[k] = s_any[2][threadIdx.x];
                 a.p.sray_d[k] = s_any[3][threadIdx.x];
             }
+        }
+        if constexpr (SAMP) {
+            if (want_e) {  // (any_cap is 3 x ext_cap while sampling is active: set_tiles_internal)
+                const uint32_t k = shard * a.any_cap + slot[3];
+                if constexpr (MCPT_NT & 8) {
+                    st_s(a.p.sray_o + k, s_any[4][threadIdx.x]);
+                    st_s(a.p.sray_d + k, s_any[5][threadIdx.x]);
+                } else {
+                    a.p.sray_o[k] = s_any[4][threadIdx.x];
+                    a.p.sray_d[k] = s_any[5][threadIdx.x];
+                }
+            }
+            n_emit += (uint32_t)__popcll(__ballot(want_e));
         }
         MCPT_MARK("m_count");
         // per-wave ray counts from lane masks (wave-uniform scalars: no registers held across the
@@ -1213,6 +1294,8 @@ __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_k
         if (n_docc) atomicAdd(sc_ctr + C_OCC_DONE_OCC, n_docc);
         if (n_skip) atomicAdd(sc_ctr + C_SKIP_EXT, n_skip);
         if (n_inpl) atomicAdd(sc_ctr + C_SKIP_INPLACE, n_inpl);
+        if constexpr (SAMP)
+            if (n_emit) atomicAdd(a.cnt->tot_emit + shard, (unsigned long long)n_emit);
     }
 }
 
@@ -1451,8 +1534,8 @@ __global__ __launch_bounds__(kTraceBlock) MCPT_TRACE_ATTR void k_trace(TraceArgs
 #define RAY_O v3(px.x, py.x, pz.x)
 #define RAY_INV v3(px.y, py.y, pz.y)
     int ref = kEnd, leaf = kEnd, sp = 0, tri = -1;
-    // best: the closest hit's t, or -1 for an any-hit ray (its kind: best < 0; an accepted t is never
-    // below +-0); io: the ray's signed culling scale (cull_iota; |io| = inf: an infinite inverse
+    // best: the closest hit's t, or -tmax for an any-hit ray (its kind: best < 0; an accepted t is never
+    // below +-0, and an any-hit ray accepts t < -best at every acceptance site); io: the ray's signed culling scale (cull_iota; |io| = inf: an infinite inverse
     // component, the slab() path)
     float best = K_HUGE, cut = K_HUGE, io = K_INF_F;
     uint32_t bsid = 0;  // shared triangle phase: scene id of the closest hit so far (tri >= 0)
@@ -1488,7 +1571,10 @@ __global__ __launch_bounds__(kTraceBlock) MCPT_TRACE_ATTR void k_trace(TraceArgs
             // (rid: the result index -- a dense set's ray carried it in o.w, see the refill)
             if constexpr (MCPT_NT & 4) __builtin_nontemporal_store((uint8_t)(tri < 0), a.vis + rid);
             else a.vis[rid] = (uint8_t)(tri < 0);  // wf_shadow (wavefront_kernels.cu:274-293)
-            if (tri >= 0 && occ_rec) {  // the cell's occluder (occ_hit1)
+            // the cell's occluder (occ_hit1).  A finite ray (an emitter ray: best > -K_HUGE) records none:
+            // the table then holds what it holds without emitter sampling, and so do the counts of the
+            // rays it resolves (mcpt_debug_ray_counts)
+            if (tri >= 0 && occ_rec && best == -K_HUGE) {
                 // (hashed again here rather than kept from d.w: a register held over the whole
                 // traversal, or a reload of the record, costs more than the hash on occluded rays)
                 uint32_t* w = sc.occ + (size_t)occ_index(sc, RAY_O, d) * kOccWays + (uint32_t)tri % kOccWays;
@@ -1581,7 +1667,9 @@ __global__ __launch_bounds__(kTraceBlock) MCPT_TRACE_ATTR void k_trace(TraceArgs
                     pz.x = o4.z;
                     d = xyz(d4);
                     tri = -1;
-                    best = kind ? -1.f : K_HUGE;
+                    // any hit: -tmax, the ray's end in d.w (0, as every ray but an emitter ray carries
+                    // it: to infinity, K_HUGE as the reference's tmax)
+                    best = kind ? -(d4.w > 0.f ? d4.w : K_HUGE) : K_HUGE;
                     if constexpr (kCount) {
                         if (kind) {  // the any-hit set's counts start here (see tot_n)
                             tot_n1 -= tot_n;
@@ -1825,6 +1913,9 @@ __global__ __launch_bounds__(kTraceBlock) MCPT_TRACE_ATTR void k_trace(TraceArgs
                 const V3 pd = v3(__int_as_float(__builtin_amdgcn_ds_bpermute(oa, __float_as_int(d.x))),
                                  __int_as_float(__builtin_amdgcn_ds_bpermute(oa, __float_as_int(d.y))),
                                  __int_as_float(__builtin_amdgcn_ds_bpermute(oa, __float_as_int(d.z))));
+                // the owner's end: an any-hit ray's tmax (-best), K_HUGE for a closest-hit ray
+                const float ob = __int_as_float(__builtin_amdgcn_ds_bpermute(oa, __float_as_int(best)));
+                const float oend = ob < 0.f ? -ob : K_HUGE;
                 if (p < total) {
                     const int id = (oleaf & 0xffffff) + (int)k;
                     const float4* tp = sc.tri + kTriF4 * id;
@@ -1833,7 +1924,7 @@ __global__ __launch_bounds__(kTraceBlock) MCPT_TRACE_ATTR void k_trace(TraceArgs
                                      "v"(w1.w), "v"(w2.x), "v"(w2.y));
                     float t;
                     if (tri_test_t(po, pd, v3(w0.x, w0.y, w0.z), v3(w0.w, w1.x, w1.y), v3(w1.z, w1.w, w2.x), t) &&
-                        !(t < 0.f) && t < K_HUGE) {
+                        !(t < 0.f) && t < oend) {
                         const uint64_t key = ((uint64_t)__float_as_uint(t + 0.f) << 32) |
                                              (((uint32_t)__float_as_int(w2.y) << 3) | k);
                         __hip_atomic_fetch_min(&s_key[ow], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1876,7 +1967,7 @@ __global__ __launch_bounds__(kTraceBlock) MCPT_TRACE_ATTR void k_trace(TraceArgs
                 const bool acc = tri_test_t(RAY_O, d, v3(w0.x, w0.y, w0.z), v3(w0.w, w1.x, w1.y), v3(w1.z, w1.w, w2.x), t);
                 MCPT_MARK("t_tri2");
                 if (acc && !(t < 0.f) &&
-                    (best < 0.f ? t < K_HUGE
+                    (best < 0.f ? t < -best
                           : (t < best ||
                              (t == best && tri >= 0 && __float_as_int(w2.y) < __float_as_int(sc.tri[kTriF4 * tri + 2].y))))) {
                     if (best < 0.f) {
@@ -2157,6 +2248,14 @@ int launch_geometry(int dev, LaunchGeom& g) {
     }
     g.mat_blocks[0] = (uint32_t)std::max(1, cus * std::max(1, mat0) / kShards) * (uint32_t)kShards;
     g.mat_blocks[1] = (uint32_t)std::max(1, cus * std::max(1, mat1) / kShards) * (uint32_t)kShards;
+    {  // the emitter-sampling instantiations' grids (24 KiB of LDS per block)
+        int ms0 = 0, ms1 = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&ms0, k_material<false, true>, kBlock, 0) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&ms1, k_material<true, true>, kBlock, 0) != hipSuccess)
+            return -1;
+        g.mat_blocks_samp[0] = (uint32_t)std::max(1, cus * std::max(1, ms0) / kShards) * (uint32_t)kShards;
+        g.mat_blocks_samp[1] = (uint32_t)std::max(1, cus * std::max(1, ms1) / kShards) * (uint32_t)kShards;
+    }
     int prim = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&prim, k_primary, kBlock, 0) != hipSuccess) return -1;
     g.prim_blocks = (uint32_t)std::max(1, cus * std::max(1, prim) / kShards) * (uint32_t)kShards;
@@ -2179,6 +2278,20 @@ void launch_shade(const ShadeArgs& args, int nblocks, const LaunchGeom& g, bool 
     const uint32_t G = shade_grid((uint32_t)nblocks, g);
     // (a.emis is set only for a table with a non-zero entry: a context without emission launches
     // the instantiations it always launched)
+    // Emitter sampling active (a.nee2 set, which implies a.emis): the sampling
+    // instantiations of both kernels.  Every other context launches what it launched before.
+    if (a.nee2 && a.emis) {
+        if (fixed_mode) {
+            if (a.budget) hipLaunchKernelGGL((k_shade<true, true, true, true>), dim3(G), dim3(kBlock), 0, s, a);
+            else hipLaunchKernelGGL((k_shade<true, false, true, true>), dim3(G), dim3(kBlock), 0, s, a);
+            hipLaunchKernelGGL((k_material<true, true>), dim3(g.mat_blocks_samp[1]), dim3(kBlock), 0, s, a);
+        } else {
+            if (a.budget) hipLaunchKernelGGL((k_shade<false, true, true, true>), dim3(G), dim3(kBlock), 0, s, a);
+            else hipLaunchKernelGGL((k_shade<false, false, true, true>), dim3(G), dim3(kBlock), 0, s, a);
+            hipLaunchKernelGGL((k_material<false, true>), dim3(g.mat_blocks_samp[0]), dim3(kBlock), 0, s, a);
+        }
+        return;
+    }
     if (fixed_mode) {
         if (a.emis) {
             if (a.budget) hipLaunchKernelGGL((k_shade<true, true, true>), dim3(G), dim3(kBlock), 0, s, a);

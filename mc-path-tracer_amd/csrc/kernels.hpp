@@ -17,7 +17,9 @@
 //   beta          float4 [P]    throughput, (f_sample/pdf_sample).x
 //   nee0 / nee1   float4 [P]    precomputed light / BRDF MIS terms, ratio .y / .z
 //   flags         u32    [P]    dead, len, MIS condition bits, the path's sample index (bits 13..31)
-//   vis           u8     [2P]   any-hit results
+//   vis           u8     [2P]   any-hit results ([3P] while emitter sampling is active: the emitter
+//                               ray of path p at 2P + p)
+//   nee2          float4 [P]    the emitter sample's term (only while emitter sampling is active)
 //   samples       u32    [P]    film sample count (dFilm.samples)
 //   Ld            float4 [P]    film radiance (dFilm.Ld)
 #pragma once
@@ -200,6 +202,9 @@ struct CounterBlock {
     unsigned long long tot_prim;  // primary rays resolved from the candidate table (part of tot_ext)
     unsigned long long tot_skip[4];  // C_SKIP_EXT, C_SKIP_ANY, C_SKIP_MAT, C_SKIP_INPLACE
     unsigned long long tot_done[2];  // C_OCC_DONE_VIS, C_OCC_DONE_OCC
+    // emitter rays made (k_material's sampling instantiation, one word per queue shard; they are pushed
+    // onto the any-hit queue, so tot_any_q includes them, and are no part of tot_any)
+    unsigned long long tot_emit[kShards];
 };
 static_assert(C_PH + kPhaseWords <= C_SKIP_INPLACE, "counter words overlap");
 
@@ -266,6 +271,18 @@ struct ShadeArgs {
     // float4 each; nullptr: no table, or one without a non-zero entry.  Where it is set, launch_shade
     // runs k_shade's emission instantiation; the others never look at this field.
     const float4* emis;
+    // Emitter sampling (mcpt_set_emitter_sampling), set only while it is active
+    // (switched on and a non-empty emitter table): launch_shade then runs the sampling instantiations
+    // of k_shade and k_material; the others never look at these fields.  emit_cdf / emit_ent: the
+    // emitter table on the device, emit_n entries in scene-id order, an entry {record index, pick
+    // probability bits}.  nee2: the emitter sample's term per path; its visibility byte is
+    // p.vis[emit_vis0 + path] (emit_vis0 = 2P: k_trace's finish writes at the index in o.w as ever).
+    // Made emitter rays are counted per queue shard in cnt->tot_emit.
+    const float* emit_cdf;
+    const uint2* emit_ent;
+    int emit_n;
+    uint32_t emit_vis0;
+    float4* nee2;
 };
 // k_primary_build: the table of a W x H film.  stats: [0] pixels with a list, [1] overflow pixels.
 struct PrimaryBuildArgs {
@@ -329,6 +346,7 @@ struct LaunchGeom {
     uint32_t trace_parts;    // k_trace work partitions, MCPT_TRACE_PARTS (1..kMaxParts)
     uint32_t ndies;          // XCDs
     uint32_t mat_blocks[2];  // k_material grid [reference mode, fixed mode]
+    uint32_t mat_blocks_samp[2];  // ... of its emitter-sampling instantiations
     uint32_t prim_blocks;    // k_primary grid (resident blocks, a multiple of the shard count)
     uint32_t shade_grid;     // k_shade grid cap (resident blocks x MCPT_SHADE_GRID; 0: one block per shading block)
     uint32_t refill_min, tri_min;  // MCPT_REFILL_MIN, MCPT_TRI_MIN
@@ -343,6 +361,12 @@ void launch_primary(const ShadeArgs& a, const LaunchGeom& g, hipStream_t s);  //
 void launch_trace(const TraceArgs& a, const LaunchGeom& g, hipStream_t s);
 void launch_accumulate(CounterBlock* c, uint32_t nparts, uint32_t* occ_gate, hipStream_t s);
 int shade_sections(unsigned long long* out, int n, int reset);  // -DMCPT_DIAG_SHADE builds (else 0)
+
+// ---- emitter sampling (emitter.hip) ----
+// k_emitter_weights: per triangle record r of the scene, weight[r] = area * luminance(Le[material]) with
+// the sampling arithmetic's own area (0.5 sqrt(dot(c, c)), c = cross(e1, e2) of the record as stored),
+// 0 for a non-emissive material, and id[r] = the record's scene triangle id.
+void launch_emitter_weights(const DevScene& sc, const float4* emis, float* weight, uint32_t* id, hipStream_t s);
 
 // ---- scene tables (scene_tables.hip) ----
 // Occluder records (DevScene::occ_rec): for each triangle record t, {leaf mn, margin} {leaf mx,

@@ -10,6 +10,7 @@
 // denoise, adaptive sampling, temporal accumulation) are postprocess.cpp; scene upload and
 // geometry update are scene_upload.cpp; the per-stage parity harness (mcpt_stage_run) and the
 // mcpt_debug_* entries beyond the counter reads below are stage_run.cpp.
+#include <chrono>
 #include <cstdio>
 
 #include "runtime_internal.hpp"
@@ -94,6 +95,8 @@ int mcpt_debug_ray_counts(const mcpt_ctx* c, uint64_t* out) {
     out[1] = ok ? t.tot_ext_q : 0;  // extension rays k_trace traversed
     out[2] = ok ? t.tot_any : 0;    // shadow + BRDF visibility rays
     out[3] = ok ? t.tot_any_q : 0;  // any-hit rays k_trace traversed
+    // (emitter rays share the any-hit queue and are no rays of the reference: mcpt_debug_emitter_stats)
+    for (int k = 0; ok && k < kShards; k++) out[3] -= t.tot_emit[k];
     out[4] = ok ? t.tot_occ : 0;    // any-hit rays the occluder cache resolved in k_material
     return MCPT_OK;
 }
@@ -178,6 +181,7 @@ int mcpt_set_material_emission(mcpt_ctx* c, int32_t nmat, const float* rgb) {
     if (changed) {
         c->film_stale = true;
         c->tp.ok = false;  // the history's colours belong to the old lighting
+        return emitter_table_refresh(c);  // emitter sampling's table follows the emission (section 17)
     }
     return MCPT_OK;
 }
@@ -191,13 +195,124 @@ int mcpt_material_emission_read(mcpt_ctx* c, float* rgb, int32_t* nmat) {
     return em.lit;
 }
 
+// ---- emitter sampling ----
+static int set_tiles_internal(mcpt_ctx* c, const std::vector<int2>& t);
+
+// The any-hit queue holds two rays per material evaluation, three while emitter sampling is active:
+// the queues are re-sized for the current tile set when that changes.
+static int emitter_queues(mcpt_ctx* c) {
+    const uint32_t mult = c->es.active() ? 3u : 2u;
+    if (c->any_mult == mult || !c->P) {
+        c->any_mult = mult;
+        return MCPT_OK;
+    }
+    c->any_mult = mult;
+    return set_tiles_internal(c, std::vector<int2>(c->tiles_h));
+}
+
+extern "C++" int emitter_table_refresh(mcpt_ctx* c) {
+    EmitterSampling& es = c->es;
+    if (!es.on || !c->scene.ok) return MCPT_OK;
+    const bool was_active = es.active();
+    mcpt_host::EmitterTable now;
+    es.build_ms = 0.f;
+    const float4* emis = c->em.dev_table();
+    const uint32_t ntri = c->scene.dev.ntri;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (emis && ntri) {
+        TmpScope tmp(c);
+        float* dw = nullptr;
+        uint32_t* did = nullptr;
+        int rc;
+        if ((rc = dalloc(c, tmp.L, &dw, ntri)) || (rc = dalloc(c, tmp.L, &did, ntri))) return rc;
+        const auto t0 = std::chrono::steady_clock::now();
+        launch_emitter_weights(c->scene.dev, emis, dw, did, c->stream);
+        HIPCHK(c, hipGetLastError());
+        std::vector<float> w(ntri);
+        std::vector<uint32_t> id(ntri);
+        HIPCHK(c, hipMemcpyAsync(w.data(), dw, ntri * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(id.data(), did, ntri * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        mcpt_host::build_emitter_table(w.data(), id.data(), ntri, now);
+        const size_t n = now.cdf.size();
+        if (n) {
+            std::vector<uint2> ent(n);
+            for (size_t k = 0; k < n; k++) {
+                uint32_t bits;
+                memcpy(&bits, &now.pick[k], sizeof(bits));
+                ent[k] = make_uint2(now.rec[k], bits);
+            }
+            if (!es.cdf.ensure(n) || !es.ent.ensure(n)) {
+                es.drop_table();
+                return set_err(c, MCPT_E_NOMEM, "hipMalloc: emitter table");
+            }
+            // (the stream is idle: no launch in flight reads the old arrays)
+            HIPCHK(c, hipMemcpy(es.cdf, now.cdf.data(), n * sizeof(float), hipMemcpyHostToDevice));
+            HIPCHK(c, hipMemcpy(es.ent, ent.data(), n * sizeof(uint2), hipMemcpyHostToDevice));
+        }
+        es.build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    // The record indices are the tree's business: the film depends on the entries' triangles and values
+    const bool changed = !(now.cdf == es.tab.cdf && now.pick == es.tab.pick && now.id == es.tab.id);
+    es.tab = std::move(now);
+    if (changed || was_active != es.active()) {
+        c->film_stale = true;
+        c->tp.ok = false;
+    }
+    if (!es.active()) es.drop_streams();
+    return emitter_queues(c);
+}
+
+int mcpt_set_emitter_sampling(mcpt_ctx* c, int32_t on) {
+    if (!c) return MCPT_E_INVALID;
+    EmitterSampling& es = c->es;
+    if (es.on == (on != 0)) return MCPT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    es.on = on != 0;
+    // the switch itself changes the estimator: the film restarts, as with a change of the emission
+    c->film_stale = true;
+    c->tp.ok = false;
+    if (es.on) return emitter_table_refresh(c);
+    es.drop_table();
+    es.drop_streams();
+    return emitter_queues(c);
+}
+
+int mcpt_emitter_table_read(mcpt_ctx* c, float* cdf, float* pick, uint32_t* tri_id, int32_t* n) {
+    if (!c || !n) return set_err(c, MCPT_E_INVALID, "null argument");
+    const mcpt_host::EmitterTable& t = c->es.tab;
+    *n = (int32_t)t.cdf.size();
+    if (cdf && *n) memcpy(cdf, t.cdf.data(), t.cdf.size() * sizeof(float));
+    if (pick && *n) memcpy(pick, t.pick.data(), t.pick.size() * sizeof(float));
+    if (tri_id && *n) memcpy(tri_id, t.id.data(), t.id.size() * sizeof(uint32_t));
+    return MCPT_OK;
+}
+
+static unsigned long long emit_rays(const mcpt_ctx* c) {
+    unsigned long long s = 0;
+    if (c->totals_ok)
+        for (int k = 0; k < kShards; k++) s += c->totals.tot_emit[k];
+    return s;
+}
+
+int mcpt_debug_emitter_stats(const mcpt_ctx* c, double* out4) {
+    if (!c || !out4) return MCPT_E_INVALID;
+    out4[0] = (double)c->es.tab.cdf.size();
+    out4[1] = c->es.tab.total;
+    out4[2] = (double)emit_rays(c);
+    out4[3] = (double)c->es.build_ms;
+    return c->es.active() ? 1 : 0;
+}
+
 static int set_tiles_internal(mcpt_ctx* c, const std::vector<int2>& t) {
     // per-shard queue capacity: shard = k_shade block mod kShards (a block pushes <= one ray per thread)
     const uint32_t nblocks = (uint32_t)t.size() * (uint32_t)shade_blocks_per_tile((int)(c->tile_w * c->tile_h), (int)c->slots);
     c->ext_cap = std::max<uint32_t>(1, (nblocks + kShards - 1) / kShards) * kBlock;
-    c->any_cap = 2 * c->ext_cap;
+    const uint32_t mult = c->any_mult;  // any-hit rays per material evaluation: 2, or 3 with emitter sampling active
+    c->any_cap = mult * c->ext_cap;
     const size_t need = (size_t)kShards * c->ext_cap;
-    if (need > c->queue_alloc) {
+    if (need > c->queue_alloc || mult != c->any_alloc_mult) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (c->ext_q) (void)hipFree(c->ext_q);
         if (c->any_q) (void)hipFree(c->any_q);
@@ -207,14 +322,15 @@ static int set_tiles_internal(mcpt_ctx* c, const std::vector<int2>& t) {
         c->any_ray = nullptr;
         c->queue_alloc = 0;
         if (hipMalloc(&c->ext_q, need * sizeof(uint32_t)) != hipSuccess ||
-            hipMalloc(&c->any_q, 2 * need * sizeof(uint32_t)) != hipSuccess ||
+            hipMalloc(&c->any_q, mult * need * sizeof(uint32_t)) != hipSuccess ||
             hipMalloc(&c->mat_q, need * 8 * sizeof(uint32_t)) != hipSuccess ||  // MatRec + beta per slot
-            hipMalloc(&c->any_ray, 4 * need * sizeof(float4)) != hipSuccess)    // o + d per any-queue entry
+            hipMalloc(&c->any_ray, 2 * mult * need * sizeof(float4)) != hipSuccess)  // o + d per any-queue entry
             return set_err(c, MCPT_E_NOMEM, "queue allocation failed");
         c->queue_alloc = need;
+        c->any_alloc_mult = mult;
     }
-    c->p.sray_o = c->any_ray;  // indexed by any-queue position (kShards * any_cap = 2 * need entries)
-    c->p.sray_d = c->any_ray + 2 * c->queue_alloc;
+    c->p.sray_o = c->any_ray;  // indexed by any-queue position (kShards * any_cap = mult * need entries)
+    c->p.sray_d = c->any_ray + mult * c->queue_alloc;
     if (t.size() > c->tiles_cap) {
         if (c->tiles) HIPCHK(c, hipFree(c->tiles));
         c->tiles = nullptr;
@@ -576,6 +692,14 @@ static int enqueue_iteration(mcpt_ctx* c, size_t evbase, bool timing, const int2
     sa.skip = c->skip_discarded ? 1 : 0;
     sa.budget = c->ad.budget_on ? c->ad.budget.get() : nullptr;
     sa.emis = c->em.dev_table();
+    // emitter sampling (section 17): its table and streams only while it is active (run_iterations sized them)
+    const bool samp = c->es.active() && sa.emis && c->es.nee2.get() && c->es.vis.get();
+    sa.emit_cdf = samp ? c->es.cdf.get() : nullptr;
+    sa.emit_ent = samp ? c->es.ent.get() : nullptr;
+    sa.emit_n = samp ? (int)c->es.tab.cdf.size() : 0;
+    sa.emit_vis0 = samp ? (uint32_t)(2 * c->es.paths) : 0u;
+    sa.nee2 = samp ? c->es.nee2.get() : nullptr;
+    if (samp) sa.p.vis = c->es.vis;  // 3P bytes: the emitter rays' results behind the two of every path
     if (int rc = cam_table(c, c->W, c->H, &sa.cam_px, &sa.cam_dir)) return rc;
     prim_table(c, sa);
     const int bpt = shade_blocks_per_tile((int)(c->tile_w * c->tile_h), (int)c->slots);
@@ -608,7 +732,7 @@ static int enqueue_iteration(mcpt_ctx* c, size_t evbase, bool timing, const int2
     v.ray_at_slot = 1;  // k_material stores the any-hit rays at their queue positions
     ta.phase = c->count_work ? &c->cnt->shard[0][C_PH] : nullptr;  // loop-phase counts (mcpt_debug_trace_profile)
     ta.hit_tri = c->p.hit_tri;
-    ta.vis = c->p.vis;
+    ta.vis = sa.p.vis;
     ta.grab = &c->cnt->grab[0][0];  // reset by k_accumulate below
     ta.idle = &c->cnt->idle;
     ta.tiny_stack = c->tiny_stack ? 1 : 0;
@@ -628,6 +752,25 @@ static int run_iterations(mcpt_ctx* c, uint32_t n, mcpt_stage_stats* st, const i
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if (c->film_stale && !(c->cfg.flags & MCPT_FLAG_NO_AUTO_CLEAR) && (rc = mcpt_film_clear(c))) return rc;
+    if (c->es.active()) {
+        // Emitter sampling's per-path streams (section 17), allocated like nee0 for the current path
+        // count and only while sampling is active: the emitter terms, and the any-hit results with a
+        // third byte per path (the film's own two-byte array rests meanwhile).
+        EmitterSampling& es = c->es;
+        const size_t paths = c->npx * c->slots;
+        if (es.paths != paths || !es.nee2.get() || !es.vis.get()) {
+            if (3 * (uint64_t)paths >= (1ull << 32)) return set_err(c, MCPT_E_INVALID, "film too large for emitter sampling");
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            es.drop_streams();
+            if (!es.nee2.ensure(paths) || !es.vis.ensure(3 * paths)) {
+                es.drop_streams();
+                return set_err(c, MCPT_E_NOMEM, "hipMalloc: emitter sampling streams");
+            }
+            HIPCHK(c, hipMemset(es.nee2, 0, paths * sizeof(float4)));
+            HIPCHK(c, hipMemset(es.vis, 0, 3 * paths));
+            es.paths = paths;
+        }
+    }
     if (!tiles) {
         tiles = c->tiles;
         ntiles = (int)c->tiles_h.size();

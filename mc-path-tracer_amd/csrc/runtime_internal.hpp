@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "host/emitter_table.hpp"
 #include "kernels.hpp"
 #include "mcpt.h"
 
@@ -190,6 +191,29 @@ struct Emission {
     }
 };
 
+// Emitter sampling (mcpt_set_emitter_sampling): the switch, the emitter table
+// of the uploaded scene under the installed emission (host copy and device arrays) and the two per-path
+// streams the sampling instantiations use.  Active = switched on and a non-empty table; only then do the
+// streams exist and the kernels differ.  The table is rebuilt (emitter_table_refresh) while the switch is
+// on whenever the emission table or the geometry changes; a scene upload drops it.
+struct EmitterSampling {
+    bool on = false;
+    mcpt_host::EmitterTable tab;
+    DevBuf<float> cdf;
+    DevBuf<uint2> ent;     // {record index, pick bits} per entry
+    DevBuf<float4> nee2;   // [P]
+    DevBuf<uint8_t> vis;   // [3P]: the any-hit results with the emitter rays' third part
+    size_t paths = 0;      // P the streams were last sized (and zeroed) for
+    float build_ms = 0.f;  // the last table build: weights kernel, readback, host table, upload
+    bool active() const { return on && !tab.cdf.empty(); }
+    void drop_table() { tab = mcpt_host::EmitterTable{}; }
+    void drop_streams() {
+        nee2.reset();
+        vis.reset();
+        paths = 0;
+    }
+};
+
 // The upload-time environment knobs as the last upload read them (read_upload_env, scene_upload.cpp;
 // a geometry update takes them from here and never calls getenv)
 struct UploadKnobs {
@@ -279,6 +303,7 @@ struct mcpt_ctx {
     uint32_t trace_parts_default = 1;
     SceneState scene;
     Emission em;
+    EmitterSampling es;
     bool has_scene_before = false;  // set at the start of a re-upload
     // traversal work counters (mcpt_set_work_counters): k_trace's counting instantiation, whose six
     // per-lane counters cost the fast one its spill-free registers -- off by default
@@ -314,7 +339,9 @@ struct mcpt_ctx {
     uint32_t *ext_q = nullptr, *any_q = nullptr, *mat_q = nullptr;
     float4* any_ray = nullptr;          // any-hit rays at their queue positions: o [2 queue_alloc], then d
     uint32_t ext_cap = 0, any_cap = 0;  // per-shard capacities
-    size_t queue_alloc = 0;             // entries allocated for ext_q (any_q holds twice)
+    size_t queue_alloc = 0;             // entries allocated for ext_q (any_q holds any_alloc_mult times as many)
+    uint32_t any_mult = 2, any_alloc_mult = 0;  // any-hit rays per material evaluation: wanted (3 with emitter
+                                                // sampling active) / as the queues are allocated
     CounterBlock* cnt = nullptr;
     CounterBlock* cnt_host = nullptr;  // pinned
     CounterBlock totals{};             // host copy of the counters after the last call (valid: totals_ok)
@@ -388,6 +415,10 @@ struct TmpScope {
 // Defined in runtime.cpp (C++ linkage: `extern "C++"` where they stand inside its extern "C" block)
 hipEvent_t ev(mcpt_ctx* c, size_t i);
 int check_ready(mcpt_ctx* c);
+// The emitter table again from the current scene and emission (nothing while the switch is off or no
+// scene stands).  A table that differs bitwise from the previous one marks the film stale and drops the
+// temporal history.
+int emitter_table_refresh(mcpt_ctx* c);
 int cam_table(mcpt_ctx* c, uint32_t W, uint32_t H, const float4** px, const float4** dir);
 int film_view(mcpt_ctx* c, const float4** Ld, const uint32_t** samples);
 // n float4 of a device plane to the host: the xyz as 3 floats per element and / or the w (nullptr: not wanted)

@@ -471,6 +471,8 @@ static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
     c->has_scene_before = c->has_scene_before || sc.ok;
     sc.reset();
     c->em.drop();  // the emission table belongs to the scene that goes
+    c->es.drop_table();  // ... and the emitter table with it (the switch stays; section 17)
+    c->es.drop_streams();
     read_upload_env(sc.knobs);
     sc.gpu_upload = gpu_bvh;
     sc.ntri = d->ntri;
@@ -603,7 +605,7 @@ static int geometry_update_device(mcpt_ctx* c, int32_t ntri, const float* v0, co
     HIPCHK(c, hipEventElapsedTime(&ms[2], ev(c, EV_UPD_TREE), ev(c, EV_UPD_QUAD)));
     HIPCHK(c, hipEventElapsedTime(&ms[6], ev(c, EV_UPD_START), ev(c, EV_UPD_END)));
     scene_commit(c, s, true);
-    return MCPT_OK;
+    return emitter_table_refresh(c);  // areas and positions moved (emitter sampling, section 17)
 }
 
 extern "C" {

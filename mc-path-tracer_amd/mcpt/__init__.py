@@ -204,6 +204,9 @@ ABI = {
     "mcpt_debug_variance_ms": (C.c_int, [C.c_void_p, _f]),
     "mcpt_set_material_emission": (C.c_int, [C.c_void_p, C.c_int32, _f]),
     "mcpt_material_emission_read": (C.c_int, [C.c_void_p, _f, _i]),
+    "mcpt_set_emitter_sampling": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mcpt_emitter_table_read": (C.c_int, [C.c_void_p, _f, _f, _u, _i]),
+    "mcpt_debug_emitter_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "mcpt_scene_set_material_emission": (C.c_int, [C.c_void_p, C.c_int32, _f]),
     "mcpt_scene_get_emission": (C.c_int, [C.c_void_p, C.POINTER(_f), _i]),
     "mcpt_sync": (C.c_int, [C.c_void_p]),
@@ -528,6 +531,32 @@ class PathTracer:
         if e.ndim != 2 or e.shape[1] != 3:
             raise ValueError("emission must be an (nmat, 3) array")
         self._ck(lib().mcpt_set_material_emission(self.h, e.shape[0], fptr(e)))
+
+    def set_emitter_sampling(self, on=True):
+        """Sample emissive triangles as lights (mcpt_set_emitter_sampling).  Off by
+        default; inactive while no triangle emits.  Toggling clears the film at the next render."""
+        self._ck(lib().mcpt_set_emitter_sampling(self.h, 1 if on else 0))
+
+    def emitter_table(self):
+        """The emitter table as (cdf, pick, tri_id) arrays in ascending scene triangle id, empty when
+        sampling is off or nothing emits."""
+        n = C.c_int32(0)
+        self._ck(lib().mcpt_emitter_table_read(self.h, None, None, None, C.byref(n)))
+        cdf, pick = np.zeros(n.value, np.float32), np.zeros(n.value, np.float32)
+        tid = np.zeros(n.value, np.uint32)
+        if n.value:
+            self._ck(lib().mcpt_emitter_table_read(self.h, fptr(cdf), fptr(pick), tid.ctypes.data_as(_u), C.byref(n)))
+        return cdf, pick, tid
+
+    def emitter_stats(self):
+        """dict: entries, total weight, emitter rays made since the last film clear, the last table
+        build's ms, and whether sampling is active (mcpt_debug_emitter_stats)."""
+        out = (C.c_double * 4)()
+        rc = lib().mcpt_debug_emitter_stats(self.h, out)
+        if rc < 0:
+            self._ck(rc)
+        return {"entries": int(out[0]), "total_weight": out[1], "emitter_rays": int(out[2]), "build_ms": out[3],
+                "active": rc == 1}
 
     def emission(self):
         """The installed table as an (nmat, 3) array, or None when none is installed."""
