@@ -19,7 +19,8 @@ HDRS := include/mcpt.h $(PKG)/csrc/kernels.hpp $(PKG)/csrc/device/mcpt_core.hpp 
         $(PKG)/csrc/runtime_internal.hpp $(PKG)/csrc/host/host_internal.hpp $(PKG)/csrc/host/pair_tree.hpp \
         $(PKG)/csrc/host/emitter_table.hpp
 
-all: $(PKG)/libmcpt.so oracle/liboracle.so examples/mcpt_render tests/native/facade_test tests/native/primary_beam tests/native/occ_beam tests/native/emitter_table_host
+all: $(PKG)/libmcpt.so oracle/liboracle.so examples/mcpt_render tests/native/facade_test tests/native/primary_beam tests/native/occ_beam tests/native/emitter_table_host \
+     tests/native/env_search_host tests/native/env_search_host_san
 
 $(BUILD)/%.o: $(PKG)/csrc/% $(HDRS)
 	@mkdir -p $(dir $@)
@@ -50,11 +51,20 @@ tests/native/occ_beam: tests/native/occ_beam.cpp $(PKG)/csrc/device/occ_beam.hpp
 tests/native/emitter_table_host: tests/native/emitter_table_host.cpp $(PKG)/csrc/host/emitter_table.cpp $(PKG)/csrc/host/emitter_table.hpp
 	g++ -O2 -std=c++17 -Wall -Wextra -ffp-contract=off -I$(PKG)/csrc $< $(PKG)/csrc/host/emitter_table.cpp -o $@
 
+# Host check of the env light's guided CDF search against the plain bisection (device/mcpt_core.hpp) on the
+# CPU, and the same program under the host sanitizers (run directly: it loads nothing else)
+tests/native/env_search_host: tests/native/env_search_host.cpp $(PKG)/csrc/device/mcpt_core.hpp
+	$(HIPCC) -O2 -std=c++17 -ffp-contract=off -fno-fast-math -Iinclude -I$(PKG)/csrc $< -o $@
+tests/native/env_search_host_san: tests/native/env_search_host.cpp $(PKG)/csrc/device/mcpt_core.hpp
+	$(HIPCC) -O1 -g -std=c++17 -ffp-contract=off -fno-fast-math -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
+	    -Iinclude -I$(PKG)/csrc $< -o $@
+
 oracle/liboracle.so: oracle/mcpt_oracle.c oracle/trav_model.c oracle/mcpt_oracle.h
 	$(MAKE) -C oracle
 
 clean:
-	rm -rf $(BUILD) $(PKG)/libmcpt.so examples/mcpt_render tests/native/facade_test tests/native/primary_beam tests/native/occ_beam tests/native/emitter_table_host
+	rm -rf $(BUILD) $(PKG)/libmcpt.so examples/mcpt_render tests/native/facade_test tests/native/primary_beam tests/native/occ_beam tests/native/emitter_table_host \
+	    tests/native/env_search_host tests/native/env_search_host_san
 	$(MAKE) -C oracle clean
 
 .PHONY: all clean

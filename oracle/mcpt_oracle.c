@@ -404,6 +404,25 @@ void or_env_dir(const or_scene *sc, float ex, float ey, float *wi) {
     wi[0] = d.x; wi[1] = d.y; wi[2] = d.z;
 }
 float or_env_pdf(const or_scene *sc, float dx, float dy, float dz) { return env_pdf(sc, V(dx, dy, dz), 0); }
+/* or_env_dir / or_env_pdf in either mode (fixed: clamped indices, cell centres, the sampled cell's pdf) */
+void or_env_dir_mode(const or_scene *sc, float ex, float ey, int32_t fixed, float *wi) {
+    int W = sc->env_w, H = sc->env_h;
+    int y = (int)((float)or_upper_bound(sc->env_marginal_y, H, ey) - 1.f);
+    if (y < 0) y = 0;
+    int x = (int)((float)or_upper_bound(sc->env_conds_y + (int64_t)y * W, W, ex) - 1.f);
+    v3 d;
+    if (fixed) {
+        y = y > H - 1 ? H - 1 : y;
+        x = x < 0 ? 0 : (x > W - 1 ? W - 1 : x);
+        d = spherical_direction(((float)x + 0.5f) / (float)W, ((float)y + 0.5f) / (float)H);
+    } else {
+        d = spherical_direction((float)x / (float)W, (float)y / (float)H);
+    }
+    wi[0] = d.x; wi[1] = d.y; wi[2] = d.z;
+}
+float or_env_pdf_mode(const or_scene *sc, float dx, float dy, float dz, int32_t fixed) {
+    return env_pdf(sc, V(dx, dy, dz), fixed);
+}
 
 static void light_dir(const or_scene *sc, int id, const rng_t *r, v3 *wi, int fixed) {
     if (id == 0) *wi = env_dir(sc, r, fixed);

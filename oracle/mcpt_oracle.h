@@ -106,6 +106,9 @@ float or_rand(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t len, uint
 void or_env_fetch(const or_scene *sc, float u, float v, float *rgb);
 float or_env_pdf(const or_scene *sc, float dx, float dy, float dz);
 void or_env_dir(const or_scene *sc, float ex, float ey, float *wi);
+/* the same two in either mode (fixed != 0: quality mode) */
+void or_env_dir_mode(const or_scene *sc, float ex, float ey, int32_t fixed, float *wi);
+float or_env_pdf_mode(const or_scene *sc, float dx, float dy, float dz, int32_t fixed);
 /* BRDF hooks: params = base rgb, fresnel rgb, roughness, metallic.
  * out: f_spec rgb, f_diff rgb, pdf_spec, pdf_diff. */
 void or_brdf_eval(const float *params, const float *n, const float *wi, const float *wo, float *out);

@@ -63,6 +63,8 @@ def lib():
             "or_env_fetch": (None, [C.POINTER(OrScene), C.c_float, C.c_float, _f]),
             "or_env_pdf": (C.c_float, [C.POINTER(OrScene), C.c_float, C.c_float, C.c_float]),
             "or_env_dir": (None, [C.POINTER(OrScene), C.c_float, C.c_float, _f]),
+            "or_env_dir_mode": (None, [C.POINTER(OrScene), C.c_float, C.c_float, C.c_int32, _f]),
+            "or_env_pdf_mode": (C.c_float, [C.POINTER(OrScene), C.c_float, C.c_float, C.c_float, C.c_int32]),
             "or_brdf_eval": (None, [_f, _f, _f, _f, _f]),
             "or_brdf_sample": (None, [_f, _f, _f, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                       _f, C.c_int]),
@@ -319,6 +321,23 @@ def env_build(tex: np.ndarray):
     den = np.zeros(1, np.float32)
     lib().or_env_build(W, H, fptr(tex), fptr(my), fptr(mp), fptr(cy), fptr(pdf), fptr(den))
     return {"marginal_y": my, "marginal_p": mp, "conds_y": cy, "pdf": pdf, "denom": float(den[0])}
+
+
+def env_draws(arrays, ex, ey, fixed=False):
+    """or_env_dir_mode / or_env_pdf_mode over draws (ex[i], ey[i]): the sampled directions (n, 3) and the
+    light's pdf at each of them."""
+    s = scene_struct(arrays)
+    n = len(ex)
+    d = np.zeros((n, 3), np.float32)
+    pdf = np.zeros(n, np.float32)
+    L = lib()
+    for i in range(n):
+        if fixed:
+            L.or_env_dir_mode(C.byref(s), float(ex[i]), float(ey[i]), 1, fptr(d[i]))
+        else:
+            L.or_env_dir(C.byref(s), float(ex[i]), float(ey[i]), fptr(d[i]))
+        pdf[i] = L.or_env_pdf_mode(C.byref(s), float(d[i, 0]), float(d[i, 1]), float(d[i, 2]), int(fixed))
+    return d, pdf
 
 
 def brdf_sample(params, n, wo, seed, pixel, sample, ln, slot0, spec, fixed=False):

@@ -98,7 +98,9 @@ def test_table(c2):
 
 
 def test_native_table_builder():
-    """The host builder as a stand-alone program (built by `make`)."""
+    """The host builder as a stand-alone program (built by the Makefile, here too if it is not there yet, like
+    the other native tests)."""
+    subprocess.run(["make", "tests/native/emitter_table_host"], cwd=REPO, check=True, capture_output=True)
     exe = os.path.join(REPO, "tests", "native", "emitter_table_host")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr
