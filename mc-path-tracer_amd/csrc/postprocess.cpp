@@ -26,13 +26,9 @@ static int span_end(mcpt_ctx* c, float* ms) {
 // MCPT_OK when the last iteration since the film clear left no live path (the counters' host copy),
 // else MCPT_E_INVALID with `busy` as its text
 static int require_idle(mcpt_ctx* c, const char* busy) {
-    if (!c->totals_ok) {
-        HIPCHK(c, hipMemcpyAsync(c->cnt_host, c->cnt, sizeof(CounterBlock), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->totals = *c->cnt_host;
-        c->totals_ok = true;
-    }
-    return c->totals.last_live != 0 ? set_err(c, MCPT_E_INVALID, busy) : MCPT_OK;
+    if (!c->cnt.totals_ok)
+        if (int rc = c->cnt.refresh(c)) return rc;
+    return c->cnt.totals.last_live != 0 ? set_err(c, MCPT_E_INVALID, busy) : MCPT_OK;
 }
 // The caller's parameters, or the defaults where it passed none
 template <class P>
@@ -71,7 +67,7 @@ static bool denoise_planes_ensure(mcpt_ctx* c, bool with_vl) {
     Denoise& d = c->dn;
     d.result = -1;
     d.guided = false;
-    const size_t P = c->P;
+    const size_t P = c->film.pixels();
     const bool ok = d.col[0].ensure(P) && d.col[1].ensure(P) && d.gd.ensure(P) && d.al.ensure(P) &&
                     (!with_vl || (d.vl[0].ensure(P) && d.vl[1].ensure(P)));
     if (!ok) {
@@ -238,7 +234,7 @@ static int film_planes(mcpt_ctx* c, bool guided, const float4* Ld, const uint32_
     pa.col = c->dn.col[0];
     pa.gd = c->dn.gd;
     pa.al = c->dn.al;
-    pa.n = (uint32_t)c->P;
+    pa.n = (uint32_t)c->film.pixels();
     if (guided) {
         pa.err = c->slots >= 2 ? c->ad.err4.get() : nullptr;
         pa.vl = c->dn.vl[0];
@@ -253,7 +249,7 @@ static int film_planes(mcpt_ctx* c, bool guided, const float4* Ld, const uint32_
 // call's own path (its checks: >= 2 path slots, no paths in flight); with the variance fill on, one
 // path slot skips that call (no paths in flight all the same) and every variance is the estimate.
 static int film_denoise(mcpt_ctx* c, const DenoiseRequest& r) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    if (!c || !c->film.allocated) return set_err(c, MCPT_E_INVALID, "film not allocated");
     int rc = denoise_check_params(c, r);
     if (rc) return rc;
     if (!guides_valid(c))
@@ -294,7 +290,7 @@ int mcpt_guides_render(mcpt_ctx* c, uint32_t nsamples) {
     HIPCHK(c, hipSetDevice(c->device));
     Guides& g = c->guides;
     g.ok = false;
-    const size_t P = c->P;
+    const size_t P = c->film.pixels();
     if (!g.alb || !g.nz) {
         c->dn = Denoise{};  // (the filter's planes go too: they are re-made on demand)
         g = Guides{};
@@ -360,17 +356,17 @@ int mcpt_guides_render(mcpt_ctx* c, uint32_t nsamples) {
             ts.count = n;
             ts.shard_cap = n;
             ta.hit_tri = ht;
-            ta.grab = &c->cnt->grab[0][0];
+            ta.grab = &c->cnt.dev->grab[0][0];
             ta.tiny_stack = c->tiny_stack ? 1 : 0;
             launch_trace(ta, c->geom, c->stream);
-            HIPCHK(c, hipMemcpyAsync(&c->cnt_host->grab[0][0], &c->cnt->grab[0][0], sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemsetAsync(c->cnt->grab, 0, sizeof(c->cnt->grab), c->stream));  // hand-out counters back to 0
+            HIPCHK(c, hipMemcpyAsync(&c->cnt.host->grab[0][0], &c->cnt.dev->grab[0][0], sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemsetAsync(c->cnt.dev->grab, 0, sizeof(c->cnt.dev->grab), c->stream));  // hand-out counters back to 0
             HitRecordArgs ha{c->scene.dev, ro, rd, ht, hp, hn, ht, n};
             launch_hit_record(ha, c->stream);
             launch_guide_accum(ga, c->stream);
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipStreamSynchronize(c->stream));  // the next chunk reuses the buffers (and the staging word)
-            if (c->cnt_host->grab[0][0] < n) drained = false;
+            if (c->cnt.host->grab[0][0] < n) drained = false;
         }
     }
     if ((rc = span_end(c, &c->ms.guides))) return rc;
@@ -381,14 +377,14 @@ int mcpt_guides_render(mcpt_ctx* c, uint32_t nsamples) {
 }
 
 int mcpt_guides_read(mcpt_ctx* c, float* albedo, float* normal, float* depth, uint32_t* count) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    if (!c || !c->film.allocated) return set_err(c, MCPT_E_INVALID, "film not allocated");
     if (!guides_valid(c)) return set_err(c, MCPT_E_INVALID, "no valid guide buffers: call mcpt_guides_render first");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::vector<float> cnt(count ? c->P : 0);  // the sample counts are kept as floats
+    std::vector<float> cnt(count ? c->film.pixels() : 0);  // the sample counts are kept as floats
     int rc;
-    if ((rc = read_plane(c, c->guides.alb, c->P, albedo, count ? cnt.data() : nullptr)) ||
-        (rc = read_plane(c, c->guides.nz, c->P, normal, depth)))
+    if ((rc = read_plane(c, c->guides.alb, c->film.pixels(), albedo, count ? cnt.data() : nullptr)) ||
+        (rc = read_plane(c, c->guides.nz, c->film.pixels(), normal, depth)))
         return rc;
     for (size_t i = 0; i < cnt.size(); i++) count[i] = (uint32_t)cnt[i];
     return MCPT_OK;
@@ -405,7 +401,7 @@ int mcpt_film_denoise(mcpt_ctx* c, const mcpt_denoise_params* pp) {
 }
 
 static int denoised_check(mcpt_ctx* c) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    if (!c || !c->film.allocated) return set_err(c, MCPT_E_INVALID, "film not allocated");
     if (c->dn.result < 0) return set_err(c, MCPT_E_INVALID, "no denoised frame: call mcpt_film_denoise first");
     return MCPT_OK;
 }
@@ -416,7 +412,7 @@ int mcpt_denoised_read(mcpt_ctx* c, float* rgb) {
     if (!rgb) return set_err(c, MCPT_E_INVALID, "null argument");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    return read_plane(c, c->dn.col[c->dn.result], c->P, rgb, nullptr);
+    return read_plane(c, c->dn.col[c->dn.result], c->film.pixels(), rgb, nullptr);
 }
 
 int mcpt_denoised_read_device(mcpt_ctx* c, void* d_rgb) {
@@ -424,7 +420,7 @@ int mcpt_denoised_read_device(mcpt_ctx* c, void* d_rgb) {
     if (rc) return rc;
     if (!d_rgb) return set_err(c, MCPT_E_INVALID, "null argument");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(d_rgb, c->dn.col[c->dn.result], c->P * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_rgb, c->dn.col[c->dn.result], c->film.pixels() * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return MCPT_OK;
 }
@@ -473,7 +469,7 @@ int mcpt_denoised_variance_read(mcpt_ctx* c, float* var) {
     if (!var) return set_err(c, MCPT_E_INVALID, "null argument");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    return read_x(c, c->dn.vl[c->dn.result], c->P, var);
+    return read_x(c, c->dn.vl[c->dn.result], c->film.pixels(), var);
 }
 
 int mcpt_debug_denoise_ms(const mcpt_ctx* c, float* out10) {
@@ -489,17 +485,17 @@ int mcpt_debug_denoise_ms(const mcpt_ctx* c, float* out10) {
 // k_shade block done flags and the counter block's idle word (run_iterations resets the latter per
 // call too).  The film, the flags words' next sample indices and the ray counters stay.
 static int frame_done_reset(mcpt_ctx* c) {
-    if (c->blk_done) HIPCHK(c, hipMemsetAsync(c->blk_done, 0, c->blk_done_n, c->stream));
-    HIPCHK(c, hipMemsetAsync(&c->cnt->idle, 0, sizeof(uint32_t), c->stream));
+    if (c->film.blk_done) HIPCHK(c, hipMemsetAsync(c->film.blk_done, 0, c->film.L.blk_done_n, c->stream));
+    HIPCHK(c, hipMemsetAsync(&c->cnt.dev->idle, 0, sizeof(uint32_t), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return MCPT_OK;
 }
 // The film tiles' ownership for the current tile set and layout (OwnMap), uploaded
 static int own_map_build(mcpt_ctx* c, OwnMap* m) {
-    const uint32_t ntx = (c->W + c->tile_w - 1) / c->tile_w, nty = (c->H + c->tile_h - 1) / c->tile_h;
+    const uint32_t ntx = c->film.L.nx, nty = c->film.L.ny;
     std::vector<int32_t> own((size_t)ntx * nty, -1);
-    for (size_t i = 0; i < c->tiles_h.size(); i++) own[(size_t)c->tiles_h[i].y * ntx + (size_t)c->tiles_h[i].x] = (int32_t)i;
-    for (const int2& t : c->unpacked) own[(size_t)t.y * ntx + (size_t)t.x] = -1;  // another context's pixels
+    for (size_t i = 0; i < c->tiles.host.size(); i++) own[(size_t)c->tiles.host[i].y * ntx + (size_t)c->tiles.host[i].x] = (int32_t)i;
+    for (const int2& t : c->film.unpacked) own[(size_t)t.y * ntx + (size_t)t.x] = -1;  // another context's pixels
     if (int rc = ensure_or_nomem(c, c->ad.own_map, own.size())) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(c->ad.own_map, own.data(), own.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -514,17 +510,17 @@ static int film_error_launch(mcpt_ctx* c, const FilmErrorArgs& a) {
 }
 
 int mcpt_set_sample_budget(mcpt_ctx* c, const uint32_t* budget) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    if (!c || !c->film.allocated) return set_err(c, MCPT_E_INVALID, "film not allocated");
     HIPCHK(c, hipSetDevice(c->device));
     int rc = require_idle(c, "sample budget: paths are in flight (finish the render or clear the film)");
     if (rc) return rc;
     uint32_t mx = 0;
     if (budget) {
-        for (size_t i = 0; i < c->P; i++) mx = std::max(mx, budget[i]);
+        for (size_t i = 0; i < c->film.pixels(); i++) mx = std::max(mx, budget[i]);
         if (mx > kMaxSpp - 256) return set_err(c, MCPT_E_INVALID, "sample budget: an entry exceeds 2^19 - 256");
-        if ((rc = ensure_or_nomem(c, c->ad.budget, c->P))) return rc;
+        if ((rc = ensure_or_nomem(c, c->ad.budget, c->film.pixels()))) return rc;
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipMemcpy(c->ad.budget, budget, c->P * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->ad.budget, budget, c->film.pixels() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     c->ad.budget_on = budget != nullptr;
     c->ad.budget_max = mx;
@@ -536,33 +532,33 @@ int mcpt_sample_budget_read(mcpt_ctx* c, uint32_t* out) {
     if (!c->ad.budget_on) return set_err(c, MCPT_E_INVALID, "no sample budget installed");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out, c->ad.budget, c->P * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out, c->ad.budget, c->film.pixels() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return MCPT_OK;
 }
 
 int mcpt_set_spp(mcpt_ctx* c, int32_t spp) {
     if (!c) return MCPT_E_INVALID;
     if (spp < 0 || (uint32_t)spp > kMaxSpp - 256) return set_err(c, MCPT_E_INVALID, "spp must be 0..2^19-256");
-    if (c->P) {
+    if (c->film.allocated) {
         HIPCHK(c, hipSetDevice(c->device));
         if (int rc = require_idle(c, "set_spp: paths are in flight (finish the render or clear the film)")) return rc;
     }
     c->cfg.spp = spp;
-    return c->P ? frame_done_reset(c) : MCPT_OK;
+    return c->film.allocated ? frame_done_reset(c) : MCPT_OK;
 }
 
 int mcpt_film_error(mcpt_ctx* c) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    if (!c || !c->film.allocated) return set_err(c, MCPT_E_INVALID, "film not allocated");
     if (c->slots < 2) return set_err(c, MCPT_E_INVALID, "film error: needs at least 2 path slots (mcpt_set_path_slots)");
     HIPCHK(c, hipSetDevice(c->device));
     int rc = require_idle(c, "film error: paths are in flight");
     if (rc) return rc;
-    if ((rc = ensure_or_nomem(c, c->ad.err4, c->P))) return rc;
+    if ((rc = ensure_or_nomem(c, c->ad.err4, c->film.pixels()))) return rc;
     FilmErrorArgs a{};
     if ((rc = own_map_build(c, &a.m))) return rc;
-    a.Ld = c->p.Ld;
-    a.samples = c->p.samples;
-    a.stride = c->npx;
+    a.Ld = c->film.Ld;
+    a.samples = c->film.samples;
+    a.stride = c->film.L.npx;
     a.slots = (int)c->slots;
     a.out = c->ad.err4;
     c->ad.err_ok = false;
@@ -576,7 +572,7 @@ int mcpt_film_error_read(mcpt_ctx* c, float* out4) {
     if (!c->ad.err_ok) return set_err(c, MCPT_E_INVALID, "no film error estimate (call mcpt_film_error first)");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out4, c->ad.err4, c->P * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out4, c->ad.err4, c->film.pixels() * sizeof(float4), hipMemcpyDeviceToHost));
     return MCPT_OK;
 }
 
@@ -609,21 +605,21 @@ int mcpt_error_run(mcpt_ctx* c, uint32_t w, uint32_t h, uint32_t slots, const fl
 }
 
 int mcpt_debug_film_read_slot(mcpt_ctx* c, uint32_t slot, float* Ld, uint32_t* samples) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    if (!c || !c->film.allocated) return set_err(c, MCPT_E_INVALID, "film not allocated");
     if (slot >= c->slots) return set_err(c, MCPT_E_INVALID, "slot out of range");
     HIPCHK(c, hipSetDevice(c->device));
     SlotImageArgs a{};
     int rc = own_map_build(c, &a.m);
     if (rc) return rc;
     TmpScope tmp(c);
-    if ((rc = dalloc(c, tmp.L, &a.out_Ld, c->P)) || (rc = dalloc(c, tmp.L, &a.out_samples, c->P))) return rc;
-    a.Ld = c->p.Ld + (size_t)slot * c->npx;
-    a.samples = c->p.samples + (size_t)slot * c->npx;
+    if ((rc = dalloc(c, tmp.L, &a.out_Ld, c->film.pixels())) || (rc = dalloc(c, tmp.L, &a.out_samples, c->film.pixels()))) return rc;
+    a.Ld = c->film.Ld + (size_t)slot * c->film.L.npx;
+    a.samples = c->film.samples + (size_t)slot * c->film.L.npx;
     launch_slot_image(a, c->stream);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (Ld && (rc = read_plane(c, a.out_Ld, c->P, Ld, nullptr))) return rc;
-    if (samples) HIPCHK(c, hipMemcpy(samples, a.out_samples, c->P * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (Ld && (rc = read_plane(c, a.out_Ld, c->film.pixels(), Ld, nullptr))) return rc;
+    if (samples) HIPCHK(c, hipMemcpy(samples, a.out_samples, c->film.pixels() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return MCPT_OK;
 }
 
@@ -638,7 +634,7 @@ int mcpt_sample_budget_default_params(mcpt_sample_budget_params* p) {
 }
 
 int mcpt_budget_from_error(mcpt_ctx* c, const mcpt_sample_budget_params* pp, uint64_t* out3) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    if (!c || !c->film.allocated) return set_err(c, MCPT_E_INVALID, "film not allocated");
     const mcpt_sample_budget_params p = params_or(pp, mcpt_sample_budget_default_params);
     if (!finite_nonneg(p.target_rel_err) || !(p.target_rel_err > 0.f) || !finite_nonneg(p.lum_floor) || p.min_spp > p.max_spp ||
         p.max_spp > kMaxSpp - 256)
@@ -648,7 +644,7 @@ int mcpt_budget_from_error(mcpt_ctx* c, const mcpt_sample_budget_params* pp, uin
     HIPCHK(c, hipSetDevice(c->device));
     int rc = require_idle(c, "budget: paths are in flight");
     if (rc) return rc;
-    if ((rc = ensure_or_nomem(c, ad.budget, c->P)) || (rc = ensure_or_nomem(c, ad.bud_cnt, 4))) return rc;
+    if ((rc = ensure_or_nomem(c, ad.budget, c->film.pixels())) || (rc = ensure_or_nomem(c, ad.bud_cnt, 4))) return rc;
     BudgetArgs a{};
     if ((rc = own_map_build(c, &a.m))) return rc;
     a.err = ad.err4;
@@ -681,12 +677,12 @@ int mcpt_debug_adaptive_ms(const mcpt_ctx* c, float* out2) {
 
 int mcpt_set_seed(mcpt_ctx* c, uint64_t seed) {
     if (!c) return MCPT_E_INVALID;
-    if (c->P) {
+    if (c->film.allocated) {
         HIPCHK(c, hipSetDevice(c->device));
         if (int rc = require_idle(c, "set_seed: paths are in flight (finish the render or clear the film)")) return rc;
     }
     c->cfg.seed = seed;  // (guides_valid compares it: the guides are stale from here on)
-    return c->P ? mcpt_film_clear(c) : MCPT_OK;
+    return c->film.allocated ? mcpt_film_clear(c) : MCPT_OK;
 }
 
 int mcpt_camera_view_proj(const mcpt_camera* cam, float* out16) {
@@ -725,7 +721,7 @@ static int temporal_launch(mcpt_ctx* c, const TemporalArgs& a) {
 }
 
 int mcpt_film_temporal(mcpt_ctx* c, const mcpt_temporal_params* pp) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    if (!c || !c->film.allocated) return set_err(c, MCPT_E_INVALID, "film not allocated");
     const mcpt_temporal_params p = params_or(pp, mcpt_temporal_default_params);
     int rc = temporal_check_params(c, p);
     if (rc) return rc;
@@ -735,9 +731,9 @@ int mcpt_film_temporal(mcpt_ctx* c, const mcpt_temporal_params* pp) {
     if ((rc = require_idle(c, "temporal: paths are in flight"))) return rc;
     if (c->slots >= 2 && (rc = mcpt_film_error(c))) return rc;
     Temporal& t = c->tp;
-    bool ok = t.col.ensure(c->P) && t.vl.ensure(c->P);
+    bool ok = t.col.ensure(c->film.pixels()) && t.vl.ensure(c->film.pixels());
     for (auto& set : t.h)
-        for (auto& plane : set) ok = ok && plane.ensure(c->P);
+        for (auto& plane : set) ok = ok && plane.ensure(c->film.pixels());
     if (!ok) {
         (void)hipGetLastError();
         t = Temporal{};
@@ -748,7 +744,7 @@ int mcpt_film_temporal(mcpt_ctx* c, const mcpt_temporal_params* pp) {
     if (fill && !denoise_planes_ensure(c, true)) return set_err(c, MCPT_E_NOMEM, "temporal: plane allocation failed");
     const int prev = t.set, next = prev ^ 1;
     if (!t.ok)  // no history: N = 0 everywhere, and every tap is rejected
-        for (int k = 0; k < 3; k++) HIPCHK(c, hipMemsetAsync(t.h[prev][k], 0, c->P * sizeof(float4), c->stream));
+        for (int k = 0; k < 3; k++) HIPCHK(c, hipMemsetAsync(t.h[prev][k], 0, c->film.pixels() * sizeof(float4), c->stream));
     TemporalArgs a{};
     a.W = (int)c->W;
     a.H = (int)c->H;
@@ -787,17 +783,17 @@ int mcpt_temporal_reset(mcpt_ctx* c) {
 }
 
 int mcpt_temporal_read(mcpt_ctx* c, float* rgb, float* nsamples, float* variance, float* position) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    if (!c || !c->film.allocated) return set_err(c, MCPT_E_INVALID, "film not allocated");
     if (!c->tp.ok) return set_err(c, MCPT_E_INVALID, "no accumulated frame: call mcpt_film_temporal first");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const auto& h = c->tp.h[c->tp.set];
-    if (int rc = read_plane(c, h[0], c->P, rgb, nsamples)) return rc;
-    return read_plane(c, h[1], c->P, position, variance);
+    if (int rc = read_plane(c, h[0], c->film.pixels(), rgb, nsamples)) return rc;
+    return read_plane(c, h[1], c->film.pixels(), position, variance);
 }
 
 int mcpt_temporal_denoise(mcpt_ctx* c, const mcpt_denoise_guided_params* pp) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    if (!c || !c->film.allocated) return set_err(c, MCPT_E_INVALID, "film not allocated");
     const DenoiseRequest r = denoise_request(params_or(pp, mcpt_denoise_guided_default_params));
     int rc = denoise_check_params(c, r);
     if (rc) return rc;
@@ -806,7 +802,7 @@ int mcpt_temporal_denoise(mcpt_ctx* c, const mcpt_denoise_guided_params* pp) {
         return set_err(c, MCPT_E_INVALID, "temporal denoise: the camera, scene or seed changed since the frame was accumulated: call mcpt_guides_render and mcpt_film_temporal first");
     HIPCHK(c, hipSetDevice(c->device));
     if (!denoise_planes_ensure(c, true)) return set_err(c, MCPT_E_NOMEM, "temporal denoise: plane allocation failed");
-    const TemporalPrepArgs pa{c->tp.col, c->tp.vl, c->guides.alb, c->guides.nz, c->dn.col[0], c->dn.gd, c->dn.al, c->dn.vl[0], (uint32_t)c->P};
+    const TemporalPrepArgs pa{c->tp.col, c->tp.vl, c->guides.alb, c->guides.nz, c->dn.col[0], c->dn.gd, c->dn.al, c->dn.vl[0], (uint32_t)c->film.pixels()};
     if ((rc = span_begin(c))) return rc;
     launch_temporal_prep(pa, c->stream);
     return denoise_film_planes(c, r);

@@ -6,9 +6,10 @@
 // Differences by design: one stream, no host sync or managed-memory counter
 // readback between stages (counts stay on the device and the trace kernels are
 // persistent), a whole tile set per iteration instead of one 256x256 tile, and
-// error codes instead of exit(99).  The film's post-processing entry points (guides,
-// denoise, adaptive sampling, temporal accumulation) are postprocess.cpp; scene upload and
-// geometry update are scene_upload.cpp; the per-stage parity harness (mcpt_stage_run) and the
+// error codes instead of exit(99).  The tile set, the ray queues, the film state and the film's
+// readers are film_state.cpp; the film's post-processing entry points (guides, denoise, adaptive
+// sampling, temporal accumulation) are postprocess.cpp; scene upload and geometry update are
+// scene_upload.cpp; the per-stage parity harness (mcpt_stage_run) and the
 // mcpt_debug_* entries beyond the counter reads below are stage_run.cpp.
 #include <chrono>
 #include <cstdio>
@@ -46,11 +47,11 @@ int mcpt_create(int device, const mcpt_config* cfg, mcpt_ctx** out) {
         delete c;
         return set_err(nullptr, MCPT_E_HIP, "stream creation failed");
     }
-    if (hipMalloc(&c->cnt, sizeof(CounterBlock)) != hipSuccess || hipHostMalloc(&c->cnt_host, sizeof(CounterBlock)) != hipSuccess) {
+    if (!c->cnt.dev.ensure(1) || !c->cnt.host.alloc(1)) {
         delete c;
         return set_err(nullptr, MCPT_E_NOMEM, "counter allocation failed");
     }
-    (void)hipMemset(c->cnt, 0, sizeof(CounterBlock));
+    (void)hipMemset(c->cnt.dev, 0, sizeof(CounterBlock));
     if (launch_geometry(device, c->geom) != 0) {
         mcpt_destroy(c);
         return set_err(nullptr, MCPT_E_HIP, "occupancy query failed");
@@ -64,21 +65,10 @@ void mcpt_destroy(mcpt_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    c->scene.reset();
-    free_list(c->film_bufs);
-    free_list(c->tmp_bufs);
-    if (c->cnt) (void)hipFree(c->cnt);
-    if (c->cnt_host) (void)hipHostFree(c->cnt_host);
-    if (c->tiles) (void)hipFree(c->tiles);
-    if (c->step_tile) (void)hipFree(c->step_tile);
-    if (c->step_tile_h) (void)hipHostFree(c->step_tile_h);
-    if (c->ext_q) (void)hipFree(c->ext_q);
-    if (c->any_q) (void)hipFree(c->any_q);
-    if (c->mat_q) (void)hipFree(c->mat_q);
-    if (c->any_ray) (void)hipFree(c->any_ray);
+    c->release_buffers();  // every owner's memory goes while the device is current and the stream exists
     for (auto e : c->events) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;  // (every DevBuf of the context goes here)
+    delete c;
 }
 
 int mcpt_device_name(mcpt_ctx* c, char* buf, int32_t len) {
@@ -89,8 +79,8 @@ int mcpt_device_name(mcpt_ctx* c, char* buf, int32_t len) {
 
 int mcpt_debug_ray_counts(const mcpt_ctx* c, uint64_t* out) {
     if (!c || !out) return MCPT_E_INVALID;
-    const CounterBlock& t = c->totals;
-    const bool ok = c->totals_ok;
+    const CounterBlock& t = c->cnt.totals;
+    const bool ok = c->cnt.totals_ok;
     out[0] = ok ? t.tot_ext : 0;    // extension rays (queued + resolved in place)
     out[1] = ok ? t.tot_ext_q : 0;  // extension rays k_trace traversed
     out[2] = ok ? t.tot_any : 0;    // shadow + BRDF visibility rays
@@ -104,26 +94,26 @@ int mcpt_debug_primary_stats(const mcpt_ctx* c, double* out4) {
     if (!c || !out4) return MCPT_E_INVALID;
     out4[0] = c->prim.ok ? (double)c->prim.lists : 0.0;
     out4[1] = c->prim.ok ? (double)c->prim.over : 0.0;
-    out4[2] = c->totals_ok ? (double)c->totals.tot_prim : 0.0;
+    out4[2] = c->cnt.totals_ok ? (double)c->cnt.totals.tot_prim : 0.0;
     out4[3] = (double)c->prim.build_ms;
     return (int)std::min<uint64_t>(c->prim.builds, 0x7fffffffull);
 }
 int mcpt_debug_discard_stats(const mcpt_ctx* c, uint64_t* out4) {
     if (!c || !out4) return MCPT_E_INVALID;
-    for (int k = 0; k < 4; k++) out4[k] = c->totals_ok ? c->totals.tot_skip[k] : 0;
+    for (int k = 0; k < 4; k++) out4[k] = c->cnt.totals_ok ? c->cnt.totals.tot_skip[k] : 0;
     return MCPT_OK;
 }
 int mcpt_debug_occ_complete_stats(const mcpt_ctx* c, double* out4) {
     if (!c || !out4) return MCPT_E_INVALID;
     out4[0] = (double)c->scene.occ_done_keys;
-    out4[1] = c->totals_ok ? (double)c->totals.tot_done[0] : 0.0;
-    out4[2] = c->totals_ok ? (double)c->totals.tot_done[1] : 0.0;
+    out4[1] = c->cnt.totals_ok ? (double)c->cnt.totals.tot_done[0] : 0.0;
+    out4[2] = c->cnt.totals_ok ? (double)c->cnt.totals.tot_done[1] : 0.0;
     out4[3] = (double)c->scene.occ_done_ms;
     return MCPT_OK;
 }
 int mcpt_debug_occ_stats(const mcpt_ctx* c, uint64_t* resolved, int32_t* enabled) {
     if (!c) return MCPT_E_INVALID;
-    if (resolved) *resolved = c->totals_ok ? c->totals.tot_occ : 0;
+    if (resolved) *resolved = c->cnt.totals_ok ? c->cnt.totals.tot_occ : 0;
     if (enabled) *enabled = c->scene.dev.occ != nullptr;
     return MCPT_OK;
 }
@@ -196,18 +186,16 @@ int mcpt_material_emission_read(mcpt_ctx* c, float* rgb, int32_t* nmat) {
 }
 
 // ---- emitter sampling ----
-static int set_tiles_internal(mcpt_ctx* c, const std::vector<int2>& t);
-
 // The any-hit queue holds two rays per material evaluation, three while emitter sampling is active:
 // the queues are re-sized for the current tile set when that changes.
 static int emitter_queues(mcpt_ctx* c) {
     const uint32_t mult = c->es.active() ? 3u : 2u;
-    if (c->any_mult == mult || !c->P) {
+    if (c->any_mult == mult || !c->film.allocated) {
         c->any_mult = mult;
         return MCPT_OK;
     }
     c->any_mult = mult;
-    return set_tiles_internal(c, std::vector<int2>(c->tiles_h));
+    return set_tiles_internal(c, std::vector<int2>(c->tiles.host));
 }
 
 extern "C++" int emitter_table_refresh(mcpt_ctx* c) {
@@ -291,8 +279,8 @@ int mcpt_emitter_table_read(mcpt_ctx* c, float* cdf, float* pick, uint32_t* tri_
 
 static unsigned long long emit_rays(const mcpt_ctx* c) {
     unsigned long long s = 0;
-    if (c->totals_ok)
-        for (int k = 0; k < kShards; k++) s += c->totals.tot_emit[k];
+    if (c->cnt.totals_ok)
+        for (int k = 0; k < kShards; k++) s += c->cnt.totals.tot_emit[k];
     return s;
 }
 
@@ -303,245 +291,6 @@ int mcpt_debug_emitter_stats(const mcpt_ctx* c, double* out4) {
     out4[2] = (double)emit_rays(c);
     out4[3] = (double)c->es.build_ms;
     return c->es.active() ? 1 : 0;
-}
-
-static int set_tiles_internal(mcpt_ctx* c, const std::vector<int2>& t) {
-    // per-shard queue capacity: shard = k_shade block mod kShards (a block pushes <= one ray per thread)
-    const uint32_t nblocks = (uint32_t)t.size() * (uint32_t)shade_blocks_per_tile((int)(c->tile_w * c->tile_h), (int)c->slots);
-    c->ext_cap = std::max<uint32_t>(1, (nblocks + kShards - 1) / kShards) * kBlock;
-    const uint32_t mult = c->any_mult;  // any-hit rays per material evaluation: 2, or 3 with emitter sampling active
-    c->any_cap = mult * c->ext_cap;
-    const size_t need = (size_t)kShards * c->ext_cap;
-    if (need > c->queue_alloc || mult != c->any_alloc_mult) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->ext_q) (void)hipFree(c->ext_q);
-        if (c->any_q) (void)hipFree(c->any_q);
-        if (c->mat_q) (void)hipFree(c->mat_q);
-        if (c->any_ray) (void)hipFree(c->any_ray);
-        c->ext_q = c->any_q = c->mat_q = nullptr;
-        c->any_ray = nullptr;
-        c->queue_alloc = 0;
-        if (hipMalloc(&c->ext_q, need * sizeof(uint32_t)) != hipSuccess ||
-            hipMalloc(&c->any_q, mult * need * sizeof(uint32_t)) != hipSuccess ||
-            hipMalloc(&c->mat_q, need * 8 * sizeof(uint32_t)) != hipSuccess ||  // MatRec + beta per slot
-            hipMalloc(&c->any_ray, 2 * mult * need * sizeof(float4)) != hipSuccess)  // o + d per any-queue entry
-            return set_err(c, MCPT_E_NOMEM, "queue allocation failed");
-        c->queue_alloc = need;
-        c->any_alloc_mult = mult;
-    }
-    c->p.sray_o = c->any_ray;  // indexed by any-queue position (kShards * any_cap = mult * need entries)
-    c->p.sray_d = c->any_ray + mult * c->queue_alloc;
-    if (t.size() > c->tiles_cap) {
-        if (c->tiles) HIPCHK(c, hipFree(c->tiles));
-        c->tiles = nullptr;
-        HIPCHK(c, hipMalloc(&c->tiles, std::max<size_t>(t.size(), 1) * sizeof(int2)));
-        c->tiles_cap = (uint32_t)t.size();
-    }
-    if (!t.empty()) HIPCHK(c, hipMemcpyAsync(c->tiles, t.data(), t.size() * sizeof(int2), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->tiles_h = t;
-    return MCPT_OK;
-}
-static std::vector<int2> all_tiles(const mcpt_ctx* c) {
-    std::vector<int2> t;
-    uint32_t nx = (c->W + c->tile_w - 1) / c->tile_w, ny = (c->H + c->tile_h - 1) / c->tile_h;
-    for (uint32_t y = 0; y < ny; y++)
-        for (uint32_t x = 0; x < nx; x++) t.push_back(make_int2((int)x, (int)y));
-    return t;
-}
-
-int mcpt_film_clear(mcpt_ctx* c) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
-    HIPCHK(c, hipSetDevice(c->device));
-    ClearArgs a{c->p.flags, c->p.samples, c->p.Ld, (uint32_t)(c->npx * c->slots), (uint32_t)c->npx};
-    launch_clear(a, c->stream);
-    HIPCHK(c, hipGetLastError());
-    if (c->compact) {  // the W x H film also holds pixels unpacked from other contexts (mcpt_film_unpack_tiles)
-        HIPCHK(c, hipMemsetAsync(c->film_Ld, 0, c->P * sizeof(float4), c->stream));
-        HIPCHK(c, hipMemsetAsync(c->film_samples, 0, c->P * sizeof(uint32_t), c->stream));
-    }
-    if (c->blk_done) HIPCHK(c, hipMemsetAsync(c->blk_done, 0, c->blk_done_n, c->stream));
-    // The occluder cache starts every film from the same table -- the upload's pre-fill, or empty --
-    // with its lookup gate on, so a frame's work never depends on the frames before it.  (It only
-    // ever chooses which triangle an any-hit ray tests first; the 96 MB copy takes ~0.04 ms.)
-    if (c->scene.dev.occ) {
-        if (c->scene.occ_init) {  // the upload's pre-filled table (scene-derived), the same for every frame
-            HIPCHK(c, hipMemcpyAsync(c->scene.dev.occ, c->scene.occ_init, c->scene.occ_entries_n * sizeof(uint32_t),
-                                     hipMemcpyDeviceToDevice, c->stream));
-            static const uint32_t warm[kOccGateWords] = {0u, 0u, 1u};
-            HIPCHK(c, hipMemcpyAsync(c->scene.dev.occ_gate, warm, sizeof(warm), hipMemcpyHostToDevice, c->stream));
-        } else {
-            HIPCHK(c, hipMemsetAsync(c->scene.dev.occ, 0xff, c->scene.occ_entries_n * sizeof(uint32_t), c->stream));
-            HIPCHK(c, hipMemsetAsync(c->scene.dev.occ_gate, 0, kOccGateWords * sizeof(uint32_t), c->stream));
-        }
-    }
-    c->film_stale = false;
-    c->unpacked.clear();
-    HIPCHK(c, hipMemsetAsync(c->cnt, 0, sizeof(CounterBlock), c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    memset(&c->totals, 0, sizeof(c->totals));  // the counters are now zero on the device too
-    memset(c->phase_base, 0, sizeof(c->phase_base));
-    c->totals_ok = true;
-    return MCPT_OK;
-}
-
-// Film state for the current film size, path slots, layout and tile set: the path streams (slots x
-// npx paths), the k_shade block flags and the W x H film of the slot sums (slots > 1 or compact).
-// Frees the previous film state first; the caller clears the film.
-static int alloc_film_state(mcpt_ctx* c) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    free_list(c->film_bufs);
-    {
-        DevPaths keep{};  // the queue-owned any-hit ray buffers stay
-        keep.sray_o = c->p.sray_o;
-        keep.sray_d = c->p.sray_d;
-        c->p = keep;
-    }
-    c->film_Ld = nullptr;
-    c->film_samples = nullptr;
-    c->blk_done = nullptr;
-    c->blk_done_n = 0;
-    const uint32_t w = c->W, h = c->H, tw = c->tile_w, th = c->tile_h;
-    const size_t npix = (size_t)w * h;
-    const size_t npx = c->compact ? c->tiles_h.size() * (size_t)tw * th : npix;
-    const size_t P = npx * c->slots;  // P: paths
-    c->npx = 0;
-    if (P >= (1ull << 31)) return set_err(c, MCPT_E_INVALID, "film too large for the path slots");
-    DevPaths p{};
-    int rc;
-    if ((rc = dalloc(c, c->film_bufs, &p.ray_o, P)) || (rc = dalloc(c, c->film_bufs, &p.ray_d, P)) ||
-        (rc = dalloc(c, c->film_bufs, &p.hit_tri, P)) ||
-        (rc = dalloc(c, c->film_bufs, &p.beta, P)) || (rc = dalloc(c, c->film_bufs, &p.nee0, P)) ||
-        (rc = dalloc(c, c->film_bufs, &p.nee1, P)) || (rc = dalloc(c, c->film_bufs, &p.Ld, P)) ||
-        (rc = dalloc(c, c->film_bufs, &p.flags, P)) || (rc = dalloc(c, c->film_bufs, &p.samples, P)) ||
-        (rc = dalloc(c, c->film_bufs, &p.vis, 2 * P)))
-        return rc;
-    {  // k_shade block done flags: slots x film tiles x blocks per tile
-        const size_t ntiles = (size_t)((w + tw - 1) / tw) * ((h + th - 1) / th);
-        c->blk_done_n = c->slots * ntiles * (size_t)shade_blocks_per_tile((int)(tw * th), 1);
-        if ((rc = dalloc(c, c->film_bufs, &c->blk_done, c->blk_done_n))) return rc;
-    }
-    if ((c->slots > 1 || c->compact) && ((rc = dalloc(c, c->film_bufs, &c->film_Ld, npix)) ||
-                                         (rc = dalloc(c, c->film_bufs, &c->film_samples, npix))))
-        return rc;
-    HIPCHK(c, hipMemset(p.hit_tri, 0xff, P * sizeof(int32_t)));
-    HIPCHK(c, hipMemset(p.vis, 0, 2 * P));
-    p.sray_o = c->p.sray_o;  // the any-hit rays live with the queues (set_tiles_internal)
-    p.sray_d = c->p.sray_d;
-    c->p = p;
-    c->npx = npx;
-    return MCPT_OK;
-}
-
-// (mcpt_set_path_slots re-sizes the full layout's film through this: the sample budget stays)
-static int film_resize(mcpt_ctx* c, uint32_t w, uint32_t h, uint32_t tw, uint32_t th) {
-    if (!c || w == 0 || h == 0 || tw == 0 || th == 0) return set_err(c, MCPT_E_INVALID, "bad film size");
-    if ((uint64_t)w * h >= (1ull << 31)) return set_err(c, MCPT_E_INVALID, "film too large");
-    if ((uint64_t)tw * th > (1ull << 26)) return set_err(c, MCPT_E_INVALID, "tile too large");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    free_list(c->film_bufs);
-    c->guides = Guides{};  // guide sums and filter planes: they belong to the film size
-    c->dn = Denoise{};
-    c->P = 0;
-    c->npx = 0;
-    c->p = DevPaths{};  // (set_tiles_internal below re-points the any-hit ray buffers)
-    c->blk_done = nullptr;
-    c->blk_done_n = 0;
-    c->W = w; c->H = h; c->tile_w = tw; c->tile_h = th;
-    for (uint32_t** q : {&c->ext_q, &c->any_q, &c->mat_q}) {  // re-sized for the new tile set below
-        if (*q) (void)hipFree(*q);
-        *q = nullptr;
-    }
-    if (c->any_ray) (void)hipFree(c->any_ray);
-    c->any_ray = nullptr;
-    c->queue_alloc = 0;
-    int rc = set_tiles_internal(c, all_tiles(c));
-    if (rc) return rc;
-    if ((rc = alloc_film_state(c))) return rc;
-    c->P = (size_t)w * h;
-    return mcpt_film_clear(c);
-}
-int mcpt_film_resize(mcpt_ctx* c, uint32_t w, uint32_t h, uint32_t tw, uint32_t th) {
-    if (!c || w == 0 || h == 0 || tw == 0 || th == 0) return set_err(c, MCPT_E_INVALID, "bad film size");
-    if (c->ad.bytes() || c->tp.bytes()) {  // the sample budget, the estimate and the temporal history belong to the film size
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->ad = Adaptive{};
-        c->tp = Temporal{};
-    }
-    return film_resize(c, w, h, tw, th);
-}
-
-// A new tile set.  In the compact layout the path state follows the tile set: it is re-allocated and
-// the film cleared (a tile listed twice would share its paths: rejected).
-static bool has_tile(const std::vector<int2>& v, int2 t) {
-    for (const int2& o : v)
-        if (o.x == t.x && o.y == t.y) return true;
-    return false;
-}
-static int set_tiles_checked(mcpt_ctx* c, const std::vector<int2>& t) {
-    if (!c->compact) {
-        for (const int2& x : t)
-            if (has_tile(c->unpacked, x))
-                return set_err(c, MCPT_E_INVALID, "a tile of the set holds pixels unpacked from another context: clear the film first");
-        return set_tiles_internal(c, t);
-    }
-    for (size_t i = 0; i < t.size(); i++)
-        for (size_t j = 0; j < i; j++)
-            if (t[i].x == t[j].x && t[i].y == t[j].y)
-                return set_err(c, MCPT_E_INVALID, "compact paths: a tile is listed twice");
-    const std::vector<int2> old = c->tiles_h;
-    int rc = set_tiles_internal(c, t);
-    if (rc) return rc;
-    const size_t P = c->P;
-    c->P = 0;  // the film is not allocated until the new path state is
-    if ((rc = alloc_film_state(c))) {  // e.g. out of memory: back to the previous tile set, as
-        const std::string err = c->err;  // mcpt_set_path_slots / mcpt_set_compact_paths do
-        if (set_tiles_internal(c, old) == MCPT_OK && alloc_film_state(c) == MCPT_OK) {
-            c->P = P;
-            (void)mcpt_film_clear(c);
-        }
-        return set_err(c, rc, err);
-    }
-    c->P = P;
-    return mcpt_film_clear(c);
-}
-
-int mcpt_set_tiles(mcpt_ctx* c, const uint32_t* xy, uint32_t n) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!xy) return set_tiles_checked(c, all_tiles(c));
-    std::vector<int2> t;
-    uint32_t nx = (c->W + c->tile_w - 1) / c->tile_w, ny = (c->H + c->tile_h - 1) / c->tile_h;
-    for (uint32_t i = 0; i < n; i++) {
-        if (xy[2 * i] >= nx || xy[2 * i + 1] >= ny) return set_err(c, MCPT_E_INVALID, "tile out of range");
-        t.push_back(make_int2((int)xy[2 * i], (int)xy[2 * i + 1]));
-    }
-    return set_tiles_checked(c, t);
-}
-
-int mcpt_set_compact_paths(mcpt_ctx* c, int32_t on) {
-    if (!c) return MCPT_E_INVALID;
-    const bool v = on != 0;
-    if (v == c->compact) return MCPT_OK;
-    c->compact = v;
-    if (!c->P) return MCPT_OK;  // takes effect with the film's allocation
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t P = c->P;
-    c->P = 0;
-    int rc = alloc_film_state(c);
-    if (rc) {  // e.g. out of memory: back to the previous layout
-        const std::string err = c->err;
-        c->compact = !v;
-        if (alloc_film_state(c) == MCPT_OK) {
-            c->P = P;
-            (void)mcpt_film_clear(c);
-        }
-        return set_err(c, rc, err);
-    }
-    c->P = P;
-    return mcpt_film_clear(c);
 }
 
 extern "C++" hipEvent_t ev(mcpt_ctx* c, size_t i) {
@@ -593,7 +342,7 @@ static void prim_table(mcpt_ctx* c, ShadeArgs& sa) {
     const ViewKey key = c->view();
     const bool same = t.key.same(key, ViewKey::SCENE | ViewKey::SIZE | ViewKey::CAM);
     if (same && t.failed) return;
-    const size_t qn = (size_t)kShards * c->ext_cap;
+    const size_t qn = c->queues.need;
     auto fail = [&]() {
         (void)hipGetLastError();
         (void)hipStreamSynchronize(c->stream);
@@ -641,7 +390,7 @@ static void prim_table(mcpt_ctx* c, ShadeArgs& sa) {
         t.over = st[1];
         t.build_ms = ms;
     }
-    if (qn > t.q.size()) {  // the primary queue follows the ray queues' capacity (set_tiles_internal)
+    if (qn > t.q.size()) {  // the primary queue follows the ray queues' capacity (RayQueues::ensure)
         (void)hipStreamSynchronize(c->stream);
         if (!t.q.ensure(qn)) return fail();
     }
@@ -654,18 +403,21 @@ extern "C++" int check_ready(mcpt_ctx* c) {
     if (!c) return MCPT_E_INVALID;
     if (!c->scene.ok) return set_err(c, MCPT_E_INVALID, "no scene uploaded");
     if (!c->has_cam) return set_err(c, MCPT_E_INVALID, "no camera set");
-    if (!c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
-    if (!c->ext_q || !c->any_q || !c->mat_q || !c->any_ray)  // a failed (re)allocation left none
+    if (!c->film.allocated) return set_err(c, MCPT_E_INVALID, "film not allocated");
+    if (!c->queues.ready())  // a failed (re)allocation left none
         return set_err(c, MCPT_E_NOMEM, "ray queues not allocated");
     return MCPT_OK;
 }
 
 // One wavefront iteration over the current tile set: shade -> extend -> any-hit.
 static int enqueue_iteration(mcpt_ctx* c, size_t evbase, bool timing, const int2* tiles, int ntiles, const int* tile_base) {
+    const FilmState& f = c->film;
+    const RayQueues& q = c->queues;
+    CounterBlock* const cnt = c->cnt.dev;
     ShadeArgs sa;
     sa.scene = c->scene.dev;
     sa.cam = c->cam;
-    sa.p = c->p;
+    sa.p = f.paths(q);
     sa.tiles = tiles;
     sa.ntiles = ntiles;
     sa.tile_w = (int)c->tile_w;
@@ -678,17 +430,17 @@ static int enqueue_iteration(mcpt_ctx* c, size_t evbase, bool timing, const int2
     sa.seed = c->cfg.seed;
     sa.slots = (int)c->slots;
     sa.slots_rcp = 1.0f / (float)c->slots;
-    sa.npx = (uint32_t)c->npx;
+    sa.npx = (uint32_t)f.L.npx;
     sa.compact = c->compact ? 1 : 0;
     sa.tile_base = tile_base;
-    sa.ext_q = c->ext_q;
-    sa.any_q = c->any_q;
-    sa.mat_rec = reinterpret_cast<uint4*>(c->mat_q);
-    sa.mat_beta = reinterpret_cast<float4*>(c->mat_q) + (size_t)kShards * c->ext_cap;
-    sa.ext_cap = c->ext_cap;
-    sa.any_cap = c->any_cap;
-    sa.cnt = c->cnt;
-    sa.blk_done = c->blk_done_off ? nullptr : c->blk_done;
+    sa.ext_q = q.ext;
+    sa.any_q = q.any;
+    sa.mat_rec = reinterpret_cast<uint4*>(q.mat.get());
+    sa.mat_beta = reinterpret_cast<float4*>(q.mat.get()) + q.need;
+    sa.ext_cap = q.ext_cap;
+    sa.any_cap = q.any_cap;
+    sa.cnt = cnt;
+    sa.blk_done = c->blk_done_off ? nullptr : f.blk_done.get();
     sa.skip = c->skip_discarded ? 1 : 0;
     sa.budget = c->ad.budget_on ? c->ad.budget.get() : nullptr;
     sa.emis = c->em.dev_table();
@@ -702,7 +454,7 @@ static int enqueue_iteration(mcpt_ctx* c, size_t evbase, bool timing, const int2
     if (samp) sa.p.vis = c->es.vis;  // 3P bytes: the emitter rays' results behind the two of every path
     if (int rc = cam_table(c, c->W, c->H, &sa.cam_px, &sa.cam_dir)) return rc;
     prim_table(c, sa);
-    const int bpt = shade_blocks_per_tile((int)(c->tile_w * c->tile_h), (int)c->slots);
+    const int bpt = (int)f.L.blocks_per_tile;
     if (timing) HIPCHK(c, hipEventRecord(ev(c, evbase + 0), c->stream));
     if (sa.ntiles > 0)
         launch_shade(sa, sa.ntiles * bpt, c->geom, (c->cfg.flags & MCPT_FLAG_FIXED) != 0, c->stream);
@@ -714,31 +466,31 @@ static int enqueue_iteration(mcpt_ctx* c, size_t evbase, bool timing, const int2
     ta.scene = c->scene.dev;
     ta.nshards = kShards;
     TraceSet& e = ta.set[0];
-    e.ro = c->p.ray_o;
-    e.rd = c->p.ray_d;
-    e.queue = c->ext_q;
-    e.count_ptr = &c->cnt->shard[0][C_EXT];
-    e.shard_cap = c->ext_cap;
-    e.stats = c->count_work ? &c->cnt->shard[0][C_STATS] : nullptr;  // mcpt_set_work_counters
+    e.ro = sa.p.ray_o;
+    e.rd = sa.p.ray_d;
+    e.queue = q.ext;
+    e.count_ptr = &cnt->shard[0][C_EXT];
+    e.shard_cap = q.ext_cap;
+    e.stats = c->count_work ? &cnt->shard[0][C_STATS] : nullptr;  // mcpt_set_work_counters
     e.prefiltered = 1;  // k_shade queues only rays that enter the root box
     TraceSet& v = ta.set[1];
-    v.ro = c->p.sray_o;
-    v.rd = c->p.sray_d;
-    v.queue = c->any_q;
-    v.count_ptr = &c->cnt->shard[0][C_ANY];
-    v.shard_cap = c->any_cap;
-    v.stats = c->count_work ? &c->cnt->shard[0][C_STATS + 3] : nullptr;
+    v.ro = sa.p.sray_o;
+    v.rd = sa.p.sray_d;
+    v.queue = q.any;
+    v.count_ptr = &cnt->shard[0][C_ANY];
+    v.shard_cap = q.any_cap;
+    v.stats = c->count_work ? &cnt->shard[0][C_STATS + 3] : nullptr;
     v.prefiltered = 1;
     v.ray_at_slot = 1;  // k_material stores the any-hit rays at their queue positions
-    ta.phase = c->count_work ? &c->cnt->shard[0][C_PH] : nullptr;  // loop-phase counts (mcpt_debug_trace_profile)
-    ta.hit_tri = c->p.hit_tri;
+    ta.phase = c->count_work ? &cnt->shard[0][C_PH] : nullptr;  // loop-phase counts (mcpt_debug_trace_profile)
+    ta.hit_tri = sa.p.hit_tri;
     ta.vis = sa.p.vis;
-    ta.grab = &c->cnt->grab[0][0];  // reset by k_accumulate below
-    ta.idle = &c->cnt->idle;
+    ta.grab = &cnt->grab[0][0];  // reset by k_accumulate below
+    ta.idle = &cnt->idle;
     ta.tiny_stack = c->tiny_stack ? 1 : 0;
     launch_trace(ta, c->geom, c->stream);
     if (timing) HIPCHK(c, hipEventRecord(ev(c, evbase + 2), c->stream));
-    launch_accumulate(c->cnt, c->geom.trace_parts, c->scene.dev.occ ? c->scene.dev.occ_gate : nullptr, c->stream);
+    launch_accumulate(cnt, c->geom.trace_parts, c->scene.dev.occ ? c->scene.dev.occ_gate : nullptr, c->stream);
     HIPCHK(c, hipGetLastError());
     return MCPT_OK;
 }
@@ -757,9 +509,9 @@ static int run_iterations(mcpt_ctx* c, uint32_t n, mcpt_stage_stats* st, const i
         // count and only while sampling is active: the emitter terms, and the any-hit results with a
         // third byte per path (the film's own two-byte array rests meanwhile).
         EmitterSampling& es = c->es;
-        const size_t paths = c->npx * c->slots;
+        const size_t paths = c->film.L.paths;
         if (es.paths != paths || !es.nee2.get() || !es.vis.get()) {
-            if (3 * (uint64_t)paths >= (1ull << 32)) return set_err(c, MCPT_E_INVALID, "film too large for emitter sampling");
+            if (const char* e = emitter_paths_error(paths)) return set_err(c, MCPT_E_INVALID, e);
             HIPCHK(c, hipStreamSynchronize(c->stream));
             es.drop_streams();
             if (!es.nee2.ensure(paths) || !es.vis.ensure(3 * paths)) {
@@ -772,33 +524,24 @@ static int run_iterations(mcpt_ctx* c, uint32_t n, mcpt_stage_stats* st, const i
         }
     }
     if (!tiles) {
-        tiles = c->tiles;
-        ntiles = (int)c->tiles_h.size();
+        tiles = c->tiles.dev;
+        ntiles = (int)c->tiles.host.size();
     }
-    if (!c->totals_ok) {
-        HIPCHK(c, hipMemcpyAsync(c->cnt_host, c->cnt, sizeof(CounterBlock), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->totals = *c->cnt_host;
-        c->totals_ok = true;
-    }
-    const CounterBlock before = c->totals;
+    if (!c->cnt.totals_ok && (rc = c->cnt.refresh(c))) return rc;
+    const CounterBlock before = c->cnt.totals;
     // iterations after one that traced no ray skip their kernels (k_accumulate sets the flag):
     // mcpt_render's last batch of 32 no longer pays full launches for the finished film
-    HIPCHK(c, hipMemsetAsync(&c->cnt->idle, 0, sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(&c->cnt.dev->idle, 0, sizeof(uint32_t), c->stream));
     for (uint32_t i = 0; i < n; i++) {
         // events for at most the first 4096 iterations of a call
         bool timing = i < 4096;
         if ((rc = enqueue_iteration(c, (size_t)3 * i, timing, tiles, ntiles, tile_base))) {
-            c->totals_ok = false;
+            c->cnt.totals_ok = false;
             return rc;
         }
     }
-    c->totals_ok = false;
-    HIPCHK(c, hipMemcpyAsync(c->cnt_host, c->cnt, sizeof(CounterBlock), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->totals = *c->cnt_host;
-    c->totals_ok = true;
-    const CounterBlock& after = c->totals;
+    if ((rc = c->cnt.refresh(c))) return rc;
+    const CounterBlock& after = c->cnt.totals;
     if (after.trace_short != before.trace_short)  // k_accumulate's drain check (never expected)
         return set_err(c, MCPT_E_HIP, "k_trace left queued rays untraced in " +
                                           std::to_string(after.trace_short - before.trace_short) + " launch(es)");
@@ -833,37 +576,40 @@ int mcpt_iterate(mcpt_ctx* c, uint32_t n, mcpt_stage_stats* st) { return run_ite
 int mcpt_wavefront_step(mcpt_ctx* c, uint32_t tx, uint32_t ty, mcpt_stage_stats* st) {
     int rc = check_ready(c);
     if (rc) return rc;
-    uint32_t nx = (c->W + c->tile_w - 1) / c->tile_w, ny = (c->H + c->tile_h - 1) / c->tile_h;
-    if (tx >= nx || ty >= ny) return set_err(c, MCPT_E_INVALID, "tile out of range");
+    if (tx >= c->film.L.nx || ty >= c->film.L.ny) return set_err(c, MCPT_E_INVALID, "tile out of range");
+    TileSet& ts = c->tiles;
     // compact layout: the tile's paths are those of its place in the tile set
-    int base = 0;
-    if (c->compact) {
-        base = -1;
-        for (size_t i = 0; i < c->tiles_h.size() && base < 0; i++)
-            if (c->tiles_h[i].x == (int)tx && c->tiles_h[i].y == (int)ty) base = (int)i;
-        if (base < 0) return set_err(c, MCPT_E_INVALID, "compact paths: the tile is not in the tile set");
-    }
+    const int base = c->compact ? ts.index_of(make_int2((int)tx, (int)ty)) : 0;
+    if (base < 0) return set_err(c, MCPT_E_INVALID, "compact paths: the tile is not in the tile set");
     // The one-tile set goes through its own small buffer (pinned staging, stream-ordered
     // copy): the context's tile set and queues stay as they are when their per-shard queue
     // capacity covers one tile, which it does unless the tile set is empty.
-    const uint32_t bpt = (uint32_t)shade_blocks_per_tile((int)(c->tile_w * c->tile_h), (int)c->slots);
-    const uint32_t need = std::max<uint32_t>(1, (bpt + kShards - 1) / kShards) * kBlock;
-    if (c->ext_cap >= need) {
-        if (!c->step_tile) {
+    if (c->queues.ext_cap >= one_tile_capacity(c->tile_w, c->tile_h, c->slots)) {
+        if (!ts.step || !ts.step_h) {
             HIPCHK(c, hipSetDevice(c->device));
-            HIPCHK(c, hipMalloc(&c->step_tile, 2 * sizeof(int2)));
-            HIPCHK(c, hipHostMalloc(&c->step_tile_h, 2 * sizeof(int2)));
+            if (!ts.step.ensure(2) || !ts.step_h.alloc(2))
+                return set_err(c, MCPT_E_HIP, std::string("step tile allocation failed: ") + hipGetErrorString(hipGetLastError()));
         }
-        c->step_tile_h[0] = make_int2((int)tx, (int)ty);  // the previous call's copy has completed
-        c->step_tile_h[1] = make_int2(base, 0);
-        HIPCHK(c, hipMemcpyAsync(c->step_tile, c->step_tile_h, 2 * sizeof(int2), hipMemcpyHostToDevice, c->stream));
-        return run_iterations(c, 1, st, c->step_tile, 1, reinterpret_cast<const int*>(c->step_tile + 1));
+        ts.step_h.get()[0] = make_int2((int)tx, (int)ty);  // the previous call's copy has completed
+        ts.step_h.get()[1] = make_int2(base, 0);
+        HIPCHK(c, hipMemcpyAsync(ts.step, ts.step_h, 2 * sizeof(int2), hipMemcpyHostToDevice, c->stream));
+        return run_iterations(c, 1, st, ts.step, 1, reinterpret_cast<const int*>(ts.step.get() + 1));
     }
-    std::vector<int2> saved = c->tiles_h;
+    std::vector<int2> saved = ts.host;
     if ((rc = set_tiles_internal(c, {make_int2((int)tx, (int)ty)}))) return rc;
     rc = run_iterations(c, 1, st);
     int rc2 = set_tiles_internal(c, saved);
     return rc ? rc : rc2;
+}
+
+// acc += one batch: rays, iterations, work counts and times add up, the live paths are the last batch's
+static void add(mcpt_stage_stats& acc, const mcpt_stage_stats& one) {
+    acc.extend_rays += one.extend_rays, acc.shadow_rays += one.shadow_rays, acc.vis_rays += one.vis_rays;
+    acc.iterations += one.iterations;
+    acc.ms_shade += one.ms_shade, acc.ms_extend += one.ms_extend, acc.ms_shadow += one.ms_shadow, acc.ms_total += one.ms_total;
+    acc.live_paths = one.live_paths;
+    acc.ext_nodes += one.ext_nodes, acc.ext_tests += one.ext_tests, acc.ext_hits += one.ext_hits;
+    acc.any_nodes += one.any_nodes, acc.any_tests += one.any_tests, acc.any_hits += one.any_hits;
 }
 
 int mcpt_render(mcpt_ctx* c, mcpt_stage_stats* st) {
@@ -883,17 +629,7 @@ int mcpt_render(mcpt_ctx* c, mcpt_stage_stats* st) {
     for (;;) {
         const uint32_t batch = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(8, expect > done ? expect - done : 0));
         if ((rc = run_iterations(c, batch, &one))) return rc;
-        acc.extend_rays += one.extend_rays;
-        acc.shadow_rays += one.shadow_rays;
-        acc.vis_rays += one.vis_rays;
-        acc.iterations += one.iterations;
-        acc.ms_shade += one.ms_shade;
-        acc.ms_extend += one.ms_extend;
-        acc.ms_shadow += one.ms_shadow;
-        acc.ms_total += one.ms_total;
-        acc.live_paths = one.live_paths;
-        acc.ext_nodes += one.ext_nodes; acc.ext_tests += one.ext_tests; acc.ext_hits += one.ext_hits;
-        acc.any_nodes += one.any_nodes; acc.any_tests += one.any_tests; acc.any_hits += one.any_hits;
+        add(acc, one);
         done += one.iterations;
         if (one.live_paths == 0 || done > cap) break;
     }
@@ -906,70 +642,6 @@ int mcpt_sync(mcpt_ctx* c) {
     if (!c) return MCPT_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    return MCPT_OK;
-}
-
-// The film (dFilm.Ld / samples): the path state's accumulators with one slot per pixel,
-// else their per-pixel sum in slot order (k_resolve) -- enqueued on the context stream.
-extern "C++" int film_view(mcpt_ctx* c, const float4** Ld, const uint32_t** samples) {
-    if (c->slots <= 1 && !c->compact) {
-        *Ld = c->p.Ld;
-        *samples = c->p.samples;
-        return MCPT_OK;
-    }
-    ResolveArgs a{c->p.Ld, c->p.samples, c->film_Ld, c->film_samples, (uint32_t)c->npx, (int)c->slots,
-                  c->compact ? c->tiles : nullptr, (int)c->tile_w, (int)c->tile_h, (int)c->W, (int)c->H};
-    launch_resolve(a, c->stream);
-    HIPCHK(c, hipGetLastError());
-    *Ld = c->film_Ld;
-    *samples = c->film_samples;
-    return MCPT_OK;
-}
-
-// Where another context's tile pixels are scattered (mcpt_film_unpack_tiles, mcpt_gather): the
-// pixel-indexed accumulators the film view reads beside the context's own tiles
-static void unpack_target(mcpt_ctx* c, float4** Ld, uint32_t** samples) {
-    *Ld = c->compact ? c->film_Ld : c->p.Ld;
-    *samples = c->compact ? c->film_samples : c->p.samples;
-}
-
-int mcpt_set_path_slots(mcpt_ctx* c, uint32_t slots) {
-    if (!c || slots < 1 || slots > 256) return set_err(c, MCPT_E_INVALID, "path slots must be 1..256");
-    if (slots == c->slots) return MCPT_OK;
-    if (!c->P) {
-        c->slots = slots;
-        return MCPT_OK;
-    }
-    // check the new size before touching anything: a rejected count leaves the film as it was
-    if ((uint64_t)c->npx * slots >= (1ull << 31)) return set_err(c, MCPT_E_INVALID, "film too large for the path slots");
-    const uint32_t old = c->slots;
-    c->slots = slots;
-    if (c->compact) {  // the path state of the current tile set (its queues too: their capacity follows the slots)
-        HIPCHK(c, hipSetDevice(c->device));
-        const std::vector<int2> t = c->tiles_h;
-        const size_t P = c->P;
-        c->P = 0;
-        int rc = set_tiles_internal(c, t);
-        if (!rc) rc = alloc_film_state(c);
-        if (rc != MCPT_OK) {
-            const std::string err = c->err;
-            c->slots = old;
-            if (set_tiles_internal(c, t) == MCPT_OK && alloc_film_state(c) == MCPT_OK) {
-                c->P = P;
-                (void)mcpt_film_clear(c);
-            }
-            return set_err(c, rc, err);
-        }
-        c->P = P;
-        return mcpt_film_clear(c);
-    }
-    int rc = film_resize(c, c->W, c->H, c->tile_w, c->tile_h);  // clears the film
-    if (rc != MCPT_OK) {  // e.g. out of memory: back to the old slot count and its (cleared) film
-        const std::string err = c->err;
-        c->slots = old;
-        (void)film_resize(c, c->W, c->H, c->tile_w, c->tile_h);
-        return set_err(c, rc, err);
-    }
     return MCPT_OK;
 }
 
@@ -992,206 +664,4 @@ int mcpt_set_trace_partitions(mcpt_ctx* c, uint32_t nparts) {
     return MCPT_OK;
 }
 
-int mcpt_film_read(mcpt_ctx* c, float* Ld, uint32_t* samples) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
-    HIPCHK(c, hipSetDevice(c->device));
-    const float4* fL;
-    const uint32_t* fs;
-    int rc = film_view(c, &fL, &fs);
-    if (rc) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (Ld && (rc = read_plane(c, fL, c->P, Ld, nullptr))) return rc;
-    if (samples) HIPCHK(c, hipMemcpy(samples, fs, c->P * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return MCPT_OK;
-}
-
-int mcpt_film_read_device(mcpt_ctx* c, void* dLd, void* dsamples) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
-    HIPCHK(c, hipSetDevice(c->device));
-    const float4* fL;
-    const uint32_t* fs;
-    int rc = film_view(c, &fL, &fs);
-    if (rc) return rc;
-    if (dLd) HIPCHK(c, hipMemcpyAsync(dLd, fL, c->P * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-    if (dsamples) HIPCHK(c, hipMemcpyAsync(dsamples, fs, c->P * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return MCPT_OK;
-}
-
-int mcpt_film_pack_tiles(mcpt_ctx* c, void* d_out, uint32_t* npix) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
-    uint32_t n = (uint32_t)(c->tiles_h.size() * c->tile_w * c->tile_h);
-    if (npix) *npix = n;
-    if (!d_out) return MCPT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const float4* fL;
-    const uint32_t* fs;
-    int rc = film_view(c, &fL, &fs);
-    if (rc) return rc;
-    PackArgs a{fL, fs, c->tiles, (int)c->tiles_h.size(), (int)c->tile_w, (int)c->tile_h, (int)c->W, (int)c->H, (float4*)d_out};
-    if (n) launch_pack(a, c->stream);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return MCPT_OK;
-}
-
-int mcpt_film_unpack_tiles(mcpt_ctx* c, const void* d_in, const uint32_t* xy, uint32_t n) {
-    if (!c || !c->P) return set_err(c, MCPT_E_INVALID, "film not allocated");
-    if (n == 0) return MCPT_OK;
-    if (!d_in || !xy) return set_err(c, MCPT_E_INVALID, "null argument");
-    const uint32_t nx = (c->W + c->tile_w - 1) / c->tile_w, ny = (c->H + c->tile_h - 1) / c->tile_h;
-    std::vector<int2> t(n);
-    for (uint32_t i = 0; i < n; i++) {
-        if (xy[2 * i] >= nx || xy[2 * i + 1] >= ny) return set_err(c, MCPT_E_INVALID, "tile out of range");
-        t[i] = make_int2((int)xy[2 * i], (int)xy[2 * i + 1]);
-        if (has_tile(c->tiles_h, t[i]))  // the context's own pixels would mix with its other slots
-            return set_err(c, MCPT_E_INVALID, "unpack into one of the context's own tiles");
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    int2* dt = nullptr;
-    HIPCHK(c, hipMalloc(&dt, n * sizeof(int2)));
-    hipError_t e = hipMemcpyAsync(dt, t.data(), n * sizeof(int2), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        // scattered into slot 0 of the path state (its other slots of a pixel the context never
-        // renders stay zero, so the film view's slot sum returns these values); compact layout: into
-        // the W x H film, where the film view's resolve writes only the context's own tiles
-        float4* tL;
-        uint32_t* ts;
-        unpack_target(c, &tL, &ts);
-        UnpackArgs ua{(const float4*)d_in, dt, (int)n, (int)c->tile_w, (int)c->tile_h, (int)c->W, (int)c->H, tL, ts};
-        launch_unpack(ua, c->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(dt);
-    if (e != hipSuccess) return set_err(c, MCPT_E_HIP, std::string("unpack: ") + hipGetErrorString(e));
-    for (const int2& x : t)
-        if (!has_tile(c->unpacked, x)) c->unpacked.push_back(x);
-    return MCPT_OK;
-}
-
-// Frame-end gather of a multi-GPU render inside one process (SURVEY.md 8(b) mcpt_gather, 8(e)):
-// every context's tile-set pixels, resolved over its path slots and packed 16 B/px, are copied
-// device-to-device onto the root's device (hipMemcpyPeerAsync: SDMA over xGMI between MI355X
-// dies of a node) and scattered into the root's film accumulators, so the root's film readers
-// return the whole frame.  Tile sets must not overlap the root's own tiles (the interleaved
-// partition of mcpt/parallel.py); the multi-process form sends the same packed buffers to the
-// root over RCCL and scatters them with mcpt_film_unpack_tiles (mcpt/parallel.py).
-int mcpt_gather(mcpt_ctx* const* ctxs, int32_t n, int32_t root) {
-    if (!ctxs || n < 1 || root < 0 || root >= n || !ctxs[root]) return set_err(nullptr, MCPT_E_INVALID, "bad gather arguments");
-    mcpt_ctx* R = ctxs[root];
-    for (int32_t i = 0; i < n; i++) {
-        mcpt_ctx* c = ctxs[i];
-        if (!c || !c->P) return set_err(R, MCPT_E_INVALID, "gather: a context has no film");
-        if (c->W != R->W || c->H != R->H || c->tile_w != R->tile_w || c->tile_h != R->tile_h)
-            return set_err(R, MCPT_E_INVALID, "gather: film or tile sizes differ between contexts");
-        for (int32_t j = 0; j < i; j++)
-            if (ctxs[j] == c) return set_err(R, MCPT_E_INVALID, "gather: a context is listed twice");
-        if (c != R)
-            for (const int2& x : c->tiles_h)
-                if (has_tile(R->tiles_h, x)) return set_err(R, MCPT_E_INVALID, "gather: a tile set overlaps the root's own tiles");
-    }
-    for (int32_t i = 0; i < n; i++) {
-        mcpt_ctx* c = ctxs[i];
-        if (c == R || c->tiles_h.empty()) continue;
-        const size_t npix = c->tiles_h.size() * (size_t)c->tile_w * c->tile_h;
-        // pack on the source device (its film view resolves the path slots)
-        HIPCHK(R, hipSetDevice(c->device));
-        const float4* fL;
-        const uint32_t* fs;
-        int rc = film_view(c, &fL, &fs);
-        if (rc) return set_err(R, rc, c->err);
-        float4* src = nullptr;
-        if (hipMalloc(&src, npix * sizeof(float4)) != hipSuccess) return set_err(R, MCPT_E_NOMEM, "gather: pack buffer");
-        PackArgs pa{fL, fs, c->tiles, (int)c->tiles_h.size(), (int)c->tile_w, (int)c->tile_h, (int)c->W, (int)c->H, src};
-        launch_pack(pa, c->stream);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        // copy to the root's device and scatter into its accumulators (slot 0; the other slots
-        // of pixels the root does not render are zero, so its slot sum returns these values)
-        float4* dst = nullptr;
-        int2* dt = nullptr;
-        if (e == hipSuccess) e = hipSetDevice(R->device);
-        if (e == hipSuccess && c->device != R->device) {
-            // direct xGMI access where the pair supports it; hipMemcpyPeerAsync also works
-            // without it (staged), so a refusal here is not an error
-            int can = 0;
-            if (hipDeviceCanAccessPeer(&can, R->device, c->device) == hipSuccess && can)
-                (void)hipDeviceEnablePeerAccess(c->device, 0);
-            (void)hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMalloc(&dst, npix * sizeof(float4));
-        if (e == hipSuccess) e = hipMalloc(&dt, c->tiles_h.size() * sizeof(int2));
-        if (e == hipSuccess)
-            e = hipMemcpyPeerAsync(dst, R->device, src, c->device, npix * sizeof(float4), R->stream);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(dt, c->tiles_h.data(), c->tiles_h.size() * sizeof(int2), hipMemcpyHostToDevice, R->stream);
-        if (e == hipSuccess) {
-            float4* tL;
-            uint32_t* ts;
-            unpack_target(R, &tL, &ts);
-            UnpackArgs ua{dst, dt, (int)c->tiles_h.size(), (int)R->tile_w, (int)R->tile_h, (int)R->W, (int)R->H, tL, ts};
-            launch_unpack(ua, R->stream);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(R->stream);
-        (void)hipFree(dst);
-        (void)hipFree(dt);
-        (void)hipSetDevice(c->device);
-        (void)hipFree(src);
-        if (e != hipSuccess) return set_err(R, MCPT_E_HIP, std::string("gather: ") + hipGetErrorString(e));
-        for (const int2& x : c->tiles_h)
-            if (!has_tile(R->unpacked, x)) R->unpacked.push_back(x);
-    }
-    (void)hipSetDevice(R->device);
-    return MCPT_OK;
-}
-
-int mcpt_film_size(const mcpt_ctx* c, uint32_t* w, uint32_t* h) {
-    if (!c || !w || !h) return MCPT_E_INVALID;
-    if (!c->P) return set_err(const_cast<mcpt_ctx*>(c), MCPT_E_INVALID, "film not allocated");
-    *w = c->W;
-    *h = c->H;
-    return MCPT_OK;
-}
-
-int mcpt_film_tonemap_rgba8(mcpt_ctx* c, float exposure, uint8_t* out) {
-    if (!c || !c->P || !out) return set_err(c, MCPT_E_INVALID, "bad argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    const float4* fL;
-    const uint32_t* fs;
-    int rc = film_view(c, &fL, &fs);
-    if (rc) return rc;
-    return tonemap_rgba8(c, fL, fs, exposure, out);
-}
-
 }  // extern "C"
-
-int tonemap_rgba8(mcpt_ctx* c, const float4* col, const uint32_t* samples, float exposure, uint8_t* out) {
-    DevBuf<uchar4> d;
-    DevBuf<uint32_t> ones;
-    if (!d.ensure(c->P) || (!samples && !ones.ensure(c->P))) {
-        (void)hipGetLastError();
-        return set_err(c, MCPT_E_NOMEM, "tonemap buffers");
-    }
-    hipError_t e = samples ? hipSuccess : hipMemsetD32Async((hipDeviceptr_t)ones.get(), 1, c->P, c->stream);
-    if (e == hipSuccess) {
-        TonemapArgs a{col, samples ? samples : ones.get(), d, exposure, (uint32_t)c->P};
-        launch_tonemap(a, c->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(out, d, c->P * sizeof(uchar4), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return set_err(c, MCPT_E_HIP, std::string("tonemap: ") + hipGetErrorString(e));
-    return MCPT_OK;
-}
-
-int read_plane(mcpt_ctx* c, const float4* d, size_t n, float* xyz, float* w) {
-    std::vector<float4> o(n);
-    HIPCHK(c, hipMemcpy(o.data(), d, n * sizeof(float4), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; i++) {
-        if (xyz) { xyz[3 * i] = o[i].x; xyz[3 * i + 1] = o[i].y; xyz[3 * i + 2] = o[i].z; }
-        if (w) w[i] = o[i].w;
-    }
-    return MCPT_OK;
-}

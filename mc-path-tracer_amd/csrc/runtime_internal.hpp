@@ -1,7 +1,8 @@
-// runtime_internal.hpp -- what runtime.cpp (context, film, render loop), scene_upload.cpp (scene upload
-// and geometry update), postprocess.cpp (guides, denoise, adaptive sampling, temporal accumulation) and
-// stage_run.cpp (per-stage parity harness, debug entries) share: the device context behind the mcpt_* C
-// ABI, its error helpers, the owner of a device buffer and a few host helpers.
+// runtime_internal.hpp -- what runtime.cpp (context, camera, lighting tables, render loop), film_state.cpp
+// (tile set, ray queues, film and path state, film readers), scene_upload.cpp (scene upload and geometry
+// update), postprocess.cpp (guides, denoise, adaptive sampling, temporal accumulation) and stage_run.cpp
+// (per-stage parity harness, debug entries) share: the device context behind the mcpt_* C ABI, the
+// owners of its state, its error helpers and a few host helpers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +13,7 @@
 #include <vector>
 
 #include "host/emitter_table.hpp"
+#include "host/film_layout.hpp"
 #include "kernels.hpp"
 #include "mcpt.h"
 
@@ -63,6 +65,39 @@ public:
     size_t bytes() const { return p_ ? std::max<size_t>(n_ * sizeof(T), 16) : 0; }  // as allocated
     T* get() const { return p_; }
     operator T*() const { return p_; }
+    T* operator->() const { return p_; }
+};
+
+// Owner of one hipHostMalloc'd (pinned) array of T, as DevBuf is of device memory
+template <class T>
+class PinnedBuf {
+    T* p_ = nullptr;
+
+public:
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    PinnedBuf(PinnedBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    PinnedBuf& operator=(PinnedBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            std::swap(p_, o.p_);
+        }
+        return *this;
+    }
+    ~PinnedBuf() { reset(); }
+    void reset() {
+        if (p_) (void)hipHostFree(p_);
+        p_ = nullptr;
+    }
+    bool alloc(size_t count) {  // false: the allocation failed and the buffer is empty
+        reset();
+        if (hipHostMalloc((void**)&p_, count * sizeof(T)) != hipSuccess) p_ = nullptr;
+        return p_ != nullptr;
+    }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+    T* operator->() const { return p_; }
 };
 
 // What a view-dependent product was built for.  Each product stores the key of its build and names
@@ -292,6 +327,142 @@ struct SceneState {
     }
 };
 
+// ---- what the wavefront iteration runs on (film_state.cpp) ----
+
+// The ray queues of the tile set: extension and any-hit path indices and the material records per shard,
+// and the any-hit rays at their queue positions (k_material stores them there, so the path streams'
+// sray_o / sray_d point here).  Re-allocated only when the need grows or the any-hit multiplier changes.
+struct RayQueues {
+    DevBuf<uint32_t> ext, any, mat;     // mat: MatRec + beta per extension-queue entry (8 words)
+    DevBuf<float4> any_ray;             // o [mult * alloc], then d
+    uint32_t ext_cap = 0, any_cap = 0;  // per-shard capacities of the current tile set
+    size_t need = 0;                    // ... and its extension-queue entries (kShards * ext_cap <= alloc)
+    size_t alloc = 0;                   // entries ext is allocated for (any holds mult times as many)
+    uint32_t mult = 0;                  // any-hit rays per material evaluation the queues are allocated for
+    bool ready() const { return ext && any && mat && any_ray; }
+    bool fits(const FilmLayout& L) const { return L.queue_need <= alloc && L.any_mult == mult; }
+    void release() {
+        ext.reset(), any.reset(), mat.reset(), any_ray.reset();
+        alloc = 0;
+    }
+    // The capacities of L; queues that do not fit it are released and allocated anew (the caller has
+    // synchronised the stream).  false: an allocation failed and all four are empty.
+    bool ensure(const FilmLayout& L) {
+        ext_cap = L.ext_cap;
+        any_cap = L.any_cap;
+        need = L.queue_need;
+        if (fits(L)) return true;
+        release();
+        const size_t m = L.any_mult;
+        if (!ext.ensure(need) || !any.ensure(m * need) || !mat.ensure(need * 8) || !any_ray.ensure(2 * m * need)) {
+            release();
+            return false;
+        }
+        alloc = need;
+        mult = L.any_mult;
+        return true;
+    }
+    // any-hit rays, indexed by any-queue position (kShards * any_cap = mult * need entries)
+    float4* sray_o() const { return any_ray; }
+    float4* sray_d() const { return any_ray ? any_ray + (size_t)mult * alloc : nullptr; }
+};
+
+// -1, or the index of tile t in v
+inline int tile_index(const std::vector<int2>& v, int2 t) {
+    for (size_t i = 0; i < v.size(); i++)
+        if (v[i].x == t.x && v[i].y == t.y) return (int)i;
+    return -1;
+}
+
+// The tile set the iterations run over (device and host copy; the device array only grows) and
+// mcpt_wavefront_step's one-tile set: device + pinned staging, 16 B each (the tile, then its index in
+// the tile set, ShadeArgs::tile_base).
+struct TileSet {
+    DevBuf<int2> dev;
+    std::vector<int2> host;
+    DevBuf<int2> step;
+    PinnedBuf<int2> step_h;
+    int index_of(int2 t) const { return tile_index(host, t); }
+    // every tile of the film's grid, row by row
+    static std::vector<int2> all(const FilmLayout& L) {
+        std::vector<int2> t;
+        for (uint32_t y = 0; y < L.ny; y++)
+            for (uint32_t x = 0; x < L.nx; x++) t.push_back(make_int2((int)x, (int)y));
+        return t;
+    }
+    // n (x, y) pairs as tiles of the grid -> out.  Returns n, or the index of the first pair outside
+    // the grid: out then holds the tiles before it.
+    static uint32_t parse(const uint32_t* xy, uint32_t n, const FilmLayout& L, std::vector<int2>& out) {
+        out.clear();
+        for (uint32_t i = 0; i < n; i++) {
+            if (xy[2 * i] >= L.nx || xy[2 * i + 1] >= L.ny) return i;
+            out.push_back(make_int2((int)xy[2 * i], (int)xy[2 * i + 1]));
+        }
+        return n;
+    }
+};
+
+// The film: the path streams (slots x npx paths), the k_shade block done flags and, with more than one
+// slot or in the compact layout, the W x H planes of the slot sums -- allocated together for one
+// layout (alloc_film_state), exact sizes.  allocated: the film exists (the mcpt_film_* entries' test).
+struct FilmState {
+    FilmLayout L{};  // what the buffers were last allocated for (the tile set's capacities of now: RayQueues)
+    bool allocated = false;
+    DevBuf<float4> ray_o, ray_d, beta, nee0, nee1, Ld;
+    DevBuf<int32_t> hit_tri;
+    DevBuf<uint32_t> flags, samples;
+    DevBuf<uint8_t> vis;          // [2 paths]
+    DevBuf<uint8_t> blk_done;     // ShadeArgs::blk_done
+    DevBuf<float4> sum_Ld;        // slots > 1 or compact: the film, W x H (sum of the slot accumulators)
+    DevBuf<uint32_t> sum_samples;
+    // tiles holding pixels scattered in from another context (mcpt_film_unpack_tiles, mcpt_gather)
+    // since the last film clear: the full layout's slot 0 holds them, so they may not become own
+    // tiles before a clear (their sample count restarts from the flags word while Ld accumulates)
+    std::vector<int2> unpacked;
+
+    size_t pixels() const { return allocated ? L.npix : 0; }  // W * H of an allocated film, else 0
+    void release() {
+        // (in the order alloc allocates them)
+        ray_o.reset(), ray_d.reset(), hit_tri.reset(), beta.reset(), nee0.reset(), nee1.reset(), Ld.reset();
+        flags.reset(), samples.reset(), vis.reset(), blk_done.reset(), sum_Ld.reset(), sum_samples.reset();
+        allocated = false;
+    }
+    // Everything released, then allocated for layout l.  false: an allocation failed (hipGetLastError
+    // has the cause) and everything is released.
+    bool alloc(const FilmLayout& l) {
+        release();
+        L = l;
+        const size_t P = l.paths;
+        const bool ok = ray_o.ensure(P) && ray_d.ensure(P) && hit_tri.ensure(P) && beta.ensure(P) && nee0.ensure(P) &&
+                        nee1.ensure(P) && Ld.ensure(P) && flags.ensure(P) && samples.ensure(P) && vis.ensure(2 * P) &&
+                        blk_done.ensure(l.blk_done_n) && (!l.sum_planes || (sum_Ld.ensure(l.npix) && sum_samples.ensure(l.npix)));
+        if (!ok) release();
+        return ok;
+    }
+    // The path streams as the kernels take them; the any-hit rays live with the queues
+    DevPaths paths(const RayQueues& q) const {
+        DevPaths p{};
+        p.ray_o = ray_o, p.ray_d = ray_d, p.sray_o = q.sray_o(), p.sray_d = q.sray_d();
+        p.beta = beta, p.nee0 = nee0, p.nee1 = nee1, p.Ld = Ld;
+        p.hit_tri = hit_tri;
+        p.flags = flags, p.samples = samples;
+        p.vis = vis;
+        return p;
+    }
+};
+
+struct mcpt_ctx;
+// The counter block: on the device, its pinned staging copy, and the host copy of the totals after the
+// last call (valid: totals_ok; refresh reads them back when they are not).
+struct Counters {
+    DevBuf<CounterBlock> dev;
+    PinnedBuf<CounterBlock> host;
+    CounterBlock totals{};
+    bool totals_ok = false;
+    unsigned long long phase_base[kPhaseWords] = {};  // mcpt_debug_trace_profile's reset point
+    int refresh(mcpt_ctx* c);  // device -> host -> totals, one stream synchronisation
+};
+
 struct mcpt_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -321,47 +492,24 @@ struct mcpt_ctx {
     // Camera::update, Camera.cu:207, and Scene::notify, Scene.cu:534-545): a change marks the
     // film stale and the next iteration clears it first (unless MCPT_FLAG_NO_AUTO_CLEAR).
     bool film_stale = false;
-    // film + paths
+    // film + paths: the settings here, the buffers in their owners
     uint32_t W = 0, H = 0, tile_w = 256, tile_h = 256;
-    size_t P = 0;      // pixels (W * H)
     uint32_t slots = 1;  // path slots per pixel (mcpt_set_path_slots); path state holds slots * npx paths
-    // Path layout (mcpt_set_compact_paths).  Full: npx = P, path index = slot * P + pixel id.  Compact:
+    // Path layout (mcpt_set_compact_paths).  Full: npx = W * H, path index = slot * npx + pixel id.  Compact:
     // the path state covers the tile set only, npx = tile-set tiles x tile pixels (ShadeArgs::npx).
     bool compact = false;
-    size_t npx = 0;
-    float4* film_Ld = nullptr;     // slots > 1 or compact: the film, W x H (sum of the slot accumulators)
-    uint32_t* film_samples = nullptr;
-    std::vector<void*> film_bufs;
-    uint8_t* blk_done = nullptr;  // k_shade block done flags (ShadeArgs::blk_done), in film_bufs
-    size_t blk_done_n = 0;
+    uint32_t any_mult = 2;  // any-hit rays per material evaluation wanted: 3 with emitter sampling active
     bool blk_done_off = getenv("MCPT_NO_BLOCK_DONE") != nullptr;  // A/B switch: every block runs
-    DevPaths p{};
-    uint32_t *ext_q = nullptr, *any_q = nullptr, *mat_q = nullptr;
-    float4* any_ray = nullptr;          // any-hit rays at their queue positions: o [2 queue_alloc], then d
-    uint32_t ext_cap = 0, any_cap = 0;  // per-shard capacities
-    size_t queue_alloc = 0;             // entries allocated for ext_q (any_q holds any_alloc_mult times as many)
-    uint32_t any_mult = 2, any_alloc_mult = 0;  // any-hit rays per material evaluation: wanted (3 with emitter
-                                                // sampling active) / as the queues are allocated
-    CounterBlock* cnt = nullptr;
-    CounterBlock* cnt_host = nullptr;  // pinned
-    CounterBlock totals{};             // host copy of the counters after the last call (valid: totals_ok)
-    bool totals_ok = false;
-    int2* step_tile = nullptr;         // mcpt_wavefront_step's one-tile set: device + pinned staging (16 B:
-    int2* step_tile_h = nullptr;       // the tile, then its index in the tile set, ShadeArgs::tile_base)
-    int2* tiles = nullptr;
-    std::vector<int2> tiles_h;
-    // tiles holding pixels scattered in from another context (mcpt_film_unpack_tiles, mcpt_gather)
-    // since the last film clear: the full layout's slot 0 holds them, so they may not become own
-    // tiles before a clear (their sample count restarts from the flags word while Ld accumulates)
-    std::vector<int2> unpacked;
-    uint32_t tiles_cap = 0;
+    TileSet tiles;
+    RayQueues queues;
+    FilmState film;
+    Counters cnt;
     std::vector<hipEvent_t> events;
     // scratch of one call (TmpScope; the stage runs)
     std::vector<void*> tmp_bufs;
     float last_stage_ms = 0.f;
     int gpu_bvh_builder = MCPT_GPU_BVH_PLOC;  // mcpt_set_gpu_bvh_builder
     bool tiny_stack = false;  // mcpt_debug_tiny_lds_stack: k_trace with a 2-entry LDS stack (tests)
-    unsigned long long phase_base[kPhaseWords] = {};  // mcpt_debug_trace_profile's reset point
     // film post-processing (postprocess.cpp)
     Guides guides;
     Denoise dn;
@@ -371,6 +519,16 @@ struct mcpt_ctx {
     StageMs ms;
 
     ViewKey view() const { return ViewKey{scene_gen, cfg.seed, W, H, cam}; }
+    // The layout of the settings above over a tile set of ntiles tiles
+    FilmLayout layout(size_t ntiles) const { return film_layout(W, H, tile_w, tile_h, slots, compact, ntiles, any_mult); }
+    // The owners' device memory goes while the device is current and the stream still exists (mcpt_destroy)
+    void release_buffers() {
+        scene.reset();
+        free_list(tmp_bufs);
+        tiles = TileSet{}, queues = RayQueues{}, film = FilmState{}, cnt = Counters{};
+        cam_tab = CamTable{}, prim.release(), em = Emission{}, es = EmitterSampling{};
+        guides = Guides{}, dn = Denoise{}, ad = Adaptive{}, tp = Temporal{};
+    }
 };
 
 inline int set_err(mcpt_ctx* c, int rc, const std::string& msg) {
@@ -412,6 +570,15 @@ struct TmpScope {
     TmpScope& operator=(const TmpScope&) = delete;
 };
 
+inline int Counters::refresh(mcpt_ctx* c) {
+    totals_ok = false;
+    HIPCHK(c, hipMemcpyAsync(host, dev, sizeof(CounterBlock), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    totals = *host;
+    totals_ok = true;
+    return MCPT_OK;
+}
+
 // Defined in runtime.cpp (C++ linkage: `extern "C++"` where they stand inside its extern "C" block)
 hipEvent_t ev(mcpt_ctx* c, size_t i);
 int check_ready(mcpt_ctx* c);
@@ -420,6 +587,9 @@ int check_ready(mcpt_ctx* c);
 // temporal history.
 int emitter_table_refresh(mcpt_ctx* c);
 int cam_table(mcpt_ctx* c, uint32_t W, uint32_t H, const float4** px, const float4** dir);
+// Defined in film_state.cpp
+// The tile set t: queues sized for it (RayQueues::ensure), the tiles uploaded.  The film state stays.
+int set_tiles_internal(mcpt_ctx* c, const std::vector<int2>& t);
 int film_view(mcpt_ctx* c, const float4** Ld, const uint32_t** samples);
 // n float4 of a device plane to the host: the xyz as 3 floats per element and / or the w (nullptr: not wanted)
 int read_plane(mcpt_ctx* c, const float4* d, size_t n, float* xyz, float* w);

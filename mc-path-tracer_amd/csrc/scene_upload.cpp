@@ -274,9 +274,9 @@ static int occ_fill(mcpt_ctx* c, DevScene& s, float* ms) {
         ts.count = nkeys;
         ts.shard_cap = nkeys;
         ta.vis = pvis;
-        ta.grab = &c->cnt->grab[0][0];
+        ta.grab = &c->cnt.dev->grab[0][0];
         launch_trace(ta, c->geom, c->stream);
-        HIPCHK(c, hipMemsetAsync(c->cnt->grab, 0, sizeof(c->cnt->grab), c->stream));  // hand-out counters back to 0
+        HIPCHK(c, hipMemsetAsync(c->cnt.dev->grab, 0, sizeof(c->cnt.dev->grab), c->stream));  // hand-out counters back to 0
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipEventRecord(ev(c, EV_B1), c->stream));
         if (ms) {

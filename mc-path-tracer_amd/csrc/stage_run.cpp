@@ -83,7 +83,7 @@ static int stage_run_paths(mcpt_ctx* c, int stage, const mcpt_path_view* in, mcp
     }
     std::vector<uint8_t> vis(2 * (size_t)n, 0);
     if (in->vis) vis.assign(in->vis, in->vis + 2 * (size_t)n);
-    CounterBlock* hc = c->cnt_host;  // pinned staging (the context's counters stay on the device)
+    CounterBlock* hc = c->cnt.host;  // pinned staging (the context's counters stay on the device)
     memset(hc, 0, sizeof(CounterBlock));
     std::vector<uint4> rec;
     std::vector<float4> rbeta;
@@ -273,14 +273,14 @@ int mcpt_stage_run(mcpt_ctx* c, int stage, const mcpt_soa_view* in, mcpt_soa_vie
         if ((rc = dalloc(c, tmp.L, &steps, n))) return rc;
         ts.ray_steps = steps;
     }
-    ta.grab = &c->cnt->grab[0][0];
+    ta.grab = &c->cnt.dev->grab[0][0];
     HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
     ta.tiny_stack = c->tiny_stack ? 1 : 0;
     launch_trace(ta, c->geom, c->stream);
     HIPCHK(c, hipEventRecord(ev(c, 1), c->stream));
     uint32_t grab0 = 0;  // drain check: the one shard is partition 0's
-    HIPCHK(c, hipMemcpyAsync(&c->cnt_host->grab[0][0], &c->cnt->grab[0][0], sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->cnt->grab, 0, sizeof(c->cnt->grab), c->stream));  // hand-out counters back to 0
+    HIPCHK(c, hipMemcpyAsync(&c->cnt.host->grab[0][0], &c->cnt.dev->grab[0][0], sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->cnt.dev->grab, 0, sizeof(c->cnt.dev->grab), c->stream));  // hand-out counters back to 0
     if (stage == MCPT_STAGE_EXTEND) {
         HitRecordArgs ha{c->scene.dev, dro, drd, ht, hp, hn, ht, n};  // ht: positions in, scene indices out
         launch_hit_record(ha, c->stream);
@@ -288,7 +288,7 @@ int mcpt_stage_run(mcpt_ctx* c, int stage, const mcpt_soa_view* in, mcpt_soa_vie
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipEventElapsedTime(&c->last_stage_ms, c->events[0], c->events[1]));
-    grab0 = c->cnt_host->grab[0][0];
+    grab0 = c->cnt.host->grab[0][0];
     if (grab0 < n) return set_err(c, MCPT_E_HIP, "k_trace left rays untraced");
     if (steps) HIPCHK(c, hipMemcpy(out->steps, steps, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (stage == MCPT_STAGE_EXTEND) {
@@ -313,25 +313,25 @@ int mcpt_stage_run(mcpt_ctx* c, int stage, const mcpt_soa_view* in, mcpt_soa_vie
 }
 
 int mcpt_debug_queue_rays(mcpt_ctx* c, int which, float* ro, float* rd, uint32_t* n_inout) {
-    if (!c || !c->P || !n_inout || (which != 0 && which != 1)) return set_err(c, MCPT_E_INVALID, "bad argument");
+    if (!c || !c->film.allocated || !n_inout || (which != 0 && which != 1)) return set_err(c, MCPT_E_INVALID, "bad argument");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     CounterBlock cb;
-    HIPCHK(c, hipMemcpy(&cb, c->cnt, sizeof(cb), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&cb, c->cnt.dev, sizeof(cb), hipMemcpyDeviceToHost));
     // k_accumulate reset the live counters; the queues still hold the last iteration's entries
     uint32_t n = which == 0 ? cb.last_ext : 0;
     if (which == 1) return set_err(c, MCPT_E_INVALID, "any-hit queue length is not retained");
     if (!ro || !rd) { *n_inout = n; return MCPT_OK; }
     n = std::min(n, *n_inout);
-    std::vector<uint32_t> all((size_t)kShards * c->ext_cap), q;
-    HIPCHK(c, hipMemcpy(all.data(), c->ext_q, all.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> all((size_t)kShards * c->queues.ext_cap), q;
+    HIPCHK(c, hipMemcpy(all.data(), c->queues.ext, all.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (int sh = 0; sh < kShards; sh++)
-        for (uint32_t k = 0; k < cb.last_ext_shard[sh] && q.size() < n; k++) q.push_back(all[(size_t)sh * c->ext_cap + k]);
+        for (uint32_t k = 0; k < cb.last_ext_shard[sh] && q.size() < n; k++) q.push_back(all[(size_t)sh * c->queues.ext_cap + k]);
     n = (uint32_t)q.size();
-    const size_t np = c->npx * c->slots;
+    const size_t np = c->film.L.paths;
     std::vector<float4> o(np), d(np);
-    HIPCHK(c, hipMemcpy(o.data(), c->p.ray_o, np * sizeof(float4), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(d.data(), c->p.ray_d, np * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(o.data(), c->film.ray_o, np * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(d.data(), c->film.ray_d, np * sizeof(float4), hipMemcpyDeviceToHost));
     for (uint32_t i = 0; i < n; i++) {
         float4 a = o[q[i]], b = d[q[i]];
         ro[3 * i] = a.x; ro[3 * i + 1] = a.y; ro[3 * i + 2] = a.z;
@@ -402,10 +402,10 @@ int mcpt_debug_hbm_copy(mcpt_ctx* c, uint64_t bytes, uint32_t iters, double* gbp
 int mcpt_debug_trace_profile(mcpt_ctx* c, uint64_t* out12, int reset) {
     if (!c || !out12) return MCPT_E_INVALID;
     for (int i = 0; i < 12; i++) out12[i] = 0;
-    if (!c->totals_ok) return 0;
-    for (int i = 0; i < kPhaseWords; i++) out12[i] = c->totals.tot_phase[i] - c->phase_base[i];
+    if (!c->cnt.totals_ok) return 0;
+    for (int i = 0; i < kPhaseWords; i++) out12[i] = c->cnt.totals.tot_phase[i] - c->cnt.phase_base[i];
     if (reset)
-        for (int i = 0; i < kPhaseWords; i++) c->phase_base[i] = c->totals.tot_phase[i];
+        for (int i = 0; i < kPhaseWords; i++) c->cnt.phase_base[i] = c->cnt.totals.tot_phase[i];
     return kPhaseWords;
 }
 // Not part of mcpt.h: entry / exit s_memrealtime (100 MHz) stamps of the last k_trace launch's first n
