@@ -3,7 +3,7 @@
 // INTEGRATION.md): build a BASELINE config scene with the host builder, upload it,
 // run the wavefront iterations until every pixel has its samples, write PNG + PFM.
 //
-//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>] [--emissive <mat> <r> <g> <b>]... [--env-color <r> <g> <b>] [--sample-emitters]
+//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>] [--emissive <mat> <r> <g> <b>]... [--env-color <r> <g> <b>] [--sample-emitters] [--emitter-mis]
 //
 // --denoise renders the first-hit guide buffers (default 4 guide samples per pixel), filters the film
 // with the default parameters and writes <out_prefix>_denoised.png beside the raw image.
@@ -35,7 +35,9 @@
 // is a Cornell box lit by its ceiling alone.  Emitters are not sampled as lights, so small ones are noisy,
 // unless --sample-emitters turns emitter sampling on: every vertex then draws a
 // point on an emissive triangle and traces a shadow ray to it (`mcpt_render 2 64 --emissive 7 40 40 40
-// --env-color 0 0 0 --sample-emitters` is the box lit by one small sphere).
+// --env-color 0 0 0 --sample-emitters` is the box lit by one small sphere).  --emitter-mis implies
+// --sample-emitters and weights the emitter sample against collected emission (multiple importance
+// sampling): the choice for emitters that touch other surfaces, as that sphere does.
 // --tiles-per-call uses the reference orchestration (one 256x256 tile per call,
 // wavefront_kernels.cu:377-442 + Film::update_tile_position) instead of batch mode.
 #include <math.h>
@@ -67,7 +69,7 @@ static void warp(const mcpt_scene_desc& d, float amp, uint32_t frame, uint32_t f
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>] [--emissive <mat> <r> <g> <b>]... [--env-color <r> <g> <b>] [--sample-emitters]\n", argv[0]);
+        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>] [--emissive <mat> <r> <g> <b>]... [--env-color <r> <g> <b>] [--sample-emitters] [--emitter-mis]\n", argv[0]);
         return 2;
     }
     const Cfg cfgs[6] = {{0, 0, 0, 0, {0, 0, 0}, 0, ""},
@@ -83,7 +85,7 @@ int main(int argc, char** argv) {
     std::string out = (argc > 3 && argv[3][0] != '-') ? argv[3] : "mcpt_render";
     bool gpu_bvh = false, ref_bvh = false, fixed = false, per_tile = false;
     uint32_t slots = 1, guide_samples = 0, guided_samples = 0;  // guide_samples / guided_samples > 0: denoise [guided]
-    bool adaptive = false, slots_given = false, variance_fill = false, sample_emitters = false;
+    bool adaptive = false, slots_given = false, variance_fill = false, sample_emitters = false, emitter_mis = false;
     mcpt_sample_budget_params ap;
     mcpt_sample_budget_default_params(&ap);
     uint32_t rounds = 2;
@@ -122,6 +124,7 @@ int main(int argc, char** argv) {
         if (!strcmp(argv[i], "--fixed")) fixed = true;
         if (!strcmp(argv[i], "--variance-fill")) variance_fill = true;
         if (!strcmp(argv[i], "--sample-emitters")) sample_emitters = true;
+        if (!strcmp(argv[i], "--emitter-mis")) sample_emitters = emitter_mis = true;
         if (!strcmp(argv[i], "--tiles-per-call")) per_tile = true;
         if (!strcmp(argv[i], "--slots") && i + 1 < argc) { slots = (uint32_t)atoi(argv[++i]); slots_given = true; }
         if (!strcmp(argv[i], "--adaptive")) {
@@ -176,6 +179,7 @@ int main(int argc, char** argv) {
     int rc = gpu_bvh ? mcpt_scene_upload_gpu_bvh(ctx, &d) : mcpt_scene_upload(ctx, &d);
     if (!rc && em_rgb) rc = mcpt_set_material_emission(ctx, em_nmat, em_rgb);
     if (!rc && sample_emitters) rc = mcpt_set_emitter_sampling(ctx, 1);
+    if (!rc && emitter_mis) rc = mcpt_set_emitter_mis(ctx, 1);
     // Camera::update
     mcpt_camera_params cp{{c.pos[0], c.pos[1], c.pos[2]}, -90.f, c.pitch, 0.785398163f, (float)c.w / (float)c.h,
                           0.01f, 1e4f, 1e-4f, 35.f};

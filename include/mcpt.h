@@ -600,6 +600,25 @@ int mcpt_material_emission_read(mcpt_ctx *ctx, float *rgb, int32_t *nmat);
 int mcpt_set_emitter_sampling(mcpt_ctx *ctx, int32_t on);
 int mcpt_emitter_table_read(mcpt_ctx *ctx, float *cdf, float *pick, uint32_t *tri_id, int32_t *n);
 int mcpt_debug_emitter_stats(const mcpt_ctx *ctx, double *out4);
+/* ---- emitter MIS: multiple importance sampling between the emitter sample and
+ * collected emission.  A switch beside emitter sampling, off by default, in effect only while emitter
+ * sampling is active and the switch is on; otherwise the context launches the kernels and renders the
+ * films it did before.  While in effect the emitter sample's term carries the power-heuristic weight of
+ * its area pdf (as a solid angle) against the BRDF's pdf of its direction, and a path collects emission
+ * at every vertex again (section 16's condition), at len >= 2 weighted by the power heuristic of the
+ * pdf its direction had as the previous vertex's continuation sample against the pdf the emitter sample
+ * has for the point hit; the primary hit collects with weight 1.  Paths, rays, random draws and every ray
+ * count, emitter rays included, are those of emitter sampling without MIS; only the film differs.  The
+ * two pdfs are taken from ray origins 0.009 apart along the normal (the light rays' and the extension
+ * rays' offsets), so the weights sum to one only up to that offset.
+ *
+ * mcpt_set_emitter_mis: turning the switch on or off while emitter sampling is active marks the film
+ * stale and drops the temporal history as mcpt_set_emitter_sampling does; the same value again, and any
+ * change while sampling is not active, does nothing beyond storing the switch.  It survives scene
+ * uploads, as the sampling switch does.  mcpt_stage_run is unaffected.
+ * mcpt_debug_emitter_mis: 1 while MIS is in effect, 0 while it is not, or an error code. */
+int mcpt_set_emitter_mis(mcpt_ctx *ctx, int32_t on);
+int mcpt_debug_emitter_mis(const mcpt_ctx *ctx);
 int mcpt_sync(mcpt_ctx *ctx);
 int mcpt_device_name(mcpt_ctx *ctx, char *buf, int32_t len);
 /* diagnostics: rays of the current extension (which=0) or any-hit (which=1) queue, and the

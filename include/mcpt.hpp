@@ -694,6 +694,14 @@ public:
     void set_emitter_sampling(bool on) {
         detail::check(mcpt_set_emitter_sampling(ctx_, on ? 1 : 0), ctx_, "set_emitter_sampling");
     }
+    // MIS between the emitter sample and collected emission (mcpt.h): a switch
+    // beside emitter sampling, off by default, in effect only while sampling is active.
+    void set_emitter_mis(bool on) { detail::check(mcpt_set_emitter_mis(ctx_, on ? 1 : 0), ctx_, "set_emitter_mis"); }
+    bool emitter_mis() const {
+        const int rc = mcpt_debug_emitter_mis(ctx_);
+        if (rc < 0) detail::check(rc, ctx_, "emitter_mis");
+        return rc == 1;
+    }
     // The emitter table in ascending scene triangle id; returns the entry count (0: off, or nothing emits)
     int emitter_table(std::vector<float>& cdf, std::vector<float>& pick, std::vector<uint32_t>& tri_id) {
         int32_t n = 0;

@@ -1,6 +1,7 @@
-// emitter.hip -- emitter sampling's setup kernel: one weight per triangle record,
-// from which the host builds the emitter table (host/emitter_table.cpp).  The per-vertex sampling itself
-// is part of k_material (kernels.hip).
+// emitter.hip -- emitter sampling's setup kernels: one weight per triangle record, from which the host
+// builds the emitter table (host/emitter_table.cpp), and the table's pick
+// probability keyed by record for the MIS collection weight (section 18).  The per-vertex sampling itself
+// is part of k_material, the collection weight of k_shade (kernels.hip).
 #include "kernels.hpp"
 
 namespace mcpt_dev {
@@ -30,6 +31,24 @@ void launch_emitter_weights(const DevScene& sc, const float4* emis, float* weigh
     if (!sc.ntri) return;
     hipLaunchKernelGGL(k_emitter_weights, dim3((sc.ntri + 255u) / 256u), dim3(256), 0, s, sc.tri, sc.tri_sh, emis, sc.ntri,
                        weight, id);
+}
+
+// pick_rec[ent[k].x] = entry k's pick probability: the emitter table keyed by
+// triangle record, for the collection weight of a path that hits an emitter (k_shade's MIS
+// instantiation).  The array is cleared first, so a record that is no entry reads 0.  Entries have
+// distinct records: no two threads write one word.
+__global__ __launch_bounds__(256) void k_emitter_pick_rec(const uint2* ent, uint32_t n, float* pick_rec, uint32_t ntri) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const uint2 e = ent[k];
+    if (e.x < ntri) pick_rec[e.x] = __uint_as_float(e.y);
+}
+
+void launch_emitter_pick_rec(const uint2* ent, uint32_t n, float* pick_rec, uint32_t ntri, hipStream_t s) {
+    if (!ntri) return;
+    (void)hipMemsetAsync(pick_rec, 0, (size_t)ntri * sizeof(float), s);  // (an error surfaces at the caller's check)
+    if (!n) return;
+    hipLaunchKernelGGL(k_emitter_pick_rec, dim3((n + 255u) / 256u), dim3(256), 0, s, ent, n, pick_rec, ntri);
 }
 
 }  // namespace mcpt_dev

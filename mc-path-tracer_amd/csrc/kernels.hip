@@ -514,7 +514,10 @@ struct MatOut {
 //
 // SAMP (emitter sampling active): one emitter sample beside everything else, from
 // RNG slots of its own, so the other draws, rays and terms are those of the plain instantiation.
-template <bool FIXED, bool SAMP = false>
+// MIS (with SAMP): the emitter sample carries its power-heuristic weight against
+// the BRDF's pdf of its direction, and nee2.w stores the continuation direction's pdf for the
+// collection weight of the next logic pass.
+template <bool FIXED, bool SAMP = false, bool MIS = false>
 __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix, uint32_t sidx, uint32_t len,
                                  V3 beta_store, int32_t htri, float4* stage, bool occ_on, bool no_cont, bool& want_e) {
     const DevScene& sc = a.scene;
@@ -540,6 +543,7 @@ __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix
     // (:335-343) wait for the occluder cache (material_brdf_terms).
     uint32_t nf = 0;
     V3 rr;
+    [[maybe_unused]] float pdf_cont = 0.f;  // MIS: pdf_s of the continuation direction (0: no_cont, never read)
     if (no_cont) {
         // k_shade's mark (reference mode): the next logic pass adds this vertex's MIS terms and then
         // ends the path by roulette, so the continuation sample is never read.  The pass multiplies
@@ -554,6 +558,7 @@ __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix
         float pdf_s;
         V3 f_s;
         brdf_f_pdf(m, n, wi_s, wo, f_s, pdf_s);
+        if constexpr (MIS) pdf_cont = pdf_s;
         if ((f_s.x == 0.f && f_s.y == 0.f && f_s.z == 0.f) || pdf_s == 0.f) nf |= F_FZERO;
         rr = f_s / pdf_s;
         const V3 new_o = pos + n * 0.001f;  // :358
@@ -662,7 +667,13 @@ __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix
         float pdf_be;
         brdf_f_pdf(m, n, edir, wo, f_e, pdf_be);
         const int mat_e = __float_as_int(sc.tri_sh[3 * (size_t)ent.x + 2].y);
-        V3 cE = (f_e * ld3f4(a.emis + mat_e)) / pdf_e;
+        V3 cE;
+        if constexpr (MIS) {  // the light sample's expression order (cL)
+            const float wE = power_heuristic(pdf_e, pdf_be);
+            cE = ((f_e * ld3f4(a.emis + mat_e)) * wE) / pdf_e;
+        } else {
+            cE = (f_e * ld3f4(a.emis + mat_e)) / pdf_e;
+        }
         const bool ok = dist > 0.f && cosl > 0.f && pdf_e > 0.f && pdf_e < K_INF_F && __builtin_fabsf(cE.x) < K_INF_F &&
                         __builtin_fabsf(cE.y) < K_INF_F && __builtin_fabsf(cE.z) < K_INF_F;
         if (ok) {
@@ -673,7 +684,7 @@ __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix
             cE = v3(0.f, 0.f, 0.f);
             a.p.vis[a.emit_vis0 + pid] = 0;
         }
-        st_s(a.nee2 + pid, f4(cE, 0.f));
+        st_s(a.nee2 + pid, f4(cE, MIS ? pdf_cont : 0.f));
     }
     // the BRDF sample's direction and visibility ray (its light terms come after the occluder
     // cache, material_brdf_terms)
@@ -794,6 +805,32 @@ __device__ inline uint32_t udiv_small(uint32_t n, uint32_t d, float rcp) {
     return q;
 }
 
+// The collection weight of path pid, which reached triangle record htri by the continuation ray still
+// stored for it: the power heuristic between pdf_s, the pdf that ray's direction
+// had as a BRDF sample (nee2.w, k_material), and pdf_c, the solid-angle pdf the emitter sample has for
+// the point hit: pick / area * t^2 / cos at the light, by the emitter sample's own expressions over
+// the record as stored.  1 where pdf_c is not a finite number > 0 (a record that is no table entry has
+// pick 0) or the weight is not in [0, 1].  Everything is loaded here: nothing is carried to this point.
+// ray_o / ray_d: the streams that hold the ray (shade_vblock: a path the skip switch ended keeps it in
+// nee0 / nee1).
+__device__ inline float mis_collect_weight(const ShadeArgs& a, const float4* ray_o, const float4* ray_d, uint32_t pid,
+                                           int32_t htri) {
+    const float pick = a.pick_rec[htri];
+    const float pdf_s = ld_s(a.nee2 + pid).w;
+    const V3 o = ld3f4(ray_o + pid), d = ld3f4(ray_d + pid);
+    const float4* tp = a.scene.tri + (size_t)kTriF4 * htri;
+    const float4 w0 = tp[0], w1 = tp[1], w2 = tp[2];
+    const V3 v0 = v3(w0.x, w0.y, w0.z), e1 = v3(w0.w, w1.x, w1.y), e2 = v3(w1.z, w1.w, w2.x);
+    const V3 c = cross(e1, e2);
+    const float lc = __builtin_sqrtf(dot(c, c)), area = 0.5f * lc;
+    const float t = dot(v0 - o, c) / dot(d, c), d2 = t * t;
+    const float cosl = __builtin_fabsf(dot(normalize(c), d));
+    const float pdf_c = ((pick / area) * d2) / cosl;
+    float wC = power_heuristic(pdf_s, pdf_c);
+    if (!(pdf_c > 0.f && pdf_c < K_INF_F) || !(wC >= 0.f && wC <= 1.f)) wC = 1.f;
+    return wC;
+}
+
 // One shading block: logic + generate for kBlock pixels of a path slot, then the block's pushes.
 // MAP: the pixel's sample budget (ShadeArgs::budget) stands in for spp.  An instantiation of its own,
 // so the no-map kernel is the code it was.
@@ -804,7 +841,10 @@ __device__ inline uint32_t udiv_small(uint32_t n, uint32_t d, float rcp) {
 // sample's term of the previous vertex (ShadeArgs::nee2, its visibility byte at emit_vis0 + path) where
 // it adds the light sample's, and collects emission at the primary hit only: at len >= 2 the previous
 // vertex's emitter sample stands for that light.
-template <bool FIXED, bool MAP, bool EMIT, bool SAMP = false>
+// MIS (with SAMP): collection comes back at len >= 2, weighted by the power
+// heuristic between the pdf the previous vertex's continuation sample had (nee2.w) and the pdf the
+// emitter sample of that vertex would have had for the point hit (mis_collect_weight).
+template <bool FIXED, bool MAP, bool EMIT, bool SAMP = false, bool MIS = false>
 __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeArgs& a, int vb, const VBlk& v) {
     const DevScene& sc = a.scene;
     const int slot = (int)(v.sr & 0xffu);
@@ -847,6 +887,11 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
     bool bg = false;
     V3 bg_film = v3(0.f, 0.f, 0.f), bg_dir = bg_film;
     bool em = false, em_dirty = false;  // collects emission; its film already differs from the stored one
+    // MIS: the path collects at len >= 2, with the weight formed after the pushes from its stored ray
+    // (mis_collect_weight).  Where the skip switch ends the path here (dd), the generate below replaces
+    // that ray, so it is kept in nee0 / nee1 of the path: this pass has read them, and the next reader
+    // (the logic pass at len 2 of the new sample) comes after k_material has written them.
+    [[maybe_unused]] bool em_weighted = false;
     bool finished = true;  // dead with its last sample done (or no pixel): see blk_done
     if (valid) {
         // Every load the logic may need is issued up front, in one round: the
@@ -943,8 +988,9 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
                 // len <= max_depth, a non-zero sample, the roulette survived (beta_store is final).
                 // The skip switch's early end below (dd) is such a path too: the reference runs its
                 // material stage.  Its film is written once, after the pushes, with the emission.
-                em = !terminate && (!SAMP || len == 1);
+                em = !terminate && (!SAMP || MIS || len == 1);
                 if (em) {
+                    if constexpr (MIS) em_weighted = len > 1;
                     em_dirty = film_dirty;
                     bg_film = film;
                     cont_htri = htri;
@@ -963,6 +1009,12 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
                     dd = true;
                     dd_vis = !(((l_id == sc.nlights) ? 0 : l_id) > 0);
                     terminate = true;
+                    if constexpr (MIS) {  // (em holds) the stored ray moves out of the generate's way
+                        if (len > 1) {
+                            st_s(a.p.nee0 + pid, ld_s(a.p.ray_o + pid));
+                            st_s(a.p.nee1 + pid, ld_s(a.p.ray_d + pid));
+                        }
+                    }
                 } else if (!FIXED && len + 1u > (uint32_t)a.rr_depth) {
                     // Its roulette reads the throughput this pass stores and a keyed draw: decided now,
                     // k_material makes no continuation sample.  (Fixed mode tests the throughput after
@@ -1088,7 +1140,20 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
         MCPT_MARK("emission");
         if (em) {  // film += Le[mat(hit_tri)] * beta_store, two-sided (emissive_L: no normal test)
             const int mat = __float_as_int(sc.tri_sh[3 * cont_htri + 2].y);  // the word k_material reads (hit_record)
-            const V3 film = bg_film + ld3f4(a.emis + mat) * beta_store;
+            V3 film;
+            if constexpr (MIS) {
+                // weighted; where the surface does not emit the term is not formed
+                const V3 le = ld3f4(a.emis + mat);
+                film = bg_film;
+                if (le.x != 0.f || le.y != 0.f || le.z != 0.f) {
+                    const float wC =
+                        em_weighted ? mis_collect_weight(a, dd ? a.p.nee0 : a.p.ray_o, dd ? a.p.nee1 : a.p.ray_d, pid, cont_htri)
+                             : 1.f;
+                    film = bg_film + (le * beta_store) * wC;
+                }
+            } else {
+                film = bg_film + ld3f4(a.emis + mat) * beta_store;
+            }
             if (em_dirty || __float_as_uint(film.x) != __float_as_uint(bg_film.x) ||
                 __float_as_uint(film.y) != __float_as_uint(bg_film.y) || __float_as_uint(film.z) != __float_as_uint(bg_film.z))
                 a.p.Ld[pid] = f4(film, 0.f);
@@ -1106,7 +1171,7 @@ __device__ __attribute__((always_inline)) inline void shade_vblock(const ShadeAr
 // (one workgroup per shading block, G = the block count) paid ~0.2 ms per launch just to dispatch
 // and retire config 2's 246K workgroups once they had all finished (the frame's last ~20
 // iterations; 64 iterations per frame).
-template <bool FIXED, bool MAP, bool EMIT, bool SAMP = false>
+template <bool FIXED, bool MAP, bool EMIT, bool SAMP = false, bool MIS = false>
 __global__ __launch_bounds__(kBlock) MCPT_SHADE_ATTR void k_shade(ShadeArgs a) {
     if (a.cnt->idle) return;  // the tile set is complete (an earlier iteration of the call traced no ray)
     __shared__ uint64_t s_live[kBlock / 64];
@@ -1127,7 +1192,7 @@ __global__ __launch_bounds__(kBlock) MCPT_SHADE_ATTR void k_shade(ShadeArgs a) {
         if (!((s_live[j >> 6] >> (j & 63)) & 1ull)) continue;
         // the arguments re-read per shading block (kernarg_fresh): hoisted out of the loop, the
         // struct's fields took the SGPR file and spilled (89 SGPRs, 54 -> 86 VGPRs)
-        shade_vblock<FIXED, MAP, EMIT, SAMP>(kernarg_fresh<ShadeArgs>(), (int)(blockIdx.x + j * G), s_vb[j]);
+        shade_vblock<FIXED, MAP, EMIT, SAMP, MIS>(kernarg_fresh<ShadeArgs>(), (int)(blockIdx.x + j * G), s_vb[j]);
     }
 }
 
@@ -1141,7 +1206,8 @@ __global__ __launch_bounds__(kBlock) MCPT_SHADE_ATTR void k_shade(ShadeArgs a) {
 // SAMP: the emitter-sampling instantiation, launched only while sampling is
 // active: a third staged ray (six LDS slabs, 24 KiB per block: 96 KiB per CU at 4 waves per SIMD, of 160)
 // pushed onto the any-hit queue with the result index 2P + path.
-template <bool FIXED, bool SAMP = false>
+// MIS (with SAMP): the weighted emitter sample and pdf_s in nee2.w (material()).
+template <bool FIXED, bool SAMP = false, bool MIS = false>
 __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_kernarg) {
     (void)a_kernarg;  // read through kernarg_fresh (the same bytes: it is the kernel's only argument)
     const ShadeArgs& a = kernarg_fresh<ShadeArgs>();
@@ -1171,8 +1237,8 @@ __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_k
             const uint4 q = ld_s(a.mat_rec + shard * a.ext_cap + i);  // {pid, pixel, sample index | len << 24, hit_tri}
             const float4 b4 = ld_s(a.mat_beta + shard * a.ext_cap + i);
             mpid = q.x;
-            mo = material<FIXED, SAMP>(a, mpid, q.y, q.z & (kRecNoCont - 1u), q.z >> kRecLenShift, xyz(b4), (int32_t)q.w,
-                                 &s_any[0][0], occ_on, (q.z & kRecNoCont) != 0u, want_e);
+            mo = material<FIXED, SAMP, MIS>(a, mpid, q.y, q.z & (kRecNoCont - 1u), q.z >> kRecLenShift, xyz(b4), (int32_t)q.w,
+                                            &s_any[0][0], occ_on, (q.z & kRecNoCont) != 0u, want_e);
             // the occluder cache (see occ_hit1), before the BRDF sample's light terms: a ray it
             // resolves gets its wf_shadow result here and is not queued
             MCPT_MARK("m_occ");
@@ -2280,6 +2346,18 @@ void launch_shade(const ShadeArgs& args, int nblocks, const LaunchGeom& g, bool 
     // the instantiations it always launched)
     // Emitter sampling active (a.nee2 set, which implies a.emis): the sampling
     // instantiations of both kernels.  Every other context launches what it launched before.
+    if (a.nee2 && a.emis && a.pick_rec) {  // ... with MIS in effect (section 18): instantiations of their own again
+        if (fixed_mode) {
+            if (a.budget) hipLaunchKernelGGL((k_shade<true, true, true, true, true>), dim3(G), dim3(kBlock), 0, s, a);
+            else hipLaunchKernelGGL((k_shade<true, false, true, true, true>), dim3(G), dim3(kBlock), 0, s, a);
+            hipLaunchKernelGGL((k_material<true, true, true>), dim3(g.mat_blocks_samp[1]), dim3(kBlock), 0, s, a);
+        } else {
+            if (a.budget) hipLaunchKernelGGL((k_shade<false, true, true, true, true>), dim3(G), dim3(kBlock), 0, s, a);
+            else hipLaunchKernelGGL((k_shade<false, false, true, true, true>), dim3(G), dim3(kBlock), 0, s, a);
+            hipLaunchKernelGGL((k_material<false, true, true>), dim3(g.mat_blocks_samp[0]), dim3(kBlock), 0, s, a);
+        }
+        return;
+    }
     if (a.nee2 && a.emis) {
         if (fixed_mode) {
             if (a.budget) hipLaunchKernelGGL((k_shade<true, true, true, true>), dim3(G), dim3(kBlock), 0, s, a);

@@ -19,7 +19,8 @@
 //   flags         u32    [P]    dead, len, MIS condition bits, the path's sample index (bits 13..31)
 //   vis           u8     [2P]   any-hit results ([3P] while emitter sampling is active: the emitter
 //                               ray of path p at 2P + p)
-//   nee2          float4 [P]    the emitter sample's term (only while emitter sampling is active)
+//   nee2          float4 [P]    the emitter sample's term (only while emitter sampling is active); .w: 0, or
+//                               with MIS (section 18) the pdf of the continuation direction
 //   samples       u32    [P]    film sample count (dFilm.samples)
 //   Ld            float4 [P]    film radiance (dFilm.Ld)
 #pragma once
@@ -283,6 +284,11 @@ struct ShadeArgs {
     int emit_n;
     uint32_t emit_vis0;
     float4* nee2;
+    // MIS between the emitter sample and collected emission (mcpt_set_emitter_mis),
+    // set only while it is in effect (emitter sampling active and the switch on): launch_shade then
+    // runs the MIS instantiations; the others never look at this field.  pick_rec[r]: the emitter
+    // table's pick probability of triangle record r, 0 for a record that is no entry.
+    const float* pick_rec;
 };
 // k_primary_build: the table of a W x H film.  stats: [0] pixels with a list, [1] overflow pixels.
 struct PrimaryBuildArgs {
@@ -367,6 +373,10 @@ int shade_sections(unsigned long long* out, int n, int reset);  // -DMCPT_DIAG_S
 // the sampling arithmetic's own area (0.5 sqrt(dot(c, c)), c = cross(e1, e2) of the record as stored),
 // 0 for a non-emissive material, and id[r] = the record's scene triangle id.
 void launch_emitter_weights(const DevScene& sc, const float4* emis, float* weight, uint32_t* id, hipStream_t s);
+// k_emitter_pick_rec: pick_rec[r] = the pick probability of the emitter table's
+// entry whose record is r, 0 for every other of the ntri records.  ent: the table's n device entries
+// {record index, pick bits}.
+void launch_emitter_pick_rec(const uint2* ent, uint32_t n, float* pick_rec, uint32_t ntri, hipStream_t s);
 
 // ---- scene tables (scene_tables.hip) ----
 // Occluder records (DevScene::occ_rec): for each triangle record t, {leaf mn, margin} {leaf mx,

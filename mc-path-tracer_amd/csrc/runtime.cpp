@@ -198,12 +198,37 @@ static int emitter_queues(mcpt_ctx* c) {
     return set_tiles_internal(c, std::vector<int2>(c->tiles.host));
 }
 
+// pick_rec: the table's pick keyed by triangle record, from the device entries of
+// the current table, while MIS is in effect; dropped otherwise.  It follows the table: rebuilt with
+// every table build (the record order may have changed) and when the MIS switch turns on.
+static int emitter_pick_refresh(mcpt_ctx* c) {
+    EmitterSampling& es = c->es;
+    const uint32_t ntri = c->scene.ok ? c->scene.dev.ntri : 0u;
+    if (!es.mis_active() || !ntri) {
+        es.drop_pick();
+        return MCPT_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // no launch in flight reads the old array
+    es.pick_ok = false;
+    if (!es.pick_rec.ensure(ntri)) {
+        es.drop_pick();
+        return set_err(c, MCPT_E_NOMEM, "hipMalloc: emitter pick table");
+    }
+    launch_emitter_pick_rec(es.ent, (uint32_t)es.tab.cdf.size(), es.pick_rec, ntri, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    es.pick_ok = true;
+    return MCPT_OK;
+}
+
 extern "C++" int emitter_table_refresh(mcpt_ctx* c) {
     EmitterSampling& es = c->es;
     if (!es.on || !c->scene.ok) return MCPT_OK;
     const bool was_active = es.active();
     mcpt_host::EmitterTable now;
     es.build_ms = 0.f;
+    es.pick_ok = false;  // (belongs to the entries about to be replaced; emitter_pick_refresh below)
     const float4* emis = c->em.dev_table();
     const uint32_t ntri = c->scene.dev.ntri;
     HIPCHK(c, hipSetDevice(c->device));
@@ -248,6 +273,7 @@ extern "C++" int emitter_table_refresh(mcpt_ctx* c) {
         c->tp.ok = false;
     }
     if (!es.active()) es.drop_streams();
+    if (int rc = emitter_pick_refresh(c)) return rc;
     return emitter_queues(c);
 }
 
@@ -265,6 +291,26 @@ int mcpt_set_emitter_sampling(mcpt_ctx* c, int32_t on) {
     es.drop_table();
     es.drop_streams();
     return emitter_queues(c);
+}
+
+// ---- MIS between emitter samples and collected emission ----
+int mcpt_set_emitter_mis(mcpt_ctx* c, int32_t on) {
+    if (!c) return MCPT_E_INVALID;
+    EmitterSampling& es = c->es;
+    if (es.mis == (on != 0)) return MCPT_OK;
+    es.mis = on != 0;
+    if (!es.active()) return MCPT_OK;  // takes effect with sampling, whose own changes restart the film
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    // the estimator changes: the film restarts, as with mcpt_set_emitter_sampling
+    c->film_stale = true;
+    c->tp.ok = false;
+    return emitter_pick_refresh(c);
+}
+
+int mcpt_debug_emitter_mis(const mcpt_ctx* c) {
+    if (!c) return MCPT_E_INVALID;
+    return c->es.mis_active() ? 1 : 0;
 }
 
 int mcpt_emitter_table_read(mcpt_ctx* c, float* cdf, float* pick, uint32_t* tri_id, int32_t* n) {
@@ -451,6 +497,10 @@ static int enqueue_iteration(mcpt_ctx* c, size_t evbase, bool timing, const int2
     sa.emit_n = samp ? (int)c->es.tab.cdf.size() : 0;
     sa.emit_vis0 = samp ? (uint32_t)(2 * c->es.paths) : 0u;
     sa.nee2 = samp ? c->es.nee2.get() : nullptr;
+    // ... and MIS (section 18) only while it is in effect, with pick_rec of the current table
+    if (samp && c->es.mis && !(c->es.pick_ok && c->es.pick_rec.get()))
+        return set_err(c, MCPT_E_INVALID, "emitter MIS: no pick table for the current emitter table");
+    sa.pick_rec = samp && c->es.mis ? c->es.pick_rec.get() : nullptr;
     if (samp) sa.p.vis = c->es.vis;  // 3P bytes: the emitter rays' results behind the two of every path
     if (int rc = cam_table(c, c->W, c->H, &sa.cam_px, &sa.cam_dir)) return rc;
     prim_table(c, sa);

@@ -240,8 +240,22 @@ struct EmitterSampling {
     DevBuf<uint8_t> vis;   // [3P]: the any-hit results with the emitter rays' third part
     size_t paths = 0;      // P the streams were last sized (and zeroed) for
     float build_ms = 0.f;  // the last table build: weights kernel, readback, host table, upload
+    // MIS between emitter samples and collected emission (mcpt_set_emitter_mis):
+    // the switch, and the table's pick keyed by triangle record, which follows the table's life and
+    // exists only while MIS is in effect (pick_ok: built for the current table and record order).
+    bool mis = false;
+    DevBuf<float> pick_rec;  // [ntri]
+    bool pick_ok = false;
     bool active() const { return on && !tab.cdf.empty(); }
-    void drop_table() { tab = mcpt_host::EmitterTable{}; }
+    bool mis_active() const { return mis && active(); }
+    void drop_pick() {
+        pick_rec.reset();
+        pick_ok = false;
+    }
+    void drop_table() {
+        tab = mcpt_host::EmitterTable{};
+        drop_pick();
+    }
     void drop_streams() {
         nee2.reset();
         vis.reset();

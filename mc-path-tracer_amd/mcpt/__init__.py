@@ -207,6 +207,8 @@ ABI = {
     "mcpt_set_emitter_sampling": (C.c_int, [C.c_void_p, C.c_int32]),
     "mcpt_emitter_table_read": (C.c_int, [C.c_void_p, _f, _f, _u, _i]),
     "mcpt_debug_emitter_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "mcpt_set_emitter_mis": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mcpt_debug_emitter_mis": (C.c_int, [C.c_void_p]),
     "mcpt_scene_set_material_emission": (C.c_int, [C.c_void_p, C.c_int32, _f]),
     "mcpt_scene_get_emission": (C.c_int, [C.c_void_p, C.POINTER(_f), _i]),
     "mcpt_sync": (C.c_int, [C.c_void_p]),
@@ -537,6 +539,12 @@ class PathTracer:
         default; inactive while no triangle emits.  Toggling clears the film at the next render."""
         self._ck(lib().mcpt_set_emitter_sampling(self.h, 1 if on else 0))
 
+    def set_emitter_mis(self, on=True):
+        """Multiple importance sampling between the emitter sample and collected emission
+        (mcpt_set_emitter_mis).  Off by default; in effect only while emitter
+        sampling is active, and toggling it then clears the film at the next render."""
+        self._ck(lib().mcpt_set_emitter_mis(self.h, 1 if on else 0))
+
     def emitter_table(self):
         """The emitter table as (cdf, pick, tri_id) arrays in ascending scene triangle id, empty when
         sampling is off or nothing emits."""
@@ -550,13 +558,17 @@ class PathTracer:
 
     def emitter_stats(self):
         """dict: entries, total weight, emitter rays made since the last film clear, the last table
-        build's ms, and whether sampling is active (mcpt_debug_emitter_stats)."""
+        build's ms, whether sampling is active (mcpt_debug_emitter_stats) and whether MIS is in effect
+        (mcpt_debug_emitter_mis)."""
         out = (C.c_double * 4)()
         rc = lib().mcpt_debug_emitter_stats(self.h, out)
         if rc < 0:
             self._ck(rc)
+        mis = lib().mcpt_debug_emitter_mis(self.h)
+        if mis < 0:
+            self._ck(mis)
         return {"entries": int(out[0]), "total_weight": out[1], "emitter_rays": int(out[2]), "build_ms": out[3],
-                "active": rc == 1}
+                "active": rc == 1, "mis": mis == 1}
 
     def emission(self):
         """The installed table as an (nmat, 3) array, or None when none is installed."""
