@@ -3,7 +3,7 @@
 // INTEGRATION.md): build a BASELINE config scene with the host builder, upload it,
 // run the wavefront iterations until every pixel has its samples, write PNG + PFM.
 //
-//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>] [--emissive <mat> <r> <g> <b>]... [--env-color <r> <g> <b>] [--sample-emitters] [--emitter-mis]
+//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>] [--emissive <mat> <r> <g> <b>]... [--env-color <r> <g> <b>] [--sample-emitters] [--emitter-mis] [--checker <mat> <n>]...
 //
 // --denoise renders the first-hit guide buffers (default 4 guide samples per pixel), filters the film
 // with the default parameters and writes <out_prefix>_denoised.png beside the raw image.
@@ -38,6 +38,10 @@
 // --env-color 0 0 0 --sample-emitters` is the box lit by one small sphere).  --emitter-mis implies
 // --sample-emitters and weights the emitter sample against collected emission (multiple importance
 // sampling): the choice for emitters that touch other surfaces, as that sphere does.
+// --checker puts an <n> x <n> two-colour procedural checker (16 x 16 texels per square, so the bilinear
+// filter softens only the squares' edges) on material <mat> as its base-colour texture (DESIGN.md section
+// 19; repeatable), over the uvs the mesh came with: `mcpt_render 1 64 --checker 0 8` is config 1's mesh
+// (Cube.glb, each face a quarter of the uv square wide) with 2 x 2 squares per face.
 // --tiles-per-call uses the reference orchestration (one 256x256 tile per call,
 // wavefront_kernels.cu:377-442 + Film::update_tile_position) instead of batch mode.
 #include <math.h>
@@ -69,7 +73,7 @@ static void warp(const mcpt_scene_desc& d, float amp, uint32_t frame, uint32_t f
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>] [--emissive <mat> <r> <g> <b>]... [--env-color <r> <g> <b>] [--sample-emitters] [--emitter-mis]\n", argv[0]);
+        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>] [--emissive <mat> <r> <g> <b>]... [--env-color <r> <g> <b>] [--sample-emitters] [--emitter-mis] [--checker <mat> <n>]...\n", argv[0]);
         return 2;
     }
     const Cfg cfgs[6] = {{0, 0, 0, 0, {0, 0, 0}, 0, ""},
@@ -94,6 +98,7 @@ int main(int argc, char** argv) {
     uint32_t a_frames = 0;  // > 0: --animate
     float a_amp = 0.f;
     std::vector<float> emissive;  // --emissive: {mat, r, g, b} per use
+    std::vector<int> checker;     // --checker: {mat, n} per use
     float env_rgb[3] = {0.f, 0.f, 0.f};
     bool env_given = false;
     for (int i = 2; i < argc; i++) {
@@ -106,6 +111,15 @@ int main(int argc, char** argv) {
         if (!strcmp(argv[i], "--emissive")) {
             if (i + 4 >= argc) { fprintf(stderr, "--emissive needs <mat> <r> <g> <b>\n"); return 2; }
             for (int k = 0; k < 4; k++) emissive.push_back((float)atof(argv[++i]));
+            continue;
+        }
+        if (!strcmp(argv[i], "--checker")) {
+            if (i + 2 >= argc || atoi(argv[i + 1]) < 0 || atoi(argv[i + 2]) < 1 || atoi(argv[i + 2]) > 1024) {
+                fprintf(stderr, "--checker needs <mat> <n> (n in 1..1024)\n");
+                return 2;
+            }
+            checker.push_back(atoi(argv[++i]));
+            checker.push_back(atoi(argv[++i]));
             continue;
         }
         if (!strcmp(argv[i], "--env-color")) {
@@ -159,6 +173,14 @@ int main(int argc, char** argv) {
     int src = !s || mcpt_scene_make_proxy(s, id, assets);
     if (!src && env_given) src = mcpt_scene_set_env_color(s, env_rgb, 1.f);
     for (size_t k = 0; !src && k < emissive.size(); k += 4) src = mcpt_scene_set_material_emission(s, (int32_t)emissive[k], &emissive[k + 1]);
+    for (size_t k = 0; !src && k < checker.size(); k += 2) {  // dark / light squares, opaque
+        const int sq = 16, n = checker[k + 1] * sq;  // texels per square, per side
+        std::vector<uint8_t> px((size_t)n * n * 4, 255);
+        for (int y = 0; y < n; y++)
+            for (int x = 0; x < n; x++)
+                for (int ch = 0; ch < 3; ch++) px[4 * ((size_t)y * n + x) + ch] = ((x / sq + y / sq) & 1) ? 255 : 40;
+        src = mcpt_scene_set_material_texture(s, checker[k], n, n, px.data());
+    }
     if (src || (ref_bvh ? mcpt_scene_build(s, 8) : mcpt_scene_build_ex(s, &bp))) {
         fprintf(stderr, "scene: %s\n", mcpt_last_error(nullptr));
         return 1;
@@ -178,6 +200,15 @@ int main(int argc, char** argv) {
     }
     int rc = gpu_bvh ? mcpt_scene_upload_gpu_bvh(ctx, &d) : mcpt_scene_upload(ctx, &d);
     if (!rc && em_rgb) rc = mcpt_set_material_emission(ctx, em_nmat, em_rgb);
+    {  // ... and so do its textures and uvs
+        const mcpt_texture* tex = nullptr;
+        const int32_t* mat_tex = nullptr;
+        const float *uv0 = nullptr, *uv1 = nullptr, *uv2 = nullptr;
+        int32_t ntex = 0, nmat = 0, ntri = 0;
+        if (!rc) rc = mcpt_scene_get_textures(s, &tex, &ntex, &mat_tex, &nmat);
+        if (!rc && tex && !(rc = mcpt_scene_get_uv(s, &uv0, &uv1, &uv2, &ntri)))
+            rc = mcpt_set_material_textures(ctx, ntri, uv0, uv1, uv2, ntex, tex, nmat, mat_tex);
+    }
     if (!rc && sample_emitters) rc = mcpt_set_emitter_sampling(ctx, 1);
     if (!rc && emitter_mis) rc = mcpt_set_emitter_mis(ctx, 1);
     // Camera::update

@@ -619,6 +619,51 @@ int mcpt_debug_emitter_stats(const mcpt_ctx *ctx, double *out4);
  * mcpt_debug_emitter_mis: 1 while MIS is in effect, 0 while it is not, or an error code. */
 int mcpt_set_emitter_mis(mcpt_ctx *ctx, int32_t on);
 int mcpt_debug_emitter_mis(const mcpt_ctx *ctx);
+/* ---- base-colour textures: per-hit albedo from a texture lookup in the material
+ * stage.  For a hit with Moller-Trumbore u, v and w = (1 - u) - v on a triangle with corner uvs uv0, uv1,
+ * uv2:
+ *   tc   = (u * uv1 + v * uv2) + w * uv0         fp32 per component, this order (Triangle.cu:79)
+ *   T    = the bilinear lookup of the material's texture at tc: normalised coordinates, wrap addressing,
+ *          8-bit fractional weights, texel = byte / 255 correctly rounded, rgb only (dTexture.cu:107-117)
+ *   base = base_factor * T                        one fp32 multiply per channel (the glTF rule)
+ * and the BRDF's f and pdf of every part of the material stage, the emitter sample's and MIS's BRDF pdf
+ * use this base.  Fresnel, roughness and metallic stay per material.  Row 0 of a texture is v in
+ * [0, 1 / h): glTF's orientation, no flip.  Texels are used as stored: there is no sRGB decode (the
+ * reference has none), and alpha is ignored.  Texels arrive decoded: reading the PNG / JPEG images
+ * embedded in a glb is out of scope here.  Paths, random draws, ray counts, emission and every table do
+ * not depend on the textures; while a set is in effect the albedo guide (mcpt_guides_render) accumulates
+ * the same base at the first hit.  Opt-in: a context without a set, or with one whose every material
+ * index is -1, launches the kernels it launched before.
+ *
+ * mcpt_set_material_textures installs a set (everything copied): uv0 / uv1 / uv2, 2 * ntri floats each,
+ * the corners' uvs in the uploaded desc's triangle order; textures[k] = {w, h, rgba8} with w * h RGBA8
+ * texels, row-major; mat_tex[m] = the texture of material m, or -1.  ntex == 0 or textures == NULL
+ * removes the set.  MCPT_E_INVALID, the installed set staying: no scene, ntri or nmat different from the
+ * uploaded scene's, a NULL array, an index outside [-1, ntex), w or h outside 1..16384, a NULL texel
+ * pointer, 2^31 texels or more in total.  A set that differs bitwise from the installed one marks the film
+ * stale and drops the temporal history as mcpt_set_material_emission does, and makes the guide buffers
+ * stale (their albedo changes); an identical set does nothing.  mcpt_scene_update_geometry* keeps the set
+ * (a rebuild re-orders the device's uv stream); a scene upload drops it.
+ * mcpt_stage_run(MCPT_STAGE_MATERIAL) applies it.
+ * mcpt_material_textures_read: the set's sizes (*ntri, *ntex, *nmat; all 0: none installed), mat_tex,
+ * texture `tex`'s size and texels (ignored when tex < 0; MCPT_E_INVALID when tex >= *ntex) and the uvs in
+ * desc order; every output may be NULL.
+ * mcpt_texture_sample_run: the lookup alone, out_rgb[3 i ..] = T(uv[2 i], uv[2 i + 1]) for n host uv
+ * pairs over a caller image; it needs neither a scene nor a film.
+ * mcpt_debug_texture_stats: device bytes the set holds, materials with a texture, and 1 / 0 for whether
+ * the textured kernels are in effect (any may be NULL). */
+typedef struct mcpt_texture {
+    int32_t w, h;
+    const uint8_t *rgba8;
+} mcpt_texture;
+int mcpt_set_material_textures(mcpt_ctx *ctx, int32_t ntri, const float *uv0, const float *uv1, const float *uv2,
+                               int32_t ntex, const mcpt_texture *textures, int32_t nmat, const int32_t *mat_tex);
+int mcpt_material_textures_read(mcpt_ctx *ctx, int32_t *ntri, int32_t *ntex, int32_t *nmat, int32_t *mat_tex,
+                                int32_t tex, int32_t *w, int32_t *h, uint8_t *rgba8, float *uv0, float *uv1,
+                                float *uv2);
+int mcpt_texture_sample_run(mcpt_ctx *ctx, int32_t w, int32_t h, const uint8_t *rgba8, uint32_t n, const float *uv,
+                            float *out_rgb);
+int mcpt_debug_texture_stats(const mcpt_ctx *ctx, uint64_t *bytes, int32_t *textured_materials, int32_t *in_effect);
 int mcpt_sync(mcpt_ctx *ctx);
 int mcpt_device_name(mcpt_ctx *ctx, char *buf, int32_t len);
 /* diagnostics: rays of the current extension (which=0) or any-hit (which=1) queue, and the
@@ -729,6 +774,24 @@ int mcpt_scene_add_mesh(mcpt_scene *s, int32_t ntri, const float *v0, const floa
  * scene desc does not carry the table. */
 int mcpt_scene_set_material_emission(mcpt_scene *s, int32_t mat, const float *rgb);
 int mcpt_scene_get_emission(const mcpt_scene *s, const float **rgb, int32_t *nmat);
+/* Base-colour textures (mcpt_set_material_textures takes what the getters return).  The glb reader keeps
+ * every primitive's TEXCOORD_0 (a float VEC2 accessor; absent: zeros) through mcpt_scene_transform and the
+ * BVH's reordering.  It does not decode the PNG / JPEG images embedded in a glb: texels arrive decoded,
+ * through mcpt_scene_set_material_texture.
+ * mcpt_scene_set_mesh_uv: the corners' uvs of material mat's triangles (one material per added mesh), 2
+ * floats per triangle in each array, in the order the mesh's triangles were added.
+ * mcpt_scene_set_material_texture: attaches a copy of the w x h RGBA8 image (row 0 = v in [0, 1 / h), no
+ * sRGB decode, alpha ignored) to material mat, replacing its previous one; rgba8 == NULL detaches.
+ * MCPT_E_INVALID: mat out of range, w or h outside 1..16384, a NULL uv array.
+ * mcpt_scene_get_textures: the textures, *ntex of them (*textures = NULL, *ntex = 0 when no material has
+ * one) and the nmat texture indices (-1: none).  mcpt_scene_get_uv: the built scene's uvs, 2 * ntri floats
+ * each, in the desc's triangle order.  The pointers are owned by the scene (valid until it changes).  The
+ * scene desc does not carry any of this. */
+int mcpt_scene_set_mesh_uv(mcpt_scene *s, int32_t mat, const float *uv0, const float *uv1, const float *uv2);
+int mcpt_scene_set_material_texture(mcpt_scene *s, int32_t mat, int32_t w, int32_t h, const uint8_t *rgba8);
+int mcpt_scene_get_textures(const mcpt_scene *s, const mcpt_texture **textures, int32_t *ntex,
+                            const int32_t **mat_tex, int32_t *nmat);
+int mcpt_scene_get_uv(const mcpt_scene *s, const float **uv0, const float **uv1, const float **uv2, int32_t *ntri);
 int mcpt_scene_set_env_hdr(mcpt_scene *s, const char *path, int32_t mode);
 /* flags MCPT_ENV_DEVICE_TABLES: keep the texture only; mcpt_scene_upload then builds the tables on
  * the device (for large maps: the host build is several serial passes over every texel). */

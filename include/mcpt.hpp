@@ -245,6 +245,32 @@ public:
         detail::check(mcpt_scene_get_emission(s_, &rgb, &nmat), nullptr, "Scene::material_emission");
         return rgb ? std::vector<float>(rgb, rgb + 3 * (size_t)nmat) : std::vector<float>();
     }
+    // MI355X extension: base-colour textures (mcpt.h).  The corner uvs of material
+    // `mat`'s triangles (2 floats per triangle in each array, in the order they were added; load keeps a
+    // glb's TEXCOORD_0), and a decoded w x h RGBA8 image attached to the material (empty: detach).
+    // PathTracer installs the scene's textures after it uploads the scene.
+    void set_mesh_uv(int32_t mat, const std::vector<float>& uv0, const std::vector<float>& uv1, const std::vector<float>& uv2) {
+        detail::check(mcpt_scene_set_mesh_uv(s_, mat, uv0.data(), uv1.data(), uv2.data()), nullptr, "Scene::set_mesh_uv");
+        notify();
+    }
+    void set_material_texture(int32_t mat, int32_t w, int32_t h, const std::vector<uint8_t>& rgba8) {
+        if (!rgba8.empty() && rgba8.size() != (size_t)w * (size_t)h * 4)
+            throw Error(MCPT_E_INVALID, "Scene::set_material_texture: w * h * 4 bytes");
+        detail::check(mcpt_scene_set_material_texture(s_, mat, w, h, rgba8.empty() ? nullptr : rgba8.data()), nullptr,
+                      "Scene::set_material_texture");
+        notify();
+    }
+    // The built scene's textures and uvs onto a context that holds its upload (nothing without a texture)
+    void install_textures(mcpt_ctx* ctx) const {
+        const mcpt_texture* tex = nullptr;
+        const int32_t* mat_tex = nullptr;
+        int32_t ntex = 0, nmat = 0, ntri = 0;
+        detail::check(mcpt_scene_get_textures(s_, &tex, &ntex, &mat_tex, &nmat), nullptr, "Scene::install_textures");
+        if (!tex || !ntex) return;
+        const float *uv0 = nullptr, *uv1 = nullptr, *uv2 = nullptr;
+        detail::check(mcpt_scene_get_uv(s_, &uv0, &uv1, &uv2, &ntri), nullptr, "Scene::install_textures");
+        detail::check(mcpt_set_material_textures(ctx, ntri, uv0, uv1, uv2, ntex, tex, nmat, mat_tex), ctx, "scene textures");
+    }
     // MI355X extension: the BASELINE config proxies of SURVEY.md 8(d) (geometry + environment).
     void make_proxy(int config_id, const std::string& asset_dir) {
         detail::check(mcpt_scene_make_proxy(s_, config_id, asset_dir.c_str()), nullptr, "Scene::make_proxy");
@@ -780,6 +806,7 @@ private:
             detail::check(mcpt_scene_upload(ctx_, &d), ctx_, "scene upload");
             const std::vector<float> em = scene.material_emission();  // the upload dropped the previous table
             if (!em.empty()) detail::check(mcpt_set_material_emission(ctx_, d.nmat, em.data()), ctx_, "scene emission");
+            scene.install_textures(ctx_);  // ... and the previous texture set (section 19)
             scene_ = &scene;
             scene_state_ = st;
             edited = true;

@@ -4,6 +4,7 @@
 // host models of occ_coords (tests/native/occ_beam.cpp, tools/occ_list_model.cpp) keep copies.
 #pragma once
 #include "device/mcpt_core.hpp"
+#include "device/texture.hpp"
 #include "kernels.hpp"
 
 namespace mcpt_dev {
@@ -27,11 +28,21 @@ constexpr int kEnd = -1;  // not a valid leaf: offset + count <= ntri < 2^24
 // Hit record of ray (o, d) on triangle tri, as dTriangle::hit builds it
 // (Triangle.cu:66-92): Moller-Trumbore t/u/v, the interpolated normal
 // normalised twice (identity transform), position o + t d, material id.
-__device__ inline void hit_record(const DevScene& sc, V3 o, V3 d, int tri, V3& pos, V3& nrm, int& mat, float& t_out) {
+// TEX (base-colour textures): also the hit's texture coordinate (tu, tv) from the
+// record's three uvs (uvs: TexView::uv), fetched with the other loads.
+template <bool TEX>
+__device__ inline void hit_record_t(const DevScene& sc, const float2* uvs, V3 o, V3 d, int tri, V3& pos, V3& nrm, int& mat,
+                                    float& t_out, float& tu, float& tv) {
     const float4* tp = sc.tri + kTriF4 * tri;
     const float4 w0 = tp[0], w1 = tp[1], w2 = tp[2];
     const float4* sp4 = sc.tri_sh + 3 * tri;
     const float4 s0 = sp4[0], s1 = sp4[1], s2 = sp4[2];
+    [[maybe_unused]] float2 c0, c1, c2;
+    if constexpr (TEX) {
+        const float2* up = uvs + 3 * (size_t)tri;
+        c0 = up[0], c1 = up[1], c2 = up[2];
+        __asm__ volatile("" ::"v"(c0.x), "v"(c0.y), "v"(c1.x), "v"(c1.y), "v"(c2.x), "v"(c2.y));
+    }
     // All six loads in one round trip: the compiler otherwise issues the vertex load after
     // the determinant test and the shading record after the whole test (three serialised
     // fetches; the hit is known to exist, so every value is used).
@@ -47,6 +58,14 @@ __device__ inline void hit_record(const DevScene& sc, V3 o, V3 d, int tri, V3& p
     pos = o + d * t;                               // :86
     mat = __float_as_int(s2.y);                    // material id bits
     t_out = t;
+    if constexpr (TEX) {
+        tu = mcpt::tex_coord(u, v, w, c0.x, c1.x, c2.x);  // Triangle.cu:79
+        tv = mcpt::tex_coord(u, v, w, c0.y, c1.y, c2.y);
+    }
+}
+__device__ inline void hit_record(const DevScene& sc, V3 o, V3 d, int tri, V3& pos, V3& nrm, int& mat, float& t_out) {
+    float tu, tv;
+    hit_record_t<false>(sc, nullptr, o, d, tri, pos, nrm, mat, t_out, tu, tv);
 }
 
 // The occluder table's key of a ray (the cache itself: kernels.hip).  Here, with the knob, because

@@ -134,6 +134,68 @@ int mcpt_scene_get_emission(const mcpt_scene* s, const float** rgb, int32_t* nma
     return MCPT_OK;
 }
 
+// ---- base-colour textures ----
+int mcpt_scene_set_mesh_uv(mcpt_scene* s, int32_t mat, const float* uv0, const float* uv1, const float* uv2) {
+    if (!s || !uv0 || !uv1 || !uv2) return fail(s, MCPT_E_INVALID, "null argument");
+    if (mat < 0 || (size_t)mat >= s->s.mat_tex.size()) return fail(s, MCPT_E_INVALID, "material id out of range");
+    const float* src[3] = {uv0, uv1, uv2};
+    size_t i = 0;  // the mesh's triangles in add order
+    for (mcpt_host::Tri& t : s->s.tris)
+        if (t.mat == mat) {
+            for (int k = 0; k < 3; k++) { t.uv[k][0] = src[k][2 * i]; t.uv[k][1] = src[k][2 * i + 1]; }
+            i++;
+        }
+    if (s->s.built) s->s.gather_uv();
+    return MCPT_OK;
+}
+
+int mcpt_scene_set_material_texture(mcpt_scene* s, int32_t mat, int32_t w, int32_t h, const uint8_t* rgba8) {
+    if (!s) return fail(s, MCPT_E_INVALID, "null scene");
+    if (mat < 0 || (size_t)mat >= s->s.mat_tex.size()) return fail(s, MCPT_E_INVALID, "material id out of range");
+    if (!rgba8) {  // detach (the texture itself stays in the list: the other indices keep their meaning)
+        s->s.mat_tex[mat] = -1;
+        return MCPT_OK;
+    }
+    if (w < 1 || w > 16384 || h < 1 || h > 16384) return fail(s, MCPT_E_INVALID, "texture width and height must be 1..16384");
+    mcpt_host::Texture t;
+    t.w = w;
+    t.h = h;
+    t.rgba8.assign(rgba8, rgba8 + (size_t)w * h * 4);
+    int32_t& k = s->s.mat_tex[mat];
+    if (k >= 0) {
+        s->s.textures[k] = std::move(t);  // the material's own texture is replaced
+    } else {
+        k = (int32_t)s->s.textures.size();
+        s->s.textures.push_back(std::move(t));
+    }
+    return MCPT_OK;
+}
+
+int mcpt_scene_get_textures(const mcpt_scene* s, const mcpt_texture** textures, int32_t* ntex, const int32_t** mat_tex,
+                            int32_t* nmat) {
+    if (!s || !textures || !ntex || !mat_tex || !nmat) return MCPT_E_INVALID;
+    const mcpt_host::Scene& sc = s->s;
+    bool any = false;
+    for (int32_t k : sc.mat_tex) any = any || k >= 0;
+    sc.tex_views.clear();
+    for (const mcpt_host::Texture& t : sc.textures) sc.tex_views.push_back(mcpt_texture{t.w, t.h, t.rgba8.data()});
+    *nmat = (int32_t)sc.mat_tex.size();
+    *mat_tex = sc.mat_tex.data();
+    *ntex = any ? (int32_t)sc.tex_views.size() : 0;
+    *textures = any ? sc.tex_views.data() : nullptr;
+    return MCPT_OK;
+}
+
+int mcpt_scene_get_uv(const mcpt_scene* s, const float** uv0, const float** uv1, const float** uv2, int32_t* ntri) {
+    if (!s || !uv0 || !uv1 || !uv2 || !ntri) return MCPT_E_INVALID;
+    if (!s->s.built) return fail(const_cast<mcpt_scene*>(s), MCPT_E_INVALID, "scene not built");
+    *ntri = (int32_t)s->s.f_id.size();
+    *uv0 = s->s.f_uv0.data();
+    *uv1 = s->s.f_uv1.data();
+    *uv2 = s->s.f_uv2.data();
+    return MCPT_OK;
+}
+
 int mcpt_scene_bvh_depth(const mcpt_scene* s) { return s ? s->s.bvh_depth : MCPT_E_INVALID; }
 
 int mcpt_camera_make(const mcpt_camera_params* p, mcpt_camera* out) {

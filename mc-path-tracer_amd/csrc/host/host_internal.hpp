@@ -14,6 +14,13 @@ struct Tri {
     mcpt::V3 p[3];
     mcpt::V3 n[3];
     int mat;
+    float uv[3][2] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};  // TEXCOORD_0 of the corners (absent: zeros)
+};
+
+// A base-colour texture attached to a material: decoded RGBA8 texels, row 0 first
+struct Texture {
+    int w = 0, h = 0;
+    std::vector<uint8_t> rgba8;
 };
 
 struct Scene {
@@ -22,6 +29,11 @@ struct Scene {
     std::vector<float> materials;   // 8 floats per material (dMaterial.cuh:11-33)
     std::vector<float> emission;    // 3 floats per material: emitted radiance (dMaterial.cuh:14-24, emissive_L)
     std::vector<float> dir_lights;  // 7 floats per light (DirectionalLight.h)
+    // base-colour textures (dMaterial.cu:14-26 base_color_texture): the attached textures and, per
+    // material, its texture's index or -1; tex_views: what mcpt_scene_get_textures hands out
+    std::vector<Texture> textures;
+    std::vector<int32_t> mat_tex;
+    mutable std::vector<mcpt_texture> tex_views;
     // environment light (EnvironmentLight.h:17-40); default Color 0.8 (Scene.cu:21)
     int env_mode = 0;
     float env_color[3] = {0.8f, 0.8f, 0.8f};
@@ -35,13 +47,16 @@ struct Scene {
     std::vector<float> f_v0, f_v1, f_v2, f_n0, f_n1, f_n2;
     std::vector<int32_t> f_mat;
     std::vector<int32_t> f_id;  // original triangle index of each BVH-ordered slot
+    std::vector<float> f_uv0, f_uv1, f_uv2;  // the corners' uvs, 2 floats per BVH-ordered slot (not in the desc)
     std::vector<float> node_bmin, node_bmax;
     std::vector<int32_t> node_offset, node_nprims, node_axis;
     std::string err;
 
     void add_mesh(const std::vector<mcpt::V3>& pos, const std::vector<mcpt::V3>& nrm,
-                  const std::vector<uint32_t>& idx, mcpt::V3 base, mcpt::V3 emit = mcpt::v3(0.f, 0.f, 0.f));
+                  const std::vector<uint32_t>& idx, mcpt::V3 base, mcpt::V3 emit = mcpt::v3(0.f, 0.f, 0.f),
+                  const std::vector<float>* uv = nullptr);  // uv: 2 floats per vertex, or none (zeros)
     bool has_emission() const;  // some material emits
+    void gather_uv();           // f_uv0..2 from tris by f_id (build, and a uv change on a built scene)
     void transform(const float* xf16);
     int load_glb(const char* path, const float* xf16, std::string& err);
     int set_env_hdr(const char* path, int mode, std::string& err, bool host_tables = true);

@@ -139,6 +139,14 @@ static void subdivide_all(Scene& s, int levels) {
             b.p[0] = mp[0]; b.p[1] = t.p[1]; b.p[2] = mp[1]; b.n[0] = mn[0]; b.n[1] = t.n[1]; b.n[2] = mn[1];
             c.p[0] = mp[2]; c.p[1] = mp[1]; c.p[2] = t.p[2]; c.n[0] = mn[2]; c.n[1] = mn[1]; c.n[2] = t.n[2];
             d.p[0] = mp[0]; d.p[1] = mp[1]; d.p[2] = mp[2]; d.n[0] = mn[0]; d.n[1] = mn[1]; d.n[2] = mn[2];
+            for (int j = 0; j < 2; j++) {  // the corners' uvs follow their positions
+                float mu[3];
+                for (int k = 0; k < 3; k++) mu[k] = (t.uv[k][j] + t.uv[(k + 1) % 3][j]) * 0.5f;
+                a.uv[1][j] = mu[0]; a.uv[2][j] = mu[2];
+                b.uv[0][j] = mu[0]; b.uv[2][j] = mu[1];
+                c.uv[0][j] = mu[2]; c.uv[1][j] = mu[1];
+                d.uv[0][j] = mu[0]; d.uv[1][j] = mu[1]; d.uv[2][j] = mu[2];
+            }
             out.push_back(a); out.push_back(b); out.push_back(c); out.push_back(d);
         }
         s.tris.swap(out);

@@ -199,15 +199,18 @@ static M4 trs_matrix(const float* t, const float* q, const float* s) {  // glTF 
 // Scene
 // ---------------------------------------------------------------------------
 void Scene::add_mesh(const std::vector<V3>& pos, const std::vector<V3>& nrm, const std::vector<uint32_t>& idx,
-                     V3 base, V3 emit) {
+                     V3 base, V3 emit, const std::vector<float>* uv) {
     int mat_id = (int)(materials.size() / 8);
     float mp[8] = {base.x, base.y, base.z, 0.04f, 0.04f, 0.04f, 1.f, 0.f};  // dMaterial.cuh:13-18, Scene.cu:306-307
     materials.insert(materials.end(), mp, mp + 8);
     const float em[3] = {emit.x, emit.y, emit.z};
     emission.insert(emission.end(), em, em + 3);
+    mat_tex.push_back(-1);
     for (size_t i = 0; i + 2 < idx.size(); i += 3) {
         Tri t;
         for (int k = 0; k < 3; k++) { t.p[k] = pos[idx[i + k]]; t.n[k] = nrm[idx[i + k]]; }
+        if (uv)
+            for (int k = 0; k < 3; k++) { t.uv[k][0] = (*uv)[2 * idx[i + k]]; t.uv[k][1] = (*uv)[2 * idx[i + k] + 1]; }
         t.mat = mat_id;
         tris.push_back(t);
     }
@@ -380,7 +383,12 @@ int Scene::load_glb(const char* path, const float* xf16, std::string& err) {
                             em = mcpt::v3((float)ef->arr[0].num * strength, (float)ef->arr[1].num * strength,
                                           (float)ef->arr[2].num * strength);
                     }
-                    add_mesh(pos, nrm, idx, bc, em);
+                    // TEXCOORD_0 (a float VEC2 accessor; Mesh.cu's texcoord): kept per corner for the
+                    // base-colour texture lookup, zeros where the primitive has none
+                    std::vector<float> uv;
+                    bool has_uv = attrs->get("TEXCOORD_0") && read_accessor((int)attrs->numv("TEXCOORD_0", -1), uv, dummy, nc) &&
+                                  nc == 2 && uv.size() == 2 * nv;
+                    add_mesh(pos, nrm, idx, bc, em, has_uv ? &uv : nullptr);
                 }
             }
         }
@@ -937,8 +945,19 @@ int Scene::build(const mcpt_bvh_params& prm, std::string& err) {
         for (int k = 0; k < 6; k++) { dst[k][0] = src[k].x; dst[k][1] = src[k].y; dst[k][2] = src[k].z; }
         f_mat[i] = t.mat;
     }
+    gather_uv();
     built = true;
     return MCPT_OK;
+}
+
+void Scene::gather_uv() {
+    const size_t N = f_id.size();
+    f_uv0.resize(2 * N); f_uv1.resize(2 * N); f_uv2.resize(2 * N);
+    float* dst[3] = {f_uv0.data(), f_uv1.data(), f_uv2.data()};
+    for (size_t i = 0; i < N; i++) {
+        const Tri& t = tris[(size_t)f_id[i]];
+        for (int k = 0; k < 3; k++) { dst[k][2 * i] = t.uv[k][0]; dst[k][2 * i + 1] = t.uv[k][1]; }
+    }
 }
 
 void Scene::desc(mcpt_scene_desc* d) const {

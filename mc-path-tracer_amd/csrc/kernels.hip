@@ -502,6 +502,7 @@ struct MatOut {
     int matid, light_id;
     uint32_t flags;  // the flags word (F_CONDB added by material_brdf_terms)
     float rrz;       // nee1.w
+    V3 base;         // TEX: the hit's shaded base colour, for material_brdf_terms (never set otherwise)
 };
 
 // Light choice + wf_mat_mix for the continuing path pid of pixel `pix` (vertex len, sample
@@ -517,7 +518,11 @@ struct MatOut {
 // MIS (with SAMP): the emitter sample carries its power-heuristic weight against
 // the BRDF's pdf of its direction, and nee2.w stores the continuation direction's pdf for the
 // collection weight of the next logic pass.
-template <bool FIXED, bool SAMP = false, bool MIS = false>
+// TEX (base-colour textures installed): the material's base colour is its factor
+// times the texture lookup at the hit's texture coordinate (device/texture.hpp); everything after reads
+// that Mat, so f and pdf of all three parts, the emitter sample's and MIS's BRDF pdf follow.  Draws, rays
+// and counts do not depend on it.
+template <bool FIXED, bool SAMP = false, bool MIS = false, bool TEX = false>
 __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix, uint32_t sidx, uint32_t len,
                                  V3 beta_store, int32_t htri, float4* stage, bool occ_on, bool no_cont, bool& want_e) {
     const DevScene& sc = a.scene;
@@ -532,9 +537,17 @@ __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix
     V3 pos, n;
     int mat;
     float t_hit;
-    hit_record(sc, ro, rdir, htri, pos, n, mat, t_hit);
+    [[maybe_unused]] float tu, tv;
+    if constexpr (TEX) hit_record_t<true>(sc, a.tex.uv, ro, rdir, htri, pos, n, mat, t_hit, tu, tv);
+    else hit_record(sc, ro, rdir, htri, pos, n, mat, t_hit);
     const V3 wo = -rdir;
-    const Mat m = load_mat(sc.mats + 8 * mat);
+    Mat m_ld = load_mat(sc.mats + 8 * mat);
+    if constexpr (TEX) {
+        MCPT_MARK("m_tex");
+        m_ld.base = mcpt::tex_base(a.tex, mat, m_ld.base, tu, tv);
+        mo.base = m_ld.base;
+    }
+    const Mat m = m_ld;
     // The three parts of wf_mat_mix draw from disjoint RNG slots and share only the hit
     // record, so they are evaluated in the order that lets each store its results at
     // once (short register live ranges): the continuation first (:353-358, its ratio
@@ -718,13 +731,17 @@ __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix
 // The BRDF sample's light terms (wavefront_kernels.cu:331-343) and the path's last two words:
 // nee1 = (cB, f_s / pdf_s .z) and the flags word (F_CONDB).  cB is evaluated only for a
 // visibility ray that may be unoccluded (need_cb): one the occluder cache resolved is never read.
-template <bool FIXED>
+// TEX: with the base colour material() shaded with (MatOut::base: three registers across the occluder
+// cache instead of a second lookup's four gathers).
+template <bool FIXED, bool TEX = false>
 __device__ inline void material_brdf_terms(const ShadeArgs& a, uint32_t pid, const MatOut& mo) {
     const DevScene& sc = a.scene;
     V3 cB = v3(0.f, 0.f, 0.f);
     uint32_t nf = mo.flags;
     if (mo.need_cb) {
-        const Mat m = load_mat(sc.mats + 8 * mo.matid);
+        Mat m_ld = load_mat(sc.mats + 8 * mo.matid);
+        if constexpr (TEX) m_ld.base = mo.base;
+        const Mat m = m_ld;
         V3 f_b;
         float pdfb_x;
         brdf_f_pdf(m, mo.n, mo.wi_b, mo.wo, f_b, pdfb_x);
@@ -1207,7 +1224,8 @@ __global__ __launch_bounds__(kBlock) MCPT_SHADE_ATTR void k_shade(ShadeArgs a) {
 // active: a third staged ray (six LDS slabs, 24 KiB per block: 96 KiB per CU at 4 waves per SIMD, of 160)
 // pushed onto the any-hit queue with the result index 2P + path.
 // MIS (with SAMP): the weighted emitter sample and pdf_s in nee2.w (material()).
-template <bool FIXED, bool SAMP = false, bool MIS = false>
+// TEX: the textured instantiations, launched only while a texture set is in effect.
+template <bool FIXED, bool SAMP = false, bool MIS = false, bool TEX = false>
 __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_kernarg) {
     (void)a_kernarg;  // read through kernarg_fresh (the same bytes: it is the kernel's only argument)
     const ShadeArgs& a = kernarg_fresh<ShadeArgs>();
@@ -1237,7 +1255,7 @@ __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_k
             const uint4 q = ld_s(a.mat_rec + shard * a.ext_cap + i);  // {pid, pixel, sample index | len << 24, hit_tri}
             const float4 b4 = ld_s(a.mat_beta + shard * a.ext_cap + i);
             mpid = q.x;
-            mo = material<FIXED, SAMP, MIS>(a, mpid, q.y, q.z & (kRecNoCont - 1u), q.z >> kRecLenShift, xyz(b4), (int32_t)q.w,
+            mo = material<FIXED, SAMP, MIS, TEX>(a, mpid, q.y, q.z & (kRecNoCont - 1u), q.z >> kRecLenShift, xyz(b4), (int32_t)q.w,
                                             &s_any[0][0], occ_on, (q.z & kRecNoCont) != 0u, want_e);
             // the occluder cache (see occ_hit1), before the BRDF sample's light terms: a ray it
             // resolves gets its wf_shadow result here and is not queued
@@ -1287,7 +1305,7 @@ __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_k
                 }
             }
             MCPT_MARK("m_bterms");
-            material_brdf_terms<FIXED>(a, mpid, mo);
+            material_brdf_terms<FIXED, TEX>(a, mpid, mo);
         }
         MCPT_MARK("m_push");
         uint32_t slot[SAMP ? 4 : 3], total[SAMP ? 4 : 3];
@@ -2338,6 +2356,18 @@ static uint32_t shade_grid(uint32_t nblocks, const LaunchGeom& g) {
     uint32_t G = g.shade_grid ? std::min(nblocks, g.shade_grid) : nblocks;
     return std::max(G, (nblocks + kBlock - 1) / kBlock);
 }
+// k_material for a launch: the textured instantiation while a texture set is in effect (a.tex.uv set;
+// DESIGN.md section 19), on its twin's grid; every other context launches what it launched before.
+template <bool SAMP, bool MIS>
+static void launch_material(const ShadeArgs& a, const uint32_t* blocks, bool fixed_mode, hipStream_t s) {
+    if (a.tex.uv) {
+        if (fixed_mode) hipLaunchKernelGGL((k_material<true, SAMP, MIS, true>), dim3(blocks[1]), dim3(kBlock), 0, s, a);
+        else hipLaunchKernelGGL((k_material<false, SAMP, MIS, true>), dim3(blocks[0]), dim3(kBlock), 0, s, a);
+    } else {
+        if (fixed_mode) hipLaunchKernelGGL((k_material<true, SAMP, MIS>), dim3(blocks[1]), dim3(kBlock), 0, s, a);
+        else hipLaunchKernelGGL((k_material<false, SAMP, MIS>), dim3(blocks[0]), dim3(kBlock), 0, s, a);
+    }
+}
 void launch_shade(const ShadeArgs& args, int nblocks, const LaunchGeom& g, bool fixed_mode, hipStream_t s) {
     ShadeArgs a = args;
     a.shade_vblocks = (uint32_t)nblocks;
@@ -2350,24 +2380,22 @@ void launch_shade(const ShadeArgs& args, int nblocks, const LaunchGeom& g, bool 
         if (fixed_mode) {
             if (a.budget) hipLaunchKernelGGL((k_shade<true, true, true, true, true>), dim3(G), dim3(kBlock), 0, s, a);
             else hipLaunchKernelGGL((k_shade<true, false, true, true, true>), dim3(G), dim3(kBlock), 0, s, a);
-            hipLaunchKernelGGL((k_material<true, true, true>), dim3(g.mat_blocks_samp[1]), dim3(kBlock), 0, s, a);
         } else {
             if (a.budget) hipLaunchKernelGGL((k_shade<false, true, true, true, true>), dim3(G), dim3(kBlock), 0, s, a);
             else hipLaunchKernelGGL((k_shade<false, false, true, true, true>), dim3(G), dim3(kBlock), 0, s, a);
-            hipLaunchKernelGGL((k_material<false, true, true>), dim3(g.mat_blocks_samp[0]), dim3(kBlock), 0, s, a);
         }
+        launch_material<true, true>(a, g.mat_blocks_samp, fixed_mode, s);
         return;
     }
     if (a.nee2 && a.emis) {
         if (fixed_mode) {
             if (a.budget) hipLaunchKernelGGL((k_shade<true, true, true, true>), dim3(G), dim3(kBlock), 0, s, a);
             else hipLaunchKernelGGL((k_shade<true, false, true, true>), dim3(G), dim3(kBlock), 0, s, a);
-            hipLaunchKernelGGL((k_material<true, true>), dim3(g.mat_blocks_samp[1]), dim3(kBlock), 0, s, a);
         } else {
             if (a.budget) hipLaunchKernelGGL((k_shade<false, true, true, true>), dim3(G), dim3(kBlock), 0, s, a);
             else hipLaunchKernelGGL((k_shade<false, false, true, true>), dim3(G), dim3(kBlock), 0, s, a);
-            hipLaunchKernelGGL((k_material<false, true>), dim3(g.mat_blocks_samp[0]), dim3(kBlock), 0, s, a);
         }
+        launch_material<true, false>(a, g.mat_blocks_samp, fixed_mode, s);
         return;
     }
     if (fixed_mode) {
@@ -2376,15 +2404,14 @@ void launch_shade(const ShadeArgs& args, int nblocks, const LaunchGeom& g, bool 
             else hipLaunchKernelGGL((k_shade<true, false, true>), dim3(G), dim3(kBlock), 0, s, a);
         } else if (a.budget) hipLaunchKernelGGL((k_shade<true, true, false>), dim3(G), dim3(kBlock), 0, s, a);
         else hipLaunchKernelGGL((k_shade<true, false, false>), dim3(G), dim3(kBlock), 0, s, a);
-        hipLaunchKernelGGL(k_material<true>, dim3(g.mat_blocks[1]), dim3(kBlock), 0, s, a);
     } else {
         if (a.emis) {
             if (a.budget) hipLaunchKernelGGL((k_shade<false, true, true>), dim3(G), dim3(kBlock), 0, s, a);
             else hipLaunchKernelGGL((k_shade<false, false, true>), dim3(G), dim3(kBlock), 0, s, a);
         } else if (a.budget) hipLaunchKernelGGL((k_shade<false, true, false>), dim3(G), dim3(kBlock), 0, s, a);
         else hipLaunchKernelGGL((k_shade<false, false, false>), dim3(G), dim3(kBlock), 0, s, a);
-        hipLaunchKernelGGL(k_material<false>, dim3(g.mat_blocks[0]), dim3(kBlock), 0, s, a);
     }
+    launch_material<false, false>(a, g.mat_blocks, fixed_mode, s);
 }
 // One of the two shading kernels alone (mcpt_stage_run's LOGIC / GENERATE and MATERIAL stages).
 void launch_shade_stage(bool material_stage, const ShadeArgs& args, int nblocks, const LaunchGeom& g, bool fixed_mode,
@@ -2399,8 +2426,7 @@ void launch_shade_stage(bool material_stage, const ShadeArgs& args, int nblocks,
         } else if (fixed_mode) hipLaunchKernelGGL((k_shade<true, false, false>), dim3(G), dim3(kBlock), 0, s, a);
         else hipLaunchKernelGGL((k_shade<false, false, false>), dim3(G), dim3(kBlock), 0, s, a);
     } else {
-        if (fixed_mode) hipLaunchKernelGGL(k_material<true>, dim3(g.mat_blocks[1]), dim3(kBlock), 0, s, a);
-        else hipLaunchKernelGGL(k_material<false>, dim3(g.mat_blocks[0]), dim3(kBlock), 0, s, a);
+        launch_material<false, false>(a, g.mat_blocks, fixed_mode, s);
     }
 }
 // Persistent grid: the device's resident waves rounded to a multiple of the shard count.

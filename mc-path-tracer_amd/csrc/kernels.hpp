@@ -32,6 +32,7 @@
 #include "device/mcpt_core.hpp"
 #include "device/occ_beam.hpp"
 #include "device/temporal.hpp"
+#include "device/texture.hpp"
 #include "device/variance.hpp"
 
 namespace mcpt_dev {
@@ -289,6 +290,10 @@ struct ShadeArgs {
     // runs the MIS instantiations; the others never look at this field.  pick_rec[r]: the emitter
     // table's pick probability of triangle record r, 0 for a record that is no entry.
     const float* pick_rec;
+    // Base-colour textures (mcpt_set_material_textures), set only while a set with
+    // a textured material is installed (tex.uv != nullptr): launch_shade then runs k_material's textured
+    // instantiations; the others never look at this field, and k_shade has none.
+    mcpt::TexView tex;
 };
 // k_primary_build: the table of a W x H film.  stats: [0] pixels with a list, [1] overflow pixels.
 struct PrimaryBuildArgs {
@@ -523,6 +528,24 @@ void launch_denoise_pass(const DenoiseGuidedArgs& a, int lds_max_stride, hipStre
 void launch_denoise_prep(const DenoiseGuidedPrepArgs& a, hipStream_t s);
 void launch_guide_rays(const GuideArgs& a, hipStream_t s);
 void launch_guide_accum(const GuideArgs& a, hipStream_t s);
+
+// ---- base-colour textures (texture.hip) ----
+// k_guide_accum_tex: k_guide_accum while textures are installed.  It rebuilds the chunk's hit records
+// itself (rays a.ro / a.rd, triangle record rec[i] or -1: k_hit_record's arithmetic) and adds
+// tex_base at the hit's texture coordinate as the albedo; normal, depth and count as k_guide_accum.
+struct GuideTexArgs {
+    GuideArgs g;
+    DevScene scene;
+    mcpt::TexView tex;
+    const int32_t* rec;
+};
+void launch_guide_accum_tex(const GuideTexArgs& a, hipStream_t s);
+// k_tex_sample: out[i] = tex_bilinear_rgba8(tex, w, h, uv[i]) for n uv pairs (mcpt_texture_sample_run)
+void launch_tex_sample(const uint32_t* tex, int w, int h, const float2* uv, float* out_rgb, uint32_t n, hipStream_t s);
+// k_tex_uv_records: the uv stream in record order: out[3 p + k] = uv_k[order[p]] (order == nullptr: p),
+// uv0 / uv1 / uv2 in desc order
+void launch_tex_uv_records(const float2* uv0, const float2* uv1, const float2* uv2, const uint32_t* order, float2* out,
+                           uint32_t ntri, hipStream_t s);
 
 // ---- adaptive sampling (adaptive.hip) ----
 // Which accumulator holds a film pixel.  own == nullptr: every pixel is the caller's and pixel o's

@@ -333,6 +333,7 @@ int mcpt_guides_render(mcpt_ctx* c, uint32_t nsamples) {
     ga.mats = c->scene.dev.mats;
     ga.g_alb = g.alb;
     ga.g_nz = g.nz;
+    const mcpt::TexView tex = c->tx.view();
     if ((rc = span_begin(c))) return rc;
     HIPCHK(c, hipMemsetAsync(g.alb, 0, P * sizeof(float4), c->stream));
     HIPCHK(c, hipMemsetAsync(g.nz, 0, P * sizeof(float4), c->stream));
@@ -361,9 +362,13 @@ int mcpt_guides_render(mcpt_ctx* c, uint32_t nsamples) {
             launch_trace(ta, c->geom, c->stream);
             HIPCHK(c, hipMemcpyAsync(&c->cnt.host->grab[0][0], &c->cnt.dev->grab[0][0], sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipMemsetAsync(c->cnt.dev->grab, 0, sizeof(c->cnt.dev->grab), c->stream));  // hand-out counters back to 0
-            HitRecordArgs ha{c->scene.dev, ro, rd, ht, hp, hn, ht, n};
-            launch_hit_record(ha, c->stream);
-            launch_guide_accum(ga, c->stream);
+            if (tex.uv) {  // textures in effect (section 19): the albedo is the shaded base colour at the hit
+                launch_guide_accum_tex(GuideTexArgs{ga, c->scene.dev, tex, ht}, c->stream);
+            } else {
+                HitRecordArgs ha{c->scene.dev, ro, rd, ht, hp, hn, ht, n};
+                launch_hit_record(ha, c->stream);
+                launch_guide_accum(ga, c->stream);
+            }
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipStreamSynchronize(c->stream));  // the next chunk reuses the buffers (and the staging word)
             if (c->cnt.host->grab[0][0] < n) drained = false;

@@ -502,6 +502,10 @@ static int enqueue_iteration(mcpt_ctx* c, size_t evbase, bool timing, const int2
         return set_err(c, MCPT_E_INVALID, "emitter MIS: no pick table for the current emitter table");
     sa.pick_rec = samp && c->es.mis ? c->es.pick_rec.get() : nullptr;
     if (samp) sa.p.vis = c->es.vis;  // 3P bytes: the emitter rays' results behind the two of every path
+    // base-colour textures (section 19): only a set with a textured material, in the current record order
+    if (c->tx.textured > 0 && !c->tx.dev_ok)
+        return set_err(c, MCPT_E_INVALID, "textures: no uv stream for the current record order");
+    sa.tex = c->tx.view();
     if (int rc = cam_table(c, c->W, c->H, &sa.cam_px, &sa.cam_dir)) return rc;
     prim_table(c, sa);
     const int bpt = (int)f.L.blocks_per_tile;

@@ -226,6 +226,37 @@ struct Emission {
     }
 };
 
+// Base-colour textures (mcpt_set_material_textures): the installed set on the host
+// (uvs in desc order, 2 floats per triangle and corner; the textures' sizes, first texels and the atlas;
+// the per-material index) and on the device: the uv stream in record order, the atlas and the per-material
+// {first texel, w, h, index}.  Only a set with a textured material reaches the kernels (view()): without,
+// the context launches what it launched before.  The uv stream follows the record order, so a rebuild
+// permutes it again (textures_reorder); a scene upload drops the set.
+struct Textures {
+    std::vector<float> uv[3];
+    std::vector<int32_t> tw, th, mat_tex;
+    std::vector<uint32_t> first;  // texture k's first texel in the atlas
+    std::vector<uint32_t> atlas;
+    DevBuf<float2> d_uv, d_stage;  // [3 ntri] record order; [3 ntri] desc order, the permutation's input
+    DevBuf<uint32_t> d_atlas;
+    DevBuf<int4> d_mat;
+    int32_t textured = 0;  // materials with a texture
+    bool dev_ok = false;   // the device arrays stand for the current record order
+    bool installed() const { return !mat_tex.empty(); }
+    mcpt::TexView view() const {
+        if (!(textured > 0 && dev_ok)) return mcpt::TexView{nullptr, nullptr, nullptr};
+        return mcpt::TexView{d_uv.get(), d_atlas.get(), d_mat.get()};
+    }
+    size_t bytes() const { return installed() ? d_uv.bytes() + d_stage.bytes() + d_atlas.bytes() + d_mat.bytes() : 0; }
+    void drop() {
+        for (auto& u : uv) u.clear();
+        tw.clear(), th.clear(), mat_tex.clear(), first.clear(), atlas.clear();
+        d_uv.reset(), d_stage.reset(), d_atlas.reset(), d_mat.reset();
+        textured = 0;
+        dev_ok = false;
+    }
+};
+
 // Emitter sampling (mcpt_set_emitter_sampling): the switch, the emitter table
 // of the uploaded scene under the installed emission (host copy and device arrays) and the two per-path
 // streams the sampling instantiations use.  Active = switched on and a non-empty table; only then do the
@@ -489,6 +520,7 @@ struct mcpt_ctx {
     SceneState scene;
     Emission em;
     EmitterSampling es;
+    Textures tx;
     bool has_scene_before = false;  // set at the start of a re-upload
     // traversal work counters (mcpt_set_work_counters): k_trace's counting instantiation, whose six
     // per-lane counters cost the fast one its spill-free registers -- off by default
@@ -540,7 +572,7 @@ struct mcpt_ctx {
         scene.reset();
         free_list(tmp_bufs);
         tiles = TileSet{}, queues = RayQueues{}, film = FilmState{}, cnt = Counters{};
-        cam_tab = CamTable{}, prim.release(), em = Emission{}, es = EmitterSampling{};
+        cam_tab = CamTable{}, prim.release(), em = Emission{}, es = EmitterSampling{}, tx.drop();
         guides = Guides{}, dn = Denoise{}, ad = Adaptive{}, tp = Temporal{};
     }
 };
@@ -601,6 +633,9 @@ int check_ready(mcpt_ctx* c);
 // temporal history.
 int emitter_table_refresh(mcpt_ctx* c);
 int cam_table(mcpt_ctx* c, uint32_t W, uint32_t H, const float4** px, const float4** dir);
+// Defined in scene_upload.cpp: the installed texture set's uv stream again in the scene's current record
+// order (nothing without a set); MCPT_GEOM_REBUILD calls it after the new tree is adopted.
+int textures_reorder(mcpt_ctx* c);
 // Defined in film_state.cpp
 // The tile set t: queues sized for it (RayQueues::ensure), the tiles uploaded.  The film state stays.
 int set_tiles_internal(mcpt_ctx* c, const std::vector<int2>& t);

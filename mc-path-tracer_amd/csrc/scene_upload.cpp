@@ -473,6 +473,7 @@ static int scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d, bool gpu_bvh) {
     c->em.drop();  // the emission table belongs to the scene that goes
     c->es.drop_table();  // ... and the emitter table with it (the switch stays; section 17)
     c->es.drop_streams();
+    c->tx.drop();  // ... and the texture set: its uvs are the old scene's triangles' (section 19)
     read_upload_env(sc.knobs);
     sc.gpu_upload = gpu_bvh;
     sc.ntri = d->ntri;
@@ -565,6 +566,7 @@ static int geometry_rebuild(mcpt_ctx* c, DevScene& s, int32_t ntri, const float*
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     // the old tree goes
+    c->tx.dev_ok = false;  // (the uv stream belongs to the old record order: textures_reorder, after the commit)
     g.release(g.bvh_nodes), g.release(s.tri), g.release(s.tri_sh), g.release(g.order), g.release(g.quads), g.release(g.quad_src);
     g.nquads = 0;
     g.pair_nodes = nullptr;
@@ -605,10 +607,161 @@ static int geometry_update_device(mcpt_ctx* c, int32_t ntri, const float* v0, co
     HIPCHK(c, hipEventElapsedTime(&ms[2], ev(c, EV_UPD_TREE), ev(c, EV_UPD_QUAD)));
     HIPCHK(c, hipEventElapsedTime(&ms[6], ev(c, EV_UPD_START), ev(c, EV_UPD_END)));
     scene_commit(c, s, true);
+    // a rebuild re-sorted the records: the textures' uv stream follows (section 19; a refit keeps the order)
+    if (mode == MCPT_GEOM_REBUILD && (rc = textures_reorder(c))) return rc;
     return emitter_table_refresh(c);  // areas and positions moved (emitter sampling, section 17)
 }
 
+// ---- base-colour textures ----
+// The uv stream of t in the scene's record order: the desc-order uvs staged on the device, permuted by
+// the upload's order array (a device-built tree stores its records in Morton order; nullptr: identity).
+static int textures_uv_stream(mcpt_ctx* c, Textures& t) {
+    const size_t n = (size_t)c->scene.ntri;
+    t.dev_ok = false;
+    if (!t.installed()) return MCPT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // no launch in flight reads the old stream
+    if (!t.d_uv.ensure(3 * n) || !t.d_stage.ensure(3 * n)) {
+        (void)hipGetLastError();
+        return set_err(c, MCPT_E_NOMEM, "hipMalloc: texture uv stream");
+    }
+    for (int k = 0; k < 3 && n; k++)
+        HIPCHK(c, hipMemcpy(t.d_stage.get() + k * n, t.uv[k].data(), n * sizeof(float2), hipMemcpyHostToDevice));
+    launch_tex_uv_records(t.d_stage.get(), t.d_stage.get() + n, t.d_stage.get() + 2 * n, c->scene.order, t.d_uv, (uint32_t)n,
+                          c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    t.dev_ok = true;
+    return MCPT_OK;
+}
+int textures_reorder(mcpt_ctx* c) { return textures_uv_stream(c, c->tx); }
+
+static int textures_install(mcpt_ctx* c, int32_t ntri, const float* uv0, const float* uv1, const float* uv2, int32_t ntex,
+                            const mcpt_texture* tex, int32_t nmat, const int32_t* mat_tex) {
+    if (!c) return MCPT_E_INVALID;
+    if (!c->scene.ok) return set_err(c, MCPT_E_INVALID, "no scene uploaded");
+    auto changed = [c] {  // what a changed set means to the film, the history and the guides
+        c->film_stale = true;
+        c->tp.ok = false;
+        c->guides.ok = false;
+    };
+    if (ntex == 0 || !tex) {  // removal
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        const bool was = c->tx.textured > 0;
+        c->tx.drop();
+        if (was) changed();
+        return MCPT_OK;
+    }
+    if (ntri != c->scene.ntri) return set_err(c, MCPT_E_INVALID, "textures: ntri differs from the uploaded scene's");
+    if (nmat != c->scene.nmat) return set_err(c, MCPT_E_INVALID, "textures: nmat differs from the uploaded scene's");
+    if (ntex < 0 || !mat_tex || (ntri > 0 && (!uv0 || !uv1 || !uv2))) return set_err(c, MCPT_E_INVALID, "textures: null array");
+    uint64_t total = 0;
+    for (int32_t k = 0; k < ntex; k++) {
+        if (tex[k].w < 1 || tex[k].w > 16384 || tex[k].h < 1 || tex[k].h > 16384)
+            return set_err(c, MCPT_E_INVALID, "textures: width and height must be 1..16384");
+        if (!tex[k].rgba8) return set_err(c, MCPT_E_INVALID, "textures: null texel pointer");
+        total += (uint64_t)tex[k].w * (uint64_t)tex[k].h;
+        if (total >= (1ull << 31)) return set_err(c, MCPT_E_INVALID, "textures: 2^31 texels or more in total");
+    }
+    for (int32_t m = 0; m < nmat; m++)
+        if (mat_tex[m] < -1 || mat_tex[m] >= ntex) return set_err(c, MCPT_E_INVALID, "textures: material texture index out of range");
+    Textures now;
+    const float* src[3] = {uv0, uv1, uv2};
+    for (int k = 0; k < 3; k++) now.uv[k].assign(src[k], src[k] + 2 * (size_t)ntri);
+    now.mat_tex.assign(mat_tex, mat_tex + nmat);
+    now.atlas.resize((size_t)total);
+    uint32_t at = 0;
+    for (int32_t k = 0; k < ntex; k++) {
+        const size_t px = (size_t)tex[k].w * (size_t)tex[k].h;
+        now.tw.push_back(tex[k].w), now.th.push_back(tex[k].h), now.first.push_back(at);
+        memcpy(now.atlas.data() + at, tex[k].rgba8, px * 4);
+        at += (uint32_t)px;
+    }
+    std::vector<int4> dm((size_t)nmat);
+    for (int32_t m = 0; m < nmat; m++) {
+        const int32_t k = mat_tex[m];
+        dm[m] = k < 0 ? make_int4(0, 0, 0, -1) : make_int4((int)now.first[k], now.tw[k], now.th[k], k);
+        now.textured += k >= 0;
+    }
+    const Textures& was = c->tx;
+    auto same_bytes = [](const auto& a, const auto& b) {
+        return a.size() == b.size() && (a.empty() || memcmp(a.data(), b.data(), a.size() * sizeof(a[0])) == 0);
+    };
+    if (was.installed() && same_bytes(was.uv[0], now.uv[0]) && same_bytes(was.uv[1], now.uv[1]) && same_bytes(was.uv[2], now.uv[2]) &&
+        same_bytes(was.tw, now.tw) && same_bytes(was.th, now.th) && same_bytes(was.mat_tex, now.mat_tex) &&
+        same_bytes(was.atlas, now.atlas) && (was.dev_ok || was.textured == 0))
+        return MCPT_OK;  // an identical set does nothing
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // no launch in flight reads the old set
+    if (!now.d_atlas.ensure(now.atlas.size()) || !now.d_mat.ensure(dm.size())) {
+        (void)hipGetLastError();
+        return set_err(c, MCPT_E_NOMEM, "hipMalloc: texture atlas");  // (the installed set stays)
+    }
+    HIPCHK(c, hipMemcpy(now.d_atlas, now.atlas.data(), now.atlas.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (!dm.empty()) HIPCHK(c, hipMemcpy(now.d_mat, dm.data(), dm.size() * sizeof(int4), hipMemcpyHostToDevice));
+    if (int rc = textures_uv_stream(c, now)) return rc;
+    // what the film depends on is the shaded base colour: a set without a textured material shades as none
+    const bool differs = was.textured > 0 || now.textured > 0;
+    c->tx = std::move(now);
+    if (differs) changed();
+    return MCPT_OK;
+}
+
 extern "C" {
+
+int mcpt_set_material_textures(mcpt_ctx* c, int32_t ntri, const float* uv0, const float* uv1, const float* uv2, int32_t ntex,
+                               const mcpt_texture* textures, int32_t nmat, const int32_t* mat_tex) {
+    return textures_install(c, ntri, uv0, uv1, uv2, ntex, textures, nmat, mat_tex);
+}
+int mcpt_material_textures_read(mcpt_ctx* c, int32_t* ntri, int32_t* ntex, int32_t* nmat, int32_t* mat_tex, int32_t tex,
+                                int32_t* w, int32_t* h, uint8_t* rgba8, float* uv0, float* uv1, float* uv2) {
+    if (!c) return MCPT_E_INVALID;
+    const Textures& t = c->tx;
+    if (ntri) *ntri = (int32_t)(t.uv[0].size() / 2);
+    if (ntex) *ntex = (int32_t)t.tw.size();
+    if (nmat) *nmat = (int32_t)t.mat_tex.size();
+    if (!t.installed()) return MCPT_OK;
+    if (tex >= (int32_t)t.tw.size()) return set_err(c, MCPT_E_INVALID, "textures: no such texture");
+    if (mat_tex) memcpy(mat_tex, t.mat_tex.data(), t.mat_tex.size() * sizeof(int32_t));
+    if (tex >= 0) {
+        if (w) *w = t.tw[tex];
+        if (h) *h = t.th[tex];
+        if (rgba8) memcpy(rgba8, t.atlas.data() + t.first[tex], (size_t)t.tw[tex] * t.th[tex] * 4);
+    }
+    float* dst[3] = {uv0, uv1, uv2};
+    for (int k = 0; k < 3; k++)
+        if (dst[k] && !t.uv[k].empty()) memcpy(dst[k], t.uv[k].data(), t.uv[k].size() * sizeof(float));
+    return MCPT_OK;
+}
+int mcpt_texture_sample_run(mcpt_ctx* c, int32_t w, int32_t h, const uint8_t* rgba8, uint32_t n, const float* uv,
+                            float* out_rgb) {
+    if (!c) return MCPT_E_INVALID;
+    if (w < 1 || w > 16384 || h < 1 || h > 16384 || !rgba8) return set_err(c, MCPT_E_INVALID, "texture sample: bad image");
+    if (n == 0) return MCPT_OK;
+    if (!uv || !out_rgb || n >= (1u << 28)) return set_err(c, MCPT_E_INVALID, "texture sample: bad uv / output array");
+    HIPCHK(c, hipSetDevice(c->device));
+    TmpScope tmp(c);
+    uint32_t* d_tex = nullptr;
+    float2* d_uv = nullptr;
+    float* d_out = nullptr;
+    int rc;
+    if ((rc = dupload(c, tmp.L, &d_tex, reinterpret_cast<const uint32_t*>(rgba8), (size_t)w * h)) ||
+        (rc = dupload(c, tmp.L, &d_uv, reinterpret_cast<const float2*>(uv), (size_t)n)) || (rc = dalloc(c, tmp.L, &d_out, 3 * (size_t)n)))
+        return rc;
+    launch_tex_sample(d_tex, w, h, d_uv, d_out, n, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out_rgb, d_out, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MCPT_OK;
+}
+int mcpt_debug_texture_stats(const mcpt_ctx* c, uint64_t* bytes, int32_t* textured_materials, int32_t* in_effect) {
+    if (!c) return MCPT_E_INVALID;
+    if (bytes) *bytes = (uint64_t)c->tx.bytes();
+    if (textured_materials) *textured_materials = c->tx.textured;
+    if (in_effect) *in_effect = c->tx.view().uv ? 1 : 0;
+    return MCPT_OK;
+}
 
 int mcpt_scene_upload(mcpt_ctx* c, const mcpt_scene_desc* d) { return scene_upload(c, d, false); }
 int mcpt_scene_upload_gpu_bvh(mcpt_ctx* c, const mcpt_scene_desc* d) { return scene_upload(c, d, true); }

@@ -103,6 +103,10 @@ class BvhInfo(C.Structure):  # mcpt_bvh_info
                 ("rounds", C.c_int32), ("root_mn", C.c_float * 3), ("root_mx", C.c_float * 3), ("cull_p", C.c_float)]
 
 
+class Texture(C.Structure):  # mcpt_texture: a decoded RGBA8 image
+    _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("rgba8", C.POINTER(C.c_uint8))]
+
+
 class PathView(C.Structure):  # mcpt_path_view: path state at the shading stages' boundary
     _fields_ = [("film_w", C.c_uint32), ("film_h", C.c_uint32), ("flags", _u), ("samples", _u), ("hit_tri", _i),
                 ("ray_o", _f), ("ray_d", _f), ("beta", _f), ("nee0", _f), ("nee1", _f),
@@ -211,6 +215,14 @@ ABI = {
     "mcpt_debug_emitter_mis": (C.c_int, [C.c_void_p]),
     "mcpt_scene_set_material_emission": (C.c_int, [C.c_void_p, C.c_int32, _f]),
     "mcpt_scene_get_emission": (C.c_int, [C.c_void_p, C.POINTER(_f), _i]),
+    "mcpt_set_material_textures": (C.c_int, [C.c_void_p, C.c_int32, _f, _f, _f, C.c_int32, C.POINTER(Texture), C.c_int32, _i]),
+    "mcpt_material_textures_read": (C.c_int, [C.c_void_p, _i, _i, _i, _i, C.c_int32, _i, _i, C.POINTER(C.c_uint8), _f, _f, _f]),
+    "mcpt_texture_sample_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_uint32, _f, _f]),
+    "mcpt_debug_texture_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), _i, _i]),
+    "mcpt_scene_set_mesh_uv": (C.c_int, [C.c_void_p, C.c_int32, _f, _f, _f]),
+    "mcpt_scene_set_material_texture": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
+    "mcpt_scene_get_textures": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(Texture)), _i, C.POINTER(_i), _i]),
+    "mcpt_scene_get_uv": (C.c_int, [C.c_void_p, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), _i]),
     "mcpt_sync": (C.c_int, [C.c_void_p]),
     "mcpt_device_name": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
     "mcpt_debug_queue_rays": (C.c_int, [C.c_void_p, C.c_int, _f, _f, _u]),
@@ -329,6 +341,16 @@ def _arr(ptr, n, dtype):
     return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ct)), shape=(n,)).copy()
 
 
+def _rgba8(img) -> np.ndarray:
+    """An (h, w, 4) contiguous uint8 image from an (h, w, 4) or (h, w, 3) one (alpha 255)."""
+    a = np.asarray(img)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in (3, 4) or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("a texture is an (h, w, 4) or (h, w, 3) uint8 image")
+    if a.shape[2] == 3:
+        a = np.concatenate([a, np.full(a.shape[:2] + (1,), 255, np.uint8)], axis=2)
+    return np.ascontiguousarray(a)
+
+
 class Scene:
     """Host scene builder (Scene.cu) -- owns flat BVH-ordered arrays after build()."""
 
@@ -371,6 +393,45 @@ class Scene:
             return None  # (an older variant library: no emission)
         _check(lib().mcpt_scene_get_emission(self.h, C.byref(p), C.byref(n)))
         return _arr(p, 3 * n.value, np.float32).reshape(n.value, 3) if p else None
+
+    def set_uv(self, mat, uv0, uv1, uv2):
+        """Corner uvs of material ``mat``'s triangles, (n, 2) each, in the order the mesh's triangles were
+        added (mcpt_scene_set_mesh_uv).  The library reads 2 floats per triangle of
+        the mesh from each array."""
+        u = [np.ascontiguousarray(a, np.float32).reshape(-1, 2) for a in (uv0, uv1, uv2)]
+        if not (len(u[0]) == len(u[1]) == len(u[2])):
+            raise ValueError("uv0, uv1 and uv2 must have one row per triangle of the mesh")
+        d = SceneDesc()
+        if lib().mcpt_scene_get_desc(self.h, C.byref(d)) == MCPT_OK and 0 <= int(mat) < d.nmat:  # built: the size is known
+            if len(u[0]) != int((_arr(d.mat, d.ntri, np.int32) == int(mat)).sum()):
+                raise ValueError("uv0, uv1 and uv2 must have one row per triangle of the mesh")
+        return self._ck(lib().mcpt_scene_set_mesh_uv(self.h, int(mat), *[fptr(a) for a in u]))
+
+    def set_texture(self, mat, img_u8):
+        """Attach a base-colour texture to material ``mat``: an (h, w, 4) or (h, w, 3) uint8 image, row 0
+        = v in [0, 1/h), used as stored (no sRGB decode; alpha ignored).  None detaches.
+        PathTracer.upload_scene installs the scene's textures after the upload."""
+        if img_u8 is None:
+            return self._ck(lib().mcpt_scene_set_material_texture(self.h, int(mat), 0, 0, None))
+        img = _rgba8(img_u8)
+        return self._ck(lib().mcpt_scene_set_material_texture(self.h, int(mat), img.shape[1], img.shape[0],
+                                                              img.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def textures(self):
+        """None when no material has a texture, else {"textures": [(h, w, 4) uint8, ...], "mat_tex": int32
+        (nmat,)} (copies)."""
+        t, mt, nt, nm = C.POINTER(Texture)(), _i(), C.c_int32(0), C.c_int32(0)
+        _check(lib().mcpt_scene_get_textures(self.h, C.byref(t), C.byref(nt), C.byref(mt), C.byref(nm)))
+        if not t or nt.value == 0:
+            return None
+        imgs = [np.ctypeslib.as_array(t[k].rgba8, shape=(t[k].h, t[k].w, 4)).copy() for k in range(nt.value)]
+        return {"textures": imgs, "mat_tex": _arr(mt, nm.value, np.int32)}
+
+    def uv(self):
+        """The built scene's corner uvs (uv0, uv1, uv2), (ntri, 2) each, in the desc's triangle order."""
+        p, n = [_f(), _f(), _f()], C.c_int32(0)
+        _check(lib().mcpt_scene_get_uv(self.h, C.byref(p[0]), C.byref(p[1]), C.byref(p[2]), C.byref(n)))
+        return tuple(_arr(q, 2 * n.value, np.float32).reshape(n.value, 2) for q in p)
 
     def set_env_hdr(self, path, mode=1, device_tables=False):
         """EnvironmentLight from an .hdr.  device_tables=True keeps the texture only; the
@@ -434,6 +495,8 @@ class Scene:
         out["env_conds_y"] = _arr(d.env_conds_y, W * H, np.float32).reshape(H, W) if d.env_conds_y else np.zeros(0, np.float32)
         out["env_pdf"] = _arr(d.env_pdf, W * H, np.float32).reshape(H, W) if d.env_pdf else np.zeros(0, np.float32)
         out["tri_id"] = _arr(d.tri_id, T, np.int32) if d.tri_id else np.arange(T, dtype=np.int32)
+        if hasattr(lib(), "mcpt_scene_get_uv"):  # (an older variant library has none)
+            out["uv0"], out["uv1"], out["uv2"] = self.uv()  # not part of the desc
         return out
 
 
@@ -522,6 +585,68 @@ class PathTracer:
         e = scene.emission() if isinstance(scene, Scene) else None
         if e is not None:
             self.set_emission(e)
+        # ... and no textures: a Scene's are installed likewise
+        if isinstance(scene, Scene) and hasattr(lib(), "mcpt_scene_get_textures"):
+            t = scene.textures()
+            if t is not None:
+                self.set_textures(*scene.uv(), t["textures"], t["mat_tex"])
+
+    def set_textures(self, uv0=None, uv1=None, uv2=None, textures=None, mat_tex=None):
+        """Base-colour textures (mcpt_set_material_textures): the corner uvs, (ntri, 2)
+        each in the uploaded desc's triangle order, a list of (h, w, 4) / (h, w, 3) uint8 images, and per
+        material a texture index or -1.  No arguments (or no textures) remove the set.  A change clears the
+        film at the next render and makes the guide buffers stale."""
+        if not textures:
+            self._ck(lib().mcpt_set_material_textures(self.h, 0, None, None, None, 0, None, 0, None))
+            return
+        u = [np.ascontiguousarray(a, np.float32).reshape(-1, 2) for a in (uv0, uv1, uv2)]
+        if not (len(u[0]) == len(u[1]) == len(u[2])):
+            raise ValueError("uv0, uv1 and uv2 must have one row per triangle")
+        imgs = [_rgba8(t) for t in textures]
+        arr = (Texture * len(imgs))()
+        for k, im in enumerate(imgs):
+            arr[k].w, arr[k].h = im.shape[1], im.shape[0]
+            arr[k].rgba8 = im.ctypes.data_as(C.POINTER(C.c_uint8))
+        mt = np.ascontiguousarray(mat_tex, np.int32).reshape(-1)
+        self._ck(lib().mcpt_set_material_textures(self.h, len(u[0]), fptr(u[0]), fptr(u[1]), fptr(u[2]), len(imgs), arr,
+                                                  len(mt), mt.ctypes.data_as(_i)))
+
+    def textures(self):
+        """The installed set as {"uv0", "uv1", "uv2": (ntri, 2), "textures": [(h, w, 4) uint8], "mat_tex":
+        int32 (nmat,)}, or None when none is installed."""
+        nt, nx, nm = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        L = lib().mcpt_material_textures_read
+        self._ck(L(self.h, C.byref(nt), C.byref(nx), C.byref(nm), None, -1, None, None, None, None, None, None))
+        if nx.value == 0 and nm.value == 0:
+            return None
+        u = [np.zeros((nt.value, 2), np.float32) for _ in range(3)]
+        mt = np.zeros(nm.value, np.int32)
+        self._ck(L(self.h, None, None, None, mt.ctypes.data_as(_i), -1, None, None, None, fptr(u[0]), fptr(u[1]), fptr(u[2])))
+        imgs = []
+        for k in range(nx.value):
+            w, h = C.c_int32(0), C.c_int32(0)
+            self._ck(L(self.h, None, None, None, None, k, C.byref(w), C.byref(h), None, None, None, None))
+            im = np.zeros((h.value, w.value, 4), np.uint8)
+            self._ck(L(self.h, None, None, None, None, k, None, None, im.ctypes.data_as(C.POINTER(C.c_uint8)), None, None, None))
+            imgs.append(im)
+        return {"uv0": u[0], "uv1": u[1], "uv2": u[2], "textures": imgs, "mat_tex": mt}
+
+    def texture_sample(self, img, uv):
+        """The texture lookup alone on the device (mcpt_texture_sample_run): (n, 3) float32 for (n, 2) uvs
+        over an (h, w, 4) / (h, w, 3) uint8 image.  Needs neither a scene nor a film."""
+        im = _rgba8(img)
+        c = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        out = np.zeros((len(c), 3), np.float32)
+        self._ck(lib().mcpt_texture_sample_run(self.h, im.shape[1], im.shape[0], im.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                               len(c), fptr(c), fptr(out)))
+        return out
+
+    def texture_stats(self):
+        """dict: device bytes the installed set holds, materials with a texture, and whether the textured
+        kernels are in effect (mcpt_debug_texture_stats)."""
+        b, m, on = C.c_uint64(0), C.c_int32(0), C.c_int32(0)
+        self._ck(lib().mcpt_debug_texture_stats(self.h, C.byref(b), C.byref(m), C.byref(on)))
+        return {"bytes": int(b.value), "textured_materials": int(m.value), "in_effect": bool(on.value)}
 
     def set_emission(self, rgb=None):
         """Per-material emitted radiance, (nmat, 3) for the uploaded scene's materials, or None to
