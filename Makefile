@@ -15,7 +15,7 @@ SRCS := $(PKG)/csrc/kernels.hip $(PKG)/csrc/scene_tables.hip $(PKG)/csrc/film.hi
         $(PKG)/csrc/host/image_io.cpp $(PKG)/csrc/host/emitter_table.cpp
 OBJS := $(patsubst $(PKG)/csrc/%,$(BUILD)/%.o,$(SRCS))
 HDRS := include/mcpt.h $(PKG)/csrc/kernels.hpp $(PKG)/csrc/device/mcpt_core.hpp $(PKG)/csrc/device/scene_dev.hpp \
-        $(PKG)/csrc/device/primary_beam.hpp $(PKG)/csrc/device/occ_beam.hpp $(PKG)/csrc/device/denoise.hpp $(PKG)/csrc/device/adaptive.hpp $(PKG)/csrc/device/temporal.hpp $(PKG)/csrc/device/variance.hpp $(PKG)/csrc/device/texture.hpp \
+        $(PKG)/csrc/device/primary_beam.hpp $(PKG)/csrc/device/occ_beam.hpp $(PKG)/csrc/device/denoise.hpp $(PKG)/csrc/device/adaptive.hpp $(PKG)/csrc/device/temporal.hpp $(PKG)/csrc/device/variance.hpp $(PKG)/csrc/device/texture.hpp $(PKG)/csrc/device/k_material_body.inc \
         $(PKG)/csrc/runtime_internal.hpp $(PKG)/csrc/host/host_internal.hpp $(PKG)/csrc/host/pair_tree.hpp \
         $(PKG)/csrc/host/emitter_table.hpp $(PKG)/csrc/host/film_layout.hpp
 

@@ -3,7 +3,7 @@
 // INTEGRATION.md): build a BASELINE config scene with the host builder, upload it,
 // run the wavefront iterations until every pixel has its samples, write PNG + PFM.
 //
-//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>] [--emissive <mat> <r> <g> <b>]... [--env-color <r> <g> <b>] [--sample-emitters] [--emitter-mis] [--checker <mat> <n>]...
+//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>] [--emissive <mat> <r> <g> <b>]... [--env-color <r> <g> <b>] [--sample-emitters] [--emitter-mis] [--checker <mat> <n>]... [--checker-mr <mat> <n>]...
 //
 // --denoise renders the first-hit guide buffers (default 4 guide samples per pixel), filters the film
 // with the default parameters and writes <out_prefix>_denoised.png beside the raw image.
@@ -42,6 +42,9 @@
 // filter softens only the squares' edges) on material <mat> as its base-colour texture (DESIGN.md section
 // 19; repeatable), over the uvs the mesh came with: `mcpt_render 1 64 --checker 0 8` is config 1's mesh
 // (Cube.glb, each face a quarter of the uv square wide) with 2 x 2 squares per face.
+// --checker-mr puts the same checker on material <mat> as its metallic-roughness texture (DESIGN.md section
+// 20; repeatable) and sets the material's metallic factor to 1: the squares alternate G = B = 255 (rough
+// metal: the material's own roughness) with G = 26, B = 255 (roughness a tenth of it: near-mirror metal).
 // --tiles-per-call uses the reference orchestration (one 256x256 tile per call,
 // wavefront_kernels.cu:377-442 + Film::update_tile_position) instead of batch mode.
 #include <math.h>
@@ -73,7 +76,7 @@ static void warp(const mcpt_scene_desc& d, float amp, uint32_t frame, uint32_t f
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>] [--emissive <mat> <r> <g> <b>]... [--env-color <r> <g> <b>] [--sample-emitters] [--emitter-mis] [--checker <mat> <n>]...\n", argv[0]);
+        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>] [--emissive <mat> <r> <g> <b>]... [--env-color <r> <g> <b>] [--sample-emitters] [--emitter-mis] [--checker <mat> <n>]... [--checker-mr <mat> <n>]...\n", argv[0]);
         return 2;
     }
     const Cfg cfgs[6] = {{0, 0, 0, 0, {0, 0, 0}, 0, ""},
@@ -99,6 +102,7 @@ int main(int argc, char** argv) {
     float a_amp = 0.f;
     std::vector<float> emissive;  // --emissive: {mat, r, g, b} per use
     std::vector<int> checker;     // --checker: {mat, n} per use
+    std::vector<int> checker_mr;  // --checker-mr: {mat, n} per use
     float env_rgb[3] = {0.f, 0.f, 0.f};
     bool env_given = false;
     for (int i = 2; i < argc; i++) {
@@ -120,6 +124,15 @@ int main(int argc, char** argv) {
             }
             checker.push_back(atoi(argv[++i]));
             checker.push_back(atoi(argv[++i]));
+            continue;
+        }
+        if (!strcmp(argv[i], "--checker-mr")) {
+            if (i + 2 >= argc || atoi(argv[i + 1]) < 0 || atoi(argv[i + 2]) < 1 || atoi(argv[i + 2]) > 1024) {
+                fprintf(stderr, "--checker-mr needs <mat> <n> (n in 1..1024)\n");
+                return 2;
+            }
+            checker_mr.push_back(atoi(argv[++i]));
+            checker_mr.push_back(atoi(argv[++i]));
             continue;
         }
         if (!strcmp(argv[i], "--env-color")) {
@@ -181,12 +194,24 @@ int main(int argc, char** argv) {
                 for (int ch = 0; ch < 3; ch++) px[4 * ((size_t)y * n + x) + ch] = ((x / sq + y / sq) & 1) ? 255 : 40;
         src = mcpt_scene_set_material_texture(s, checker[k], n, n, px.data());
     }
+    for (size_t k = 0; !src && k < checker_mr.size(); k += 2) {  // rough / near-mirror squares, metallic throughout
+        const int sq = 16, n = checker_mr[k + 1] * sq;
+        std::vector<uint8_t> px((size_t)n * n * 4, 255);
+        for (int y = 0; y < n; y++)
+            for (int x = 0; x < n; x++) px[4 * ((size_t)y * n + x) + 1] = ((x / sq + y / sq) & 1) ? 255 : 26;
+        src = mcpt_scene_set_material_mr_texture(s, checker_mr[k], n, n, px.data());
+    }
     if (src || (ref_bvh ? mcpt_scene_build(s, 8) : mcpt_scene_build_ex(s, &bp))) {
         fprintf(stderr, "scene: %s\n", mcpt_last_error(nullptr));
         return 1;
     }
     mcpt_scene_desc d;
     mcpt_scene_get_desc(s, &d);
+    // --checker-mr: the textured materials' metallic factor is 1 (the builder's materials have 0, which
+    // would scale the texture's B channel away); the desc then points at this copy of the parameters
+    std::vector<float> mat_params(d.mat_params, d.mat_params + 8 * (size_t)d.nmat);
+    for (size_t k = 0; k < checker_mr.size(); k += 2) mat_params[8 * (size_t)checker_mr[k] + 7] = 1.f;
+    if (!checker_mr.empty()) d.mat_params = mat_params.data();
     const float* em_rgb = nullptr;  // the scene's emission table travels beside the desc
     int32_t em_nmat = 0;
     mcpt_scene_get_emission(s, &em_rgb, &em_nmat);
@@ -202,12 +227,13 @@ int main(int argc, char** argv) {
     if (!rc && em_rgb) rc = mcpt_set_material_emission(ctx, em_nmat, em_rgb);
     {  // ... and so do its textures and uvs
         const mcpt_texture* tex = nullptr;
-        const int32_t* mat_tex = nullptr;
+        const int32_t *mat_tex = nullptr, *mat_mr = nullptr;
         const float *uv0 = nullptr, *uv1 = nullptr, *uv2 = nullptr;
-        int32_t ntex = 0, nmat = 0, ntri = 0;
+        int32_t ntex = 0, nmat = 0, ntri = 0, nmr = 0;
         if (!rc) rc = mcpt_scene_get_textures(s, &tex, &ntex, &mat_tex, &nmat);
+        if (!rc) rc = mcpt_scene_get_material_mr(s, &mat_mr, &nmr);
         if (!rc && tex && !(rc = mcpt_scene_get_uv(s, &uv0, &uv1, &uv2, &ntri)))
-            rc = mcpt_set_material_textures(ctx, ntri, uv0, uv1, uv2, ntex, tex, nmat, mat_tex);
+            rc = mcpt_set_material_texture_maps(ctx, ntri, uv0, uv1, uv2, ntex, tex, nmat, mat_tex, mat_mr);
     }
     if (!rc && sample_emitters) rc = mcpt_set_emitter_sampling(ctx, 1);
     if (!rc && emitter_mis) rc = mcpt_set_emitter_mis(ctx, 1);

@@ -627,7 +627,8 @@ int mcpt_debug_emitter_mis(const mcpt_ctx *ctx);
  *          8-bit fractional weights, texel = byte / 255 correctly rounded, rgb only (dTexture.cu:107-117)
  *   base = base_factor * T                        one fp32 multiply per channel (the glTF rule)
  * and the BRDF's f and pdf of every part of the material stage, the emitter sample's and MIS's BRDF pdf
- * use this base.  Fresnel, roughness and metallic stay per material.  Row 0 of a texture is v in
+ * use this base.  Fresnel stays per material, and so do roughness and metallic unless a
+ * metallic-roughness texture is installed (section 20, below).  Row 0 of a texture is v in
  * [0, 1 / h): glTF's orientation, no flip.  Texels are used as stored: there is no sRGB decode (the
  * reference has none), and alpha is ignored.  Texels arrive decoded: reading the PNG / JPEG images
  * embedded in a glb is out of scope here.  Paths, random draws, ray counts, emission and every table do
@@ -664,6 +665,36 @@ int mcpt_material_textures_read(mcpt_ctx *ctx, int32_t *ntri, int32_t *ntex, int
 int mcpt_texture_sample_run(mcpt_ctx *ctx, int32_t w, int32_t h, const uint8_t *rgba8, uint32_t n, const float *uv,
                             float *out_rgb);
 int mcpt_debug_texture_stats(const mcpt_ctx *ctx, uint64_t *bytes, int32_t *textured_materials, int32_t *in_effect);
+/* ---- metallic-roughness textures: per-hit roughness and metallic from a second
+ * lookup at the same texture coordinate tc, in a texture of the same list:
+ *   T     = the section-19 lookup of the material's metallic-roughness texture at tc, unchanged, over rgb
+ *   rough = max(rough_factor * T.g, 0.00001)       one fp32 multiply, then the clamp every roughness gets
+ *   metal = metal_factor * T.b                     one fp32 multiply
+ * (the glTF rule: factor times texel; rough_factor is the material's stored roughness, before the clamp).
+ * R and A are ignored; texels are used as stored.  A material whose MR index is -1 keeps its factors.  The
+ * two textures of a material are independent: either, both or none, of any two sizes.  Every part of the
+ * material stage reads the textured values: the continuation, light and BRDF samples, the emitter sample's
+ * f and the MIS weight's BRDF pdf.  Unlike the base colour, roughness and metallic decide whether a
+ * continuation sample is valid (f == 0 or pdf == 0 ends the path), so ray counts depend on the set at every
+ * depth.  The albedo guide stays base colour only.
+ *
+ * mcpt_set_material_texture_maps is mcpt_set_material_textures with a second index array: mat_mr[m] = the
+ * metallic-roughness texture of material m in the same list, or -1; mat_mr == NULL means all -1, and
+ * mcpt_set_material_textures is this call with NULL.  Every rule of that call holds, for both arrays: an
+ * index outside [-1, ntex) in either is refused, a bitwise-identical set (mat_mr included) does nothing, a
+ * differing one marks the film stale, drops the temporal history and makes the guides stale unless neither
+ * set textures a material in either array.  A set with an MR-textured material launches k_material's
+ * metallic-roughness instantiations; a set with base-colour textures only, or none, launches what it
+ * launched before.
+ * mcpt_material_mr_read: *nmat (0: no set installed) and the nmat MR indices (either may be NULL).
+ * mcpt_debug_texture_mr_stats: materials with an MR texture, and 1 / 0 for whether the metallic-roughness
+ * kernels are in effect (either may be NULL).  mcpt_debug_texture_stats' in_effect is 1 whenever either
+ * kind of textured kernel is. */
+int mcpt_set_material_texture_maps(mcpt_ctx *ctx, int32_t ntri, const float *uv0, const float *uv1, const float *uv2,
+                                   int32_t ntex, const mcpt_texture *textures, int32_t nmat, const int32_t *mat_tex,
+                                   const int32_t *mat_mr);
+int mcpt_material_mr_read(mcpt_ctx *ctx, int32_t *nmat, int32_t *mat_mr);
+int mcpt_debug_texture_mr_stats(const mcpt_ctx *ctx, int32_t *mr_materials, int32_t *mr_in_effect);
 int mcpt_sync(mcpt_ctx *ctx);
 int mcpt_device_name(mcpt_ctx *ctx, char *buf, int32_t len);
 /* diagnostics: rays of the current extension (which=0) or any-hit (which=1) queue, and the
@@ -792,6 +823,15 @@ int mcpt_scene_set_material_texture(mcpt_scene *s, int32_t mat, int32_t w, int32
 int mcpt_scene_get_textures(const mcpt_scene *s, const mcpt_texture **textures, int32_t *ntex,
                             const int32_t **mat_tex, int32_t *nmat);
 int mcpt_scene_get_uv(const mcpt_scene *s, const float **uv0, const float **uv1, const float **uv2, int32_t *ntri);
+/* Metallic-roughness textures (mcpt_set_material_texture_maps takes what the getters
+ * return).  mcpt_scene_set_material_mr_texture: attaches a copy of the w x h RGBA8 image to material mat as
+ * its metallic-roughness texture (G: roughness, B: metallic; R and A ignored), replacing its previous one;
+ * rgba8 == NULL detaches.  The refusals are mcpt_scene_set_material_texture's.  The image joins the list
+ * mcpt_scene_get_textures returns, which then hands out that list when a material has a texture of either
+ * kind; a scene without MR textures returns what it returned before.
+ * mcpt_scene_get_material_mr: the nmat MR indices into that list (-1: none), owned by the scene. */
+int mcpt_scene_set_material_mr_texture(mcpt_scene *s, int32_t mat, int32_t w, int32_t h, const uint8_t *rgba8);
+int mcpt_scene_get_material_mr(const mcpt_scene *s, const int32_t **mat_mr, int32_t *nmat);
 int mcpt_scene_set_env_hdr(mcpt_scene *s, const char *path, int32_t mode);
 /* flags MCPT_ENV_DEVICE_TABLES: keep the texture only; mcpt_scene_upload then builds the tables on
  * the device (for large maps: the host build is several serial passes over every texel). */

@@ -260,16 +260,36 @@ public:
                       "Scene::set_material_texture");
         notify();
     }
-    // The built scene's textures and uvs onto a context that holds its upload (nothing without a texture)
+    // MI355X extension: metallic-roughness textures (mcpt.h).  A decoded w x h RGBA8
+    // image whose G channel scales material `mat`'s roughness and whose B channel its metallic (empty:
+    // detach); independent of the material's base-colour texture.
+    void set_material_mr_texture(int32_t mat, int32_t w, int32_t h, const std::vector<uint8_t>& rgba8) {
+        if (!rgba8.empty() && rgba8.size() != (size_t)w * (size_t)h * 4)
+            throw Error(MCPT_E_INVALID, "Scene::set_material_mr_texture: w * h * 4 bytes");
+        detail::check(mcpt_scene_set_material_mr_texture(s_, mat, w, h, rgba8.empty() ? nullptr : rgba8.data()), nullptr,
+                      "Scene::set_material_mr_texture");
+        notify();
+    }
+    // Per material the index of its metallic-roughness texture in the scene's texture list, or -1
+    std::vector<int32_t> material_mr() const {
+        const int32_t* mr = nullptr;
+        int32_t nmat = 0;
+        detail::check(mcpt_scene_get_material_mr(s_, &mr, &nmat), nullptr, "Scene::material_mr");
+        return std::vector<int32_t>(mr, mr + nmat);
+    }
+    // The built scene's textures (of both kinds) and uvs onto a context that holds its upload (nothing
+    // without a texture)
     void install_textures(mcpt_ctx* ctx) const {
         const mcpt_texture* tex = nullptr;
-        const int32_t* mat_tex = nullptr;
-        int32_t ntex = 0, nmat = 0, ntri = 0;
+        const int32_t *mat_tex = nullptr, *mat_mr = nullptr;
+        int32_t ntex = 0, nmat = 0, ntri = 0, nmr = 0;
         detail::check(mcpt_scene_get_textures(s_, &tex, &ntex, &mat_tex, &nmat), nullptr, "Scene::install_textures");
         if (!tex || !ntex) return;
+        detail::check(mcpt_scene_get_material_mr(s_, &mat_mr, &nmr), nullptr, "Scene::install_textures");
         const float *uv0 = nullptr, *uv1 = nullptr, *uv2 = nullptr;
         detail::check(mcpt_scene_get_uv(s_, &uv0, &uv1, &uv2, &ntri), nullptr, "Scene::install_textures");
-        detail::check(mcpt_set_material_textures(ctx, ntri, uv0, uv1, uv2, ntex, tex, nmat, mat_tex), ctx, "scene textures");
+        detail::check(mcpt_set_material_texture_maps(ctx, ntri, uv0, uv1, uv2, ntex, tex, nmat, mat_tex, mat_mr), ctx,
+                      "scene textures");
     }
     // MI355X extension: the BASELINE config proxies of SURVEY.md 8(d) (geometry + environment).
     void make_proxy(int config_id, const std::string& asset_dir) {

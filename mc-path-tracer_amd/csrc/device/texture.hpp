@@ -11,6 +11,13 @@
 //
 // Row 0 of a texture is v in [0, 1 / H): glTF's orientation, no flip.  Texels are used as stored:
 // no sRGB decode (the reference's texture objects have none).  Alpha is ignored.
+//
+// Metallic-roughness textures (tex_mr below) use the same tc and the same lookup:
+//   T     = tex_bilinear_rgba8(MR texture of the material, tc)     over rgb, unchanged
+//   rough = fmx(rough_factor * T.y, BRDF_EPS)   one fp32 multiply, then load_mat's clamp (G channel)
+//   metal = metal_factor * T.z                  one fp32 multiply (B channel)
+// rough_factor is the raw mat_params[6], not load_mat's clamped value.  R and A are ignored.  The two
+// textures of a material are independent: either, both or none, of any two sizes.
 #pragma once
 #include "device/mcpt_core.hpp"
 
@@ -21,6 +28,9 @@ struct TexView {
     const float2* uv;       // 3 per triangle record (uv0, uv1, uv2), in record order like DevScene::tri_sh
     const uint32_t* atlas;  // every texture's RGBA8 texels (r in the low byte), row-major, one after the other
     const int4* mat;        // per material {first texel in the atlas, w, h, texture index}; w == 0: untextured
+    // Metallic-roughness entries (section 20) live in the same allocation, in front of the base-colour
+    // ones and mirrored: material m's is mat[-1 - m], the same four words.  Only k_material's MR
+    // instantiations read them, and only a set with an MR-textured material launches those.
 };
 
 // c / 255 rounded to nearest fp32, c = 0..255.  The fp64 product is within 2^-52 of the quotient,
@@ -62,6 +72,20 @@ MCPT_HD V3 tex_base(const TexView& t, int mat, V3 base_factor, float tu, float t
     const int4 e = t.mat[mat];
     if (e.y <= 0) return base_factor;
     return base_factor * tex_bilinear_rgba8(t.atlas + e.x, e.y, e.z, tu, tv);
+}
+
+// The shaded roughness and metallic of material `mat` at (tu, tv): (rough_factor, metal_factor) times the
+// G and B channels of its MR texture, the roughness clamped as load_mat clamps it; the clamped factor and
+// the metallic factor for a material without one.  rough_factor is the raw mat_params[6].
+MCPT_HD void tex_mr(const TexView& t, int mat, float rough_factor, float metal_factor, float tu, float tv, float& rough,
+                    float& metal) {
+    const int4 e = t.mat[-1 - mat];
+    rough = fmx(rough_factor, BRDF_EPS);
+    metal = metal_factor;
+    if (e.y <= 0) return;
+    const V3 T = tex_bilinear_rgba8(t.atlas + e.x, e.y, e.z, tu, tv);
+    rough = fmx(rough_factor * T.y, BRDF_EPS);
+    metal = metal_factor * T.z;
 }
 
 }  // namespace mcpt

@@ -149,11 +149,14 @@ int mcpt_scene_set_mesh_uv(mcpt_scene* s, int32_t mat, const float* uv0, const f
     return MCPT_OK;
 }
 
-int mcpt_scene_set_material_texture(mcpt_scene* s, int32_t mat, int32_t w, int32_t h, const uint8_t* rgba8) {
+// Attaches the image to material mat through the index array idx (mat_tex: base colour; mat_mr:
+// metallic-roughness, section 20): both kinds share the texture list.
+static int scene_attach_texture(mcpt_scene* s, std::vector<int32_t> mcpt_host::Scene::*idx, int32_t mat, int32_t w, int32_t h,
+                                const uint8_t* rgba8) {
     if (!s) return fail(s, MCPT_E_INVALID, "null scene");
     if (mat < 0 || (size_t)mat >= s->s.mat_tex.size()) return fail(s, MCPT_E_INVALID, "material id out of range");
     if (!rgba8) {  // detach (the texture itself stays in the list: the other indices keep their meaning)
-        s->s.mat_tex[mat] = -1;
+        (s->s.*idx)[mat] = -1;
         return MCPT_OK;
     }
     if (w < 1 || w > 16384 || h < 1 || h > 16384) return fail(s, MCPT_E_INVALID, "texture width and height must be 1..16384");
@@ -161,7 +164,7 @@ int mcpt_scene_set_material_texture(mcpt_scene* s, int32_t mat, int32_t w, int32
     t.w = w;
     t.h = h;
     t.rgba8.assign(rgba8, rgba8 + (size_t)w * h * 4);
-    int32_t& k = s->s.mat_tex[mat];
+    int32_t& k = (s->s.*idx)[mat];
     if (k >= 0) {
         s->s.textures[k] = std::move(t);  // the material's own texture is replaced
     } else {
@@ -171,12 +174,26 @@ int mcpt_scene_set_material_texture(mcpt_scene* s, int32_t mat, int32_t w, int32
     return MCPT_OK;
 }
 
+int mcpt_scene_set_material_texture(mcpt_scene* s, int32_t mat, int32_t w, int32_t h, const uint8_t* rgba8) {
+    return scene_attach_texture(s, &mcpt_host::Scene::mat_tex, mat, w, h, rgba8);
+}
+int mcpt_scene_set_material_mr_texture(mcpt_scene* s, int32_t mat, int32_t w, int32_t h, const uint8_t* rgba8) {
+    return scene_attach_texture(s, &mcpt_host::Scene::mat_mr, mat, w, h, rgba8);
+}
+int mcpt_scene_get_material_mr(const mcpt_scene* s, const int32_t** mat_mr, int32_t* nmat) {
+    if (!s || !mat_mr || !nmat) return MCPT_E_INVALID;
+    *nmat = (int32_t)s->s.mat_mr.size();
+    *mat_mr = s->s.mat_mr.data();
+    return MCPT_OK;
+}
+
 int mcpt_scene_get_textures(const mcpt_scene* s, const mcpt_texture** textures, int32_t* ntex, const int32_t** mat_tex,
                             int32_t* nmat) {
     if (!s || !textures || !ntex || !mat_tex || !nmat) return MCPT_E_INVALID;
     const mcpt_host::Scene& sc = s->s;
     bool any = false;
     for (int32_t k : sc.mat_tex) any = any || k >= 0;
+    for (int32_t k : sc.mat_mr) any = any || k >= 0;  // (section 20: the list holds MR images too)
     sc.tex_views.clear();
     for (const mcpt_host::Texture& t : sc.textures) sc.tex_views.push_back(mcpt_texture{t.w, t.h, t.rgba8.data()});
     *nmat = (int32_t)sc.mat_tex.size();

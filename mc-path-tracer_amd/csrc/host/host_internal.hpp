@@ -33,6 +33,7 @@ struct Scene {
     // material, its texture's index or -1; tex_views: what mcpt_scene_get_textures hands out
     std::vector<Texture> textures;
     std::vector<int32_t> mat_tex;
+    std::vector<int32_t> mat_mr;  // metallic-roughness textures: indices into the same list
     mutable std::vector<mcpt_texture> tex_views;
     // environment light (EnvironmentLight.h:17-40); default Color 0.8 (Scene.cu:21)
     int env_mode = 0;

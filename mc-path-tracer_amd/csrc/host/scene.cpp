@@ -206,6 +206,7 @@ void Scene::add_mesh(const std::vector<V3>& pos, const std::vector<V3>& nrm, con
     const float em[3] = {emit.x, emit.y, emit.z};
     emission.insert(emission.end(), em, em + 3);
     mat_tex.push_back(-1);
+    mat_mr.push_back(-1);
     for (size_t i = 0; i + 2 < idx.size(); i += 3) {
         Tri t;
         for (int k = 0; k < 3; k++) { t.p[k] = pos[idx[i + k]]; t.n[k] = nrm[idx[i + k]]; }

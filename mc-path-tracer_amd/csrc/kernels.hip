@@ -21,6 +21,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <type_traits>
 
 #include "device/mcpt_core.hpp"
 #include "device/scene_dev.hpp"
@@ -521,10 +522,17 @@ struct MatOut {
 // TEX (base-colour textures installed): the material's base colour is its factor
 // times the texture lookup at the hit's texture coordinate (device/texture.hpp); everything after reads
 // that Mat, so f and pdf of all three parts, the emitter sample's and MIS's BRDF pdf follow.  Draws, rays
-// and counts do not depend on it.
-template <bool FIXED, bool SAMP = false, bool MIS = false, bool TEX = false>
+// and counts do not depend on it.  TEX is a level: 0 none, 1 base colour, 2 base colour and
+// metallic-roughness: the second lookup follows the first at once, while little
+// else is live, and gives the Mat its roughness and metallic (device/texture.hpp tex_mr), so a2, the
+// sampled half vector, the Fresnel mix and both pdfs vary per hit.  There F_FZERO, and so the rays that
+// follow, do depend on the set.  What material_brdf_terms needs of the shaded Mat (base, roughness,
+// metallic) waits in the thread's five LDS words of tex_stash, not in registers across the occluder cache:
+// the instantiations sit at the 128 VGPRs of four waves per SIMD.
+template <bool FIXED, bool SAMP = false, bool MIS = false, int TEX = 0>
 __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix, uint32_t sidx, uint32_t len,
-                                 V3 beta_store, int32_t htri, float4* stage, bool occ_on, bool no_cont, bool& want_e) {
+                                 V3 beta_store, int32_t htri, float4* stage, bool occ_on, bool no_cont, bool& want_e,
+                                 [[maybe_unused]] float* tex_stash = nullptr) {
     const DevScene& sc = a.scene;
     MatOut mo{};
 #pragma unroll
@@ -538,14 +546,23 @@ __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix
     int mat;
     float t_hit;
     [[maybe_unused]] float tu, tv;
-    if constexpr (TEX) hit_record_t<true>(sc, a.tex.uv, ro, rdir, htri, pos, n, mat, t_hit, tu, tv);
+    if constexpr (TEX != 0) hit_record_t<true>(sc, a.tex.uv, ro, rdir, htri, pos, n, mat, t_hit, tu, tv);
     else hit_record(sc, ro, rdir, htri, pos, n, mat, t_hit);
     const V3 wo = -rdir;
     Mat m_ld = load_mat(sc.mats + 8 * mat);
-    if constexpr (TEX) {
+    if constexpr (TEX != 0) {
         MCPT_MARK("m_tex");
         m_ld.base = mcpt::tex_base(a.tex, mat, m_ld.base, tu, tv);
-        mo.base = m_ld.base;
+        if constexpr (TEX == 1) mo.base = m_ld.base;
+    }
+    if constexpr (TEX == 2) {
+        MCPT_MARK("m_tex_mr");
+        mcpt::tex_mr(a.tex, mat, sc.mats[8 * mat + 6], m_ld.metal, tu, tv, m_ld.rough, m_ld.metal);
+        tex_stash[0 * kBlock + threadIdx.x] = m_ld.base.x;
+        tex_stash[1 * kBlock + threadIdx.x] = m_ld.base.y;
+        tex_stash[2 * kBlock + threadIdx.x] = m_ld.base.z;
+        tex_stash[3 * kBlock + threadIdx.x] = m_ld.rough;
+        tex_stash[4 * kBlock + threadIdx.x] = m_ld.metal;
     }
     const Mat m = m_ld;
     // The three parts of wf_mat_mix draw from disjoint RNG slots and share only the hit
@@ -732,15 +749,22 @@ __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix
 // nee1 = (cB, f_s / pdf_s .z) and the flags word (F_CONDB).  cB is evaluated only for a
 // visibility ray that may be unoccluded (need_cb): one the occluder cache resolved is never read.
 // TEX: with the base colour material() shaded with (MatOut::base: three registers across the occluder
-// cache instead of a second lookup's four gathers).
-template <bool FIXED, bool TEX = false>
-__device__ inline void material_brdf_terms(const ShadeArgs& a, uint32_t pid, const MatOut& mo) {
+// cache instead of a second lookup's four gathers); TEX == 2: and with its roughness and metallic, all
+// five from the thread's LDS words (material()).
+template <bool FIXED, int TEX = 0>
+__device__ inline void material_brdf_terms(const ShadeArgs& a, uint32_t pid, const MatOut& mo,
+                                           [[maybe_unused]] const float* tex_stash = nullptr) {
     const DevScene& sc = a.scene;
     V3 cB = v3(0.f, 0.f, 0.f);
     uint32_t nf = mo.flags;
     if (mo.need_cb) {
         Mat m_ld = load_mat(sc.mats + 8 * mo.matid);
-        if constexpr (TEX) m_ld.base = mo.base;
+        if constexpr (TEX == 1) m_ld.base = mo.base;
+        if constexpr (TEX == 2) {
+            m_ld.base = v3(tex_stash[0 * kBlock + threadIdx.x], tex_stash[1 * kBlock + threadIdx.x], tex_stash[2 * kBlock + threadIdx.x]);
+            m_ld.rough = tex_stash[3 * kBlock + threadIdx.x];
+            m_ld.metal = tex_stash[4 * kBlock + threadIdx.x];
+        }
         const Mat m = m_ld;
         V3 f_b;
         float pdfb_x;
@@ -1225,162 +1249,29 @@ __global__ __launch_bounds__(kBlock) MCPT_SHADE_ATTR void k_shade(ShadeArgs a) {
 // pushed onto the any-hit queue with the result index 2P + path.
 // MIS (with SAMP): the weighted emitter sample and pdf_s in nee2.w (material()).
 // TEX: the textured instantiations, launched only while a texture set is in effect.
-template <bool FIXED, bool SAMP = false, bool MIS = false, bool TEX = false>
+// The body is device/k_material_body.inc, included into k_material (texture levels 0 and 1, under the
+// names it had) and into its TexMr overload (level 2).
+template <bool FIXED, bool SAMP = false, bool MIS = false, bool TEX_ON = false>
 __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_kernarg) {
     (void)a_kernarg;  // read through kernarg_fresh (the same bytes: it is the kernel's only argument)
-    const ShadeArgs& a = kernarg_fresh<ShadeArgs>();
-    if (a.cnt->idle) return;  // the tile set is complete
-    const uint32_t shard = blockIdx.x % kShards, w_in = blockIdx.x / kShards, bps = gridDim.x / kShards;
-    uint32_t* sc_ctr = a.cnt->shard[shard];
-    const uint32_t n = sc_ctr[C_MAT];
-    const int lane = threadIdx.x & 63;
-    uint32_t n_ext = 0, n_any = 0, n_vis = 0, n_occ = 0, occ_try = 0, n_skip = 0, n_inpl = 0, n_dvis = 0, n_docc = 0;
-    uint32_t n_emit = 0;  // SAMP: emitter rays made
-    (void)n_emit;
-    const bool occ_on = a.scene.occ && a.scene.occ_gate[0] == 0 && a.scene.occ_gate[2] != 0;  // see DevScene::occ_gate
-    // Any-hit rays are staged here (light ray o/d, BRDF visibility ray o/d) and stored after
-    // the block push at their queue positions: the block's rays of one kind land contiguously,
-    // so k_trace reads them densely and without the queue-entry hop (the pid-indexed layout
-    // wrote and read 32-B pieces of partly used lines).
-    __shared__ float4 s_any[SAMP ? 6 : 4][kBlock];
-    for (uint32_t base = w_in * kBlock; base < n; base += bps * kBlock) {  // block-uniform trip count
-        const ShadeArgs& a = kernarg_fresh<ShadeArgs>();  // this trip's loads (see kernarg_fresh)
-        const uint32_t i = base + threadIdx.x;
-        MatOut mo{};
-        bool want_e = false;  // SAMP: the emitter ray
-        uint32_t mpid = 0;
-        bool occ_l = false, occ_b = false, try_l = false, try_b = false;  // resolved by / tested against the occluder cache
-        bool done_l = false, done_b = false, clr_l = false, clr_b = false;  // ... from a complete entry / as unoccluded
-        if (i < n) {
-            const uint4 q = ld_s(a.mat_rec + shard * a.ext_cap + i);  // {pid, pixel, sample index | len << 24, hit_tri}
-            const float4 b4 = ld_s(a.mat_beta + shard * a.ext_cap + i);
-            mpid = q.x;
-            mo = material<FIXED, SAMP, MIS, TEX>(a, mpid, q.y, q.z & (kRecNoCont - 1u), q.z >> kRecLenShift, xyz(b4), (int32_t)q.w,
-                                            &s_any[0][0], occ_on, (q.z & kRecNoCont) != 0u, want_e);
-            // the occluder cache (see occ_hit1), before the BRDF sample's light terms: a ray it
-            // resolves gets its wf_shadow result here and is not queued
-            MCPT_MARK("m_occ");
-            if (occ_on) {
-                try_l = mo.want_l;
-                try_b = mo.want_b;
-                const V3 ol = xyz(s_any[0][threadIdx.x]), dl = xyz(s_any[1][threadIdx.x]);
-                const V3 ob = xyz(s_any[2][threadIdx.x]), db = xyz(s_any[3][threadIdx.x]);
-                if (mo.want_l) {
-                    const int r = occ_hit1(a.scene, ol, dl, mo.el, done_l);
-                    occ_l = r == kOccHit;
-                    clr_l = r == kOccMaybe;
-                }
-                if (mo.want_b) {
-                    const int r = occ_hit1(a.scene, ob, db, mo.eb, done_b);
-                    occ_b = r == kOccHit;
-                    clr_b = r == kOccMaybe;
-                }
-                if (clr_l || clr_b) {
-                    bool m_l, m_b;
-                    occ_member2(a.scene, ol, dl, mo.kl, ob, db, mo.kb, m_l, m_b);
-                    clr_l = clr_l && m_l;
-                    clr_b = clr_b && m_b;
-                }
-                // unoccluded by a complete entry: wf_shadow's result for a ray that finds nothing
-                if (clr_l) {
-                    a.p.vis[2 * mpid] = 1;
-                    mo.want_l = false;
-                    mo.trivial_any++;
-                }
-                if (clr_b) {
-                    a.p.vis[2 * mpid + 1] = 1;
-                    mo.want_b = false;
-                    mo.trivial_any++;
-                }
-                if (occ_l) {
-                    a.p.vis[2 * mpid] = 0;
-                    mo.want_l = false;
-                    mo.trivial_any++;
-                }
-                if (occ_b) {
-                    a.p.vis[2 * mpid + 1] = 0;
-                    mo.want_b = false;
-                    mo.need_cb = false;
-                    mo.trivial_any++;
-                }
-            }
-            MCPT_MARK("m_bterms");
-            material_brdf_terms<FIXED, TEX>(a, mpid, mo);
-        }
-        MCPT_MARK("m_push");
-        uint32_t slot[SAMP ? 4 : 3], total[SAMP ? 4 : 3];
-        if constexpr (SAMP) {
-            bool want[4] = {mo.want_ext, mo.want_l, mo.want_b, want_e};
-            uint32_t* ctr[4] = {sc_ctr + C_EXT, sc_ctr + C_ANY, sc_ctr + C_ANY, sc_ctr + C_ANY};
-            block_push<4>(want, ctr, slot, total);
-        } else {
-            bool want[3] = {mo.want_ext, mo.want_l, mo.want_b};
-            uint32_t* ctr[3] = {sc_ctr + C_EXT, sc_ctr + C_ANY, sc_ctr + C_ANY};
-            block_push<3>(want, ctr, slot, total);
-        }
-        if (mo.want_ext) st_q(a.ext_q + shard * a.ext_cap + slot[0], mpid);
-        // (the any-hit rays carry their result index in o.w: no queue entries)
-        if (mo.want_l) {
-            const uint32_t k = shard * a.any_cap + slot[1];
-            if constexpr (MCPT_NT & 8) {
-                st_s(a.p.sray_o + k, s_any[0][threadIdx.x]);
-                st_s(a.p.sray_d + k, s_any[1][threadIdx.x]);
-            } else {
-                a.p.sray_o[k] = s_any[0][threadIdx.x];
-                a.p.sray_d[k] = s_any[1][threadIdx.x];
-            }
-        }
-        if (mo.want_b) {
-            const uint32_t k = shard * a.any_cap + slot[2];
-            if constexpr (MCPT_NT & 8) {
-                st_s(a.p.sray_o + k, s_any[2][threadIdx.x]);
-                st_s(a.p.sray_d + k, s_any[3][threadIdx.x]);
-            } else {
-                a.p.sray_o[k] = s_any[2][threadIdx.x];
-                a.p.sray_d[k] = s_any[3][threadIdx.x];
-            }
-        }
-        if constexpr (SAMP) {
-            if (want_e) {  // (any_cap is 3 x ext_cap while sampling is active: set_tiles_internal)
-                const uint32_t k = shard * a.any_cap + slot[3];
-                if constexpr (MCPT_NT & 8) {
-                    st_s(a.p.sray_o + k, s_any[4][threadIdx.x]);
-                    st_s(a.p.sray_d + k, s_any[5][threadIdx.x]);
-                } else {
-                    a.p.sray_o[k] = s_any[4][threadIdx.x];
-                    a.p.sray_d[k] = s_any[5][threadIdx.x];
-                }
-            }
-            n_emit += (uint32_t)__popcll(__ballot(want_e));
-        }
-        MCPT_MARK("m_count");
-        // per-wave ray counts from lane masks (wave-uniform scalars: no registers held across the
-        // next trip's material())
-        n_occ += (uint32_t)(__popcll(__ballot(occ_l)) + __popcll(__ballot(occ_b)));
-        occ_try += (uint32_t)(__popcll(__ballot(try_l)) + __popcll(__ballot(try_b)));
-        n_dvis += (uint32_t)(__popcll(__ballot(clr_l)) + __popcll(__ballot(clr_b)));
-        n_docc += (uint32_t)(__popcll(__ballot(occ_l && done_l)) + __popcll(__ballot(occ_b && done_b)));
-        // queued + resolved-in-place rays + those the next logic pass would discard (counted, not made)
-        n_ext += (uint32_t)__popcll(__ballot(mo.want_ext || mo.trivial_ext || mo.skip_ext));
-        n_skip += (uint32_t)__popcll(__ballot(mo.skip_ext));
-        n_inpl += (uint32_t)__popcll(__ballot(mo.doomed_inplace));
-        n_any += (uint32_t)(__popcll(__ballot(mo.want_l)) + __popcll(__ballot(mo.want_b)) +
-                            __popcll(__ballot(mo.trivial_any >= 1u)) + __popcll(__ballot(mo.trivial_any >= 2u)));
-        n_vis += (uint32_t)__popcll(__ballot(mo.vis_ray));
-    }
-    if (lane == 0) {
-        if (n_ext) atomicAdd(sc_ctr + C_EXT_RAYS, n_ext);
-        if (n_any) atomicAdd(sc_ctr + C_ANY_RAYS, n_any);
-        if (n_vis) atomicAdd(sc_ctr + C_VIS, n_vis);
-        if (n_occ) atomicAdd(sc_ctr + C_OCC, n_occ);
-        if (occ_try) atomicAdd(sc_ctr + C_OCC_TRY, occ_try);
-        if (n_dvis) atomicAdd(sc_ctr + C_OCC_DONE_VIS, n_dvis);
-        if (n_docc) atomicAdd(sc_ctr + C_OCC_DONE_OCC, n_docc);
-        if (n_skip) atomicAdd(sc_ctr + C_SKIP_EXT, n_skip);
-        if (n_inpl) atomicAdd(sc_ctr + C_SKIP_INPLACE, n_inpl);
-        if constexpr (SAMP)
-            if (n_emit) atomicAdd(a.cnt->tot_emit + shard, (unsigned long long)n_emit);
-    }
+    constexpr int TEX = TEX_ON ? 1 : 0;
+    constexpr float* tex_stash = nullptr;
+#include "device/k_material_body.inc"
+}
+// The metallic-roughness instantiations, launched only while a set with an
+// MR-textured material is in effect: base colour and MR per material, each with its own w == 0 test.
+// An overload of k_material told apart by a leading tag type, k_material<TexMr, FIXED, SAMP, MIS>: the
+// third texture level without a change to the twelve older instantiations' template arguments, so
+// their symbols, and with them their place in a comparison of two builds by name, stay.
+struct TexMr {};
+template <typename LEVEL, bool FIXED, bool SAMP = false, bool MIS = false>
+__global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_kernarg) {
+    static_assert(std::is_same<LEVEL, TexMr>::value, "the tag selects the metallic-roughness level");
+    (void)a_kernarg;
+    constexpr int TEX = 2;
+    __shared__ float s_tex[5][kBlock];  // base colour, roughness, metallic of the thread's path (5 KiB)
+    float* const tex_stash = &s_tex[0][0];
+#include "device/k_material_body.inc"
 }
 
 // ---------------------------------------------------------------------------
@@ -2358,9 +2249,13 @@ static uint32_t shade_grid(uint32_t nblocks, const LaunchGeom& g) {
 }
 // k_material for a launch: the textured instantiation while a texture set is in effect (a.tex.uv set;
 // DESIGN.md section 19), on its twin's grid; every other context launches what it launched before.
+// tex_mr (the host's choice, no kernel argument; section 20): the set has an MR-textured material.
 template <bool SAMP, bool MIS>
-static void launch_material(const ShadeArgs& a, const uint32_t* blocks, bool fixed_mode, hipStream_t s) {
-    if (a.tex.uv) {
+static void launch_material(const ShadeArgs& a, const uint32_t* blocks, bool fixed_mode, bool tex_mr, hipStream_t s) {
+    if (a.tex.uv && tex_mr) {
+        if (fixed_mode) hipLaunchKernelGGL((k_material<TexMr, true, SAMP, MIS>), dim3(blocks[1]), dim3(kBlock), 0, s, a);
+        else hipLaunchKernelGGL((k_material<TexMr, false, SAMP, MIS>), dim3(blocks[0]), dim3(kBlock), 0, s, a);
+    } else if (a.tex.uv) {
         if (fixed_mode) hipLaunchKernelGGL((k_material<true, SAMP, MIS, true>), dim3(blocks[1]), dim3(kBlock), 0, s, a);
         else hipLaunchKernelGGL((k_material<false, SAMP, MIS, true>), dim3(blocks[0]), dim3(kBlock), 0, s, a);
     } else {
@@ -2368,7 +2263,7 @@ static void launch_material(const ShadeArgs& a, const uint32_t* blocks, bool fix
         else hipLaunchKernelGGL((k_material<false, SAMP, MIS>), dim3(blocks[0]), dim3(kBlock), 0, s, a);
     }
 }
-void launch_shade(const ShadeArgs& args, int nblocks, const LaunchGeom& g, bool fixed_mode, hipStream_t s) {
+void launch_shade(const ShadeArgs& args, int nblocks, const LaunchGeom& g, bool fixed_mode, bool tex_mr, hipStream_t s) {
     ShadeArgs a = args;
     a.shade_vblocks = (uint32_t)nblocks;
     const uint32_t G = shade_grid((uint32_t)nblocks, g);
@@ -2384,7 +2279,7 @@ void launch_shade(const ShadeArgs& args, int nblocks, const LaunchGeom& g, bool 
             if (a.budget) hipLaunchKernelGGL((k_shade<false, true, true, true, true>), dim3(G), dim3(kBlock), 0, s, a);
             else hipLaunchKernelGGL((k_shade<false, false, true, true, true>), dim3(G), dim3(kBlock), 0, s, a);
         }
-        launch_material<true, true>(a, g.mat_blocks_samp, fixed_mode, s);
+        launch_material<true, true>(a, g.mat_blocks_samp, fixed_mode, tex_mr, s);
         return;
     }
     if (a.nee2 && a.emis) {
@@ -2395,7 +2290,7 @@ void launch_shade(const ShadeArgs& args, int nblocks, const LaunchGeom& g, bool 
             if (a.budget) hipLaunchKernelGGL((k_shade<false, true, true, true>), dim3(G), dim3(kBlock), 0, s, a);
             else hipLaunchKernelGGL((k_shade<false, false, true, true>), dim3(G), dim3(kBlock), 0, s, a);
         }
-        launch_material<true, false>(a, g.mat_blocks_samp, fixed_mode, s);
+        launch_material<true, false>(a, g.mat_blocks_samp, fixed_mode, tex_mr, s);
         return;
     }
     if (fixed_mode) {
@@ -2411,11 +2306,11 @@ void launch_shade(const ShadeArgs& args, int nblocks, const LaunchGeom& g, bool 
         } else if (a.budget) hipLaunchKernelGGL((k_shade<false, true, false>), dim3(G), dim3(kBlock), 0, s, a);
         else hipLaunchKernelGGL((k_shade<false, false, false>), dim3(G), dim3(kBlock), 0, s, a);
     }
-    launch_material<false, false>(a, g.mat_blocks, fixed_mode, s);
+    launch_material<false, false>(a, g.mat_blocks, fixed_mode, tex_mr, s);
 }
 // One of the two shading kernels alone (mcpt_stage_run's LOGIC / GENERATE and MATERIAL stages).
 void launch_shade_stage(bool material_stage, const ShadeArgs& args, int nblocks, const LaunchGeom& g, bool fixed_mode,
-                        hipStream_t s) {
+                        bool tex_mr, hipStream_t s) {
     ShadeArgs a = args;
     a.shade_vblocks = (uint32_t)nblocks;
     if (!material_stage) {
@@ -2426,7 +2321,7 @@ void launch_shade_stage(bool material_stage, const ShadeArgs& args, int nblocks,
         } else if (fixed_mode) hipLaunchKernelGGL((k_shade<true, false, false>), dim3(G), dim3(kBlock), 0, s, a);
         else hipLaunchKernelGGL((k_shade<false, false, false>), dim3(G), dim3(kBlock), 0, s, a);
     } else {
-        launch_material<false, false>(a, g.mat_blocks, fixed_mode, s);
+        launch_material<false, false>(a, g.mat_blocks, fixed_mode, tex_mr, s);
     }
 }
 // Persistent grid: the device's resident waves rounded to a multiple of the shard count.

@@ -365,9 +365,11 @@ struct LaunchGeom {
 
 // ---- wavefront iteration (kernels.hip) ----
 int launch_geometry(int device, LaunchGeom& g);  // device must be current
-void launch_shade(const ShadeArgs& a, int nblocks, const LaunchGeom& g, bool fixed_mode, hipStream_t s);
+// tex_mr: the installed texture set has a metallic-roughness textured material:
+// with a.tex set, k_material<TexMr, ...> in place of k_material's textured instantiation.
+void launch_shade(const ShadeArgs& a, int nblocks, const LaunchGeom& g, bool fixed_mode, bool tex_mr, hipStream_t s);
 void launch_shade_stage(bool material_stage, const ShadeArgs& a, int nblocks, const LaunchGeom& g, bool fixed_mode,
-                        hipStream_t s);
+                        bool tex_mr, hipStream_t s);
 void launch_primary(const ShadeArgs& a, const LaunchGeom& g, hipStream_t s);  // k_primary: after k_shade, before k_trace
 void launch_trace(const TraceArgs& a, const LaunchGeom& g, hipStream_t s);
 void launch_accumulate(CounterBlock* c, uint32_t nparts, uint32_t* occ_gate, hipStream_t s);

@@ -503,7 +503,8 @@ static int enqueue_iteration(mcpt_ctx* c, size_t evbase, bool timing, const int2
     sa.pick_rec = samp && c->es.mis ? c->es.pick_rec.get() : nullptr;
     if (samp) sa.p.vis = c->es.vis;  // 3P bytes: the emitter rays' results behind the two of every path
     // base-colour textures (section 19): only a set with a textured material, in the current record order
-    if (c->tx.textured > 0 && !c->tx.dev_ok)
+    // (a metallic-roughness textured material counts as well: section 20)
+    if (c->tx.shaded() && !c->tx.dev_ok)
         return set_err(c, MCPT_E_INVALID, "textures: no uv stream for the current record order");
     sa.tex = c->tx.view();
     if (int rc = cam_table(c, c->W, c->H, &sa.cam_px, &sa.cam_dir)) return rc;
@@ -511,7 +512,7 @@ static int enqueue_iteration(mcpt_ctx* c, size_t evbase, bool timing, const int2
     const int bpt = (int)f.L.blocks_per_tile;
     if (timing) HIPCHK(c, hipEventRecord(ev(c, evbase + 0), c->stream));
     if (sa.ntiles > 0)
-        launch_shade(sa, sa.ntiles * bpt, c->geom, (c->cfg.flags & MCPT_FLAG_FIXED) != 0, c->stream);
+        launch_shade(sa, sa.ntiles * bpt, c->geom, (c->cfg.flags & MCPT_FLAG_FIXED) != 0, c->tx.textured_mr > 0, c->stream);
     if (timing) HIPCHK(c, hipEventRecord(ev(c, evbase + 1), c->stream));
     // primary rays with a candidate list (part of the extend stage's time)
     if (sa.ntiles > 0) launch_primary(sa, c->geom, c->stream);

@@ -232,27 +232,33 @@ struct Emission {
 // {first texel, w, h, index}.  Only a set with a textured material reaches the kernels (view()): without,
 // the context launches what it launched before.  The uv stream follows the record order, so a rebuild
 // permutes it again (textures_reorder); a scene upload drops the set.
+// Metallic-roughness textures (section 20): mat_mr indexes the same texture list (all -1 where the caller
+// gave none); d_mat holds 2 nmat entries, the MR ones in front and mirrored (material m's at nmat - 1 - m),
+// the base-colour ones behind, where view().mat points (device/texture.hpp TexView).  A set with an
+// MR-textured material launches k_material<TexMr, ...>.
 struct Textures {
     std::vector<float> uv[3];
-    std::vector<int32_t> tw, th, mat_tex;
+    std::vector<int32_t> tw, th, mat_tex, mat_mr;
     std::vector<uint32_t> first;  // texture k's first texel in the atlas
     std::vector<uint32_t> atlas;
     DevBuf<float2> d_uv, d_stage;  // [3 ntri] record order; [3 ntri] desc order, the permutation's input
     DevBuf<uint32_t> d_atlas;
     DevBuf<int4> d_mat;
-    int32_t textured = 0;  // materials with a texture
-    bool dev_ok = false;   // the device arrays stand for the current record order
+    int32_t textured = 0;     // materials with a base-colour texture
+    int32_t textured_mr = 0;  // materials with a metallic-roughness texture
+    bool dev_ok = false;      // the device arrays stand for the current record order
     bool installed() const { return !mat_tex.empty(); }
+    bool shaded() const { return textured > 0 || textured_mr > 0; }  // some material shades through a lookup
     mcpt::TexView view() const {
-        if (!(textured > 0 && dev_ok)) return mcpt::TexView{nullptr, nullptr, nullptr};
-        return mcpt::TexView{d_uv.get(), d_atlas.get(), d_mat.get()};
+        if (!(shaded() && dev_ok)) return mcpt::TexView{nullptr, nullptr, nullptr};
+        return mcpt::TexView{d_uv.get(), d_atlas.get(), d_mat.get() + mat_tex.size()};
     }
     size_t bytes() const { return installed() ? d_uv.bytes() + d_stage.bytes() + d_atlas.bytes() + d_mat.bytes() : 0; }
     void drop() {
         for (auto& u : uv) u.clear();
-        tw.clear(), th.clear(), mat_tex.clear(), first.clear(), atlas.clear();
+        tw.clear(), th.clear(), mat_tex.clear(), mat_mr.clear(), first.clear(), atlas.clear();
         d_uv.reset(), d_stage.reset(), d_atlas.reset(), d_mat.reset();
-        textured = 0;
+        textured = textured_mr = 0;
         dev_ok = false;
     }
 };

@@ -637,7 +637,7 @@ static int textures_uv_stream(mcpt_ctx* c, Textures& t) {
 int textures_reorder(mcpt_ctx* c) { return textures_uv_stream(c, c->tx); }
 
 static int textures_install(mcpt_ctx* c, int32_t ntri, const float* uv0, const float* uv1, const float* uv2, int32_t ntex,
-                            const mcpt_texture* tex, int32_t nmat, const int32_t* mat_tex) {
+                            const mcpt_texture* tex, int32_t nmat, const int32_t* mat_tex, const int32_t* mat_mr) {
     if (!c) return MCPT_E_INVALID;
     if (!c->scene.ok) return set_err(c, MCPT_E_INVALID, "no scene uploaded");
     auto changed = [c] {  // what a changed set means to the film, the history and the guides
@@ -648,7 +648,7 @@ static int textures_install(mcpt_ctx* c, int32_t ntri, const float* uv0, const f
     if (ntex == 0 || !tex) {  // removal
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        const bool was = c->tx.textured > 0;
+        const bool was = c->tx.shaded();
         c->tx.drop();
         if (was) changed();
         return MCPT_OK;
@@ -666,10 +666,15 @@ static int textures_install(mcpt_ctx* c, int32_t ntri, const float* uv0, const f
     }
     for (int32_t m = 0; m < nmat; m++)
         if (mat_tex[m] < -1 || mat_tex[m] >= ntex) return set_err(c, MCPT_E_INVALID, "textures: material texture index out of range");
+    for (int32_t m = 0; mat_mr && m < nmat; m++)
+        if (mat_mr[m] < -1 || mat_mr[m] >= ntex)
+            return set_err(c, MCPT_E_INVALID, "textures: material metallic-roughness texture index out of range");
     Textures now;
     const float* src[3] = {uv0, uv1, uv2};
     for (int k = 0; k < 3; k++) now.uv[k].assign(src[k], src[k] + 2 * (size_t)ntri);
     now.mat_tex.assign(mat_tex, mat_tex + nmat);
+    if (mat_mr) now.mat_mr.assign(mat_mr, mat_mr + nmat);
+    else now.mat_mr.assign((size_t)nmat, -1);
     now.atlas.resize((size_t)total);
     uint32_t at = 0;
     for (int32_t k = 0; k < ntex; k++) {
@@ -678,11 +683,15 @@ static int textures_install(mcpt_ctx* c, int32_t ntri, const float* uv0, const f
         memcpy(now.atlas.data() + at, tex[k].rgba8, px * 4);
         at += (uint32_t)px;
     }
-    std::vector<int4> dm((size_t)nmat);
+    // 2 nmat entries: the base-colour ones at nmat + m (TexView::mat points there), the metallic-roughness
+    // ones in front of them and mirrored, at nmat - 1 - m (TexView::mat[-1 - m]; section 20)
+    std::vector<int4> dm(2 * (size_t)nmat);
+    auto entry = [&now](int32_t k) { return k < 0 ? make_int4(0, 0, 0, -1) : make_int4((int)now.first[k], now.tw[k], now.th[k], k); };
     for (int32_t m = 0; m < nmat; m++) {
-        const int32_t k = mat_tex[m];
-        dm[m] = k < 0 ? make_int4(0, 0, 0, -1) : make_int4((int)now.first[k], now.tw[k], now.th[k], k);
-        now.textured += k >= 0;
+        dm[(size_t)nmat + m] = entry(now.mat_tex[m]);
+        dm[(size_t)nmat - 1 - m] = entry(now.mat_mr[m]);
+        now.textured += now.mat_tex[m] >= 0;
+        now.textured_mr += now.mat_mr[m] >= 0;
     }
     const Textures& was = c->tx;
     auto same_bytes = [](const auto& a, const auto& b) {
@@ -690,7 +699,7 @@ static int textures_install(mcpt_ctx* c, int32_t ntri, const float* uv0, const f
     };
     if (was.installed() && same_bytes(was.uv[0], now.uv[0]) && same_bytes(was.uv[1], now.uv[1]) && same_bytes(was.uv[2], now.uv[2]) &&
         same_bytes(was.tw, now.tw) && same_bytes(was.th, now.th) && same_bytes(was.mat_tex, now.mat_tex) &&
-        same_bytes(was.atlas, now.atlas) && (was.dev_ok || was.textured == 0))
+        same_bytes(was.mat_mr, now.mat_mr) && same_bytes(was.atlas, now.atlas) && (was.dev_ok || !was.shaded()))
         return MCPT_OK;  // an identical set does nothing
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // no launch in flight reads the old set
@@ -701,8 +710,9 @@ static int textures_install(mcpt_ctx* c, int32_t ntri, const float* uv0, const f
     HIPCHK(c, hipMemcpy(now.d_atlas, now.atlas.data(), now.atlas.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     if (!dm.empty()) HIPCHK(c, hipMemcpy(now.d_mat, dm.data(), dm.size() * sizeof(int4), hipMemcpyHostToDevice));
     if (int rc = textures_uv_stream(c, now)) return rc;
-    // what the film depends on is the shaded base colour: a set without a textured material shades as none
-    const bool differs = was.textured > 0 || now.textured > 0;
+    // what the film depends on is what the lookups shade: a set without a textured material (in either
+    // index array) shades as none
+    const bool differs = was.shaded() || now.shaded();
     c->tx = std::move(now);
     if (differs) changed();
     return MCPT_OK;
@@ -712,7 +722,23 @@ extern "C" {
 
 int mcpt_set_material_textures(mcpt_ctx* c, int32_t ntri, const float* uv0, const float* uv1, const float* uv2, int32_t ntex,
                                const mcpt_texture* textures, int32_t nmat, const int32_t* mat_tex) {
-    return textures_install(c, ntri, uv0, uv1, uv2, ntex, textures, nmat, mat_tex);
+    return textures_install(c, ntri, uv0, uv1, uv2, ntex, textures, nmat, mat_tex, nullptr);
+}
+int mcpt_set_material_texture_maps(mcpt_ctx* c, int32_t ntri, const float* uv0, const float* uv1, const float* uv2, int32_t ntex,
+                                   const mcpt_texture* textures, int32_t nmat, const int32_t* mat_tex, const int32_t* mat_mr) {
+    return textures_install(c, ntri, uv0, uv1, uv2, ntex, textures, nmat, mat_tex, mat_mr);
+}
+int mcpt_material_mr_read(mcpt_ctx* c, int32_t* nmat, int32_t* mat_mr) {
+    if (!c) return MCPT_E_INVALID;
+    if (nmat) *nmat = (int32_t)c->tx.mat_mr.size();
+    if (mat_mr && !c->tx.mat_mr.empty()) memcpy(mat_mr, c->tx.mat_mr.data(), c->tx.mat_mr.size() * sizeof(int32_t));
+    return MCPT_OK;
+}
+int mcpt_debug_texture_mr_stats(const mcpt_ctx* c, int32_t* mr_materials, int32_t* mr_in_effect) {
+    if (!c) return MCPT_E_INVALID;
+    if (mr_materials) *mr_materials = c->tx.textured_mr;
+    if (mr_in_effect) *mr_in_effect = c->tx.view().uv && c->tx.textured_mr > 0 ? 1 : 0;
+    return MCPT_OK;
 }
 int mcpt_material_textures_read(mcpt_ctx* c, int32_t* ntri, int32_t* ntex, int32_t* nmat, int32_t* mat_tex, int32_t tex,
                                 int32_t* w, int32_t* h, uint8_t* rgba8, float* uv0, float* uv1, float* uv2) {

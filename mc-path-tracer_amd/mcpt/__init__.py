@@ -223,6 +223,11 @@ ABI = {
     "mcpt_scene_set_material_texture": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "mcpt_scene_get_textures": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(Texture)), _i, C.POINTER(_i), _i]),
     "mcpt_scene_get_uv": (C.c_int, [C.c_void_p, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), _i]),
+    "mcpt_set_material_texture_maps": (C.c_int, [C.c_void_p, C.c_int32, _f, _f, _f, C.c_int32, C.POINTER(Texture), C.c_int32, _i, _i]),
+    "mcpt_material_mr_read": (C.c_int, [C.c_void_p, _i, _i]),
+    "mcpt_debug_texture_mr_stats": (C.c_int, [C.c_void_p, _i, _i]),
+    "mcpt_scene_set_material_mr_texture": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
+    "mcpt_scene_get_material_mr": (C.c_int, [C.c_void_p, C.POINTER(_i), _i]),
     "mcpt_sync": (C.c_int, [C.c_void_p]),
     "mcpt_device_name": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
     "mcpt_debug_queue_rays": (C.c_int, [C.c_void_p, C.c_int, _f, _f, _u]),
@@ -417,15 +422,32 @@ class Scene:
         return self._ck(lib().mcpt_scene_set_material_texture(self.h, int(mat), img.shape[1], img.shape[0],
                                                               img.ctypes.data_as(C.POINTER(C.c_uint8))))
 
+    def set_mr_texture(self, mat, img_u8):
+        """Attach a metallic-roughness texture to material ``mat``: an image as
+        set_texture takes it, whose G channel scales the material's roughness and whose B channel its
+        metallic (R and alpha ignored; used as stored).  None detaches.  Independent of the material's
+        base-colour texture; PathTracer.upload_scene installs it with the rest."""
+        if img_u8 is None:
+            return self._ck(lib().mcpt_scene_set_material_mr_texture(self.h, int(mat), 0, 0, None))
+        img = _rgba8(img_u8)
+        return self._ck(lib().mcpt_scene_set_material_mr_texture(self.h, int(mat), img.shape[1], img.shape[0],
+                                                                 img.ctypes.data_as(C.POINTER(C.c_uint8))))
+
     def textures(self):
-        """None when no material has a texture, else {"textures": [(h, w, 4) uint8, ...], "mat_tex": int32
-        (nmat,)} (copies)."""
+        """None when no material has a texture of either kind, else {"textures": [(h, w, 4) uint8, ...],
+        "mat_tex": int32 (nmat,), "mat_mr": int32 (nmat,)} (copies): per material the index of its
+        base-colour and of its metallic-roughness texture in the one list, or -1."""
         t, mt, nt, nm = C.POINTER(Texture)(), _i(), C.c_int32(0), C.c_int32(0)
         _check(lib().mcpt_scene_get_textures(self.h, C.byref(t), C.byref(nt), C.byref(mt), C.byref(nm)))
         if not t or nt.value == 0:
             return None
         imgs = [np.ctypeslib.as_array(t[k].rgba8, shape=(t[k].h, t[k].w, 4)).copy() for k in range(nt.value)]
-        return {"textures": imgs, "mat_tex": _arr(mt, nm.value, np.int32)}
+        out = {"textures": imgs, "mat_tex": _arr(mt, nm.value, np.int32), "mat_mr": np.full(nm.value, -1, np.int32)}
+        if hasattr(lib(), "mcpt_scene_get_material_mr"):  # (an older variant library has none)
+            mr, nr = _i(), C.c_int32(0)
+            _check(lib().mcpt_scene_get_material_mr(self.h, C.byref(mr), C.byref(nr)))
+            out["mat_mr"] = _arr(mr, nr.value, np.int32)
+        return out
 
     def uv(self):
         """The built scene's corner uvs (uv0, uv1, uv2), (ntri, 2) each, in the desc's triangle order."""
@@ -589,13 +611,15 @@ class PathTracer:
         if isinstance(scene, Scene) and hasattr(lib(), "mcpt_scene_get_textures"):
             t = scene.textures()
             if t is not None:
-                self.set_textures(*scene.uv(), t["textures"], t["mat_tex"])
+                self.set_textures(*scene.uv(), t["textures"], t["mat_tex"], mat_mr=t["mat_mr"] if (t["mat_mr"] >= 0).any() else None)
 
-    def set_textures(self, uv0=None, uv1=None, uv2=None, textures=None, mat_tex=None):
+    def set_textures(self, uv0=None, uv1=None, uv2=None, textures=None, mat_tex=None, mat_mr=None):
         """Base-colour textures (mcpt_set_material_textures): the corner uvs, (ntri, 2)
         each in the uploaded desc's triangle order, a list of (h, w, 4) / (h, w, 3) uint8 images, and per
         material a texture index or -1.  No arguments (or no textures) remove the set.  A change clears the
-        film at the next render and makes the guide buffers stale."""
+        film at the next render and makes the guide buffers stale.
+        mat_mr (mcpt_set_material_texture_maps; section 20): per material the index of its
+        metallic-roughness texture in the same list, or -1; None: no material has one (the older call)."""
         if not textures:
             self._ck(lib().mcpt_set_material_textures(self.h, 0, None, None, None, 0, None, 0, None))
             return
@@ -608,12 +632,19 @@ class PathTracer:
             arr[k].w, arr[k].h = im.shape[1], im.shape[0]
             arr[k].rgba8 = im.ctypes.data_as(C.POINTER(C.c_uint8))
         mt = np.ascontiguousarray(mat_tex, np.int32).reshape(-1)
-        self._ck(lib().mcpt_set_material_textures(self.h, len(u[0]), fptr(u[0]), fptr(u[1]), fptr(u[2]), len(imgs), arr,
-                                                  len(mt), mt.ctypes.data_as(_i)))
+        if mat_mr is None:
+            self._ck(lib().mcpt_set_material_textures(self.h, len(u[0]), fptr(u[0]), fptr(u[1]), fptr(u[2]), len(imgs), arr,
+                                                      len(mt), mt.ctypes.data_as(_i)))
+            return
+        mr = np.ascontiguousarray(mat_mr, np.int32).reshape(-1)
+        if len(mr) != len(mt):
+            raise ValueError("mat_tex and mat_mr must have one entry per material")
+        self._ck(lib().mcpt_set_material_texture_maps(self.h, len(u[0]), fptr(u[0]), fptr(u[1]), fptr(u[2]), len(imgs), arr,
+                                                      len(mt), mt.ctypes.data_as(_i), mr.ctypes.data_as(_i)))
 
     def textures(self):
         """The installed set as {"uv0", "uv1", "uv2": (ntri, 2), "textures": [(h, w, 4) uint8], "mat_tex":
-        int32 (nmat,)}, or None when none is installed."""
+        int32 (nmat,), "mat_mr": int32 (nmat,)}, or None when none is installed."""
         nt, nx, nm = C.c_int32(0), C.c_int32(0), C.c_int32(0)
         L = lib().mcpt_material_textures_read
         self._ck(L(self.h, C.byref(nt), C.byref(nx), C.byref(nm), None, -1, None, None, None, None, None, None))
@@ -629,7 +660,10 @@ class PathTracer:
             im = np.zeros((h.value, w.value, 4), np.uint8)
             self._ck(L(self.h, None, None, None, None, k, None, None, im.ctypes.data_as(C.POINTER(C.c_uint8)), None, None, None))
             imgs.append(im)
-        return {"uv0": u[0], "uv1": u[1], "uv2": u[2], "textures": imgs, "mat_tex": mt}
+        mr = np.full(nm.value, -1, np.int32)
+        if hasattr(lib(), "mcpt_material_mr_read"):  # (an older variant library has none)
+            self._ck(lib().mcpt_material_mr_read(self.h, None, mr.ctypes.data_as(_i)))
+        return {"uv0": u[0], "uv1": u[1], "uv2": u[2], "textures": imgs, "mat_tex": mt, "mat_mr": mr}
 
     def texture_sample(self, img, uv):
         """The texture lookup alone on the device (mcpt_texture_sample_run): (n, 3) float32 for (n, 2) uvs
@@ -642,11 +676,21 @@ class PathTracer:
         return out
 
     def texture_stats(self):
-        """dict: device bytes the installed set holds, materials with a texture, and whether the textured
-        kernels are in effect (mcpt_debug_texture_stats)."""
+        """dict: device bytes the installed set holds, materials with a base-colour texture, and whether
+        textured kernels (of either kind) are in effect (mcpt_debug_texture_stats).  While a set is installed
+        also "mr_materials", the materials with a metallic-roughness texture, and "mr_in_effect", whether the
+        metallic-roughness kernels are (mcpt_debug_texture_mr_stats); a context without a set returns the
+        three keys it always returned (read the other two with .get)."""
         b, m, on = C.c_uint64(0), C.c_int32(0), C.c_int32(0)
         self._ck(lib().mcpt_debug_texture_stats(self.h, C.byref(b), C.byref(m), C.byref(on)))
-        return {"bytes": int(b.value), "textured_materials": int(m.value), "in_effect": bool(on.value)}
+        out = {"bytes": int(b.value), "textured_materials": int(m.value), "in_effect": bool(on.value)}
+        if hasattr(lib(), "mcpt_debug_texture_mr_stats"):  # (an older variant library has none)
+            n = C.c_int32(0)
+            self._ck(lib().mcpt_material_mr_read(self.h, C.byref(n), None))
+            if n.value:
+                self._ck(lib().mcpt_debug_texture_mr_stats(self.h, C.byref(m), C.byref(on)))
+                out["mr_materials"], out["mr_in_effect"] = int(m.value), bool(on.value)
+        return out
 
     def set_emission(self, rgb=None):
         """Per-material emitted radiance, (nmat, 3) for the uploaded scene's materials, or None to

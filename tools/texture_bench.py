@@ -13,6 +13,12 @@ kernel trace of this program separates them:
 
 The ray counts of the two cases differ beyond rr_depth (the roulette tests a throughput the base colour
 has scaled), so the figures come with the material evaluations (= shadow rays) of a frame.
+
+--mr (profiles/textures_mr.json): the same setup with a second 1024 x 1024 image on
+the same walls as their metallic-roughness texture (G, B in 64..255: the walls' roughness 1 becomes 0.25
+.. 1 per hit, their metallic 0 stays 0), frames with the base-colour set alone and with base + MR alternating on one context: k_material's textured
+instantiation against k_material<TexMr, ...> (a name of its own in the trace).  The counts change with the set at
+every depth (F_FZERO), so the cost per material evaluation is reported too.
 Prints one JSON line.
 """
 import argparse
@@ -38,9 +44,11 @@ def kstats(d):
     for path in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
         for row in csv.DictReader(open(path)):
             m = re.search(r"k_material<(\w+), (\w+), (\w+), (\w+)>", row["Name"])
-            if not m:
+            r = re.search(r"k_material<(?:\w+::)*TexMr, (\w+), (\w+), (\w+)>", row["Name"])
+            if not (m or r):
                 continue
-            key = "fixed=%s samp=%s mis=%s tex=%s" % tuple(int(x in ("true", "1")) for x in m.groups())
+            key = "fixed=%s samp=%s mis=%s tex=%s" % tuple(int(x in ("true", "1")) for x in m.groups()) if m else \
+                "fixed=%s samp=%s mis=%s tex=mr" % tuple(int(x in ("true", "1")) for x in r.groups())
             out[key] = {"calls": int(row["Calls"]), "total_ms": float(row["TotalDurationNs"]) / 1e6,
                         "us_per_launch": float(row["AverageNs"]) / 1e3}
     return out
@@ -62,6 +70,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--spp", type=int, default=None)
+    ap.add_argument("--mr", action="store_true", help="base-colour set against base + metallic-roughness (section 20)")
     ap.add_argument("--kstats", metavar="DIR", default=None, help="summarise a kernel trace of this program and exit")
     a = ap.parse_args()
     if a.kstats:
@@ -76,6 +85,9 @@ def main():
     walls = (0, 1, 2, 3, 4)
     uv, imgs, mat_tex = wall_set(scene.arrays(), a.size, walls)
     pt = mcpt.PathTracer(0, mcpt.default_config(spp=spp, max_depth=rc.max_depth))
+    if a.mr:  # a second image on the same walls, both index arrays set
+        imgs = imgs + [np.random.default_rng(20).integers(64, 256, (a.size, a.size, 4)).astype(np.uint8)]
+        mat_mr = np.where(mat_tex >= 0, 1, -1).astype(np.int32)
     pt.upload_scene(scene)
     pt.set_camera(mcpt.config_camera(rc))
     pt.set_path_slots(slots)
@@ -84,10 +96,12 @@ def main():
     def case(k):
         if k == "walls_textured":
             pt.set_textures(*uv, imgs, mat_tex)
+        elif k == "walls_textured_mr":
+            pt.set_textures(*uv, imgs, mat_tex, mat_mr=mat_mr)
         else:
             pt.set_textures()
 
-    rows = {"none": [], "walls_textured": []}
+    rows = {"walls_textured": [], "walls_textured_mr": []} if a.mr else {"none": [], "walls_textured": []}
     shade = {k: [] for k in rows}
     iters, rays, stats = {}, {}, {}
     for i in range(a.warmup + a.repeats):
@@ -105,6 +119,10 @@ def main():
                 shade[k].append(st.ms_shade / max(1, st.iterations))
     pt.close()
     med = lambda v: float(statistics.median(v))
+    extra = {}
+    if a.mr:  # the counts differ between the two sets: cost per material evaluation (= shadow ray)
+        extra["frame_ns_per_material_evaluation"] = {k: 1e6 * med(v) / max(1, rays[k][1]) for k, v in rows.items()}
+        extra["shade_stage_ns_per_material_evaluation"] = {k: 1e6 * med(v) * iters[k] / max(1, rays[k][1]) for k, v in shade.items()}
     print(json.dumps({
         "config": 2, "frame": [rc.width, rc.height], "spp": spp, "slots": slots, "repeats": a.repeats,
         "texture": [a.size, a.size], "textured_materials": list(walls), "device": pt.device,
@@ -112,7 +130,7 @@ def main():
         "ms_per_frame_all": {k: [round(x, 3) for x in v] for k, v in rows.items()},
         "shade_stage_ms_per_iteration_median": {k: med(v) for k, v in shade.items()},
         "iterations_per_frame": iters, "rays": rays, "material_evaluations": {k: v[1] for k, v in rays.items()},
-        "texture_stats": stats}))
+        "texture_stats": stats, **extra}))
 
 
 if __name__ == "__main__":
