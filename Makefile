@@ -12,7 +12,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-f
             -fhip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-function -Iinclude -I$(PKG)/csrc $(EXTRA_HIPFLAGS)
 SRCS := $(PKG)/csrc/kernels.hip $(PKG)/csrc/scene_tables.hip $(PKG)/csrc/film.hip $(PKG)/csrc/bvh_build.hip $(PKG)/csrc/env_build.hip $(PKG)/csrc/denoise.hip $(PKG)/csrc/adaptive.hip $(PKG)/csrc/temporal.hip $(PKG)/csrc/variance.hip $(PKG)/csrc/refit.hip $(PKG)/csrc/emitter.hip $(PKG)/csrc/texture.hip $(PKG)/csrc/runtime.cpp $(PKG)/csrc/film_state.cpp $(PKG)/csrc/stage_run.cpp $(PKG)/csrc/scene_upload.cpp $(PKG)/csrc/postprocess.cpp \
         $(PKG)/csrc/host/scene.cpp $(PKG)/csrc/host/proxies.cpp $(PKG)/csrc/host/capi_host.cpp $(PKG)/csrc/host/pair_tree.cpp \
-        $(PKG)/csrc/host/image_io.cpp $(PKG)/csrc/host/emitter_table.cpp
+        $(PKG)/csrc/host/image_io.cpp $(PKG)/csrc/host/emitter_table.cpp $(PKG)/csrc/host/tangents.cpp
 OBJS := $(patsubst $(PKG)/csrc/%,$(BUILD)/%.o,$(SRCS))
 HDRS := include/mcpt.h $(PKG)/csrc/kernels.hpp $(PKG)/csrc/device/mcpt_core.hpp $(PKG)/csrc/device/scene_dev.hpp \
         $(PKG)/csrc/device/primary_beam.hpp $(PKG)/csrc/device/occ_beam.hpp $(PKG)/csrc/device/denoise.hpp $(PKG)/csrc/device/adaptive.hpp $(PKG)/csrc/device/temporal.hpp $(PKG)/csrc/device/variance.hpp $(PKG)/csrc/device/texture.hpp $(PKG)/csrc/device/k_material_body.inc \

@@ -3,7 +3,7 @@
 // INTEGRATION.md): build a BASELINE config scene with the host builder, upload it,
 // run the wavefront iterations until every pixel has its samples, write PNG + PFM.
 //
-//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>] [--emissive <mat> <r> <g> <b>]... [--env-color <r> <g> <b>] [--sample-emitters] [--emitter-mis] [--checker <mat> <n>]... [--checker-mr <mat> <n>]...
+//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>] [--emissive <mat> <r> <g> <b>]... [--env-color <r> <g> <b>] [--sample-emitters] [--emitter-mis] [--checker <mat> <n>]... [--checker-mr <mat> <n>]... [--bumps <mat> <n> <scale>]...
 //
 // --denoise renders the first-hit guide buffers (default 4 guide samples per pixel), filters the film
 // with the default parameters and writes <out_prefix>_denoised.png beside the raw image.
@@ -42,6 +42,9 @@
 // filter softens only the squares' edges) on material <mat> as its base-colour texture (DESIGN.md section
 // 19; repeatable), over the uvs the mesh came with: `mcpt_render 1 64 --checker 0 8` is config 1's mesh
 // (Cube.glb, each face a quarter of the uv square wide) with 2 x 2 squares per face.
+// --bumps puts an <n> x <n> grid of procedural dimples (16 x 16 texels each) on material <mat> as its
+// tangent-space normal map with the given scale (repeatable), with the built scene's
+// tangents: `mcpt_render 2 64 --bumps 0 8 1.0` is config 2 with a dimpled wall.
 // --checker-mr puts the same checker on material <mat> as its metallic-roughness texture (DESIGN.md section
 // 20; repeatable) and sets the material's metallic factor to 1: the squares alternate G = B = 255 (rough
 // metal: the material's own roughness) with G = 26, B = 255 (roughness a tenth of it: near-mirror metal).
@@ -76,7 +79,7 @@ static void warp(const mcpt_scene_desc& d, float amp, uint32_t frame, uint32_t f
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>] [--emissive <mat> <r> <g> <b>]... [--env-color <r> <g> <b>] [--sample-emitters] [--emitter-mis] [--checker <mat> <n>]... [--checker-mr <mat> <n>]...\n", argv[0]);
+        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>] [--emissive <mat> <r> <g> <b>]... [--env-color <r> <g> <b>] [--sample-emitters] [--emitter-mis] [--checker <mat> <n>]... [--checker-mr <mat> <n>]... [--bumps <mat> <n> <scale>]...\n", argv[0]);
         return 2;
     }
     const Cfg cfgs[6] = {{0, 0, 0, 0, {0, 0, 0}, 0, ""},
@@ -103,6 +106,7 @@ int main(int argc, char** argv) {
     std::vector<float> emissive;  // --emissive: {mat, r, g, b} per use
     std::vector<int> checker;     // --checker: {mat, n} per use
     std::vector<int> checker_mr;  // --checker-mr: {mat, n} per use
+    std::vector<float> bumps;     // --bumps: {mat, n, scale} per use
     float env_rgb[3] = {0.f, 0.f, 0.f};
     bool env_given = false;
     for (int i = 2; i < argc; i++) {
@@ -124,6 +128,16 @@ int main(int argc, char** argv) {
             }
             checker.push_back(atoi(argv[++i]));
             checker.push_back(atoi(argv[++i]));
+            continue;
+        }
+        if (!strcmp(argv[i], "--bumps")) {
+            if (i + 3 >= argc || atoi(argv[i + 1]) < 0 || atoi(argv[i + 2]) < 1 || atoi(argv[i + 2]) > 1024) {
+                fprintf(stderr, "--bumps needs <mat> <n> <scale> (n in 1..1024)\n");
+                return 2;
+            }
+            bumps.push_back((float)atoi(argv[++i]));
+            bumps.push_back((float)atoi(argv[++i]));
+            bumps.push_back((float)atof(argv[++i]));
             continue;
         }
         if (!strcmp(argv[i], "--checker-mr")) {
@@ -201,6 +215,23 @@ int main(int argc, char** argv) {
             for (int x = 0; x < n; x++) px[4 * ((size_t)y * n + x) + 1] = ((x / sq + y / sq) & 1) ? 255 : 26;
         src = mcpt_scene_set_material_mr_texture(s, checker_mr[k], n, n, px.data());
     }
+    for (size_t k = 0; !src && k < bumps.size(); k += 3) {  // n x n dimples: the normal of the height field -(1 - r^2)^2
+        const int sq = 16, nb = (int)bumps[k + 1], n = nb * sq;
+        std::vector<uint8_t> px((size_t)n * n * 4, 255);
+        for (int y = 0; y < n; y++)
+            for (int x = 0; x < n; x++) {
+                const float fx = ((x % sq) + 0.5f) / sq * 2.f - 1.f, fy = ((y % sq) + 0.5f) / sq * 2.f - 1.f;
+                const float r2 = fx * fx + fy * fy, g = r2 < 1.f ? 4.f * (1.f - r2) : 0.f;  // dh/dr / r of the dimple
+                float nx = -g * fx * 0.5f, ny = -g * fy * 0.5f, nz = 1.f;
+                const float l = sqrtf(nx * nx + ny * ny + nz * nz);
+                nx /= l, ny /= l, nz /= l;
+                uint8_t* q = &px[4 * ((size_t)y * n + x)];
+                q[0] = (uint8_t)lrintf((nx * 0.5f + 0.5f) * 255.f);
+                q[1] = (uint8_t)lrintf((ny * 0.5f + 0.5f) * 255.f);
+                q[2] = (uint8_t)lrintf((nz * 0.5f + 0.5f) * 255.f);
+            }
+        src = mcpt_scene_set_material_normal_texture(s, (int32_t)bumps[k], n, n, px.data(), bumps[k + 2]);
+    }
     if (src || (ref_bvh ? mcpt_scene_build(s, 8) : mcpt_scene_build_ex(s, &bp))) {
         fprintf(stderr, "scene: %s\n", mcpt_last_error(nullptr));
         return 1;
@@ -232,8 +263,19 @@ int main(int argc, char** argv) {
         int32_t ntex = 0, nmat = 0, ntri = 0, nmr = 0;
         if (!rc) rc = mcpt_scene_get_textures(s, &tex, &ntex, &mat_tex, &nmat);
         if (!rc) rc = mcpt_scene_get_material_mr(s, &mat_mr, &nmr);
-        if (!rc && tex && !(rc = mcpt_scene_get_uv(s, &uv0, &uv1, &uv2, &ntri)))
-            rc = mcpt_set_material_texture_maps(ctx, ntri, uv0, uv1, uv2, ntex, tex, nmat, mat_tex, mat_mr);
+        if (!rc && tex && !(rc = mcpt_scene_get_uv(s, &uv0, &uv1, &uv2, &ntri))) {
+            if (bumps.empty()) {
+                rc = mcpt_set_material_texture_maps(ctx, ntri, uv0, uv1, uv2, ntex, tex, nmat, mat_tex, mat_mr);
+            } else {  // --bumps: the scene's tangents, normal indices and scales as well
+                const int32_t* mat_nrm = nullptr;
+                const float *nrm_scale = nullptr, *t0 = nullptr, *t1 = nullptr, *t2 = nullptr;
+                int32_t nn = 0, nt = 0;
+                rc = mcpt_scene_get_material_normal(s, &mat_nrm, &nrm_scale, &nn);
+                if (!rc) rc = mcpt_scene_get_tangents(s, &t0, &t1, &t2, &nt);
+                const mcpt_texture_set set{ntri, uv0, uv1, uv2, t0, t1, t2, ntex, tex, nmat, mat_tex, mat_mr, mat_nrm, nrm_scale};
+                if (!rc) rc = mcpt_set_material_texture_set(ctx, &set);
+            }
+        }
     }
     if (!rc && sample_emitters) rc = mcpt_set_emitter_sampling(ctx, 1);
     if (!rc && emitter_mis) rc = mcpt_set_emitter_mis(ctx, 1);

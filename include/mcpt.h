@@ -695,6 +695,76 @@ int mcpt_set_material_texture_maps(mcpt_ctx *ctx, int32_t ntri, const float *uv0
                                    const int32_t *mat_mr);
 int mcpt_material_mr_read(mcpt_ctx *ctx, int32_t *nmat, int32_t *mat_mr);
 int mcpt_debug_texture_mr_stats(const mcpt_ctx *ctx, int32_t *mr_materials, int32_t *mr_in_effect);
+/* ---- normal-map textures: per-hit shading normals from a tangent-space lookup at
+ * the same texture coordinate tc, in a texture of the same list.  For a hit on a triangle with vertex
+ * normals N_i and vertex tangents (T_i, s_i), i = 0, 1, 2, all fp32 in this order:
+ *   t   = the section-19 lookup of the material's normal texture at tc, unchanged, over rgb
+ *   c.x = (2 t.x - 1) * scale    c.y = (2 t.y - 1) * scale    c.z = 2 t.z - 1         (glTF: z is "up")
+ *   B_i = cross(N_i, T_i) * s_i                                                          glTF's bitangent
+ *   m_i = (T_i * c.x + B_i * c.y) + N_i * c.z                                            per vertex
+ *   nrm = normalize(normalize((m_1 * u + m_2 * v) + m_0 * w))           the hit record's two lines, on m_i
+ * The perturbation is applied to the three vertex normals before the hit record interpolates them;
+ * interpolation is linear, so this is the usual perturbation of the interpolated frame.  glTF's inner
+ * normalize(c) is left out (a positive scalar the hit record's normalisation removes).  A material whose
+ * normal index is -1 keeps N_i.  Texels are used as stored; alpha is ignored.  nrm stands for the hit's
+ * normal everywhere the material stage reads it: the sampling frames, every f and pdf, the emitter sample
+ * and its MIS pdf, and the offsets of the ray origins.  There is no separate geometric normal: a strong
+ * perturbation can let light leak through a surface (DESIGN.md names a geometric-normal guard as a
+ * follow-up).  Ray counts depend on the set at every depth.  The first-hit normal guide accumulates nrm; the
+ * albedo guide is unchanged.
+ *
+ * mcpt_texture_set describes a whole set; NULL means absent.  ntri .. mat_mr are the arguments of
+ * mcpt_set_material_texture_maps.  tan0 / tan1 / tan2: 4 ntri floats each, {T.x, T.y, T.z, s} of corner 0 /
+ * 1 / 2 per triangle, in the uploaded desc's triangle order (mcpt_tangents_from_uv makes them; all three or
+ * none).  mat_nrm[m]: the normal texture of material m in the same list, or -1 (NULL: all -1).  nrm_scale:
+ * one float per material (NULL: all 1).
+ * mcpt_set_material_texture_set installs it.  mcpt_set_material_textures and mcpt_set_material_texture_maps
+ * are this call with the new fields NULL, and behave as before.  Every rule of those calls holds for the new
+ * arrays: everything is copied and checked before anything changes, MCPT_E_INVALID leaves the installed
+ * set, a bitwise-identical set (the new fields and their absence included) does nothing, a differing one
+ * marks the film stale, drops the temporal history and makes the guides stale (unless it differs only in
+ * normal-map fields that no lookup reads: their presence, the scale of a material without a normal map, the
+ * tangents while no material has one; such a set is installed and read back, nothing else), a geometry update keeps the
+ * set (a rebuild permutes the tangent stream with the uv stream), an upload drops it.  Refused beyond the
+ * older calls' refusals: a mat_nrm index outside [-1, ntex), a non-negative mat_nrm entry without tangents,
+ * a non-finite nrm_scale or tangent component, one or two of the three tangent arrays.
+ * A set with a normal-mapped material launches k_material's normal-map instantiations (base colour, MR and
+ * normal per material); every other set launches what it launched before.
+ * mcpt_material_normal_read: *nmat (0: no set installed, or one installed without any of the new fields)
+ * and *ntri_tan (the triangles the installed tangents cover: 0 without tangents), then whichever of mat_nrm
+ * (nmat), nrm_scale (nmat), tan0 / tan1 / tan2 (4 ntri_tan floats each) is not NULL.
+ * mcpt_debug_texture_normal_stats: materials with a normal map, and 1 / 0 for whether the normal-map kernels
+ * are in effect (either may be NULL).  mcpt_debug_texture_stats' in_effect is 1 whenever any textured level
+ * is launched. */
+typedef struct mcpt_texture_set {
+    int32_t ntri;
+    const float *uv0, *uv1, *uv2;
+    const float *tan0, *tan1, *tan2;
+    int32_t ntex;
+    const mcpt_texture *textures;
+    int32_t nmat;
+    const int32_t *mat_tex, *mat_mr, *mat_nrm;
+    const float *nrm_scale;
+} mcpt_texture_set;
+int mcpt_set_material_texture_set(mcpt_ctx *ctx, const mcpt_texture_set *set);
+int mcpt_material_normal_read(mcpt_ctx *ctx, int32_t *nmat, int32_t *ntri_tan, int32_t *mat_nrm, float *nrm_scale, float *tan0,
+                              float *tan1, float *tan2);
+int mcpt_debug_texture_normal_stats(const mcpt_ctx *ctx, int32_t *nrm_materials, int32_t *nrm_in_effect);
+/* Vertex tangents from texture coordinates (host/tangents.cpp; no device call).  Per triangle, in double on
+ * the float inputs and in this order:
+ *   e1 = v1 - v0, e2 = v2 - v0;  (du1, dv1) = uv1 - uv0, (du2, dv2) = uv2 - uv0
+ *   det = du1 * dv2 - du2 * dv1;  r = 1 / det
+ *   Tt = (e1 * dv2 - e2 * dv1) * r        Bt = (e2 * du1 - e1 * du2) * r
+ * and per corner i with normal N_i (dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z):
+ *   q = Tt - N_i * dot(N_i, Tt);  l = sqrt(dot(q, q));  T_i = q / l
+ *   s_i = -1 if dot(cross(N_i, T_i), Bt) < 0, else +1
+ * rounded to float into tan_i[4 t ..] = {T_i, s_i}.  Where det is 0 or not finite, or l is 0 or not finite:
+ * T_i = normalize(cross(N_i, e_k)), e_k the coordinate axis of N_i's smallest component in magnitude (the
+ * first such on a tie), or (1, 0, 0) where that cross has no finite non-zero length; s_i = +1.
+ * Arrays: 3 ntri floats (v, n), 2 ntri (uv), 4 ntri (tan).  MCPT_E_INVALID on a NULL array or ntri < 0. */
+int mcpt_tangents_from_uv(int32_t ntri, const float *v0, const float *v1, const float *v2, const float *n0, const float *n1,
+                          const float *n2, const float *uv0, const float *uv1, const float *uv2, float *tan0, float *tan1,
+                          float *tan2);
 int mcpt_sync(mcpt_ctx *ctx);
 int mcpt_device_name(mcpt_ctx *ctx, char *buf, int32_t len);
 /* diagnostics: rays of the current extension (which=0) or any-hit (which=1) queue, and the
@@ -832,6 +902,19 @@ int mcpt_scene_get_uv(const mcpt_scene *s, const float **uv0, const float **uv1,
  * mcpt_scene_get_material_mr: the nmat MR indices into that list (-1: none), owned by the scene. */
 int mcpt_scene_set_material_mr_texture(mcpt_scene *s, int32_t mat, int32_t w, int32_t h, const uint8_t *rgba8);
 int mcpt_scene_get_material_mr(const mcpt_scene *s, const int32_t **mat_mr, int32_t *nmat);
+/* Normal maps (mcpt_set_material_texture_set takes what the getters return).
+ * mcpt_scene_set_material_normal_texture: attaches a copy of the w x h RGBA8 image to material mat as its
+ * tangent-space normal map with the given scale (finite, or refused), replacing its previous one; rgba8 ==
+ * NULL detaches.  The other refusals are mcpt_scene_set_material_texture's.  The image joins the one list
+ * mcpt_scene_get_textures returns, which hands that list out when a material has a texture of any kind.
+ * mcpt_scene_get_material_normal: the nmat normal indices into that list (-1: none) and the nmat scales (1
+ * where none was set), owned by the scene.
+ * mcpt_scene_get_tangents: the built scene's vertex tangents, mcpt_tangents_from_uv over its vertices,
+ * normals and uvs, 4 ntri floats per corner in the desc's triangle order, owned by the scene (valid until
+ * the scene changes or is built again). */
+int mcpt_scene_set_material_normal_texture(mcpt_scene *s, int32_t mat, int32_t w, int32_t h, const uint8_t *rgba8, float scale);
+int mcpt_scene_get_material_normal(const mcpt_scene *s, const int32_t **mat_nrm, const float **nrm_scale, int32_t *nmat);
+int mcpt_scene_get_tangents(const mcpt_scene *s, const float **tan0, const float **tan1, const float **tan2, int32_t *ntri);
 int mcpt_scene_set_env_hdr(mcpt_scene *s, const char *path, int32_t mode);
 /* flags MCPT_ENV_DEVICE_TABLES: keep the texture only; mcpt_scene_upload then builds the tables on
  * the device (for large maps: the host build is several serial passes over every texel). */

@@ -277,8 +277,45 @@ public:
         detail::check(mcpt_scene_get_material_mr(s_, &mr, &nmat), nullptr, "Scene::material_mr");
         return std::vector<int32_t>(mr, mr + nmat);
     }
-    // The built scene's textures (of both kinds) and uvs onto a context that holds its upload (nothing
-    // without a texture)
+    // MI355X extension: normal maps (mcpt.h).  A decoded w x h RGBA8 tangent-space
+    // normal map on material `mat` (empty: detach) with a scale on its R and G components; independent of
+    // the material's other textures.
+    void set_material_normal_texture(int32_t mat, int32_t w, int32_t h, const std::vector<uint8_t>& rgba8, float scale = 1.f) {
+        if (!rgba8.empty() && rgba8.size() != (size_t)w * (size_t)h * 4)
+            throw Error(MCPT_E_INVALID, "Scene::set_material_normal_texture: w * h * 4 bytes");
+        detail::check(mcpt_scene_set_material_normal_texture(s_, mat, w, h, rgba8.empty() ? nullptr : rgba8.data(), scale), nullptr,
+                      "Scene::set_material_normal_texture");
+        notify();
+    }
+    // Per material the index of its normal map in the scene's texture list, or -1
+    std::vector<int32_t> material_normal() const {
+        const int32_t* mn = nullptr;
+        const float* sc = nullptr;
+        int32_t nmat = 0;
+        detail::check(mcpt_scene_get_material_normal(s_, &mn, &sc, &nmat), nullptr, "Scene::material_normal");
+        return std::vector<int32_t>(mn, mn + nmat);
+    }
+    // Per material the scale of its normal map (1 where none was set)
+    std::vector<float> material_normal_scale() const {
+        const int32_t* mn = nullptr;
+        const float* sc = nullptr;
+        int32_t nmat = 0;
+        detail::check(mcpt_scene_get_material_normal(s_, &mn, &sc, &nmat), nullptr, "Scene::material_normal_scale");
+        return std::vector<float>(sc, sc + nmat);
+    }
+    // The built scene's vertex tangents: corner k's {T.x, T.y, T.z, s}, 4 floats per triangle in the desc's
+    // triangle order (mcpt_tangents_from_uv over the built vertices, normals and uvs)
+    std::array<std::vector<float>, 3> tangents() const {
+        const float* t[3] = {nullptr, nullptr, nullptr};
+        int32_t ntri = 0;
+        detail::check(mcpt_scene_get_tangents(s_, &t[0], &t[1], &t[2], &ntri), nullptr, "Scene::tangents");
+        std::array<std::vector<float>, 3> out;
+        for (int k = 0; k < 3; k++) out[k].assign(t[k], t[k] + 4 * (size_t)ntri);
+        return out;
+    }
+    // The built scene's textures (of every kind) and uvs onto a context that holds its upload (nothing
+    // without a texture); with a normal map, the scene's tangents and scales through
+    // mcpt_set_material_texture_set, else the older call
     void install_textures(mcpt_ctx* ctx) const {
         const mcpt_texture* tex = nullptr;
         const int32_t *mat_tex = nullptr, *mat_mr = nullptr;
@@ -288,6 +325,20 @@ public:
         detail::check(mcpt_scene_get_material_mr(s_, &mat_mr, &nmr), nullptr, "Scene::install_textures");
         const float *uv0 = nullptr, *uv1 = nullptr, *uv2 = nullptr;
         detail::check(mcpt_scene_get_uv(s_, &uv0, &uv1, &uv2, &ntri), nullptr, "Scene::install_textures");
+        const int32_t* mat_nrm = nullptr;
+        const float* nrm_scale = nullptr;
+        int32_t nn = 0;
+        detail::check(mcpt_scene_get_material_normal(s_, &mat_nrm, &nrm_scale, &nn), nullptr, "Scene::install_textures");
+        bool mapped = false;
+        for (int32_t m = 0; m < nn; m++) mapped = mapped || mat_nrm[m] >= 0;
+        if (mapped) {
+            const float *t0 = nullptr, *t1 = nullptr, *t2 = nullptr;
+            int32_t nt = 0;
+            detail::check(mcpt_scene_get_tangents(s_, &t0, &t1, &t2, &nt), nullptr, "Scene::install_textures");
+            const mcpt_texture_set set{ntri, uv0, uv1, uv2, t0, t1, t2, ntex, tex, nmat, mat_tex, mat_mr, mat_nrm, nrm_scale};
+            detail::check(mcpt_set_material_texture_set(ctx, &set), ctx, "scene textures");
+            return;
+        }
         detail::check(mcpt_set_material_texture_maps(ctx, ntri, uv0, uv1, uv2, ntex, tex, nmat, mat_tex, mat_mr), ctx,
                       "scene textures");
     }

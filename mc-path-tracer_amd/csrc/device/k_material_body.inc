@@ -2,8 +2,9 @@
 // one text, so that k_material's instantiations stay the code they were while k_material<TexMr, ...> adds the
 // metallic-roughness level (DESIGN.md section 20).  The including kernel defines
 //   FIXED, SAMP, MIS   its template arguments
-//   TEX                the texture level: 0 none, 1 base colour, 2 base colour and metallic-roughness
-//   tex_stash          level 2: the block's 5 x kBlock LDS floats (material()); else nullptr
+//   TEX                the texture level: 0 none, 1 base colour, 2 base colour and metallic-roughness,
+//                      3 those and the normal map (DESIGN.md section 21)
+//   tex_stash          levels 2 and 3: the block's 5 x kBlock LDS floats (material()); else nullptr
     const ShadeArgs& a = kernarg_fresh<ShadeArgs>();
     if (a.cnt->idle) return;  // the tile set is complete
     const uint32_t shard = blockIdx.x % kShards, w_in = blockIdx.x / kShards, bps = gridDim.x / kShards;

@@ -63,6 +63,54 @@ __device__ inline void hit_record_t(const DevScene& sc, const float2* uvs, V3 o,
         tv = mcpt::tex_coord(u, v, w, c0.y, c1.y, c2.y);
     }
 }
+// hit_record_t<true> under normal maps (device/texture.hpp): the material's normal
+// texture is looked up at the hit's texture coordinate, the three vertex normals are perturbed with the
+// record's vertex tangents (a material without a normal map keeps them: selection), and the hit record's own
+// two normalisation lines run on the result.
+// Registers decide the order of the loads.  k_material's sampling instantiations sit at the 128 VGPRs of four
+// waves per SIMD, and whatever this function holds across the lookup's two dependent fetches (the material's
+// entry, then four gathers) comes on top of what the kernel holds across the function.  With the nine normal
+// words or the twelve tangent words held there, however the tangent loads were placed (with the record's
+// other loads, behind the triangle test, behind the lookup), those instantiations spilled 6 VGPRs.  So the
+// first round trip fetches the vertices, the uvs and the material id only, and a second one behind the lookup
+// fetches the normals, from lines the first has just brought in, and the tangents together.
+__device__ inline void hit_record_n(const DevScene& sc, const mcpt::TexView& tex, V3 o, V3 d, int tri, V3& pos, V3& nrm,
+                                    int& mat, float& t_out, float& tu, float& tv) {
+    const float4* tp = sc.tri + kTriF4 * tri;
+    const float4 w0 = tp[0], w1 = tp[1], w2 = tp[2];
+    const float4* sp4 = sc.tri_sh + 3 * tri;
+    const float mat_bits = reinterpret_cast<const float*>(sp4)[9];  // (n2.z, mat, -, -): the material id
+    const float2* up = tex.uv + 3 * (size_t)tri;
+    const float2 c0 = up[0], c1 = up[1], c2 = up[2];
+    __asm__ volatile("" ::"v"(c0.x), "v"(c0.y), "v"(c1.x), "v"(c1.y), "v"(c2.x), "v"(c2.y));
+    __asm__ volatile("" ::"v"(w0.x), "v"(w0.y), "v"(w0.z), "v"(w0.w), "v"(w1.x), "v"(w1.y), "v"(w1.z), "v"(w1.w),
+                     "v"(w2.x), "v"(mat_bits));
+    float t, u, v;
+    tri_test(o, d, v3(w0.x, w0.y, w0.z), v3(w0.w, w1.x, w1.y), v3(w1.z, w1.w, w2.x), t, u, v);
+    const float w = (1.f - u) - v;
+    mat = __float_as_int(mat_bits);
+    tu = mcpt::tex_coord(u, v, w, c0.x, c1.x, c2.x);  // Triangle.cu:79
+    tv = mcpt::tex_coord(u, v, w, c0.y, c1.y, c2.y);
+    V3 c = v3(0.f, 0.f, 0.f);
+    const bool mapped = mcpt::tex_nrm_coeffs(tex, mat, tu, tv, c);
+    int tri2 = tri;
+    __asm__ volatile("" : "+v"(tri2) : "v"(c.x), "v"(c.y), "v"(c.z));  // the second round trip waits for the lookup
+    const float4* sq4 = sc.tri_sh + 3 * tri2;
+    const float4 s0 = sq4[0], s1 = sq4[1];
+    const float s2x = reinterpret_cast<const float*>(sq4)[8];
+    V3 n0 = v3(s0.x, s0.y, s0.z), n1 = v3(s0.w, s1.x, s1.y), n2 = v3(s1.z, s1.w, s2x);
+    if (mapped) {
+        const float4* gp = reinterpret_cast<const float4*>(tex.uv + mcpt::tex_tan_offset(sc.ntri)) + 3 * (size_t)tri2;
+        const float4 g0 = gp[0], g1 = gp[1], g2 = gp[2];
+        n0 = mcpt::tex_nrm_vertex(n0, xyz(g0), g0.w, c);
+        n1 = mcpt::tex_nrm_vertex(n1, xyz(g1), g1.w, c);
+        n2 = mcpt::tex_nrm_vertex(n2, xyz(g2), g2.w, c);
+    }
+    nrm = normalize((n1 * u + n2 * v) + n0 * w);  // Triangle.cu:76, on m_i
+    nrm = normalize(nrm);                          // identity transform, :82
+    pos = o + d * t;                               // :86
+    t_out = t;
+}
 __device__ inline void hit_record(const DevScene& sc, V3 o, V3 d, int tri, V3& pos, V3& nrm, int& mat, float& t_out) {
     float tu, tv;
     hit_record_t<false>(sc, nullptr, o, d, tri, pos, nrm, mat, t_out, tu, tv);

@@ -18,6 +18,20 @@
 //   metal = metal_factor * T.z                  one fp32 multiply (B channel)
 // rough_factor is the raw mat_params[6], not load_mat's clamped value.  R and A are ignored.  The two
 // textures of a material are independent: either, both or none, of any two sizes.
+//
+// Normal-map textures (tex_nrm_coeffs and tex_nrm_vertex below) perturb the three
+// vertex normals N_i of the hit's record before the hit record interpolates them, with the record's vertex
+// tangents (T_i, s_i), i = 0, 1, 2, at the same tc and through the same lookup.  All fp32, this order:
+//   t   = tex_bilinear_rgba8(normal texture of the material, tc)     over rgb, unchanged
+//   c.x = (2 * t.x - 1) * scale    c.y = (2 * t.y - 1) * scale    c.z = 2 * t.z - 1     (glTF: z is "up")
+//   B_i = cross(N_i, T_i) * s_i                                       glTF's bitangent
+//   m_i = (T_i * c.x + B_i * c.y) + N_i * c.z                         per vertex
+//   nrm = normalize(normalize((m_1 * u + m_2 * v) + m_0 * w))         the hit record's own two lines, on m_i
+// Interpolation is linear, so this is the usual perturbation of the interpolated frame.  glTF's inner
+// normalize(c) is left out: a common positive scalar that the hit record's normalisation removes.  A
+// material without a normal texture keeps m_i = N_i by selection, not by arithmetic.  Texels are used as
+// stored; alpha is ignored.  nrm stands for the hit record's normal everywhere the material stage reads it
+// (frames, f and pdf, the emitter sample, the ray origins' offsets): there is no separate geometric normal.
 #pragma once
 #include "device/mcpt_core.hpp"
 
@@ -31,7 +45,14 @@ struct TexView {
     // Metallic-roughness entries (section 20) live in the same allocation, in front of the base-colour
     // ones and mirrored: material m's is mat[-1 - m], the same four words.  Only k_material's MR
     // instantiations read them, and only a set with an MR-textured material launches those.
+    // Normal maps (section 21) add no field either.  The tangent stream, three float4 {T.xyz, s} per
+    // record in record order, lies behind the uv stream in its allocation, at uv + tex_tan_offset(ntri)
+    // (ntri: DevScene::ntri).  Material m's normal entry {first texel, w, h, scale bits} lies in front of
+    // the atlas in its allocation, mirrored: ((const int4*)atlas)[-1 - m]; w == 0: no normal map.  Only the
+    // normal-map kernels read either, and only a set with a normal-mapped material launches those.
 };
+// The tangent stream's place behind the 3 ntri float2 of the uv stream, in float2 units (16-byte aligned)
+MCPT_HD size_t tex_tan_offset(uint32_t ntri) { return (3 * (size_t)ntri + 1) & ~(size_t)1; }
 
 // c / 255 rounded to nearest fp32, c = 0..255.  The fp64 product is within 2^-52 of the quotient,
 // and no quotient k / 255 lies that close to the midpoint of two floats (255 = 2^8 - 1: the
@@ -86,6 +107,24 @@ MCPT_HD void tex_mr(const TexView& t, int mat, float rough_factor, float metal_f
     const V3 T = tex_bilinear_rgba8(t.atlas + e.x, e.y, e.z, tu, tv);
     rough = fmx(rough_factor * T.y, BRDF_EPS);
     metal = metal_factor * T.z;
+}
+
+// The tangent-space coefficients c of material `mat` at (tu, tv) from its normal texture (section 21, the
+// head of this file); false for a material without one (the caller then keeps N_i: selection).
+MCPT_HD bool tex_nrm_coeffs(const TexView& t, int mat, float tu, float tv, V3& c) {
+    const int4 e = reinterpret_cast<const int4*>(t.atlas)[-1 - mat];
+    if (e.y <= 0) return false;
+    const V3 T = tex_bilinear_rgba8(t.atlas + e.x, e.y, e.z, tu, tv);
+    const float scale = __builtin_bit_cast(float, e.w);
+    c.x = (2.f * T.x - 1.f) * scale;
+    c.y = (2.f * T.y - 1.f) * scale;
+    c.z = 2.f * T.z - 1.f;
+    return true;
+}
+// m_i of one vertex: normal N, tangent T with handedness s, coefficients c
+MCPT_HD V3 tex_nrm_vertex(V3 N, V3 T, float s, V3 c) {
+    const V3 B = cross(N, T) * s;
+    return (T * c.x + B * c.y) + N * c.z;
 }
 
 }  // namespace mcpt

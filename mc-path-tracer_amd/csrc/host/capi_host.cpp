@@ -150,7 +150,7 @@ int mcpt_scene_set_mesh_uv(mcpt_scene* s, int32_t mat, const float* uv0, const f
 }
 
 // Attaches the image to material mat through the index array idx (mat_tex: base colour; mat_mr:
-// metallic-roughness, section 20): both kinds share the texture list.
+// metallic-roughness, section 20; mat_nrm: normal map, section 21): all kinds share the texture list.
 static int scene_attach_texture(mcpt_scene* s, std::vector<int32_t> mcpt_host::Scene::*idx, int32_t mat, int32_t w, int32_t h,
                                 const uint8_t* rgba8) {
     if (!s) return fail(s, MCPT_E_INVALID, "null scene");
@@ -180,6 +180,36 @@ int mcpt_scene_set_material_texture(mcpt_scene* s, int32_t mat, int32_t w, int32
 int mcpt_scene_set_material_mr_texture(mcpt_scene* s, int32_t mat, int32_t w, int32_t h, const uint8_t* rgba8) {
     return scene_attach_texture(s, &mcpt_host::Scene::mat_mr, mat, w, h, rgba8);
 }
+// Normal maps: a third index array into the same list, and a scale per material
+int mcpt_scene_set_material_normal_texture(mcpt_scene* s, int32_t mat, int32_t w, int32_t h, const uint8_t* rgba8, float scale) {
+    if (s && rgba8 && !std::isfinite(scale)) return fail(s, MCPT_E_INVALID, "normal scale must be finite");
+    const int rc = scene_attach_texture(s, &mcpt_host::Scene::mat_nrm, mat, w, h, rgba8);
+    if (rc == MCPT_OK) s->s.nrm_scale[mat] = rgba8 ? scale : 1.f;
+    return rc;
+}
+int mcpt_scene_get_material_normal(const mcpt_scene* s, const int32_t** mat_nrm, const float** nrm_scale, int32_t* nmat) {
+    if (!s || !mat_nrm || !nrm_scale || !nmat) return MCPT_E_INVALID;
+    *nmat = (int32_t)s->s.mat_nrm.size();
+    *mat_nrm = s->s.mat_nrm.data();
+    *nrm_scale = s->s.nrm_scale.data();
+    return MCPT_OK;
+}
+int mcpt_scene_get_tangents(const mcpt_scene* s, const float** tan0, const float** tan1, const float** tan2, int32_t* ntri) {
+    if (!s || !tan0 || !tan1 || !tan2 || !ntri) return MCPT_E_INVALID;
+    const mcpt_host::Scene& sc = s->s;
+    if (!sc.built) return fail(const_cast<mcpt_scene*>(s), MCPT_E_INVALID, "scene not built");
+    const int32_t n = (int32_t)sc.f_id.size();
+    for (auto& t : sc.f_tan) t.assign(4 * (size_t)n, 0.f);
+    const int rc = mcpt_tangents_from_uv(n, sc.f_v0.data(), sc.f_v1.data(), sc.f_v2.data(), sc.f_n0.data(), sc.f_n1.data(),
+                                         sc.f_n2.data(), sc.f_uv0.data(), sc.f_uv1.data(), sc.f_uv2.data(), sc.f_tan[0].data(),
+                                         sc.f_tan[1].data(), sc.f_tan[2].data());
+    if (rc) return fail(const_cast<mcpt_scene*>(s), rc, "tangents: bad arrays");
+    *ntri = n;
+    *tan0 = sc.f_tan[0].data();
+    *tan1 = sc.f_tan[1].data();
+    *tan2 = sc.f_tan[2].data();
+    return MCPT_OK;
+}
 int mcpt_scene_get_material_mr(const mcpt_scene* s, const int32_t** mat_mr, int32_t* nmat) {
     if (!s || !mat_mr || !nmat) return MCPT_E_INVALID;
     *nmat = (int32_t)s->s.mat_mr.size();
@@ -194,6 +224,7 @@ int mcpt_scene_get_textures(const mcpt_scene* s, const mcpt_texture** textures, 
     bool any = false;
     for (int32_t k : sc.mat_tex) any = any || k >= 0;
     for (int32_t k : sc.mat_mr) any = any || k >= 0;  // (section 20: the list holds MR images too)
+    for (int32_t k : sc.mat_nrm) any = any || k >= 0;  // (section 21: and normal maps)
     sc.tex_views.clear();
     for (const mcpt_host::Texture& t : sc.textures) sc.tex_views.push_back(mcpt_texture{t.w, t.h, t.rgba8.data()});
     *nmat = (int32_t)sc.mat_tex.size();

@@ -34,6 +34,11 @@ struct Scene {
     std::vector<Texture> textures;
     std::vector<int32_t> mat_tex;
     std::vector<int32_t> mat_mr;  // metallic-roughness textures: indices into the same list
+    // normal maps: indices into the same list, a scale per material, and what
+    // mcpt_scene_get_tangents hands out (mcpt_tangents_from_uv over the built arrays)
+    std::vector<int32_t> mat_nrm;
+    std::vector<float> nrm_scale;
+    mutable std::vector<float> f_tan[3];
     mutable std::vector<mcpt_texture> tex_views;
     // environment light (EnvironmentLight.h:17-40); default Color 0.8 (Scene.cu:21)
     int env_mode = 0;

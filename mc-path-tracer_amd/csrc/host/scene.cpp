@@ -207,6 +207,8 @@ void Scene::add_mesh(const std::vector<V3>& pos, const std::vector<V3>& nrm, con
     emission.insert(emission.end(), em, em + 3);
     mat_tex.push_back(-1);
     mat_mr.push_back(-1);
+    mat_nrm.push_back(-1);
+    nrm_scale.push_back(1.f);
     for (size_t i = 0; i + 2 < idx.size(); i += 3) {
         Tri t;
         for (int k = 0; k < 3; k++) { t.p[k] = pos[idx[i + k]]; t.n[k] = nrm[idx[i + k]]; }

@@ -529,6 +529,9 @@ struct MatOut {
 // follow, do depend on the set.  What material_brdf_terms needs of the shaded Mat (base, roughness,
 // metallic) waits in the thread's five LDS words of tex_stash, not in registers across the occluder cache:
 // the instantiations sit at the 128 VGPRs of four waves per SIMD.
+// Level 3 is level 2 behind a hit record whose normal the material's normal map
+// perturbed (hit_record_n): n below is that normal, so the three frames, every f and pdf, the emitter sample
+// with its MIS pdf and the offsets of the ray origins follow; MatOut::n carries it to material_brdf_terms.
 template <bool FIXED, bool SAMP = false, bool MIS = false, int TEX = 0>
 __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix, uint32_t sidx, uint32_t len,
                                  V3 beta_store, int32_t htri, float4* stage, bool occ_on, bool no_cont, bool& want_e,
@@ -546,7 +549,8 @@ __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix
     int mat;
     float t_hit;
     [[maybe_unused]] float tu, tv;
-    if constexpr (TEX != 0) hit_record_t<true>(sc, a.tex.uv, ro, rdir, htri, pos, n, mat, t_hit, tu, tv);
+    if constexpr (TEX == 3) hit_record_n(sc, a.tex, ro, rdir, htri, pos, n, mat, t_hit, tu, tv);
+    else if constexpr (TEX != 0) hit_record_t<true>(sc, a.tex.uv, ro, rdir, htri, pos, n, mat, t_hit, tu, tv);
     else hit_record(sc, ro, rdir, htri, pos, n, mat, t_hit);
     const V3 wo = -rdir;
     Mat m_ld = load_mat(sc.mats + 8 * mat);
@@ -555,7 +559,7 @@ __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix
         m_ld.base = mcpt::tex_base(a.tex, mat, m_ld.base, tu, tv);
         if constexpr (TEX == 1) mo.base = m_ld.base;
     }
-    if constexpr (TEX == 2) {
+    if constexpr (TEX >= 2) {
         MCPT_MARK("m_tex_mr");
         mcpt::tex_mr(a.tex, mat, sc.mats[8 * mat + 6], m_ld.metal, tu, tv, m_ld.rough, m_ld.metal);
         tex_stash[0 * kBlock + threadIdx.x] = m_ld.base.x;
@@ -750,7 +754,7 @@ __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix
 // visibility ray that may be unoccluded (need_cb): one the occluder cache resolved is never read.
 // TEX: with the base colour material() shaded with (MatOut::base: three registers across the occluder
 // cache instead of a second lookup's four gathers); TEX == 2: and with its roughness and metallic, all
-// five from the thread's LDS words (material()).
+// five from the thread's LDS words (material()); TEX == 3 as 2 (the mapped normal is MatOut::n).
 template <bool FIXED, int TEX = 0>
 __device__ inline void material_brdf_terms(const ShadeArgs& a, uint32_t pid, const MatOut& mo,
                                            [[maybe_unused]] const float* tex_stash = nullptr) {
@@ -760,7 +764,7 @@ __device__ inline void material_brdf_terms(const ShadeArgs& a, uint32_t pid, con
     if (mo.need_cb) {
         Mat m_ld = load_mat(sc.mats + 8 * mo.matid);
         if constexpr (TEX == 1) m_ld.base = mo.base;
-        if constexpr (TEX == 2) {
+        if constexpr (TEX >= 2) {
             m_ld.base = v3(tex_stash[0 * kBlock + threadIdx.x], tex_stash[1 * kBlock + threadIdx.x], tex_stash[2 * kBlock + threadIdx.x]);
             m_ld.rough = tex_stash[3 * kBlock + threadIdx.x];
             m_ld.metal = tex_stash[4 * kBlock + threadIdx.x];
@@ -1264,11 +1268,17 @@ __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_k
 // third texture level without a change to the twelve older instantiations' template arguments, so
 // their symbols, and with them their place in a comparison of two builds by name, stay.
 struct TexMr {};
+// The normal-map instantiations, k_material<TexNrm, FIXED, SAMP, MIS>: the same
+// overload under a second tag, launched only while a set with a normal-mapped material is in effect: base
+// colour, MR and normal per material, each behind its own w == 0 test.  The TexMr instantiations keep
+// their template arguments, and with them their symbols.
+struct TexNrm {};
 template <typename LEVEL, bool FIXED, bool SAMP = false, bool MIS = false>
 __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_kernarg) {
-    static_assert(std::is_same<LEVEL, TexMr>::value, "the tag selects the metallic-roughness level");
+    static_assert(std::is_same<LEVEL, TexMr>::value || std::is_same<LEVEL, TexNrm>::value,
+                  "the tag selects the metallic-roughness or the normal-map level");
     (void)a_kernarg;
-    constexpr int TEX = 2;
+    constexpr int TEX = std::is_same<LEVEL, TexNrm>::value ? 3 : 2;
     __shared__ float s_tex[5][kBlock];  // base colour, roughness, metallic of the thread's path (5 KiB)
     float* const tex_stash = &s_tex[0][0];
 #include "device/k_material_body.inc"
@@ -2249,10 +2259,14 @@ static uint32_t shade_grid(uint32_t nblocks, const LaunchGeom& g) {
 }
 // k_material for a launch: the textured instantiation while a texture set is in effect (a.tex.uv set;
 // DESIGN.md section 19), on its twin's grid; every other context launches what it launched before.
-// tex_mr (the host's choice, no kernel argument; section 20): the set has an MR-textured material.
+// tex_level (the host's choice, no kernel argument): 2 the set has an MR-textured material (section 20),
+// 3 it has a normal-mapped one (section 21); below 2 the set alone decides.
 template <bool SAMP, bool MIS>
-static void launch_material(const ShadeArgs& a, const uint32_t* blocks, bool fixed_mode, bool tex_mr, hipStream_t s) {
-    if (a.tex.uv && tex_mr) {
+static void launch_material(const ShadeArgs& a, const uint32_t* blocks, bool fixed_mode, int tex_level, hipStream_t s) {
+    if (a.tex.uv && tex_level >= 3) {
+        if (fixed_mode) hipLaunchKernelGGL((k_material<TexNrm, true, SAMP, MIS>), dim3(blocks[1]), dim3(kBlock), 0, s, a);
+        else hipLaunchKernelGGL((k_material<TexNrm, false, SAMP, MIS>), dim3(blocks[0]), dim3(kBlock), 0, s, a);
+    } else if (a.tex.uv && tex_level == 2) {
         if (fixed_mode) hipLaunchKernelGGL((k_material<TexMr, true, SAMP, MIS>), dim3(blocks[1]), dim3(kBlock), 0, s, a);
         else hipLaunchKernelGGL((k_material<TexMr, false, SAMP, MIS>), dim3(blocks[0]), dim3(kBlock), 0, s, a);
     } else if (a.tex.uv) {
@@ -2263,7 +2277,7 @@ static void launch_material(const ShadeArgs& a, const uint32_t* blocks, bool fix
         else hipLaunchKernelGGL((k_material<false, SAMP, MIS>), dim3(blocks[0]), dim3(kBlock), 0, s, a);
     }
 }
-void launch_shade(const ShadeArgs& args, int nblocks, const LaunchGeom& g, bool fixed_mode, bool tex_mr, hipStream_t s) {
+void launch_shade(const ShadeArgs& args, int nblocks, const LaunchGeom& g, bool fixed_mode, int tex_level, hipStream_t s) {
     ShadeArgs a = args;
     a.shade_vblocks = (uint32_t)nblocks;
     const uint32_t G = shade_grid((uint32_t)nblocks, g);
@@ -2279,7 +2293,7 @@ void launch_shade(const ShadeArgs& args, int nblocks, const LaunchGeom& g, bool 
             if (a.budget) hipLaunchKernelGGL((k_shade<false, true, true, true, true>), dim3(G), dim3(kBlock), 0, s, a);
             else hipLaunchKernelGGL((k_shade<false, false, true, true, true>), dim3(G), dim3(kBlock), 0, s, a);
         }
-        launch_material<true, true>(a, g.mat_blocks_samp, fixed_mode, tex_mr, s);
+        launch_material<true, true>(a, g.mat_blocks_samp, fixed_mode, tex_level, s);
         return;
     }
     if (a.nee2 && a.emis) {
@@ -2290,7 +2304,7 @@ void launch_shade(const ShadeArgs& args, int nblocks, const LaunchGeom& g, bool 
             if (a.budget) hipLaunchKernelGGL((k_shade<false, true, true, true>), dim3(G), dim3(kBlock), 0, s, a);
             else hipLaunchKernelGGL((k_shade<false, false, true, true>), dim3(G), dim3(kBlock), 0, s, a);
         }
-        launch_material<true, false>(a, g.mat_blocks_samp, fixed_mode, tex_mr, s);
+        launch_material<true, false>(a, g.mat_blocks_samp, fixed_mode, tex_level, s);
         return;
     }
     if (fixed_mode) {
@@ -2306,11 +2320,11 @@ void launch_shade(const ShadeArgs& args, int nblocks, const LaunchGeom& g, bool 
         } else if (a.budget) hipLaunchKernelGGL((k_shade<false, true, false>), dim3(G), dim3(kBlock), 0, s, a);
         else hipLaunchKernelGGL((k_shade<false, false, false>), dim3(G), dim3(kBlock), 0, s, a);
     }
-    launch_material<false, false>(a, g.mat_blocks, fixed_mode, tex_mr, s);
+    launch_material<false, false>(a, g.mat_blocks, fixed_mode, tex_level, s);
 }
 // One of the two shading kernels alone (mcpt_stage_run's LOGIC / GENERATE and MATERIAL stages).
 void launch_shade_stage(bool material_stage, const ShadeArgs& args, int nblocks, const LaunchGeom& g, bool fixed_mode,
-                        bool tex_mr, hipStream_t s) {
+                        int tex_level, hipStream_t s) {
     ShadeArgs a = args;
     a.shade_vblocks = (uint32_t)nblocks;
     if (!material_stage) {
@@ -2321,7 +2335,7 @@ void launch_shade_stage(bool material_stage, const ShadeArgs& args, int nblocks,
         } else if (fixed_mode) hipLaunchKernelGGL((k_shade<true, false, false>), dim3(G), dim3(kBlock), 0, s, a);
         else hipLaunchKernelGGL((k_shade<false, false, false>), dim3(G), dim3(kBlock), 0, s, a);
     } else {
-        launch_material<false, false>(a, g.mat_blocks, fixed_mode, tex_mr, s);
+        launch_material<false, false>(a, g.mat_blocks, fixed_mode, tex_level, s);
     }
 }
 // Persistent grid: the device's resident waves rounded to a multiple of the shard count.

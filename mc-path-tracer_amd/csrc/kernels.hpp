@@ -365,11 +365,12 @@ struct LaunchGeom {
 
 // ---- wavefront iteration (kernels.hip) ----
 int launch_geometry(int device, LaunchGeom& g);  // device must be current
-// tex_mr: the installed texture set has a metallic-roughness textured material:
-// with a.tex set, k_material<TexMr, ...> in place of k_material's textured instantiation.
-void launch_shade(const ShadeArgs& a, int nblocks, const LaunchGeom& g, bool fixed_mode, bool tex_mr, hipStream_t s);
+// tex_level: 2 the installed texture set has a metallic-roughness textured material:
+// with a.tex set, k_material<TexMr, ...> in place of k_material's textured instantiation; 3 it has a
+// normal-mapped one (section 21): k_material<TexNrm, ...>.  Below 2 a.tex alone decides.
+void launch_shade(const ShadeArgs& a, int nblocks, const LaunchGeom& g, bool fixed_mode, int tex_level, hipStream_t s);
 void launch_shade_stage(bool material_stage, const ShadeArgs& a, int nblocks, const LaunchGeom& g, bool fixed_mode,
-                        bool tex_mr, hipStream_t s);
+                        int tex_level, hipStream_t s);
 void launch_primary(const ShadeArgs& a, const LaunchGeom& g, hipStream_t s);  // k_primary: after k_shade, before k_trace
 void launch_trace(const TraceArgs& a, const LaunchGeom& g, hipStream_t s);
 void launch_accumulate(CounterBlock* c, uint32_t nparts, uint32_t* occ_gate, hipStream_t s);
@@ -542,12 +543,19 @@ struct GuideTexArgs {
     const int32_t* rec;
 };
 void launch_guide_accum_tex(const GuideTexArgs& a, hipStream_t s);
+// k_guide_accum_nrm (section 21): k_guide_accum_tex whose hit record is hit_record_n, so the normal guide
+// accumulates the mapped normal; the albedo guide is unchanged.  Launched only under a normal-mapped set.
+void launch_guide_accum_nrm(const GuideTexArgs& a, hipStream_t s);
 // k_tex_sample: out[i] = tex_bilinear_rgba8(tex, w, h, uv[i]) for n uv pairs (mcpt_texture_sample_run)
 void launch_tex_sample(const uint32_t* tex, int w, int h, const float2* uv, float* out_rgb, uint32_t n, hipStream_t s);
 // k_tex_uv_records: the uv stream in record order: out[3 p + k] = uv_k[order[p]] (order == nullptr: p),
 // uv0 / uv1 / uv2 in desc order
 void launch_tex_uv_records(const float2* uv0, const float2* uv1, const float2* uv2, const uint32_t* order, float2* out,
                            uint32_t ntri, hipStream_t s);
+// k_tex_tangent_records (section 21): the tangent stream in record order: out[3 p + k] = tan_k[order[p]],
+// tan0 / tan1 / tan2 {T.xyz, s} in desc order
+void launch_tex_tangent_records(const float4* tan0, const float4* tan1, const float4* tan2, const uint32_t* order, float4* out,
+                                uint32_t ntri, hipStream_t s);
 
 // ---- adaptive sampling (adaptive.hip) ----
 // Which accumulator holds a film pixel.  own == nullptr: every pixel is the caller's and pixel o's

@@ -512,7 +512,7 @@ static int enqueue_iteration(mcpt_ctx* c, size_t evbase, bool timing, const int2
     const int bpt = (int)f.L.blocks_per_tile;
     if (timing) HIPCHK(c, hipEventRecord(ev(c, evbase + 0), c->stream));
     if (sa.ntiles > 0)
-        launch_shade(sa, sa.ntiles * bpt, c->geom, (c->cfg.flags & MCPT_FLAG_FIXED) != 0, c->tx.textured_mr > 0, c->stream);
+        launch_shade(sa, sa.ntiles * bpt, c->geom, (c->cfg.flags & MCPT_FLAG_FIXED) != 0, c->tx.level(), c->stream);
     if (timing) HIPCHK(c, hipEventRecord(ev(c, evbase + 1), c->stream));
     // primary rays with a candidate list (part of the extend stage's time)
     if (sa.ntiles > 0) launch_primary(sa, c->geom, c->stream);

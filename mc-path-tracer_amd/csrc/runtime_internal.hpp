@@ -236,29 +236,47 @@ struct Emission {
 // gave none); d_mat holds 2 nmat entries, the MR ones in front and mirrored (material m's at nmat - 1 - m),
 // the base-colour ones behind, where view().mat points (device/texture.hpp TexView).  A set with an
 // MR-textured material launches k_material<TexMr, ...>.
+// Normal maps (section 21): tan[k] holds corner k's {T.xyz, s}, 4 floats per triangle in desc order (empty:
+// the caller gave none), mat_nrm indexes the same texture list (all -1 where absent), nrm_scale one float
+// per material (all 1 where absent); nrm_fields records whether the caller gave any of the three, which is
+// what the read-back reports.  On the device the tangent stream lies behind the uv stream in d_uv, at
+// mcpt::tex_tan_offset(ntri) float2, in record order (textures_reorder permutes both), and the materials'
+// normal entries {first texel, w, h, scale bits} lie in front of the atlas in d_atlas, mirrored (material
+// m's at word 4 (nmat - 1 - m)): view().atlas points behind them.  No kernel argument grows.  A set with a
+// normal-mapped material launches k_material<TexNrm, ...> and k_guide_accum_nrm.
 struct Textures {
-    std::vector<float> uv[3];
-    std::vector<int32_t> tw, th, mat_tex, mat_mr;
+    std::vector<float> uv[3], tan[3], nrm_scale;
+    std::vector<int32_t> tw, th, mat_tex, mat_mr, mat_nrm;
     std::vector<uint32_t> first;  // texture k's first texel in the atlas
     std::vector<uint32_t> atlas;
-    DevBuf<float2> d_uv, d_stage;  // [3 ntri] record order; [3 ntri] desc order, the permutation's input
-    DevBuf<uint32_t> d_atlas;
+    DevBuf<float2> d_uv, d_stage;  // [3 ntri] record order (+ the tangent stream); [3 ntri] desc order, the permutation's input
+    DevBuf<float4> d_tstage;       // [3 ntri] tangents in desc order, the permutation's input
+    DevBuf<uint32_t> d_atlas;      // 4 nmat words of normal entries, then the texels
     DevBuf<int4> d_mat;
-    int32_t textured = 0;     // materials with a base-colour texture
-    int32_t textured_mr = 0;  // materials with a metallic-roughness texture
-    bool dev_ok = false;      // the device arrays stand for the current record order
+    int32_t textured = 0;      // materials with a base-colour texture
+    int32_t textured_mr = 0;   // materials with a metallic-roughness texture
+    int32_t textured_nrm = 0;  // materials with a normal map
+    bool nrm_fields = false;   // the caller gave tangents, mat_nrm or nrm_scale
+    bool dev_ok = false;       // the device arrays stand for the current record order
     bool installed() const { return !mat_tex.empty(); }
-    bool shaded() const { return textured > 0 || textured_mr > 0; }  // some material shades through a lookup
+    // some material shades through a lookup
+    bool shaded() const { return textured > 0 || textured_mr > 0 || textured_nrm > 0; }
+    // k_material's texture level while the set is in effect (launch_shade)
+    int level() const { return textured_nrm > 0 ? 3 : textured_mr > 0 ? 2 : 1; }
     mcpt::TexView view() const {
         if (!(shaded() && dev_ok)) return mcpt::TexView{nullptr, nullptr, nullptr};
-        return mcpt::TexView{d_uv.get(), d_atlas.get(), d_mat.get() + mat_tex.size()};
+        return mcpt::TexView{d_uv.get(), d_atlas.get() + 4 * mat_tex.size(), d_mat.get() + mat_tex.size()};
     }
-    size_t bytes() const { return installed() ? d_uv.bytes() + d_stage.bytes() + d_atlas.bytes() + d_mat.bytes() : 0; }
+    size_t bytes() const {
+        return installed() ? d_uv.bytes() + d_stage.bytes() + d_tstage.bytes() + d_atlas.bytes() + d_mat.bytes() : 0;
+    }
     void drop() {
         for (auto& u : uv) u.clear();
-        tw.clear(), th.clear(), mat_tex.clear(), mat_mr.clear(), first.clear(), atlas.clear();
-        d_uv.reset(), d_stage.reset(), d_atlas.reset(), d_mat.reset();
-        textured = textured_mr = 0;
+        for (auto& t : tan) t.clear();
+        tw.clear(), th.clear(), mat_tex.clear(), mat_mr.clear(), mat_nrm.clear(), nrm_scale.clear(), first.clear(), atlas.clear();
+        d_uv.reset(), d_stage.reset(), d_tstage.reset(), d_atlas.reset(), d_mat.reset();
+        textured = textured_mr = textured_nrm = 0;
+        nrm_fields = false;
         dev_ok = false;
     }
 };

@@ -621,7 +621,10 @@ static int textures_uv_stream(mcpt_ctx* c, Textures& t) {
     if (!t.installed()) return MCPT_OK;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // no launch in flight reads the old stream
-    if (!t.d_uv.ensure(3 * n) || !t.d_stage.ensure(3 * n)) {
+    // (section 21) the tangent stream, three float4 per record, behind the uv stream in the same allocation
+    const bool tans = !t.tan[0].empty();
+    const size_t tan_at = mcpt::tex_tan_offset((uint32_t)n);  // in float2
+    if (!t.d_uv.ensure(tans ? tan_at + 6 * n : 3 * n) || !t.d_stage.ensure(3 * n) || (tans && !t.d_tstage.ensure(3 * n))) {
         (void)hipGetLastError();
         return set_err(c, MCPT_E_NOMEM, "hipMalloc: texture uv stream");
     }
@@ -630,15 +633,26 @@ static int textures_uv_stream(mcpt_ctx* c, Textures& t) {
     launch_tex_uv_records(t.d_stage.get(), t.d_stage.get() + n, t.d_stage.get() + 2 * n, c->scene.order, t.d_uv, (uint32_t)n,
                           c->stream);
     HIPCHK(c, hipGetLastError());
+    if (tans) {
+        for (int k = 0; k < 3 && n; k++)
+            HIPCHK(c, hipMemcpy(t.d_tstage.get() + k * n, t.tan[k].data(), n * sizeof(float4), hipMemcpyHostToDevice));
+        launch_tex_tangent_records(t.d_tstage.get(), t.d_tstage.get() + n, t.d_tstage.get() + 2 * n, c->scene.order,
+                                   reinterpret_cast<float4*>(t.d_uv.get() + tan_at), (uint32_t)n, c->stream);
+        HIPCHK(c, hipGetLastError());
+    }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     t.dev_ok = true;
     return MCPT_OK;
 }
 int textures_reorder(mcpt_ctx* c) { return textures_uv_stream(c, c->tx); }
 
-static int textures_install(mcpt_ctx* c, int32_t ntri, const float* uv0, const float* uv1, const float* uv2, int32_t ntex,
-                            const mcpt_texture* tex, int32_t nmat, const int32_t* mat_tex, const int32_t* mat_mr) {
+static int textures_install(mcpt_ctx* c, const mcpt_texture_set& set) {
     if (!c) return MCPT_E_INVALID;
+    const int32_t ntri = set.ntri, ntex = set.ntex, nmat = set.nmat;
+    const float *uv0 = set.uv0, *uv1 = set.uv1, *uv2 = set.uv2;
+    const mcpt_texture* tex = set.textures;
+    const int32_t *mat_tex = set.mat_tex, *mat_mr = set.mat_mr, *mat_nrm = set.mat_nrm;
+    const float* tan[3] = {set.tan0, set.tan1, set.tan2};
     if (!c->scene.ok) return set_err(c, MCPT_E_INVALID, "no scene uploaded");
     auto changed = [c] {  // what a changed set means to the film, the history and the guides
         c->film_stale = true;
@@ -669,7 +683,26 @@ static int textures_install(mcpt_ctx* c, int32_t ntri, const float* uv0, const f
     for (int32_t m = 0; mat_mr && m < nmat; m++)
         if (mat_mr[m] < -1 || mat_mr[m] >= ntex)
             return set_err(c, MCPT_E_INVALID, "textures: material metallic-roughness texture index out of range");
+    // the normal-map fields (section 21)
+    const int ntan = (tan[0] != nullptr) + (tan[1] != nullptr) + (tan[2] != nullptr);
+    if (ntan != 0 && ntan != 3) return set_err(c, MCPT_E_INVALID, "textures: one or two of the three tangent arrays");
+    for (int32_t m = 0; mat_nrm && m < nmat; m++) {
+        if (mat_nrm[m] < -1 || mat_nrm[m] >= ntex)
+            return set_err(c, MCPT_E_INVALID, "textures: material normal texture index out of range");
+        if (mat_nrm[m] >= 0 && ntan == 0) return set_err(c, MCPT_E_INVALID, "textures: a normal texture needs tangents");
+    }
+    for (int32_t m = 0; set.nrm_scale && m < nmat; m++)
+        if (!std::isfinite(set.nrm_scale[m])) return set_err(c, MCPT_E_INVALID, "textures: non-finite normal scale");
+    for (int k = 0; k < 3 && ntan; k++)
+        for (size_t i = 0; i < 4 * (size_t)ntri; i++)
+            if (!std::isfinite(tan[k][i])) return set_err(c, MCPT_E_INVALID, "textures: non-finite tangent component");
     Textures now;
+    now.nrm_fields = ntan != 0 || mat_nrm || set.nrm_scale;
+    for (int k = 0; k < 3 && ntan; k++) now.tan[k].assign(tan[k], tan[k] + 4 * (size_t)ntri);
+    if (mat_nrm) now.mat_nrm.assign(mat_nrm, mat_nrm + nmat);
+    else now.mat_nrm.assign((size_t)nmat, -1);
+    if (set.nrm_scale) now.nrm_scale.assign(set.nrm_scale, set.nrm_scale + nmat);
+    else now.nrm_scale.assign((size_t)nmat, 1.f);
     const float* src[3] = {uv0, uv1, uv2};
     for (int k = 0; k < 3; k++) now.uv[k].assign(src[k], src[k] + 2 * (size_t)ntri);
     now.mat_tex.assign(mat_tex, mat_tex + nmat);
@@ -692,6 +725,17 @@ static int textures_install(mcpt_ctx* c, int32_t ntri, const float* uv0, const f
         dm[(size_t)nmat - 1 - m] = entry(now.mat_mr[m]);
         now.textured += now.mat_tex[m] >= 0;
         now.textured_mr += now.mat_mr[m] >= 0;
+        now.textured_nrm += now.mat_nrm[m] >= 0;
+    }
+    // (section 21) the normal entries {first texel, w, h, scale bits} in front of the atlas, mirrored: material
+    // m's at int4 nmat - 1 - m of the allocation (TexView::atlas points behind them)
+    std::vector<uint32_t> dn(4 * (size_t)nmat, 0u);
+    for (int32_t m = 0; m < nmat; m++) {
+        const int32_t k = now.mat_nrm[m];
+        if (k < 0) continue;
+        uint32_t* e = dn.data() + 4 * ((size_t)nmat - 1 - m);
+        e[0] = now.first[k], e[1] = (uint32_t)now.tw[k], e[2] = (uint32_t)now.th[k];
+        memcpy(e + 3, &now.nrm_scale[m], sizeof(float));
     }
     const Textures& was = c->tx;
     auto same_bytes = [](const auto& a, const auto& b) {
@@ -699,20 +743,37 @@ static int textures_install(mcpt_ctx* c, int32_t ntri, const float* uv0, const f
     };
     if (was.installed() && same_bytes(was.uv[0], now.uv[0]) && same_bytes(was.uv[1], now.uv[1]) && same_bytes(was.uv[2], now.uv[2]) &&
         same_bytes(was.tw, now.tw) && same_bytes(was.th, now.th) && same_bytes(was.mat_tex, now.mat_tex) &&
-        same_bytes(was.mat_mr, now.mat_mr) && same_bytes(was.atlas, now.atlas) && (was.dev_ok || !was.shaded()))
+        same_bytes(was.mat_mr, now.mat_mr) && same_bytes(was.atlas, now.atlas) && same_bytes(was.mat_nrm, now.mat_nrm) &&
+        same_bytes(was.nrm_scale, now.nrm_scale) && same_bytes(was.tan[0], now.tan[0]) && same_bytes(was.tan[1], now.tan[1]) &&
+        same_bytes(was.tan[2], now.tan[2]) && was.nrm_fields == now.nrm_fields && (was.dev_ok || !was.shaded()))
         return MCPT_OK;  // an identical set does nothing
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // no launch in flight reads the old set
-    if (!now.d_atlas.ensure(now.atlas.size()) || !now.d_mat.ensure(dm.size())) {
+    if (!now.d_atlas.ensure(dn.size() + now.atlas.size()) || !now.d_mat.ensure(dm.size())) {
         (void)hipGetLastError();
         return set_err(c, MCPT_E_NOMEM, "hipMalloc: texture atlas");  // (the installed set stays)
     }
-    HIPCHK(c, hipMemcpy(now.d_atlas, now.atlas.data(), now.atlas.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (!dn.empty()) HIPCHK(c, hipMemcpy(now.d_atlas, dn.data(), dn.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(now.d_atlas.get() + dn.size(), now.atlas.data(), now.atlas.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     if (!dm.empty()) HIPCHK(c, hipMemcpy(now.d_mat, dm.data(), dm.size() * sizeof(int4), hipMemcpyHostToDevice));
     if (int rc = textures_uv_stream(c, now)) return rc;
     // what the film depends on is what the lookups shade: a set without a textured material (in either
     // index array) shades as none
-    const bool differs = was.shaded() || now.shaded();
+    // ... and a set that differs from the installed one only in normal-map fields no lookup reads (their
+    // presence, the scale of a material without a normal map, the tangents while no material has one; section
+    // 21) shades as it: the new set is installed and read back, the film, the history and the guides stay
+    auto scale_in_use = [](const Textures& t, size_t m) { return t.mat_nrm[m] >= 0 ? t.nrm_scale[m] : 1.f; };
+    bool same_shading = was.installed() && (was.dev_ok || !was.shaded()) && same_bytes(was.uv[0], now.uv[0]) &&
+                        same_bytes(was.uv[1], now.uv[1]) && same_bytes(was.uv[2], now.uv[2]) && same_bytes(was.tw, now.tw) &&
+                        same_bytes(was.th, now.th) && same_bytes(was.mat_tex, now.mat_tex) && same_bytes(was.mat_mr, now.mat_mr) &&
+                        same_bytes(was.atlas, now.atlas) && same_bytes(was.mat_nrm, now.mat_nrm);
+    for (size_t m = 0; same_shading && m < now.mat_nrm.size(); m++) {
+        const float a = scale_in_use(was, m), b = scale_in_use(now, m);
+        same_shading = memcmp(&a, &b, sizeof(float)) == 0;
+    }
+    if (same_shading && now.textured_nrm > 0)
+        same_shading = same_bytes(was.tan[0], now.tan[0]) && same_bytes(was.tan[1], now.tan[1]) && same_bytes(was.tan[2], now.tan[2]);
+    const bool differs = (was.shaded() || now.shaded()) && !same_shading;
     c->tx = std::move(now);
     if (differs) changed();
     return MCPT_OK;
@@ -722,11 +783,38 @@ extern "C" {
 
 int mcpt_set_material_textures(mcpt_ctx* c, int32_t ntri, const float* uv0, const float* uv1, const float* uv2, int32_t ntex,
                                const mcpt_texture* textures, int32_t nmat, const int32_t* mat_tex) {
-    return textures_install(c, ntri, uv0, uv1, uv2, ntex, textures, nmat, mat_tex, nullptr);
+    return textures_install(c, mcpt_texture_set{ntri, uv0, uv1, uv2, nullptr, nullptr, nullptr, ntex, textures, nmat, mat_tex, nullptr,
+                                                nullptr, nullptr});
 }
 int mcpt_set_material_texture_maps(mcpt_ctx* c, int32_t ntri, const float* uv0, const float* uv1, const float* uv2, int32_t ntex,
                                    const mcpt_texture* textures, int32_t nmat, const int32_t* mat_tex, const int32_t* mat_mr) {
-    return textures_install(c, ntri, uv0, uv1, uv2, ntex, textures, nmat, mat_tex, mat_mr);
+    return textures_install(c, mcpt_texture_set{ntri, uv0, uv1, uv2, nullptr, nullptr, nullptr, ntex, textures, nmat, mat_tex, mat_mr,
+                                                nullptr, nullptr});
+}
+int mcpt_set_material_texture_set(mcpt_ctx* c, const mcpt_texture_set* set) {
+    if (!c) return MCPT_E_INVALID;
+    if (!set) return set_err(c, MCPT_E_INVALID, "textures: null set");
+    return textures_install(c, *set);
+}
+int mcpt_material_normal_read(mcpt_ctx* c, int32_t* nmat, int32_t* ntri_tan, int32_t* mat_nrm, float* nrm_scale, float* tan0,
+                              float* tan1, float* tan2) {
+    if (!c) return MCPT_E_INVALID;
+    const Textures& t = c->tx;
+    if (nmat) *nmat = t.nrm_fields ? (int32_t)t.mat_nrm.size() : 0;
+    if (ntri_tan) *ntri_tan = (int32_t)(t.tan[0].size() / 4);
+    if (!t.nrm_fields) return MCPT_OK;
+    if (mat_nrm && !t.mat_nrm.empty()) memcpy(mat_nrm, t.mat_nrm.data(), t.mat_nrm.size() * sizeof(int32_t));
+    if (nrm_scale && !t.nrm_scale.empty()) memcpy(nrm_scale, t.nrm_scale.data(), t.nrm_scale.size() * sizeof(float));
+    float* dst[3] = {tan0, tan1, tan2};
+    for (int k = 0; k < 3; k++)
+        if (dst[k] && !t.tan[k].empty()) memcpy(dst[k], t.tan[k].data(), t.tan[k].size() * sizeof(float));
+    return MCPT_OK;
+}
+int mcpt_debug_texture_normal_stats(const mcpt_ctx* c, int32_t* nrm_materials, int32_t* nrm_in_effect) {
+    if (!c) return MCPT_E_INVALID;
+    if (nrm_materials) *nrm_materials = c->tx.textured_nrm;
+    if (nrm_in_effect) *nrm_in_effect = c->tx.view().uv && c->tx.textured_nrm > 0 ? 1 : 0;
+    return MCPT_OK;
 }
 int mcpt_material_mr_read(mcpt_ctx* c, int32_t* nmat, int32_t* mat_mr) {
     if (!c) return MCPT_E_INVALID;

@@ -144,7 +144,7 @@ static int stage_run_paths(mcpt_ctx* c, int stage, const mcpt_path_view* in, mcp
     if (stage == MCPT_STAGE_LOGIC) sa.emis = c->em.dev_table();  // the context's emission
     if (mat) sa.tex = c->tx.view();  // ... and its base-colour textures (section 19)
     HIPCHK(c, hipEventRecord(ev(c, 0), c->stream));
-    launch_shade_stage(mat, sa, (int)nblocks, c->geom, (c->cfg.flags & MCPT_FLAG_FIXED) != 0, c->tx.textured_mr > 0, c->stream);
+    launch_shade_stage(mat, sa, (int)nblocks, c->geom, (c->cfg.flags & MCPT_FLAG_FIXED) != 0, c->tx.level(), c->stream);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(ev(c, 1), c->stream));
     HIPCHK(c, hipMemcpyAsync(hc, cnt, sizeof(CounterBlock), hipMemcpyDeviceToHost, c->stream));

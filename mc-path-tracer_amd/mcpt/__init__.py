@@ -107,6 +107,12 @@ class Texture(C.Structure):  # mcpt_texture: a decoded RGBA8 image
     _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("rgba8", C.POINTER(C.c_uint8))]
 
 
+class TextureSet(C.Structure):  # mcpt_texture_set: a whole texture set, NULL = absent
+    _fields_ = [("ntri", C.c_int32), ("uv0", _f), ("uv1", _f), ("uv2", _f), ("tan0", _f), ("tan1", _f), ("tan2", _f),
+                ("ntex", C.c_int32), ("textures", C.POINTER(Texture)), ("nmat", C.c_int32), ("mat_tex", _i), ("mat_mr", _i),
+                ("mat_nrm", _i), ("nrm_scale", _f)]
+
+
 class PathView(C.Structure):  # mcpt_path_view: path state at the shading stages' boundary
     _fields_ = [("film_w", C.c_uint32), ("film_h", C.c_uint32), ("flags", _u), ("samples", _u), ("hit_tri", _i),
                 ("ray_o", _f), ("ray_d", _f), ("beta", _f), ("nee0", _f), ("nee1", _f),
@@ -228,6 +234,13 @@ ABI = {
     "mcpt_debug_texture_mr_stats": (C.c_int, [C.c_void_p, _i, _i]),
     "mcpt_scene_set_material_mr_texture": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "mcpt_scene_get_material_mr": (C.c_int, [C.c_void_p, C.POINTER(_i), _i]),
+    "mcpt_set_material_texture_set": (C.c_int, [C.c_void_p, C.POINTER(TextureSet)]),
+    "mcpt_material_normal_read": (C.c_int, [C.c_void_p, _i, _i, _i, _f, _f, _f, _f]),
+    "mcpt_debug_texture_normal_stats": (C.c_int, [C.c_void_p, _i, _i]),
+    "mcpt_tangents_from_uv": (C.c_int, [C.c_int32] + [_f] * 12),
+    "mcpt_scene_set_material_normal_texture": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_float]),
+    "mcpt_scene_get_material_normal": (C.c_int, [C.c_void_p, C.POINTER(_i), C.POINTER(_f), _i]),
+    "mcpt_scene_get_tangents": (C.c_int, [C.c_void_p, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), _i]),
     "mcpt_sync": (C.c_int, [C.c_void_p]),
     "mcpt_device_name": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32]),
     "mcpt_debug_queue_rays": (C.c_int, [C.c_void_p, C.c_int, _f, _f, _u]),
@@ -346,6 +359,21 @@ def _arr(ptr, n, dtype):
     return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ct)), shape=(n,)).copy()
 
 
+def tangents_from_uv(v0, v1, v2, n0, n1, n2, uv0, uv1, uv2):
+    """Vertex tangents for normal maps (mcpt_tangents_from_uv): (tan0, tan1, tan2),
+    (ntri, 4) float32 each, {T.x, T.y, T.z, s} per corner, from (ntri, 3) vertices and normals and (ntri, 2)
+    uvs.  Double arithmetic in a stated order (include/mcpt.h), with a stated fallback where a triangle's uvs
+    are degenerate."""
+    a = [np.ascontiguousarray(x, np.float32).reshape(-1, 3) for x in (v0, v1, v2, n0, n1, n2)]
+    u = [np.ascontiguousarray(x, np.float32).reshape(-1, 2) for x in (uv0, uv1, uv2)]
+    n = len(a[0])
+    if any(len(x) != n for x in a + u):
+        raise ValueError("every array must have one row per triangle")
+    out = [np.zeros((n, 4), np.float32) for _ in range(3)]
+    _check(lib().mcpt_tangents_from_uv(n, *[fptr(x) for x in a + u + out]))
+    return tuple(out)
+
+
 def _rgba8(img) -> np.ndarray:
     """An (h, w, 4) contiguous uint8 image from an (h, w, 4) or (h, w, 3) one (alpha 255)."""
     a = np.asarray(img)
@@ -433,10 +461,29 @@ class Scene:
         return self._ck(lib().mcpt_scene_set_material_mr_texture(self.h, int(mat), img.shape[1], img.shape[0],
                                                                  img.ctypes.data_as(C.POINTER(C.c_uint8))))
 
+    def set_normal_texture(self, mat, img_u8, scale=1.0):
+        """Attach a tangent-space normal map to material ``mat``: an image as
+        set_texture takes it (R, G: the tangent and bitangent components times ``scale``, B: "up"; alpha
+        ignored; used as stored).  None detaches.  Independent of the material's other textures;
+        PathTracer.upload_scene installs it with the rest, with the built scene's tangents()."""
+        L = lib().mcpt_scene_set_material_normal_texture
+        if img_u8 is None:
+            return self._ck(L(self.h, int(mat), 0, 0, None, 1.0))
+        img = _rgba8(img_u8)
+        return self._ck(L(self.h, int(mat), img.shape[1], img.shape[0], img.ctypes.data_as(C.POINTER(C.c_uint8)), float(scale)))
+
+    def tangents(self):
+        """The built scene's vertex tangents (tan0, tan1, tan2), (ntri, 4) each, in the desc's triangle
+        order: tangents_from_uv over its vertices, normals and uvs."""
+        p, n = [_f(), _f(), _f()], C.c_int32(0)
+        self._ck(lib().mcpt_scene_get_tangents(self.h, C.byref(p[0]), C.byref(p[1]), C.byref(p[2]), C.byref(n)))
+        return tuple(_arr(q, 4 * n.value, np.float32).reshape(n.value, 4) for q in p)
+
     def textures(self):
-        """None when no material has a texture of either kind, else {"textures": [(h, w, 4) uint8, ...],
+        """None when no material has a texture of any kind, else {"textures": [(h, w, 4) uint8, ...],
         "mat_tex": int32 (nmat,), "mat_mr": int32 (nmat,)} (copies): per material the index of its
-        base-colour and of its metallic-roughness texture in the one list, or -1."""
+        base-colour and of its metallic-roughness texture in the one list, or -1; and, only when a material
+        has a normal map, "mat_nrm": int32 (nmat,) and "nrm_scale": float32 (nmat,)."""
         t, mt, nt, nm = C.POINTER(Texture)(), _i(), C.c_int32(0), C.c_int32(0)
         _check(lib().mcpt_scene_get_textures(self.h, C.byref(t), C.byref(nt), C.byref(mt), C.byref(nm)))
         if not t or nt.value == 0:
@@ -447,6 +494,12 @@ class Scene:
             mr, nr = _i(), C.c_int32(0)
             _check(lib().mcpt_scene_get_material_mr(self.h, C.byref(mr), C.byref(nr)))
             out["mat_mr"] = _arr(mr, nr.value, np.int32)
+        if hasattr(lib(), "mcpt_scene_get_material_normal"):  # (an older variant library has none)
+            mn, sc, nn = _i(), _f(), C.c_int32(0)
+            _check(lib().mcpt_scene_get_material_normal(self.h, C.byref(mn), C.byref(sc), C.byref(nn)))
+            mn = _arr(mn, nn.value, np.int32)
+            if (mn >= 0).any():
+                out["mat_nrm"], out["nrm_scale"] = mn, _arr(sc, nn.value, np.float32)
         return out
 
     def uv(self):
@@ -611,15 +664,22 @@ class PathTracer:
         if isinstance(scene, Scene) and hasattr(lib(), "mcpt_scene_get_textures"):
             t = scene.textures()
             if t is not None:
-                self.set_textures(*scene.uv(), t["textures"], t["mat_tex"], mat_mr=t["mat_mr"] if (t["mat_mr"] >= 0).any() else None)
+                kw = {}
+                if "mat_nrm" in t:  # (section 21) normal maps come with the built scene's tangents
+                    kw = dict(tangents=scene.tangents(), mat_nrm=t["mat_nrm"], nrm_scale=t["nrm_scale"])
+                self.set_textures(*scene.uv(), t["textures"], t["mat_tex"], mat_mr=t["mat_mr"] if (t["mat_mr"] >= 0).any() else None, **kw)
 
-    def set_textures(self, uv0=None, uv1=None, uv2=None, textures=None, mat_tex=None, mat_mr=None):
+    def set_textures(self, uv0=None, uv1=None, uv2=None, textures=None, mat_tex=None, mat_mr=None, tangents=None, mat_nrm=None,
+                     nrm_scale=None):
         """Base-colour textures (mcpt_set_material_textures): the corner uvs, (ntri, 2)
         each in the uploaded desc's triangle order, a list of (h, w, 4) / (h, w, 3) uint8 images, and per
         material a texture index or -1.  No arguments (or no textures) remove the set.  A change clears the
         film at the next render and makes the guide buffers stale.
         mat_mr (mcpt_set_material_texture_maps; section 20): per material the index of its
-        metallic-roughness texture in the same list, or -1; None: no material has one (the older call)."""
+        metallic-roughness texture in the same list, or -1; None: no material has one (the older call).
+        tangents, mat_nrm, nrm_scale (mcpt_set_material_texture_set; section 21): (tan0, tan1, tan2), (ntri, 4)
+        each as tangents_from_uv returns them; per material the index of its normal map in the same list,
+        or -1; one scale per material.  Each may be None (absent); all None: the older calls."""
         if not textures:
             self._ck(lib().mcpt_set_material_textures(self.h, 0, None, None, None, 0, None, 0, None))
             return
@@ -632,6 +692,27 @@ class PathTracer:
             arr[k].w, arr[k].h = im.shape[1], im.shape[0]
             arr[k].rgba8 = im.ctypes.data_as(C.POINTER(C.c_uint8))
         mt = np.ascontiguousarray(mat_tex, np.int32).reshape(-1)
+        if tangents is not None or mat_nrm is not None or nrm_scale is not None:
+            ts = TextureSet()
+            ts.ntri, ts.uv0, ts.uv1, ts.uv2 = len(u[0]), fptr(u[0]), fptr(u[1]), fptr(u[2])
+            ts.ntex, ts.textures, ts.nmat, ts.mat_tex = len(imgs), arr, len(mt), mt.ctypes.data_as(_i)
+            keep = []  # (the arrays the struct points into, alive across the call)
+            if tangents is not None:
+                tn = [np.ascontiguousarray(t, np.float32).reshape(-1, 4) for t in tangents]
+                if len(tn) != 3 or any(len(t) != len(u[0]) for t in tn):
+                    raise ValueError("tangents are three arrays with one row {T.xyz, s} per triangle")
+                ts.tan0, ts.tan1, ts.tan2 = (fptr(t) for t in tn)
+                keep += tn
+            for name, val, dt, ct in (("mat_mr", mat_mr, np.int32, _i), ("mat_nrm", mat_nrm, np.int32, _i),
+                                      ("nrm_scale", nrm_scale, np.float32, _f)):
+                if val is not None:
+                    v = np.ascontiguousarray(val, dt).reshape(-1)
+                    if len(v) != len(mt):
+                        raise ValueError(f"mat_tex and {name} must have one entry per material")
+                    setattr(ts, name, v.ctypes.data_as(ct))
+                    keep.append(v)
+            self._ck(lib().mcpt_set_material_texture_set(self.h, C.byref(ts)))
+            return
         if mat_mr is None:
             self._ck(lib().mcpt_set_material_textures(self.h, len(u[0]), fptr(u[0]), fptr(u[1]), fptr(u[2]), len(imgs), arr,
                                                       len(mt), mt.ctypes.data_as(_i)))
@@ -663,7 +744,17 @@ class PathTracer:
         mr = np.full(nm.value, -1, np.int32)
         if hasattr(lib(), "mcpt_material_mr_read"):  # (an older variant library has none)
             self._ck(lib().mcpt_material_mr_read(self.h, None, mr.ctypes.data_as(_i)))
-        return {"uv0": u[0], "uv1": u[1], "uv2": u[2], "textures": imgs, "mat_tex": mt, "mat_mr": mr}
+        out = {"uv0": u[0], "uv1": u[1], "uv2": u[2], "textures": imgs, "mat_tex": mt, "mat_mr": mr}
+        if hasattr(lib(), "mcpt_material_normal_read"):  # (an older variant library has none)
+            n, ntan = C.c_int32(0), C.c_int32(0)
+            L = lib().mcpt_material_normal_read
+            self._ck(L(self.h, C.byref(n), C.byref(ntan), None, None, None, None, None))
+            if n.value:  # the set carries normal-map fields (section 21): the keys exist only then
+                mn, sc = np.zeros(n.value, np.int32), np.zeros(n.value, np.float32)
+                tn = [np.zeros((ntan.value, 4), np.float32) for _ in range(3)]
+                self._ck(L(self.h, None, None, mn.ctypes.data_as(_i), fptr(sc), fptr(tn[0]), fptr(tn[1]), fptr(tn[2])))
+                out.update(mat_nrm=mn, nrm_scale=sc, tangents=tuple(tn) if ntan.value else None)
+        return out
 
     def texture_sample(self, img, uv):
         """The texture lookup alone on the device (mcpt_texture_sample_run): (n, 3) float32 for (n, 2) uvs
@@ -680,7 +771,10 @@ class PathTracer:
         textured kernels (of either kind) are in effect (mcpt_debug_texture_stats).  While a set is installed
         also "mr_materials", the materials with a metallic-roughness texture, and "mr_in_effect", whether the
         metallic-roughness kernels are (mcpt_debug_texture_mr_stats); a context without a set returns the
-        three keys it always returned (read the other two with .get)."""
+        three keys it always returned (read the other two with .get).  While a set with normal-map fields
+        (tangents, mat_nrm or nrm_scale) is installed also "nrm_materials", the materials
+        with a normal map, and "nrm_in_effect", whether the normal-map kernels are
+        (mcpt_debug_texture_normal_stats); no other set, and no context without one, has these two keys."""
         b, m, on = C.c_uint64(0), C.c_int32(0), C.c_int32(0)
         self._ck(lib().mcpt_debug_texture_stats(self.h, C.byref(b), C.byref(m), C.byref(on)))
         out = {"bytes": int(b.value), "textured_materials": int(m.value), "in_effect": bool(on.value)}
@@ -690,6 +784,12 @@ class PathTracer:
             if n.value:
                 self._ck(lib().mcpt_debug_texture_mr_stats(self.h, C.byref(m), C.byref(on)))
                 out["mr_materials"], out["mr_in_effect"] = int(m.value), bool(on.value)
+        if hasattr(lib(), "mcpt_debug_texture_normal_stats"):  # (an older variant library has none)
+            n = C.c_int32(0)
+            self._ck(lib().mcpt_material_normal_read(self.h, C.byref(n), None, None, None, None, None, None))
+            if n.value:  # only while a set with normal-map fields is installed
+                self._ck(lib().mcpt_debug_texture_normal_stats(self.h, C.byref(m), C.byref(on)))
+                out["nrm_materials"], out["nrm_in_effect"] = int(m.value), bool(on.value)
         return out
 
     def set_emission(self, rgb=None):

@@ -19,6 +19,11 @@ the same walls as their metallic-roughness texture (G, B in 64..255: the walls' 
 .. 1 per hit, their metallic 0 stays 0), frames with the base-colour set alone and with base + MR alternating on one context: k_material's textured
 instantiation against k_material<TexMr, ...> (a name of its own in the trace).  The counts change with the set at
 every depth (F_FZERO), so the cost per material evaluation is reported too.
+
+--normal (profiles/textures_nrm.json): --mr's setup with a third 1024 x 1024 image on the
+same walls as their normal map (R, G anywhere, B in 128..255, scale 1; tangents from mcpt.tangents_from_uv over
+the planar uvs), frames with base + MR and with base + MR + normal alternating on one context:
+k_material<TexMr, ...> against k_material<TexNrm, ...>.
 Prints one JSON line.
 """
 import argparse
@@ -45,6 +50,11 @@ def kstats(d):
         for row in csv.DictReader(open(path)):
             m = re.search(r"k_material<(\w+), (\w+), (\w+), (\w+)>", row["Name"])
             r = re.search(r"k_material<(?:\w+::)*TexMr, (\w+), (\w+), (\w+)>", row["Name"])
+            n = re.search(r"k_material<(?:\w+::)*TexNrm, (\w+), (\w+), (\w+)>", row["Name"])
+            if n:
+                out["fixed=%s samp=%s mis=%s tex=nrm" % tuple(int(x in ("true", "1")) for x in n.groups())] = {
+                    "calls": int(row["Calls"]), "total_ms": float(row["TotalDurationNs"]) / 1e6, "us_per_launch": float(row["AverageNs"]) / 1e3}
+                continue
             if not (m or r):
                 continue
             key = "fixed=%s samp=%s mis=%s tex=%s" % tuple(int(x in ("true", "1")) for x in m.groups()) if m else \
@@ -71,6 +81,7 @@ def main():
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--spp", type=int, default=None)
     ap.add_argument("--mr", action="store_true", help="base-colour set against base + metallic-roughness (section 20)")
+    ap.add_argument("--normal", action="store_true", help="base + MR against base + MR + normal map (section 21)")
     ap.add_argument("--kstats", metavar="DIR", default=None, help="summarise a kernel trace of this program and exit")
     a = ap.parse_args()
     if a.kstats:
@@ -85,9 +96,17 @@ def main():
     walls = (0, 1, 2, 3, 4)
     uv, imgs, mat_tex = wall_set(scene.arrays(), a.size, walls)
     pt = mcpt.PathTracer(0, mcpt.default_config(spp=spp, max_depth=rc.max_depth))
+    a.mr = a.mr or a.normal
     if a.mr:  # a second image on the same walls, both index arrays set
         imgs = imgs + [np.random.default_rng(20).integers(64, 256, (a.size, a.size, 4)).astype(np.uint8)]
         mat_mr = np.where(mat_tex >= 0, 1, -1).astype(np.int32)
+    if a.normal:  # a third image on the same walls, with tangents from the planar uvs
+        nimg = np.random.default_rng(21).integers(0, 256, (a.size, a.size, 4)).astype(np.uint8)
+        nimg[..., 2] = np.random.default_rng(22).integers(128, 256, (a.size, a.size)).astype(np.uint8)
+        imgs = imgs + [nimg]
+        mat_nrm = np.where(mat_tex >= 0, 2, -1).astype(np.int32)
+        sa = scene.arrays()
+        tans = mcpt.tangents_from_uv(sa["v0"], sa["v1"], sa["v2"], sa["n0"], sa["n1"], sa["n2"], *uv)
     pt.upload_scene(scene)
     pt.set_camera(mcpt.config_camera(rc))
     pt.set_path_slots(slots)
@@ -98,10 +117,14 @@ def main():
             pt.set_textures(*uv, imgs, mat_tex)
         elif k == "walls_textured_mr":
             pt.set_textures(*uv, imgs, mat_tex, mat_mr=mat_mr)
+        elif k == "walls_textured_mr_nrm":
+            pt.set_textures(*uv, imgs, mat_tex, mat_mr=mat_mr, tangents=tans, mat_nrm=mat_nrm)
         else:
             pt.set_textures()
 
     rows = {"walls_textured": [], "walls_textured_mr": []} if a.mr else {"none": [], "walls_textured": []}
+    if a.normal:
+        rows = {"walls_textured_mr": [], "walls_textured_mr_nrm": []}
     shade = {k: [] for k in rows}
     iters, rays, stats = {}, {}, {}
     for i in range(a.warmup + a.repeats):
