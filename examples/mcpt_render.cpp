@@ -3,7 +3,7 @@
 // INTEGRATION.md): build a BASELINE config scene with the host builder, upload it,
 // run the wavefront iterations until every pixel has its samples, write PNG + PFM.
 //
-//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>] [--emissive <mat> <r> <g> <b>]... [--env-color <r> <g> <b>] [--sample-emitters] [--emitter-mis] [--checker <mat> <n>]... [--checker-mr <mat> <n>]... [--bumps <mat> <n> <scale>]...
+//   mcpt_render <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>] [--emissive <mat> <r> <g> <b>]... [--env-color <r> <g> <b>] [--sample-emitters] [--emitter-mis] [--checker <mat> <n>]... [--checker-mr <mat> <n>]... [--bumps <mat> <n> <scale>]... [--glb <file>]
 //
 // --denoise renders the first-hit guide buffers (default 4 guide samples per pixel), filters the film
 // with the default parameters and writes <out_prefix>_denoised.png beside the raw image.
@@ -48,6 +48,10 @@
 // --checker-mr puts the same checker on material <mat> as its metallic-roughness texture (DESIGN.md section
 // 20; repeatable) and sets the material's metallic factor to 1: the squares alternate G = B = 255 (rough
 // metal: the material's own roughness) with G = 26, B = 255 (roughness a tenth of it: near-mirror metal).
+// --glb <file> renders a glb as authored in place of the config's meshes, under the config's
+// camera and environment: its PBR factors, its embedded PNG base-colour (sRGB), metallic-roughness and normal
+// textures and its tangents; the meshes are scaled and centred into the unit sphere at the origin, and the report
+// of what could not be honoured goes to stderr.
 // --tiles-per-call uses the reference orchestration (one 256x256 tile per call,
 // wavefront_kernels.cu:377-442 + Film::update_tile_position) instead of batch mode.
 #include <math.h>
@@ -79,7 +83,7 @@ static void warp(const mcpt_scene_desc& d, float amp, uint32_t frame, uint32_t f
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>] [--emissive <mat> <r> <g> <b>]... [--env-color <r> <g> <b>] [--sample-emitters] [--emitter-mis] [--checker <mat> <n>]... [--checker-mr <mat> <n>]... [--bumps <mat> <n> <scale>]...\n", argv[0]);
+        fprintf(stderr, "usage: %s <config 1-5> [spp] [out_prefix] [--gpu-bvh] [--reference-bvh] [--fixed] [--tiles-per-call] [--slots S] [--denoise [guide_samples]] [--denoise-guided [guide_samples]] [--adaptive <target> <min> <max> [rounds]] [--temporal <frames> <yaw_step_deg>] [--variance-fill] [--animate <frames> <amplitude>] [--emissive <mat> <r> <g> <b>]... [--env-color <r> <g> <b>] [--sample-emitters] [--emitter-mis] [--checker <mat> <n>]... [--checker-mr <mat> <n>]... [--bumps <mat> <n> <scale>]... [--glb <file>]\n", argv[0]);
         return 2;
     }
     const Cfg cfgs[6] = {{0, 0, 0, 0, {0, 0, 0}, 0, ""},
@@ -107,6 +111,7 @@ int main(int argc, char** argv) {
     std::vector<int> checker;     // --checker: {mat, n} per use
     std::vector<int> checker_mr;  // --checker-mr: {mat, n} per use
     std::vector<float> bumps;     // --bumps: {mat, n, scale} per use
+    std::string glb;              // --glb: the file rendered in place of the config's meshes
     float env_rgb[3] = {0.f, 0.f, 0.f};
     bool env_given = false;
     for (int i = 2; i < argc; i++) {
@@ -147,6 +152,11 @@ int main(int argc, char** argv) {
             }
             checker_mr.push_back(atoi(argv[++i]));
             checker_mr.push_back(atoi(argv[++i]));
+            continue;
+        }
+        if (!strcmp(argv[i], "--glb")) {
+            if (i + 1 >= argc) { fprintf(stderr, "--glb needs <file>\n"); return 2; }
+            glb = argv[++i];
             continue;
         }
         if (!strcmp(argv[i], "--env-color")) {
@@ -197,7 +207,37 @@ int main(int argc, char** argv) {
     mcpt_scene* s = mcpt_scene_new();
     // host BVH: binned 3-axis SAH (default) or BVHAccel's builder; films are identical either way
     mcpt_bvh_params bp = {MCPT_BVH_SAH3, 8, 128, 0.5f, 1.0f};
-    int src = !s || mcpt_scene_make_proxy(s, id, assets);
+    int src = !s;
+    if (!src && glb.empty()) {
+        src = mcpt_scene_make_proxy(s, id, assets);
+    } else if (!src) {
+        // --glb: the file's meshes in place of the config's, as authored, under the config's environment map; scaled
+        // uniformly and centred into the unit sphere at the origin through the loader's transform (the bounds come
+        // from a first load without flags), so the config's camera frames them
+        mcpt_scene* probe = mcpt_scene_new();
+        mcpt_scene_desc pd;
+        src = !probe || mcpt_scene_load_glb(probe, glb.c_str(), nullptr) || mcpt_scene_build(probe, 8) || mcpt_scene_get_desc(probe, &pd);
+        float xf[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+        if (!src && pd.nnodes > 0) {
+            float r2 = 0.f, ctr[3];
+            for (int k = 0; k < 3; k++) {
+                ctr[k] = 0.5f * (pd.bmin[k] + pd.bmax[k]);
+                r2 += 0.25f * (pd.bmax[k] - pd.bmin[k]) * (pd.bmax[k] - pd.bmin[k]);
+            }
+            const float sc = r2 > 0.f ? 1.f / sqrtf(r2) : 1.f;
+            xf[0] = xf[5] = xf[10] = sc;
+            for (int k = 0; k < 3; k++) xf[12 + k] = -ctr[k] * sc;
+        }
+        if (probe) mcpt_scene_free(probe);
+        if (!src) src = mcpt_scene_load_glb_ex(s, glb.c_str(), xf, MCPT_GLB_AS_AUTHORED);
+        if (!src) {
+            int32_t cnt[4];
+            std::vector<char> lines(1 << 16);
+            mcpt_scene_glb_report(s, cnt, lines.data(), (int32_t)lines.size());
+            fprintf(stderr, "glb: %d images decoded, %d skipped; %d texture slots attached, %d skipped\n%s", cnt[0], cnt[1], cnt[2], cnt[3], lines.data());
+            src = mcpt_scene_set_env_hdr(s, (std::string(assets) + "/" + c.env).c_str(), 1);
+        }
+    }
     if (!src && env_given) src = mcpt_scene_set_env_color(s, env_rgb, 1.f);
     for (size_t k = 0; !src && k < emissive.size(); k += 4) src = mcpt_scene_set_material_emission(s, (int32_t)emissive[k], &emissive[k + 1]);
     for (size_t k = 0; !src && k < checker.size(); k += 2) {  // dark / light squares, opaque
@@ -264,16 +304,24 @@ int main(int argc, char** argv) {
         if (!rc) rc = mcpt_scene_get_textures(s, &tex, &ntex, &mat_tex, &nmat);
         if (!rc) rc = mcpt_scene_get_material_mr(s, &mat_mr, &nmr);
         if (!rc && tex && !(rc = mcpt_scene_get_uv(s, &uv0, &uv1, &uv2, &ntri))) {
-            if (bumps.empty()) {
+            // the scene's normal maps (--bumps or a glb's) with its tangents, and its texture
+            // flags (a glb's sRGB base colours; section 22), through the descriptor call; else the older call
+            const uint32_t* flags = nullptr;
+            const int32_t* mat_nrm = nullptr;
+            const float *nrm_scale = nullptr, *t0 = nullptr, *t1 = nullptr, *t2 = nullptr;
+            int32_t nf = 0, nn = 0, nt = 0;
+            bool flagged = false, mapped = false;
+            rc = mcpt_scene_get_texture_flags(s, &flags, &nf);
+            if (!rc) rc = mcpt_scene_get_material_normal(s, &mat_nrm, &nrm_scale, &nn);
+            for (int32_t k = 0; !rc && k < nf; k++) flagged = flagged || flags[k] != 0;
+            for (int32_t k = 0; !rc && k < nn; k++) mapped = mapped || mat_nrm[k] >= 0;
+            if (!rc && mapped) rc = mcpt_scene_get_tangents(s, &t0, &t1, &t2, &nt);
+            if (!rc && !mapped && !flagged) {
                 rc = mcpt_set_material_texture_maps(ctx, ntri, uv0, uv1, uv2, ntex, tex, nmat, mat_tex, mat_mr);
-            } else {  // --bumps: the scene's tangents, normal indices and scales as well
-                const int32_t* mat_nrm = nullptr;
-                const float *nrm_scale = nullptr, *t0 = nullptr, *t1 = nullptr, *t2 = nullptr;
-                int32_t nn = 0, nt = 0;
-                rc = mcpt_scene_get_material_normal(s, &mat_nrm, &nrm_scale, &nn);
-                if (!rc) rc = mcpt_scene_get_tangents(s, &t0, &t1, &t2, &nt);
-                const mcpt_texture_set set{ntri, uv0, uv1, uv2, t0, t1, t2, ntex, tex, nmat, mat_tex, mat_mr, mat_nrm, nrm_scale};
-                if (!rc) rc = mcpt_set_material_texture_set(ctx, &set);
+            } else if (!rc) {
+                const mcpt_texture_set set{ntri, uv0, uv1, uv2, t0, t1, t2, ntex, tex, nmat, mat_tex, mat_mr, mapped ? mat_nrm : nullptr,
+                                           mapped ? nrm_scale : nullptr, flagged ? flags : nullptr};
+                rc = mcpt_set_material_texture_set(ctx, &set);
             }
         }
     }

@@ -17,6 +17,7 @@
  */
 #ifndef MCPT_H
 #define MCPT_H
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -303,6 +304,28 @@ int mcpt_film_write_png(mcpt_ctx *ctx, float exposure, const char *path);
 int mcpt_film_write_pfm(mcpt_ctx *ctx, const char *path);
 int mcpt_image_write_png(const char *path, uint32_t w, uint32_t h, const uint8_t *rgba8);
 int mcpt_image_write_pfm(const char *path, uint32_t w, uint32_t h, const float *rgb);
+/* PNG reader for texture images (host/png_read.cpp; an inflate and a PNG decoder of the project's own, no
+ * library, no device call).  mcpt_image_read_png_memory decodes the n bytes of a PNG payload into w x h RGBA8
+ * texels, row 0 of the file first (glTF's and section 19's orientation): what mcpt_texture and the scene's
+ * texture setters take.  With rgba8 == NULL it validates the signature and IHDR only and returns the size;
+ * otherwise cap is the buffer's size in bytes, and a cap below 4 w h is MCPT_E_INVALID (as is a NULL data, w
+ * or h).  mcpt_image_read_png is the same over a file.
+ * Accepted: colour type 0 at bit depth 1/2/4/8/16, 2 at 8/16, 3 at 1/2/4/8 with PLTE and optional tRNS, 4 at
+ * 8/16, 6 at 8/16; non-interlaced; all five filter types; one or more consecutive IDAT chunks; ancillary chunks
+ * are skipped; w and h in 1..16384.  A 16-bit sample becomes its high byte; a grey sample of depth d < 8 becomes
+ * v * (255 / (2^d - 1)); grey replicates to rgb; alpha is 255 where the file has none (tRNS counts for palette
+ * images only).
+ * Refused with MCPT_E_IO, nothing written to rgba8, w or h: a bad signature, a bad chunk CRC, chunk order
+ * violations, an unknown critical chunk, Adam7 interlace, a palette index beyond PLTE, a zlib header that is
+ * not deflate with a 32K window, a preset dictionary, a bad Adler-32, a deflate stream that is malformed
+ * (reserved block type, LEN / NLEN mismatch, over-subscribed or incomplete code lengths other than the
+ * one-code distance case, a distance beyond the bytes produced) or that yields fewer or more than
+ * h * (1 + rowbytes) bytes.  MCPT_E_NOMEM, nothing written either: the decoder's buffers cannot be allocated.
+ * mcpt_image_read_png_error: the reason of the calling thread's last MCPT_E_IO or MCPT_E_NOMEM from either
+ * call (a static string buffer; "" before any). */
+int mcpt_image_read_png_memory(const uint8_t *data, size_t n, int32_t *w, int32_t *h, uint8_t *rgba8, size_t cap);
+int mcpt_image_read_png(const char *path, int32_t *w, int32_t *h, uint8_t *rgba8, size_t cap);
+const char *mcpt_image_read_png_error(void);
 /* ---- preview denoiser: first-hit guide buffers + an edge-avoiding a-trous
  * wavelet filter (Dammertz et al. 2010) between the film and the display.  A context that never
  * calls these allocates and launches nothing for them.
@@ -629,12 +652,13 @@ int mcpt_debug_emitter_mis(const mcpt_ctx *ctx);
  * and the BRDF's f and pdf of every part of the material stage, the emitter sample's and MIS's BRDF pdf
  * use this base.  Fresnel stays per material, and so do roughness and metallic unless a
  * metallic-roughness texture is installed (section 20, below).  Row 0 of a texture is v in
- * [0, 1 / h): glTF's orientation, no flip.  Texels are used as stored: there is no sRGB decode (the
- * reference has none), and alpha is ignored.  Texels arrive decoded: reading the PNG / JPEG images
- * embedded in a glb is out of scope here.  Paths, random draws, ray counts, emission and every table do
- * not depend on the textures; while a set is in effect the albedo guide (mcpt_guides_render) accumulates
- * the same base at the first hit.  Opt-in: a context without a set, or with one whose every material
- * index is -1, launches the kernels it launched before.
+ * [0, 1 / h): glTF's orientation, no flip.  Texels are used as stored (the reference has no sRGB decode)
+ * unless the texture is flagged MCPT_TEX_SRGB (section 22, below), and alpha is ignored.  Texels arrive
+ * decoded: mcpt_image_read_png* reads a PNG file or payload into them; other codecs are out of scope.
+ * Paths, random draws, ray counts, emission and every table do not depend on the textures; while a set is
+ * in effect the albedo guide (mcpt_guides_render) accumulates the same base at the first hit.  Opt-in: a
+ * context without a set, or with one whose every material index is -1, launches the kernels it launched
+ * before.
  *
  * mcpt_set_material_textures installs a set (everything copied): uv0 / uv1 / uv2, 2 * ntri floats each,
  * the corners' uvs in the uploaded desc's triangle order; textures[k] = {w, h, rgba8} with w * h RGBA8
@@ -745,11 +769,40 @@ typedef struct mcpt_texture_set {
     int32_t nmat;
     const int32_t *mat_tex, *mat_mr, *mat_nrm;
     const float *nrm_scale;
+    const uint32_t *tex_flags; /* section 22: ntex words of MCPT_TEX_*, NULL: all 0 */
 } mcpt_texture_set;
 int mcpt_set_material_texture_set(mcpt_ctx *ctx, const mcpt_texture_set *set);
 int mcpt_material_normal_read(mcpt_ctx *ctx, int32_t *nmat, int32_t *ntri_tan, int32_t *mat_nrm, float *nrm_scale, float *tan0,
                               float *tan1, float *tan2);
 int mcpt_debug_texture_normal_stats(const mcpt_ctx *ctx, int32_t *nrm_materials, int32_t *nrm_in_effect);
+/* ---- sRGB base colour: glTF base-colour images are sRGB-encoded.  A texture whose
+ * flag word has MCPT_TEX_SRGB is decoded when, and only when, it is read as a base colour:
+ *   texel = L[c]                                  in place of c / 255, per channel, before the bilinear filter
+ * with L a table of 256 floats: x = c / 255 in double, L[c] = x / 12.92 for x <= 0.04045 (bytes 0..10), else
+ * ((x + 0.055) / 1.055)^2.4 (bytes 11..255), rounded to float; the rest of the section-19 lookup is unchanged.
+ * Metallic-roughness and normal lookups never decode, whatever the texture's flag; alpha is ignored.
+ *
+ * mcpt_texture_set::tex_flags: ntex words, NULL meaning all 0; bit 0 is MCPT_TEX_SRGB.  The two older install
+ * calls pass NULL.  Every rule of mcpt_set_material_texture_set holds for the field: an unknown bit is
+ * MCPT_E_INVALID and the installed set stays; a bitwise-identical set (the field and its absence included) does
+ * nothing; a differing one marks the film stale, drops the temporal history and makes the guides stale, unless
+ * it differs only in flags no base-colour lookup reads (the field's presence, the flag of a texture no
+ * base-colour slot uses): such a set is installed and read back, nothing else.
+ * A set with a material whose base-colour texture is flagged launches k_material's sRGB instantiations (base
+ * colour with the decode, MR and normal per material) and the albedo guide accumulates the decoded colour; every
+ * other set launches what it launched before.
+ * mcpt_material_texture_flags_read: *ntex (0: no set installed, or one installed without tex_flags) and the
+ * flag words (either may be NULL).
+ * mcpt_debug_texture_srgb_stats: materials whose base-colour texture is flagged, and 1 / 0 for whether the
+ * sRGB kernels are in effect (either may be NULL).
+ * mcpt_texture_sample_run_ex: mcpt_texture_sample_run with a flag word for the image: with MCPT_TEX_SRGB the
+ * lookup decodes every texel through the table (the base-colour lookup of a flagged texture); an unknown bit is
+ * MCPT_E_INVALID.  mcpt_texture_sample_run is this call with 0. */
+#define MCPT_TEX_SRGB 1u
+int mcpt_material_texture_flags_read(mcpt_ctx *ctx, int32_t *ntex, uint32_t *tex_flags);
+int mcpt_debug_texture_srgb_stats(const mcpt_ctx *ctx, int32_t *srgb_materials, int32_t *srgb_in_effect);
+int mcpt_texture_sample_run_ex(mcpt_ctx *ctx, int32_t w, int32_t h, const uint8_t *rgba8, uint32_t flags,
+                               uint32_t n, const float *uv, float *out_rgb);
 /* Vertex tangents from texture coordinates (host/tangents.cpp; no device call).  Per triangle, in double on
  * the float inputs and in this order:
  *   e1 = v1 - v0, e2 = v2 - v0;  (du1, dv1) = uv1 - uv0, (du2, dv2) = uv2 - uv0
@@ -877,12 +930,15 @@ int mcpt_scene_set_material_emission(mcpt_scene *s, int32_t mat, const float *rg
 int mcpt_scene_get_emission(const mcpt_scene *s, const float **rgb, int32_t *nmat);
 /* Base-colour textures (mcpt_set_material_textures takes what the getters return).  The glb reader keeps
  * every primitive's TEXCOORD_0 (a float VEC2 accessor; absent: zeros) through mcpt_scene_transform and the
- * BVH's reordering.  It does not decode the PNG / JPEG images embedded in a glb: texels arrive decoded,
- * through mcpt_scene_set_material_texture.
+ * BVH's reordering.  mcpt_scene_load_glb reads nothing else of a material but its base-colour factor;
+ * mcpt_scene_load_glb_ex (below) imports the factors, the embedded PNG textures and the tangents as authored.
+ * Otherwise texels arrive decoded, through mcpt_scene_set_material_texture (mcpt_image_read_png* decodes a PNG).
  * mcpt_scene_set_mesh_uv: the corners' uvs of material mat's triangles (one material per added mesh), 2
  * floats per triangle in each array, in the order the mesh's triangles were added.
- * mcpt_scene_set_material_texture: attaches a copy of the w x h RGBA8 image (row 0 = v in [0, 1 / h), no
- * sRGB decode, alpha ignored) to material mat, replacing its previous one; rgba8 == NULL detaches.
+ * mcpt_scene_set_material_texture: attaches a copy of the w x h RGBA8 image (row 0 = v in [0, 1 / h), used
+ * as stored -- mcpt_scene_set_material_texture_ex flags sRGB texels -- alpha ignored) to material mat,
+ * replacing its previous one (an entry that other slots use too stays theirs: the image is then appended);
+ * rgba8 == NULL detaches.
  * MCPT_E_INVALID: mat out of range, w or h outside 1..16384, a NULL uv array.
  * mcpt_scene_get_textures: the textures, *ntex of them (*textures = NULL, *ntex = 0 when no material has
  * one) and the nmat texture indices (-1: none).  mcpt_scene_get_uv: the built scene's uvs, 2 * ntri floats
@@ -915,6 +971,43 @@ int mcpt_scene_get_material_mr(const mcpt_scene *s, const int32_t **mat_mr, int3
 int mcpt_scene_set_material_normal_texture(mcpt_scene *s, int32_t mat, int32_t w, int32_t h, const uint8_t *rgba8, float scale);
 int mcpt_scene_get_material_normal(const mcpt_scene *s, const int32_t **mat_nrm, const float **nrm_scale, int32_t *nmat);
 int mcpt_scene_get_tangents(const mcpt_scene *s, const float **tan0, const float **tan1, const float **tan2, int32_t *ntri);
+/* sRGB base colour (mcpt_texture_set::tex_flags takes what the getter returns).
+ * mcpt_scene_set_material_texture_ex: mcpt_scene_set_material_texture with the image's MCPT_TEX_* flags
+ * (MCPT_TEX_SRGB: the texels are sRGB-encoded and decoded when read as a base colour); an unknown bit is
+ * MCPT_E_INVALID.  mcpt_scene_set_material_texture is this call with 0; the MR and normal setters attach
+ * unflagged images.
+ * mcpt_scene_get_texture_flags: one flag word per texture of the list mcpt_scene_get_textures returns, owned
+ * by the scene (valid until it changes). */
+int mcpt_scene_set_material_texture_ex(mcpt_scene *s, int32_t mat, int32_t w, int32_t h, const uint8_t *rgba8,
+                                       uint32_t flags);
+int mcpt_scene_get_texture_flags(const mcpt_scene *s, const uint32_t **tex_flags, int32_t *ntex);
+/* glb material import.  mcpt_scene_load_glb_ex is mcpt_scene_load_glb with flags; with 0
+ * it is that call, array for array.  An unknown bit is MCPT_E_INVALID.
+ *   MCPT_GLB_PBR_FACTORS  roughnessFactor and metallicFactor as authored (glTF's defaults 1 and 1) in place of
+ *                         the forced roughness 1 and metallic 0.
+ *   MCPT_GLB_TEXTURES     every material's pbrMetallicRoughness.baseColorTexture, .metallicRoughnessTexture and
+ *                         normalTexture (with its scale): textures[i].source -> images[j] -> bufferView -> the
+ *                         PNG reader, attached as the texture setters attach them; one glTF image becomes one
+ *                         entry of the scene's texture list, however many slots use it.  A primitive's TANGENT
+ *                         (a float VEC4 accessor) is kept: T' = normalize(M3 T), M3 the node matrix's upper
+ *                         3 x 3, s' = s sign(det M3); mcpt_scene_get_tangents returns the authored tangents for
+ *                         the triangles that have them and mcpt_tangents_from_uv's for the rest.
+ *   MCPT_GLB_SRGB         the images a base-colour slot uses carry MCPT_TEX_SRGB.
+ * A slot or image that cannot be honoured does not fail the load: the slot stays empty, the factor still
+ * applies, and the report gets a line.  The cases: an image that is not image/png, an image given by uri,
+ * texCoord != 0, KHR_texture_transform, a sampler whose wrapS / wrapT is not REPEAT (10497) or absent, an image
+ * the PNG reader refuses, an index out of range; and a TANGENT accessor with a zero or non-finite tangent or a
+ * handedness other than +-1, whose primitive takes the uv-derived tangents (a line, no count).  Sampler filters
+ * are ignored (the lookup is bilinear).
+ * mcpt_scene_glb_report: of the last load, counts4 = {images decoded, images skipped, slots attached, slots
+ * skipped} and in buf (len bytes, NUL-terminated, truncated) one newline-terminated line per skipped image or
+ * slot, naming the material, the slot and the reason; either may be NULL. */
+#define MCPT_GLB_PBR_FACTORS 1u
+#define MCPT_GLB_TEXTURES 2u
+#define MCPT_GLB_SRGB 4u
+#define MCPT_GLB_AS_AUTHORED 7u
+int mcpt_scene_load_glb_ex(mcpt_scene *s, const char *path, const float *xform16, uint32_t flags);
+int mcpt_scene_glb_report(const mcpt_scene *s, int32_t *counts4, char *buf, int32_t len);
 int mcpt_scene_set_env_hdr(mcpt_scene *s, const char *path, int32_t mode);
 /* flags MCPT_ENV_DEVICE_TABLES: keep the texture only; mcpt_scene_upload then builds the tables on
  * the device (for large maps: the host build is several serial passes over every texel). */

@@ -65,6 +65,34 @@ private:
     int code_;
 };
 
+// MI355X extension: the PNG reader (mcpt.h).  A PNG payload or file decoded into w x h
+// RGBA8 texels, row 0 of the file first: what Scene::set_material_texture takes.  Throws Error with the
+// decoder's reason for a file it refuses.
+struct Image {
+    int32_t w = 0, h = 0;
+    std::vector<uint8_t> rgba8;
+};
+inline Image read_png_memory(const uint8_t* data, size_t n) {
+    Image im;
+    int rc = mcpt_image_read_png_memory(data, n, &im.w, &im.h, nullptr, 0);
+    if (rc == MCPT_OK) {
+        im.rgba8.resize((size_t)im.w * (size_t)im.h * 4);
+        rc = mcpt_image_read_png_memory(data, n, &im.w, &im.h, im.rgba8.data(), im.rgba8.size());
+    }
+    if (rc != MCPT_OK) throw Error(rc, std::string("read_png: ") + mcpt_image_read_png_error());
+    return im;
+}
+inline Image read_png(const std::string& path) {
+    Image im;
+    int rc = mcpt_image_read_png(path.c_str(), &im.w, &im.h, nullptr, 0);
+    if (rc == MCPT_OK) {
+        im.rgba8.resize((size_t)im.w * (size_t)im.h * 4);
+        rc = mcpt_image_read_png(path.c_str(), &im.w, &im.h, im.rgba8.data(), im.rgba8.size());
+    }
+    if (rc != MCPT_OK) throw Error(rc, std::string("read_png: ") + mcpt_image_read_png_error());
+    return im;
+}
+
 namespace detail {
 inline void check(int rc, const mcpt_ctx* ctx, const char* what) {
     if (rc != MCPT_OK) {
@@ -223,6 +251,20 @@ public:
         detail::check(mcpt_scene_load_glb(s_, path.c_str(), nullptr), nullptr, "Scene::load");
         geometry_changed();
     }
+    // MI355X extension: a glb with its materials as authored (mcpt.h MCPT_GLB_*): PBR factors,
+    // embedded PNG textures, TANGENTs and the sRGB flag on base-colour images; xform16 (column-major) or nullptr.
+    void load(const std::string& path, uint32_t glb_flags, const float* xform16 = nullptr) {
+        detail::check(mcpt_scene_load_glb_ex(s_, path.c_str(), xform16, glb_flags), nullptr, "Scene::load");
+        geometry_changed();
+    }
+    // What the last load could not honour: {images decoded, images skipped, slots attached, slots skipped} and one
+    // line per skipped image or material slot
+    std::pair<std::array<int32_t, 4>, std::string> glb_report() const {
+        std::array<int32_t, 4> c{};
+        std::vector<char> buf(1 << 16);
+        detail::check(mcpt_scene_glb_report(s_, c.data(), buf.data(), (int32_t)buf.size()), nullptr, "Scene::glb_report");
+        return {c, std::string(buf.data())};
+    }
     // Triangle soup (the RenderObject path, Scene::add_render_object): 3*ntri floats per array.
     void add_mesh(int32_t ntri, const float* v0, const float* v1, const float* v2, const float* n0, const float* n1,
                   const float* n2, vec3 base_color) {
@@ -259,6 +301,22 @@ public:
         detail::check(mcpt_scene_set_material_texture(s_, mat, w, h, rgba8.empty() ? nullptr : rgba8.data()), nullptr,
                       "Scene::set_material_texture");
         notify();
+    }
+    // MI355X extension: sRGB base colour (mcpt.h).  set_material_texture with the
+    // image's MCPT_TEX_* flags: MCPT_TEX_SRGB marks sRGB-encoded texels, decoded when read as a base colour.
+    void set_material_texture(int32_t mat, int32_t w, int32_t h, const std::vector<uint8_t>& rgba8, uint32_t flags) {
+        if (!rgba8.empty() && rgba8.size() != (size_t)w * (size_t)h * 4)
+            throw Error(MCPT_E_INVALID, "Scene::set_material_texture: w * h * 4 bytes");
+        detail::check(mcpt_scene_set_material_texture_ex(s_, mat, w, h, rgba8.empty() ? nullptr : rgba8.data(), flags), nullptr,
+                      "Scene::set_material_texture");
+        notify();
+    }
+    // One flag word per texture of the scene's texture list
+    std::vector<uint32_t> texture_flags() const {
+        const uint32_t* f = nullptr;
+        int32_t ntex = 0;
+        detail::check(mcpt_scene_get_texture_flags(s_, &f, &ntex), nullptr, "Scene::texture_flags");
+        return std::vector<uint32_t>(f, f + ntex);
     }
     // MI355X extension: metallic-roughness textures (mcpt.h).  A decoded w x h RGBA8
     // image whose G channel scales material `mat`'s roughness and whose B channel its metallic (empty:
@@ -314,8 +372,8 @@ public:
         return out;
     }
     // The built scene's textures (of every kind) and uvs onto a context that holds its upload (nothing
-    // without a texture); with a normal map, the scene's tangents and scales through
-    // mcpt_set_material_texture_set, else the older call
+    // without a texture); with a normal map, the scene's tangents and scales, and with a flagged texture
+    // (section 22) the flag words, through mcpt_set_material_texture_set, else the older call
     void install_textures(mcpt_ctx* ctx) const {
         const mcpt_texture* tex = nullptr;
         const int32_t *mat_tex = nullptr, *mat_mr = nullptr;
@@ -329,13 +387,18 @@ public:
         const float* nrm_scale = nullptr;
         int32_t nn = 0;
         detail::check(mcpt_scene_get_material_normal(s_, &mat_nrm, &nrm_scale, &nn), nullptr, "Scene::install_textures");
-        bool mapped = false;
+        bool mapped = false, flagged = false;
         for (int32_t m = 0; m < nn; m++) mapped = mapped || mat_nrm[m] >= 0;
-        if (mapped) {
+        const uint32_t* flags = nullptr;
+        int32_t nf = 0;
+        detail::check(mcpt_scene_get_texture_flags(s_, &flags, &nf), nullptr, "Scene::install_textures");
+        for (int32_t k = 0; k < nf; k++) flagged = flagged || flags[k] != 0;
+        if (mapped || flagged) {
             const float *t0 = nullptr, *t1 = nullptr, *t2 = nullptr;
             int32_t nt = 0;
-            detail::check(mcpt_scene_get_tangents(s_, &t0, &t1, &t2, &nt), nullptr, "Scene::install_textures");
-            const mcpt_texture_set set{ntri, uv0, uv1, uv2, t0, t1, t2, ntex, tex, nmat, mat_tex, mat_mr, mat_nrm, nrm_scale};
+            if (mapped) detail::check(mcpt_scene_get_tangents(s_, &t0, &t1, &t2, &nt), nullptr, "Scene::install_textures");
+            const mcpt_texture_set set{ntri, uv0, uv1, uv2, t0, t1, t2, ntex, tex, nmat, mat_tex, mat_mr, mapped ? mat_nrm : nullptr,
+                                       mapped ? nrm_scale : nullptr, flagged ? flags : nullptr};
             detail::check(mcpt_set_material_texture_set(ctx, &set), ctx, "scene textures");
             return;
         }

@@ -3,8 +3,9 @@
 // metallic-roughness level (DESIGN.md section 20).  The including kernel defines
 //   FIXED, SAMP, MIS   its template arguments
 //   TEX                the texture level: 0 none, 1 base colour, 2 base colour and metallic-roughness,
-//                      3 those and the normal map (DESIGN.md section 21)
-//   tex_stash          levels 2 and 3: the block's 5 x kBlock LDS floats (material()); else nullptr
+//                      3 those and the normal map (DESIGN.md section 21), 4 level 3 with the base-colour
+//                      lookup decoding sRGB-flagged textures (DESIGN.md section 22)
+//   tex_stash          levels 2 to 4: the block's 5 x kBlock LDS floats (material()); else nullptr
     const ShadeArgs& a = kernarg_fresh<ShadeArgs>();
     if (a.cnt->idle) return;  // the tile set is complete
     const uint32_t shard = blockIdx.x % kShards, w_in = blockIdx.x / kShards, bps = gridDim.x / kShards;

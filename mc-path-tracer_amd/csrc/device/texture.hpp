@@ -9,8 +9,9 @@
 //           counts as 0 (mcpt_core.hpp; dTexture.cu:107-117)
 //   base  = base_factor * T                       one fp32 multiply per channel (the glTF rule)
 //
-// Row 0 of a texture is v in [0, 1 / H): glTF's orientation, no flip.  Texels are used as stored:
-// no sRGB decode (the reference's texture objects have none).  Alpha is ignored.
+// Row 0 of a texture is v in [0, 1 / H): glTF's orientation, no flip.  Texels are used as stored
+// (the reference's texture objects have no sRGB decode) unless the texture is flagged MCPT_TEX_SRGB and read
+// as a base colour (section 22, below).  Alpha is ignored.
 //
 // Metallic-roughness textures (tex_mr below) use the same tc and the same lookup:
 //   T     = tex_bilinear_rgba8(MR texture of the material, tc)     over rgb, unchanged
@@ -32,6 +33,12 @@
 // material without a normal texture keeps m_i = N_i by selection, not by arithmetic.  Texels are used as
 // stored; alpha is ignored.  nrm stands for the hit record's normal everywhere the material stage reads it
 // (frames, f and pdf, the emitter sample, the ray origins' offsets): there is no separate geometric normal.
+//
+// sRGB base colour (srgb_to_linear, tex_bilinear_rgba8_srgb and tex_base_srgb below): a
+// base-colour lookup of a texture flagged MCPT_TEX_SRGB is tex_bilinear_rgba8's arithmetic with
+//   texel = L[c]                                  in place of c / 255
+// L the 256 floats of device/srgb_table.hpp: decode before the filter (the glTF rule).  MR and normal lookups
+// never decode, whatever the texture's flag.  Alpha is ignored.
 #pragma once
 #include "device/mcpt_core.hpp"
 
@@ -42,6 +49,8 @@ struct TexView {
     const float2* uv;       // 3 per triangle record (uv0, uv1, uv2), in record order like DevScene::tri_sh
     const uint32_t* atlas;  // every texture's RGBA8 texels (r in the low byte), row-major, one after the other
     const int4* mat;        // per material {first texel in the atlas, w, h, texture index}; w == 0: untextured
+    // (section 22) the fourth word of a base-colour entry also carries kTexEntrySrgb for a texture flagged
+    // MCPT_TEX_SRGB; only the sRGB kernels read it, and only a set with such a material launches those.
     // Metallic-roughness entries (section 20) live in the same allocation, in front of the base-colour
     // ones and mirrored: material m's is mat[-1 - m], the same four words.  Only k_material's MR
     // instantiations read them, and only a set with an MR-textured material launches those.
@@ -61,9 +70,25 @@ MCPT_HD size_t tex_tan_offset(uint32_t ntri) { return (3 * (size_t)ntri + 1) & ~
 MCPT_HD float unorm8(uint32_t c) { return (float)((double)c * (1.0 / 255.0)); }
 MCPT_HD V3 rgb8(uint32_t t) { return v3(unorm8(t & 255u), unorm8((t >> 8) & 255u), unorm8((t >> 16) & 255u)); }
 
+// L[c], c = 0..255 (section 22): the linear value of the sRGB-encoded byte c, a literal table (one 4-byte
+// load per channel through the vector cache on the device; the table is 1 KiB)
+MCPT_HD float srgb_to_linear(uint32_t c) {
+    static constexpr float L[256] = {
+#include "device/srgb_table.hpp"
+    };
+    return L[c & 255u];
+}
+// A texel's rgb: L[c] per channel where `srgb`, else rgb8 (selection per texel, after one gather)
+MCPT_HD V3 rgb8_srgb(uint32_t t, bool srgb) {
+    if (!srgb) return rgb8(t);
+    return v3(srgb_to_linear(t & 255u), srgb_to_linear((t >> 8) & 255u), srgb_to_linear((t >> 16) & 255u));
+}
+
 // tex_bilinear (mcpt_core.hpp) over a W x H RGBA8 image: the same statements with the texel decode in
 // place of the float4 fetch.  Four 4-byte gathers; W, H in 1..16384, so every index fits an int.
-MCPT_HD V3 tex_bilinear_rgba8(const uint32_t* tex, int W, int H, float u, float v) {
+// SRGB: the decode is rgb8_srgb(c, srgb) (section 22); without it `srgb` is not read.
+template <bool SRGB>
+MCPT_HD V3 tex_bilinear_rgba8_t(const uint32_t* tex, int W, int H, float u, float v, [[maybe_unused]] bool srgb) {
     if (!(__builtin_fabsf(u) < 65536.f)) u = 0.f;
     if (!(__builtin_fabsf(v) < 65536.f)) v = 0.f;
     float x = u * (float)W - 0.5f;
@@ -74,7 +99,12 @@ MCPT_HD V3 tex_bilinear_rgba8(const uint32_t* tex, int W, int H, float u, float 
     int j0 = wrapi((int)fy, H), j1 = wrapi((int)fy + 1, H);
     const uint32_t c00 = tex[j0 * W + i0], c10 = tex[j0 * W + i1];
     const uint32_t c01 = tex[j1 * W + i0], c11 = tex[j1 * W + i1];
-    const V3 t00 = rgb8(c00), t10 = rgb8(c10), t01 = rgb8(c01), t11 = rgb8(c11);
+    V3 t00, t10, t01, t11;
+    if constexpr (SRGB) {
+        t00 = rgb8_srgb(c00, srgb), t10 = rgb8_srgb(c10, srgb), t01 = rgb8_srgb(c01, srgb), t11 = rgb8_srgb(c11, srgb);
+    } else {
+        t00 = rgb8(c00), t10 = rgb8(c10), t01 = rgb8(c01), t11 = rgb8(c11);
+    }
     float bx = 1.f - ax, by = 1.f - ay;
     float w00 = bx * by, w10 = ax * by, w01 = bx * ay, w11 = ax * ay;
     V3 o;
@@ -82,6 +112,12 @@ MCPT_HD V3 tex_bilinear_rgba8(const uint32_t* tex, int W, int H, float u, float 
     o.y = ((w00 * t00.y + w10 * t10.y) + w01 * t01.y) + w11 * t11.y;
     o.z = ((w00 * t00.z + w10 * t10.z) + w01 * t01.z) + w11 * t11.z;
     return o;
+}
+MCPT_HD V3 tex_bilinear_rgba8(const uint32_t* tex, int W, int H, float u, float v) {
+    return tex_bilinear_rgba8_t<false>(tex, W, H, u, v, false);
+}
+MCPT_HD V3 tex_bilinear_rgba8_srgb(const uint32_t* tex, int W, int H, float u, float v, bool srgb) {
+    return tex_bilinear_rgba8_t<true>(tex, W, H, u, v, srgb);
 }
 
 // The texture coordinate of a hit with Moller-Trumbore u, v and w = (1 - u) - v, one component
@@ -93,6 +129,14 @@ MCPT_HD V3 tex_base(const TexView& t, int mat, V3 base_factor, float tu, float t
     const int4 e = t.mat[mat];
     if (e.y <= 0) return base_factor;
     return base_factor * tex_bilinear_rgba8(t.atlas + e.x, e.y, e.z, tu, tv);
+}
+// tex_base under a set with an sRGB-flagged base-colour texture (section 22): the flag rides in the entry's
+// fourth word, which holds the texture index (below 2^30) and which no other lookup reads
+constexpr int kTexEntrySrgb = 1 << 30;
+MCPT_HD V3 tex_base_srgb(const TexView& t, int mat, V3 base_factor, float tu, float tv) {
+    const int4 e = t.mat[mat];
+    if (e.y <= 0) return base_factor;
+    return base_factor * tex_bilinear_rgba8_srgb(t.atlas + e.x, e.y, e.z, tu, tv, (e.w & kTexEntrySrgb) != 0);
 }
 
 // The shaded roughness and metallic of material `mat` at (tu, tv): (rough_factor, metal_factor) times the

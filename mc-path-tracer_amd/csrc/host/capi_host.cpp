@@ -1,4 +1,5 @@
 // capi_host.cpp -- extern "C" entry points of the host scene builder (mcpt_scene_*).
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -27,11 +28,28 @@ extern "C" {
 mcpt_scene* mcpt_scene_new(void) { return new (std::nothrow) mcpt_scene(); }
 void mcpt_scene_free(mcpt_scene* s) { delete s; }
 
-int mcpt_scene_load_glb(mcpt_scene* s, const char* path, const float* xform16) {
+int mcpt_scene_load_glb(mcpt_scene* s, const char* path, const float* xform16) { return mcpt_scene_load_glb_ex(s, path, xform16, 0u); }
+int mcpt_scene_load_glb_ex(mcpt_scene* s, const char* path, const float* xform16, uint32_t flags) {
     if (!s || !path) return fail(s, MCPT_E_INVALID, "null argument");
+    if (flags & ~(uint32_t)MCPT_GLB_AS_AUTHORED) return fail(s, MCPT_E_INVALID, "unknown glb flag");
     std::string err;
-    int rc = s->s.load_glb(path, xform16, err);
+    int rc;
+    try {
+        rc = s->s.load_glb(path, xform16, flags, err);
+    } catch (const std::bad_alloc&) {
+        return fail(s, MCPT_E_NOMEM, "glb: out of memory");
+    }
     return rc ? fail(s, rc, err) : MCPT_OK;
+}
+int mcpt_scene_glb_report(const mcpt_scene* s, int32_t* counts4, char* buf, int32_t len) {
+    if (!s) return MCPT_E_INVALID;
+    for (int k = 0; counts4 && k < 4; k++) counts4[k] = s->s.glb_counts[k];
+    if (buf && len > 0) {
+        const size_t n = std::min((size_t)len - 1, s->s.glb_lines.size());
+        memcpy(buf, s->s.glb_lines.data(), n);
+        buf[n] = 0;
+    }
+    return MCPT_OK;
 }
 
 int mcpt_scene_add_mesh(mcpt_scene* s, int32_t ntri, const float* v0, const float* v1, const float* v2,
@@ -152,7 +170,7 @@ int mcpt_scene_set_mesh_uv(mcpt_scene* s, int32_t mat, const float* uv0, const f
 // Attaches the image to material mat through the index array idx (mat_tex: base colour; mat_mr:
 // metallic-roughness, section 20; mat_nrm: normal map, section 21): all kinds share the texture list.
 static int scene_attach_texture(mcpt_scene* s, std::vector<int32_t> mcpt_host::Scene::*idx, int32_t mat, int32_t w, int32_t h,
-                                const uint8_t* rgba8) {
+                                const uint8_t* rgba8, uint32_t flags = 0) {
     if (!s) return fail(s, MCPT_E_INVALID, "null scene");
     if (mat < 0 || (size_t)mat >= s->s.mat_tex.size()) return fail(s, MCPT_E_INVALID, "material id out of range");
     if (!rgba8) {  // detach (the texture itself stays in the list: the other indices keep their meaning)
@@ -164,8 +182,14 @@ static int scene_attach_texture(mcpt_scene* s, std::vector<int32_t> mcpt_host::S
     t.w = w;
     t.h = h;
     t.rgba8.assign(rgba8, rgba8 + (size_t)w * h * 4);
+    t.flags = flags;
     int32_t& k = (s->s.*idx)[mat];
-    if (k >= 0) {
+    // an entry may serve several slots (a glb image is one entry however many slots use it; section 22): it is
+    // replaced in place only when this slot alone refers to it, so the other slots keep their image
+    int users = 0;
+    for (const std::vector<int32_t>* a : {&s->s.mat_tex, &s->s.mat_mr, &s->s.mat_nrm})
+        for (int32_t v : *a) users += k >= 0 && v == k;
+    if (k >= 0 && users == 1) {
         s->s.textures[k] = std::move(t);  // the material's own texture is replaced
     } else {
         k = (int32_t)s->s.textures.size();
@@ -176,6 +200,20 @@ static int scene_attach_texture(mcpt_scene* s, std::vector<int32_t> mcpt_host::S
 
 int mcpt_scene_set_material_texture(mcpt_scene* s, int32_t mat, int32_t w, int32_t h, const uint8_t* rgba8) {
     return scene_attach_texture(s, &mcpt_host::Scene::mat_tex, mat, w, h, rgba8);
+}
+// sRGB base colour: the texture carries MCPT_TEX_* flags into the set
+int mcpt_scene_set_material_texture_ex(mcpt_scene* s, int32_t mat, int32_t w, int32_t h, const uint8_t* rgba8, uint32_t flags) {
+    if (s && (flags & ~(uint32_t)MCPT_TEX_SRGB)) return fail(s, MCPT_E_INVALID, "unknown texture flag");
+    return scene_attach_texture(s, &mcpt_host::Scene::mat_tex, mat, w, h, rgba8, flags);
+}
+int mcpt_scene_get_texture_flags(const mcpt_scene* s, const uint32_t** tex_flags, int32_t* ntex) {
+    if (!s || !tex_flags || !ntex) return MCPT_E_INVALID;
+    const mcpt_host::Scene& sc = s->s;
+    sc.tex_flag_views.clear();
+    for (const mcpt_host::Texture& t : sc.textures) sc.tex_flag_views.push_back(t.flags);
+    *ntex = (int32_t)sc.tex_flag_views.size();
+    *tex_flags = sc.tex_flag_views.data();
+    return MCPT_OK;
 }
 int mcpt_scene_set_material_mr_texture(mcpt_scene* s, int32_t mat, int32_t w, int32_t h, const uint8_t* rgba8) {
     return scene_attach_texture(s, &mcpt_host::Scene::mat_mr, mat, w, h, rgba8);
@@ -204,6 +242,12 @@ int mcpt_scene_get_tangents(const mcpt_scene* s, const float** tan0, const float
                                          sc.f_n2.data(), sc.f_uv0.data(), sc.f_uv1.data(), sc.f_uv2.data(), sc.f_tan[0].data(),
                                          sc.f_tan[1].data(), sc.f_tan[2].data());
     if (rc) return fail(const_cast<mcpt_scene*>(s), rc, "tangents: bad arrays");
+    // (section 22) a triangle that came with a glb's TANGENT keeps the authored ones
+    for (int32_t i = 0; i < n; i++) {
+        const mcpt_host::Tri& t = sc.tris[(size_t)sc.f_id[(size_t)i]];
+        if (!t.has_tan) continue;
+        for (int k = 0; k < 3; k++) memcpy(&sc.f_tan[k][4 * (size_t)i], t.tan[k], 4 * sizeof(float));
+    }
     *ntri = n;
     *tan0 = sc.f_tan[0].data();
     *tan1 = sc.f_tan[1].data();

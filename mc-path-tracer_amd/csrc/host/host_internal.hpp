@@ -15,12 +15,16 @@ struct Tri {
     mcpt::V3 n[3];
     int mat;
     float uv[3][2] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};  // TEXCOORD_0 of the corners (absent: zeros)
+    // a glb's TANGENT of the corners {T.xyz, s}, transformed with the node (MCPT_GLB_TEXTURES; section 22)
+    float tan[3][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    bool has_tan = false;
 };
 
 // A base-colour texture attached to a material: decoded RGBA8 texels, row 0 first
 struct Texture {
     int w = 0, h = 0;
     std::vector<uint8_t> rgba8;
+    uint32_t flags = 0;  // MCPT_TEX_* 
 };
 
 struct Scene {
@@ -40,6 +44,7 @@ struct Scene {
     std::vector<float> nrm_scale;
     mutable std::vector<float> f_tan[3];
     mutable std::vector<mcpt_texture> tex_views;
+    mutable std::vector<uint32_t> tex_flag_views;  // what mcpt_scene_get_texture_flags hands out
     // environment light (EnvironmentLight.h:17-40); default Color 0.8 (Scene.cu:21)
     int env_mode = 0;
     float env_color[3] = {0.8f, 0.8f, 0.8f};
@@ -57,14 +62,19 @@ struct Scene {
     std::vector<float> node_bmin, node_bmax;
     std::vector<int32_t> node_offset, node_nprims, node_axis;
     std::string err;
+    // what the last load_glb could not honour (mcpt_scene_glb_report): images decoded / skipped, slots attached /
+    // skipped, and one line per skipped image or slot
+    int32_t glb_counts[4] = {0, 0, 0, 0};
+    std::string glb_lines;
 
     void add_mesh(const std::vector<mcpt::V3>& pos, const std::vector<mcpt::V3>& nrm,
                   const std::vector<uint32_t>& idx, mcpt::V3 base, mcpt::V3 emit = mcpt::v3(0.f, 0.f, 0.f),
-                  const std::vector<float>* uv = nullptr);  // uv: 2 floats per vertex, or none (zeros)
+                  const std::vector<float>* uv = nullptr,    // uv: 2 floats per vertex, or none (zeros)
+                  const std::vector<float>* tan = nullptr);  // tan: 4 floats per vertex {T.xyz, s}, or none
     bool has_emission() const;  // some material emits
     void gather_uv();           // f_uv0..2 from tris by f_id (build, and a uv change on a built scene)
     void transform(const float* xf16);
-    int load_glb(const char* path, const float* xf16, std::string& err);
+    int load_glb(const char* path, const float* xf16, uint32_t flags, std::string& err);
     int set_env_hdr(const char* path, int mode, std::string& err, bool host_tables = true);
     int build(int max_prims, std::string& err);
     int build(const mcpt_bvh_params& p, std::string& err);

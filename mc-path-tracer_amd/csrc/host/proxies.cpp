@@ -162,7 +162,7 @@ int make_proxy(Scene& s, int config_id, const std::string& dir, std::string& err
     int rc = MCPT_OK;
     switch (config_id) {
     case 1:
-        rc = s.load_glb(sphere.c_str(), nullptr, err);
+        rc = s.load_glb(sphere.c_str(), nullptr, 0u, err);
         if (!rc) rc = s.set_env_hdr(hdr029.c_str(), 1, err);
         return rc;
     case 2: {
@@ -189,7 +189,7 @@ int make_proxy(Scene& s, int config_id, const std::string& dir, std::string& err
             }
             cen[i] = c;
             float xf[16] = {r, 0, 0, 0, 0, r, 0, 0, 0, 0, r, 0, c.x, c.y, c.z, 1};
-            rc = s.load_glb(sphere.c_str(), xf, err);
+            rc = s.load_glb(sphere.c_str(), xf, 0u, err);
             if (rc) return rc;
             // spheres get distinct albedos so the image is not all grey
             const float alb[5][3] = {{0.9f, 0.9f, 0.9f}, {0.8f, 0.6f, 0.2f}, {0.2f, 0.4f, 0.8f}, {0.7f, 0.7f, 0.7f}, {0.5f, 0.8f, 0.5f}};
@@ -209,7 +209,7 @@ int make_proxy(Scene& s, int config_id, const std::string& dir, std::string& err
         return s.set_env_hdr(night.c_str(), 1, err);
     }
     case 4: {
-        rc = s.load_glb(suzanne.c_str(), nullptr, err);
+        rc = s.load_glb(suzanne.c_str(), nullptr, 0u, err);
         if (rc) return rc;
         subdivide_all(s, 2);
         s.transform(rot);

@@ -199,7 +199,7 @@ static M4 trs_matrix(const float* t, const float* q, const float* s) {  // glTF 
 // Scene
 // ---------------------------------------------------------------------------
 void Scene::add_mesh(const std::vector<V3>& pos, const std::vector<V3>& nrm, const std::vector<uint32_t>& idx,
-                     V3 base, V3 emit, const std::vector<float>* uv) {
+                     V3 base, V3 emit, const std::vector<float>* uv, const std::vector<float>* tan) {
     int mat_id = (int)(materials.size() / 8);
     float mp[8] = {base.x, base.y, base.z, 0.04f, 0.04f, 0.04f, 1.f, 0.f};  // dMaterial.cuh:13-18, Scene.cu:306-307
     materials.insert(materials.end(), mp, mp + 8);
@@ -214,18 +214,39 @@ void Scene::add_mesh(const std::vector<V3>& pos, const std::vector<V3>& nrm, con
         for (int k = 0; k < 3; k++) { t.p[k] = pos[idx[i + k]]; t.n[k] = nrm[idx[i + k]]; }
         if (uv)
             for (int k = 0; k < 3; k++) { t.uv[k][0] = (*uv)[2 * idx[i + k]]; t.uv[k][1] = (*uv)[2 * idx[i + k] + 1]; }
+        if (tan) {
+            for (int k = 0; k < 3; k++)
+                for (int c = 0; c < 4; c++) t.tan[k][c] = (*tan)[4 * idx[i + k] + c];
+            t.has_tan = true;
+        }
         t.mat = mat_id;
         tris.push_back(t);
     }
     built = false;
 }
 
+// An authored tangent {T.xyz, s} under the node matrix M (section 22): T' = normalize(M3 T), M3 the upper 3 x 3,
+// each component (m0 x + m1 y) + m2 z in float; s' = s sign(det M3)
+static float m3_det(const M4& M) {
+    const float* m = M.m;
+    return (m[0] * (m[5] * m[10] - m[9] * m[6]) - m[4] * (m[1] * m[10] - m[9] * m[2])) + m[8] * (m[1] * m[6] - m[5] * m[2]);
+}
+static void m3_tangent(const M4& M, float det, float* t4) {
+    const float* m = M.m;
+    const float x = t4[0], y = t4[1], z = t4[2];
+    const V3 T = glm_normalize(mcpt::v3((m[0] * x + m[4] * y) + m[8] * z, (m[1] * x + m[5] * y) + m[9] * z, (m[2] * x + m[6] * y) + m[10] * z));
+    t4[0] = T.x, t4[1] = T.y, t4[2] = T.z;
+    if (det < 0.f) t4[3] = -t4[3];
+}
+
 void Scene::transform(const float* xf16) {
     M4 M;
     memcpy(M.m, xf16, sizeof(M.m));
     M4 N = m4_transpose(m4_inverse(M));  // Scene.cu:212
+    const float det = m3_det(M);
     for (auto& t : tris)
         for (int k = 0; k < 3; k++) {
+            if (t.has_tan) m3_tangent(M, det, t.tan[k]);
             t.p[k] = m4_point(M, t.p[k]);
             float o[4];
             mcpt::mat_vec4(N.m, t.n[k].x, t.n[k].y, t.n[k].z, 1.f, o);  // w = 1 quirk (Scene.cu:232)
@@ -250,7 +271,12 @@ static bool read_file(const char* path, std::vector<uint8_t>& out) {
 // node transforms baked into positions, normals by transpose(inverse(M)),
 // roughness forced to 1, metallic to 0; no material => base colour (1,1,1)
 // (assimp's glTF2 default material; parity unpinned).
-int Scene::load_glb(const char* path, const float* xf16, std::string& err) {
+// With flags (mcpt.h MCPT_GLB_*): the authored roughness and metallic factors, the
+// materials' base-colour / metallic-roughness / normal textures from embedded PNG images with the primitives'
+// TANGENT accessors, and the sRGB flag on base-colour images.  flags == 0 is the reader as it was.
+int Scene::load_glb(const char* path, const float* xf16, uint32_t flags, std::string& err) {
+    for (int32_t& c : glb_counts) c = 0;
+    glb_lines.clear();
     std::vector<uint8_t> buf;
     if (!read_file(path, buf)) { err = std::string("cannot read ") + path; return MCPT_E_IO; }
     if (buf.size() < 20 || memcmp(buf.data(), "glTF", 4) != 0) { err = "not a glb file"; return MCPT_E_IO; }
@@ -304,6 +330,64 @@ int Scene::load_glb(const char* path, const float* xf16, std::string& err) {
                 else return false;
             }
         return true;
+    };
+
+    // ---- textures (MCPT_GLB_TEXTURES): image j of the file becomes one entry of the scene's texture list,
+    // however many slots use it; what cannot be honoured leaves the slot empty and a line in the report
+    const Json* jimages = root.get("images");
+    const Json* jtextures = root.get("textures");
+    const Json* jsamplers = root.get("samplers");
+    std::vector<int> image_tex(jimages ? jimages->arr.size() : 0, -2);  // -2: not tried, -1: skipped, else the index
+    std::vector<std::string> image_why(image_tex.size());
+    auto image_texture = [&](int j, std::string& why) -> int {
+        if (image_tex[j] != -2) { why = image_why[j]; return image_tex[j]; }
+        const Json& im = jimages->arr[j];
+        int k = -1;
+        const Json* mime = im.get("mimeType");
+        const int vi = (int)im.numv("bufferView", -1);
+        if (im.get("uri")) why = "image given by uri";
+        else if (mime && mime->str != "image/png") why = "image is " + mime->str + ", not image/png";
+        else if (vi < 0 || vi >= (int)views->arr.size()) why = "image bufferView out of range";
+        else {
+            const Json& v = views->arr[vi];
+            const size_t boff = (size_t)v.numv("byteOffset", 0), blen = (size_t)v.numv("byteLength", 0);
+            int32_t w = 0, h = 0;
+            if (boff > binlen || blen > binlen - boff) why = "image bufferView beyond the buffer";
+            else if (mcpt_image_read_png_memory(bin + boff, blen, &w, &h, nullptr, 0) != MCPT_OK) why = mcpt_image_read_png_error();
+            else {
+                Texture t;
+                t.w = w, t.h = h;
+                t.rgba8.resize((size_t)w * h * 4);
+                if (mcpt_image_read_png_memory(bin + boff, blen, &w, &h, t.rgba8.data(), t.rgba8.size()) != MCPT_OK) why = mcpt_image_read_png_error();
+                else {
+                    k = (int)textures.size();
+                    textures.push_back(std::move(t));
+                }
+            }
+        }
+        image_tex[j] = k;
+        image_why[j] = why;
+        glb_counts[k >= 0 ? 0 : 1]++;
+        if (k < 0) glb_lines += "image " + std::to_string(j) + ": " + why + "\n";
+        return k;
+    };
+    // the texture index of a material's slot `info` ({index, texCoord, extensions}), or -1 with the reason
+    auto slot_texture = [&](const Json* info, std::string& why) -> int {
+        const int ti = (int)info->numv("index", -1);
+        if ((int)info->numv("texCoord", 0) != 0) { why = "texCoord != 0"; return -1; }
+        const Json* ext = info->get("extensions");
+        if (ext && ext->get("KHR_texture_transform")) { why = "KHR_texture_transform"; return -1; }
+        if (!jtextures || ti < 0 || ti >= (int)jtextures->arr.size()) { why = "texture index out of range"; return -1; }
+        const Json& tx = jtextures->arr[ti];
+        if (tx.get("sampler")) {
+            const int si = (int)tx.numv("sampler", -1);
+            if (!jsamplers || si < 0 || si >= (int)jsamplers->arr.size()) { why = "sampler index out of range"; return -1; }
+            const Json& sm = jsamplers->arr[si];
+            if ((int)sm.numv("wrapS", 10497) != 10497 || (int)sm.numv("wrapT", 10497) != 10497) { why = "sampler wrap is not REPEAT"; return -1; }
+        }
+        const int ii = (int)tx.numv("source", -1);
+        if (!jimages || ii < 0 || ii >= (int)jimages->arr.size()) { why = "image index out of range"; return -1; }
+        return image_texture(ii, why);
     };
 
     M4 base = m4_identity();
@@ -370,9 +454,18 @@ int Scene::load_glb(const char* path, const float* xf16, std::string& err) {
                         if (ix >= nv) { err = "glb: index out of range"; status = MCPT_E_IO; return; }
                     V3 bc = mcpt::v3(1.f, 1.f, 1.f);
                     V3 em = mcpt::v3(0.f, 0.f, 0.f);
+                    float rough = 1.f, metal = 1.f;  // glTF's defaults (MCPT_GLB_PBR_FACTORS)
+                    const Json* slot[3] = {nullptr, nullptr, nullptr};  // base colour, MR, normal (MCPT_GLB_TEXTURES)
                     int mati = (int)pr.numv("material", -1);
                     if (mats && mati >= 0 && mati < (int)mats->arr.size()) {
                         const Json* pbr = mats->arr[mati].get("pbrMetallicRoughness");
+                        if (pbr) {
+                            rough = (float)pbr->numv("roughnessFactor", 1.0);
+                            metal = (float)pbr->numv("metallicFactor", 1.0);
+                            slot[0] = pbr->get("baseColorTexture");
+                            slot[1] = pbr->get("metallicRoughnessTexture");
+                        }
+                        slot[2] = mats->arr[mati].get("normalTexture");
                         const Json* bcf = pbr ? pbr->get("baseColorFactor") : nullptr;
                         if (bcf && bcf->arr.size() >= 3)
                             bc = mcpt::v3((float)bcf->arr[0].num, (float)bcf->arr[1].num, (float)bcf->arr[2].num);
@@ -391,7 +484,44 @@ int Scene::load_glb(const char* path, const float* xf16, std::string& err) {
                     std::vector<float> uv;
                     bool has_uv = attrs->get("TEXCOORD_0") && read_accessor((int)attrs->numv("TEXCOORD_0", -1), uv, dummy, nc) &&
                                   nc == 2 && uv.size() == 2 * nv;
-                    add_mesh(pos, nrm, idx, bc, em, has_uv ? &uv : nullptr);
+                    // TANGENT (a float VEC4 accessor), under the node matrix like the normals
+                    std::vector<float> tg;
+                    bool has_tan = (flags & MCPT_GLB_TEXTURES) && attrs->get("TANGENT") &&
+                                   read_accessor((int)attrs->numv("TANGENT", -1), tg, dummy, nc) && nc == 4 && tg.size() == 4 * nv;
+                    if (has_tan) {
+                        const float det = m3_det(M);
+                        for (size_t i = 0; i < nv; i++) m3_tangent(M, det, &tg[4 * i]);
+                        // a zero or non-finite tangent (or handedness) cannot be honoured: the primitive's triangles
+                        // take the uv-derived tangents like those of a primitive without TANGENT
+                        for (size_t i = 0; has_tan && i < 4 * nv; i++) has_tan = std::isfinite(tg[i]);
+                        for (size_t i = 0; has_tan && i < nv; i++) has_tan = tg[4 * i + 3] == 1.f || tg[4 * i + 3] == -1.f;
+                        if (!has_tan)
+                            glb_lines += "material " + std::to_string((int)pr.numv("material", -1)) +
+                                         " TANGENT: degenerate tangent, derived from the uvs instead\n";
+                    }
+                    add_mesh(pos, nrm, idx, bc, em, has_uv ? &uv : nullptr, has_tan ? &tg : nullptr);
+                    const size_t mat_id = mat_tex.size() - 1;
+                    if (flags & MCPT_GLB_PBR_FACTORS) {
+                        materials[8 * mat_id + 6] = rough;
+                        materials[8 * mat_id + 7] = metal;
+                    }
+                    if (flags & MCPT_GLB_TEXTURES) {
+                        static const char* names[3] = {"baseColorTexture", "metallicRoughnessTexture", "normalTexture"};
+                        std::vector<int32_t>* index[3] = {&mat_tex, &mat_mr, &mat_nrm};
+                        for (int k = 0; k < 3; k++) {
+                            if (!slot[k] || slot[k]->kind != Json::Obj) continue;
+                            std::string why;
+                            const int t = slot_texture(slot[k], why);
+                            glb_counts[t >= 0 ? 2 : 3]++;
+                            if (t < 0) {
+                                glb_lines += "material " + std::to_string(mati) + " " + names[k] + ": " + why + "\n";
+                                continue;
+                            }
+                            (*index[k])[mat_id] = t;
+                            if (k == 0 && (flags & MCPT_GLB_SRGB)) textures[(size_t)t].flags |= MCPT_TEX_SRGB;
+                            if (k == 2) nrm_scale[mat_id] = (float)slot[k]->numv("scale", 1.0);
+                        }
+                    }
                 }
             }
         }

@@ -532,6 +532,8 @@ struct MatOut {
 // Level 3 is level 2 behind a hit record whose normal the material's normal map
 // perturbed (hit_record_n): n below is that normal, so the three frames, every f and pdf, the emitter sample
 // with its MIS pdf and the offsets of the ray origins follow; MatOut::n carries it to material_brdf_terms.
+// Level 4 is level 3 with the base-colour lookup decoding the texels of a texture flagged
+// MCPT_TEX_SRGB through the table (device/texture.hpp tex_base_srgb); the MR and normal lookups are level 3's.
 template <bool FIXED, bool SAMP = false, bool MIS = false, int TEX = 0>
 __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix, uint32_t sidx, uint32_t len,
                                  V3 beta_store, int32_t htri, float4* stage, bool occ_on, bool no_cont, bool& want_e,
@@ -549,14 +551,15 @@ __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix
     int mat;
     float t_hit;
     [[maybe_unused]] float tu, tv;
-    if constexpr (TEX == 3) hit_record_n(sc, a.tex, ro, rdir, htri, pos, n, mat, t_hit, tu, tv);
+    if constexpr (TEX >= 3) hit_record_n(sc, a.tex, ro, rdir, htri, pos, n, mat, t_hit, tu, tv);
     else if constexpr (TEX != 0) hit_record_t<true>(sc, a.tex.uv, ro, rdir, htri, pos, n, mat, t_hit, tu, tv);
     else hit_record(sc, ro, rdir, htri, pos, n, mat, t_hit);
     const V3 wo = -rdir;
     Mat m_ld = load_mat(sc.mats + 8 * mat);
     if constexpr (TEX != 0) {
         MCPT_MARK("m_tex");
-        m_ld.base = mcpt::tex_base(a.tex, mat, m_ld.base, tu, tv);
+        if constexpr (TEX == 4) m_ld.base = mcpt::tex_base_srgb(a.tex, mat, m_ld.base, tu, tv);
+        else m_ld.base = mcpt::tex_base(a.tex, mat, m_ld.base, tu, tv);
         if constexpr (TEX == 1) mo.base = m_ld.base;
     }
     if constexpr (TEX >= 2) {
@@ -754,7 +757,7 @@ __device__ inline MatOut material(const ShadeArgs& a, uint32_t pid, uint32_t pix
 // visibility ray that may be unoccluded (need_cb): one the occluder cache resolved is never read.
 // TEX: with the base colour material() shaded with (MatOut::base: three registers across the occluder
 // cache instead of a second lookup's four gathers); TEX == 2: and with its roughness and metallic, all
-// five from the thread's LDS words (material()); TEX == 3 as 2 (the mapped normal is MatOut::n).
+// five from the thread's LDS words (material()); TEX == 3 and 4 as 2 (the mapped normal is MatOut::n).
 template <bool FIXED, int TEX = 0>
 __device__ inline void material_brdf_terms(const ShadeArgs& a, uint32_t pid, const MatOut& mo,
                                            [[maybe_unused]] const float* tex_stash = nullptr) {
@@ -1273,12 +1276,16 @@ struct TexMr {};
 // colour, MR and normal per material, each behind its own w == 0 test.  The TexMr instantiations keep
 // their template arguments, and with them their symbols.
 struct TexNrm {};
+// The sRGB instantiations, k_material<TexSrgb, FIXED, SAMP, MIS>: a third tag, launched
+// only while a set with a material whose base-colour texture is flagged MCPT_TEX_SRGB is in effect: level 3
+// with that lookup decoding through the table.  The TexMr and TexNrm instantiations keep their symbols.
+struct TexSrgb {};
 template <typename LEVEL, bool FIXED, bool SAMP = false, bool MIS = false>
 __global__ __launch_bounds__(kBlock) MCPT_MAT_ATTR void k_material(ShadeArgs a_kernarg) {
-    static_assert(std::is_same<LEVEL, TexMr>::value || std::is_same<LEVEL, TexNrm>::value,
-                  "the tag selects the metallic-roughness or the normal-map level");
+    static_assert(std::is_same<LEVEL, TexMr>::value || std::is_same<LEVEL, TexNrm>::value || std::is_same<LEVEL, TexSrgb>::value,
+                  "the tag selects the metallic-roughness, the normal-map or the sRGB level");
     (void)a_kernarg;
-    constexpr int TEX = std::is_same<LEVEL, TexNrm>::value ? 3 : 2;
+    constexpr int TEX = std::is_same<LEVEL, TexSrgb>::value ? 4 : std::is_same<LEVEL, TexNrm>::value ? 3 : 2;
     __shared__ float s_tex[5][kBlock];  // base colour, roughness, metallic of the thread's path (5 KiB)
     float* const tex_stash = &s_tex[0][0];
 #include "device/k_material_body.inc"
@@ -2260,10 +2267,14 @@ static uint32_t shade_grid(uint32_t nblocks, const LaunchGeom& g) {
 // k_material for a launch: the textured instantiation while a texture set is in effect (a.tex.uv set;
 // DESIGN.md section 19), on its twin's grid; every other context launches what it launched before.
 // tex_level (the host's choice, no kernel argument): 2 the set has an MR-textured material (section 20),
-// 3 it has a normal-mapped one (section 21); below 2 the set alone decides.
+// 3 it has a normal-mapped one (section 21), 4 one whose base-colour texture is sRGB-flagged (section 22); below
+// 2 the set alone decides.
 template <bool SAMP, bool MIS>
 static void launch_material(const ShadeArgs& a, const uint32_t* blocks, bool fixed_mode, int tex_level, hipStream_t s) {
-    if (a.tex.uv && tex_level >= 3) {
+    if (a.tex.uv && tex_level >= 4) {
+        if (fixed_mode) hipLaunchKernelGGL((k_material<TexSrgb, true, SAMP, MIS>), dim3(blocks[1]), dim3(kBlock), 0, s, a);
+        else hipLaunchKernelGGL((k_material<TexSrgb, false, SAMP, MIS>), dim3(blocks[0]), dim3(kBlock), 0, s, a);
+    } else if (a.tex.uv && tex_level == 3) {
         if (fixed_mode) hipLaunchKernelGGL((k_material<TexNrm, true, SAMP, MIS>), dim3(blocks[1]), dim3(kBlock), 0, s, a);
         else hipLaunchKernelGGL((k_material<TexNrm, false, SAMP, MIS>), dim3(blocks[0]), dim3(kBlock), 0, s, a);
     } else if (a.tex.uv && tex_level == 2) {

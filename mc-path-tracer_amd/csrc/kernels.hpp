@@ -367,7 +367,8 @@ struct LaunchGeom {
 int launch_geometry(int device, LaunchGeom& g);  // device must be current
 // tex_level: 2 the installed texture set has a metallic-roughness textured material:
 // with a.tex set, k_material<TexMr, ...> in place of k_material's textured instantiation; 3 it has a
-// normal-mapped one (section 21): k_material<TexNrm, ...>.  Below 2 a.tex alone decides.
+// normal-mapped one (section 21): k_material<TexNrm, ...>; 4 a material's base-colour texture is flagged
+// MCPT_TEX_SRGB (section 22): k_material<TexSrgb, ...>.  Below 2 a.tex alone decides.
 void launch_shade(const ShadeArgs& a, int nblocks, const LaunchGeom& g, bool fixed_mode, int tex_level, hipStream_t s);
 void launch_shade_stage(bool material_stage, const ShadeArgs& a, int nblocks, const LaunchGeom& g, bool fixed_mode,
                         int tex_level, hipStream_t s);
@@ -546,8 +547,14 @@ void launch_guide_accum_tex(const GuideTexArgs& a, hipStream_t s);
 // k_guide_accum_nrm (section 21): k_guide_accum_tex whose hit record is hit_record_n, so the normal guide
 // accumulates the mapped normal; the albedo guide is unchanged.  Launched only under a normal-mapped set.
 void launch_guide_accum_nrm(const GuideTexArgs& a, hipStream_t s);
+// k_guide_accum_srgb (section 22): k_guide_accum_nrm whose albedo is tex_base_srgb, the decoded colour.
+// Launched only under a set with a material whose base-colour texture is flagged MCPT_TEX_SRGB.
+void launch_guide_accum_srgb(const GuideTexArgs& a, hipStream_t s);
 // k_tex_sample: out[i] = tex_bilinear_rgba8(tex, w, h, uv[i]) for n uv pairs (mcpt_texture_sample_run)
 void launch_tex_sample(const uint32_t* tex, int w, int h, const float2* uv, float* out_rgb, uint32_t n, hipStream_t s);
+// k_tex_sample_srgb (section 22): the same over tex_bilinear_rgba8_srgb(..., true) (mcpt_texture_sample_run_ex
+// with MCPT_TEX_SRGB)
+void launch_tex_sample_srgb(const uint32_t* tex, int w, int h, const float2* uv, float* out_rgb, uint32_t n, hipStream_t s);
 // k_tex_uv_records: the uv stream in record order: out[3 p + k] = uv_k[order[p]] (order == nullptr: p),
 // uv0 / uv1 / uv2 in desc order
 void launch_tex_uv_records(const float2* uv0, const float2* uv1, const float2* uv2, const uint32_t* order, float2* out,

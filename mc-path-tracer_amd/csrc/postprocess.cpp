@@ -364,7 +364,9 @@ int mcpt_guides_render(mcpt_ctx* c, uint32_t nsamples) {
             HIPCHK(c, hipMemsetAsync(c->cnt.dev->grab, 0, sizeof(c->cnt.dev->grab), c->stream));  // hand-out counters back to 0
             if (tex.uv) {  // textures in effect (section 19): the albedo is the shaded base colour at the hit
                 // (a normal-mapped set, section 21: and the normal guide is the mapped normal)
-                if (c->tx.level() == 3) launch_guide_accum_nrm(GuideTexArgs{ga, c->scene.dev, tex, ht}, c->stream);
+                // (an sRGB-flagged base colour, section 22: and the albedo is the decoded colour)
+                if (c->tx.level() == 4) launch_guide_accum_srgb(GuideTexArgs{ga, c->scene.dev, tex, ht}, c->stream);
+                else if (c->tx.level() == 3) launch_guide_accum_nrm(GuideTexArgs{ga, c->scene.dev, tex, ht}, c->stream);
                 else launch_guide_accum_tex(GuideTexArgs{ga, c->scene.dev, tex, ht}, c->stream);
             } else {
                 HitRecordArgs ha{c->scene.dev, ro, rd, ht, hp, hn, ht, n};

@@ -248,6 +248,7 @@ struct Textures {
     std::vector<float> uv[3], tan[3], nrm_scale;
     std::vector<int32_t> tw, th, mat_tex, mat_mr, mat_nrm;
     std::vector<uint32_t> first;  // texture k's first texel in the atlas
+    std::vector<uint32_t> flags;  // per texture MCPT_TEX_* (section 22); empty: the caller gave none (all 0)
     std::vector<uint32_t> atlas;
     DevBuf<float2> d_uv, d_stage;  // [3 ntri] record order (+ the tangent stream); [3 ntri] desc order, the permutation's input
     DevBuf<float4> d_tstage;       // [3 ntri] tangents in desc order, the permutation's input
@@ -256,13 +257,14 @@ struct Textures {
     int32_t textured = 0;      // materials with a base-colour texture
     int32_t textured_mr = 0;   // materials with a metallic-roughness texture
     int32_t textured_nrm = 0;  // materials with a normal map
+    int32_t textured_srgb = 0;  // materials whose base-colour texture is flagged MCPT_TEX_SRGB (section 22)
     bool nrm_fields = false;   // the caller gave tangents, mat_nrm or nrm_scale
     bool dev_ok = false;       // the device arrays stand for the current record order
     bool installed() const { return !mat_tex.empty(); }
     // some material shades through a lookup
     bool shaded() const { return textured > 0 || textured_mr > 0 || textured_nrm > 0; }
     // k_material's texture level while the set is in effect (launch_shade)
-    int level() const { return textured_nrm > 0 ? 3 : textured_mr > 0 ? 2 : 1; }
+    int level() const { return textured_srgb > 0 ? 4 : textured_nrm > 0 ? 3 : textured_mr > 0 ? 2 : 1; }
     mcpt::TexView view() const {
         if (!(shaded() && dev_ok)) return mcpt::TexView{nullptr, nullptr, nullptr};
         return mcpt::TexView{d_uv.get(), d_atlas.get() + 4 * mat_tex.size(), d_mat.get() + mat_tex.size()};
@@ -273,9 +275,9 @@ struct Textures {
     void drop() {
         for (auto& u : uv) u.clear();
         for (auto& t : tan) t.clear();
-        tw.clear(), th.clear(), mat_tex.clear(), mat_mr.clear(), mat_nrm.clear(), nrm_scale.clear(), first.clear(), atlas.clear();
+        tw.clear(), th.clear(), mat_tex.clear(), mat_mr.clear(), mat_nrm.clear(), nrm_scale.clear(), first.clear(), flags.clear(), atlas.clear();
         d_uv.reset(), d_stage.reset(), d_tstage.reset(), d_atlas.reset(), d_mat.reset();
-        textured = textured_mr = textured_nrm = 0;
+        textured = textured_mr = textured_nrm = textured_srgb = 0;
         nrm_fields = false;
         dev_ok = false;
     }

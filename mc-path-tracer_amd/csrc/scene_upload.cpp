@@ -696,7 +696,12 @@ static int textures_install(mcpt_ctx* c, const mcpt_texture_set& set) {
     for (int k = 0; k < 3 && ntan; k++)
         for (size_t i = 0; i < 4 * (size_t)ntri; i++)
             if (!std::isfinite(tan[k][i])) return set_err(c, MCPT_E_INVALID, "textures: non-finite tangent component");
+    // the per-texture flags (section 22; a flagged entry's index shares its word with kTexEntrySrgb)
+    if (set.tex_flags && ntex >= mcpt::kTexEntrySrgb) return set_err(c, MCPT_E_INVALID, "textures: 2^30 textures or more with flags");
+    for (int32_t k = 0; set.tex_flags && k < ntex; k++)
+        if (set.tex_flags[k] & ~(uint32_t)MCPT_TEX_SRGB) return set_err(c, MCPT_E_INVALID, "textures: unknown texture flag");
     Textures now;
+    if (set.tex_flags) now.flags.assign(set.tex_flags, set.tex_flags + ntex);
     now.nrm_fields = ntan != 0 || mat_nrm || set.nrm_scale;
     for (int k = 0; k < 3 && ntan; k++) now.tan[k].assign(tan[k], tan[k] + 4 * (size_t)ntri);
     if (mat_nrm) now.mat_nrm.assign(mat_nrm, mat_nrm + nmat);
@@ -720,8 +725,12 @@ static int textures_install(mcpt_ctx* c, const mcpt_texture_set& set) {
     // ones in front of them and mirrored, at nmat - 1 - m (TexView::mat[-1 - m]; section 20)
     std::vector<int4> dm(2 * (size_t)nmat);
     auto entry = [&now](int32_t k) { return k < 0 ? make_int4(0, 0, 0, -1) : make_int4((int)now.first[k], now.tw[k], now.th[k], k); };
+    // (section 22) a base-colour entry's fourth word carries its texture's sRGB flag for tex_base_srgb; every
+    // other entry, and every entry of a set without a flagged base-colour texture, is the word it was
+    auto srgb = [&now](int32_t k) { return k >= 0 && !now.flags.empty() && (now.flags[k] & MCPT_TEX_SRGB) != 0; };
     for (int32_t m = 0; m < nmat; m++) {
         dm[(size_t)nmat + m] = entry(now.mat_tex[m]);
+        if (srgb(now.mat_tex[m])) dm[(size_t)nmat + m].w |= mcpt::kTexEntrySrgb, now.textured_srgb++;
         dm[(size_t)nmat - 1 - m] = entry(now.mat_mr[m]);
         now.textured += now.mat_tex[m] >= 0;
         now.textured_mr += now.mat_mr[m] >= 0;
@@ -745,7 +754,8 @@ static int textures_install(mcpt_ctx* c, const mcpt_texture_set& set) {
         same_bytes(was.tw, now.tw) && same_bytes(was.th, now.th) && same_bytes(was.mat_tex, now.mat_tex) &&
         same_bytes(was.mat_mr, now.mat_mr) && same_bytes(was.atlas, now.atlas) && same_bytes(was.mat_nrm, now.mat_nrm) &&
         same_bytes(was.nrm_scale, now.nrm_scale) && same_bytes(was.tan[0], now.tan[0]) && same_bytes(was.tan[1], now.tan[1]) &&
-        same_bytes(was.tan[2], now.tan[2]) && was.nrm_fields == now.nrm_fields && (was.dev_ok || !was.shaded()))
+        same_bytes(was.tan[2], now.tan[2]) && was.nrm_fields == now.nrm_fields && same_bytes(was.flags, now.flags) &&
+        (was.dev_ok || !was.shaded()))
         return MCPT_OK;  // an identical set does nothing
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // no launch in flight reads the old set
@@ -773,6 +783,11 @@ static int textures_install(mcpt_ctx* c, const mcpt_texture_set& set) {
     }
     if (same_shading && now.textured_nrm > 0)
         same_shading = same_bytes(was.tan[0], now.tan[0]) && same_bytes(was.tan[1], now.tan[1]) && same_bytes(was.tan[2], now.tan[2]);
+    // ... nor do the texture flags (section 22) beyond the sRGB bit of a texture some base-colour slot uses
+    auto srgb_in_use = [](const Textures& t, size_t m) {
+        return t.mat_tex[m] >= 0 && !t.flags.empty() && (t.flags[(size_t)t.mat_tex[m]] & MCPT_TEX_SRGB) != 0;
+    };
+    for (size_t m = 0; same_shading && m < now.mat_tex.size(); m++) same_shading = srgb_in_use(was, m) == srgb_in_use(now, m);
     const bool differs = (was.shaded() || now.shaded()) && !same_shading;
     c->tx = std::move(now);
     if (differs) changed();
@@ -784,12 +799,12 @@ extern "C" {
 int mcpt_set_material_textures(mcpt_ctx* c, int32_t ntri, const float* uv0, const float* uv1, const float* uv2, int32_t ntex,
                                const mcpt_texture* textures, int32_t nmat, const int32_t* mat_tex) {
     return textures_install(c, mcpt_texture_set{ntri, uv0, uv1, uv2, nullptr, nullptr, nullptr, ntex, textures, nmat, mat_tex, nullptr,
-                                                nullptr, nullptr});
+                                                nullptr, nullptr, nullptr});
 }
 int mcpt_set_material_texture_maps(mcpt_ctx* c, int32_t ntri, const float* uv0, const float* uv1, const float* uv2, int32_t ntex,
                                    const mcpt_texture* textures, int32_t nmat, const int32_t* mat_tex, const int32_t* mat_mr) {
     return textures_install(c, mcpt_texture_set{ntri, uv0, uv1, uv2, nullptr, nullptr, nullptr, ntex, textures, nmat, mat_tex, mat_mr,
-                                                nullptr, nullptr});
+                                                nullptr, nullptr, nullptr});
 }
 int mcpt_set_material_texture_set(mcpt_ctx* c, const mcpt_texture_set* set) {
     if (!c) return MCPT_E_INVALID;
@@ -848,9 +863,26 @@ int mcpt_material_textures_read(mcpt_ctx* c, int32_t* ntri, int32_t* ntex, int32
         if (dst[k] && !t.uv[k].empty()) memcpy(dst[k], t.uv[k].data(), t.uv[k].size() * sizeof(float));
     return MCPT_OK;
 }
+int mcpt_material_texture_flags_read(mcpt_ctx* c, int32_t* ntex, uint32_t* tex_flags) {
+    if (!c) return MCPT_E_INVALID;
+    if (ntex) *ntex = (int32_t)c->tx.flags.size();
+    if (tex_flags && !c->tx.flags.empty()) memcpy(tex_flags, c->tx.flags.data(), c->tx.flags.size() * sizeof(uint32_t));
+    return MCPT_OK;
+}
+int mcpt_debug_texture_srgb_stats(const mcpt_ctx* c, int32_t* srgb_materials, int32_t* srgb_in_effect) {
+    if (!c) return MCPT_E_INVALID;
+    if (srgb_materials) *srgb_materials = c->tx.textured_srgb;
+    if (srgb_in_effect) *srgb_in_effect = c->tx.view().uv && c->tx.textured_srgb > 0 ? 1 : 0;
+    return MCPT_OK;
+}
 int mcpt_texture_sample_run(mcpt_ctx* c, int32_t w, int32_t h, const uint8_t* rgba8, uint32_t n, const float* uv,
                             float* out_rgb) {
+    return mcpt_texture_sample_run_ex(c, w, h, rgba8, 0u, n, uv, out_rgb);
+}
+int mcpt_texture_sample_run_ex(mcpt_ctx* c, int32_t w, int32_t h, const uint8_t* rgba8, uint32_t flags, uint32_t n,
+                               const float* uv, float* out_rgb) {
     if (!c) return MCPT_E_INVALID;
+    if (flags & ~(uint32_t)MCPT_TEX_SRGB) return set_err(c, MCPT_E_INVALID, "texture sample: unknown texture flag");
     if (w < 1 || w > 16384 || h < 1 || h > 16384 || !rgba8) return set_err(c, MCPT_E_INVALID, "texture sample: bad image");
     if (n == 0) return MCPT_OK;
     if (!uv || !out_rgb || n >= (1u << 28)) return set_err(c, MCPT_E_INVALID, "texture sample: bad uv / output array");
@@ -863,7 +895,8 @@ int mcpt_texture_sample_run(mcpt_ctx* c, int32_t w, int32_t h, const uint8_t* rg
     if ((rc = dupload(c, tmp.L, &d_tex, reinterpret_cast<const uint32_t*>(rgba8), (size_t)w * h)) ||
         (rc = dupload(c, tmp.L, &d_uv, reinterpret_cast<const float2*>(uv), (size_t)n)) || (rc = dalloc(c, tmp.L, &d_out, 3 * (size_t)n)))
         return rc;
-    launch_tex_sample(d_tex, w, h, d_uv, d_out, n, c->stream);
+    if (flags & MCPT_TEX_SRGB) launch_tex_sample_srgb(d_tex, w, h, d_uv, d_out, n, c->stream);
+    else launch_tex_sample(d_tex, w, h, d_uv, d_out, n, c->stream);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out_rgb, d_out, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));

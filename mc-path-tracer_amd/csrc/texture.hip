@@ -6,6 +6,9 @@
 // Normal maps:
 //   k_tex_tangent_records  the per-triangle tangent stream in record order, beside k_tex_uv_records
 //   k_guide_accum_nrm      k_guide_accum_tex with the mapped normal as the normal guide
+// sRGB base colour:
+//   k_tex_sample_srgb      k_tex_sample with the texels decoded through the table
+//   k_guide_accum_srgb     k_guide_accum_nrm with the decoded base colour as the albedo guide
 #include "device/scene_dev.hpp"
 
 namespace mcpt_dev {
@@ -121,6 +124,55 @@ __global__ __launch_bounds__(256) void k_guide_accum_nrm(GuideTexArgs b) {
 }
 void launch_guide_accum_nrm(const GuideTexArgs& a, hipStream_t s) {
     if (a.g.np) hipLaunchKernelGGL(k_guide_accum_nrm, dim3((a.g.np + 255) / 256), dim3(256), 0, s, a);
+}
+
+// The lookup alone with every texel decoded through the sRGB table (section 22)
+__global__ __launch_bounds__(256) void k_tex_sample_srgb(const uint32_t* tex, int w, int h, const float2* uv, float* out,
+                                                         uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float2 c = uv[i];
+    const V3 t = mcpt::tex_bilinear_rgba8_srgb(tex, w, h, c.x, c.y, true);
+    out[3 * (size_t)i + 0] = t.x;
+    out[3 * (size_t)i + 1] = t.y;
+    out[3 * (size_t)i + 2] = t.z;
+}
+void launch_tex_sample_srgb(const uint32_t* tex, int w, int h, const float2* uv, float* out_rgb, uint32_t n, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_tex_sample_srgb, dim3((n + 255u) / 256u), dim3(256), 0, s, tex, w, h, uv, out_rgb, n);
+}
+
+// k_guide_accum_nrm under a set with an sRGB-flagged base-colour texture (section 22): the albedo guide
+// accumulates the colour k_material<TexSrgb, ...> shades with.  The hit record is hit_record_n as at level 4 (a
+// material without a normal map keeps its normals by selection); normal, depth and count as k_guide_accum_nrm.
+__global__ __launch_bounds__(256) void k_guide_accum_srgb(GuideTexArgs b) {
+    const GuideArgs& a = b.g;
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= a.np) return;
+    const uint32_t pix = a.p0 + j;
+    const int x = (int)(pix % (uint32_t)a.W), y = (int)(pix / (uint32_t)a.W);
+    if (!(x < a.W - 1 && y < a.H - 1)) return;
+    float4 ga = a.g_alb[pix], gn = a.g_nz[pix];
+    for (uint32_t s = 0; s < a.ns; s++) {
+        const size_t i = (size_t)s * a.np + j;
+        const int tri = b.rec[i];
+        V3 al = v3(1.f, 1.f, 1.f), n = v3(0.f, 0.f, 0.f);
+        float t = 0.f;
+        if (tri >= 0 && (uint32_t)tri < b.scene.ntri) {
+            V3 pos;
+            int mat;
+            float tu, tv;
+            hit_record_n(b.scene, b.tex, xyz(a.ro[i]), xyz(a.rd[i]), tri, pos, n, mat, t, tu, tv);
+            const float* m = a.mats + 8 * (size_t)mat;
+            al = mcpt::tex_base_srgb(b.tex, mat, v3(m[0], m[1], m[2]), tu, tv);
+        }
+        ga = make_float4(ga.x + al.x, ga.y + al.y, ga.z + al.z, ga.w + 1.f);
+        gn = make_float4(gn.x + n.x, gn.y + n.y, gn.z + n.z, gn.w + t);
+    }
+    a.g_alb[pix] = ga;
+    a.g_nz[pix] = gn;
+}
+void launch_guide_accum_srgb(const GuideTexArgs& a, hipStream_t s) {
+    if (a.g.np) hipLaunchKernelGGL(k_guide_accum_srgb, dim3((a.g.np + 255) / 256), dim3(256), 0, s, a);
 }
 
 }  // namespace mcpt_dev

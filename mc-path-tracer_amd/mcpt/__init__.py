@@ -110,7 +110,12 @@ class Texture(C.Structure):  # mcpt_texture: a decoded RGBA8 image
 class TextureSet(C.Structure):  # mcpt_texture_set: a whole texture set, NULL = absent
     _fields_ = [("ntri", C.c_int32), ("uv0", _f), ("uv1", _f), ("uv2", _f), ("tan0", _f), ("tan1", _f), ("tan2", _f),
                 ("ntex", C.c_int32), ("textures", C.POINTER(Texture)), ("nmat", C.c_int32), ("mat_tex", _i), ("mat_mr", _i),
-                ("mat_nrm", _i), ("nrm_scale", _f)]
+                ("mat_nrm", _i), ("nrm_scale", _f), ("tex_flags", _u)]  # tex_flags: section 22
+
+
+# mcpt_scene_load_glb_ex flags
+MCPT_GLB_PBR_FACTORS, MCPT_GLB_TEXTURES, MCPT_GLB_SRGB, MCPT_GLB_AS_AUTHORED = 1, 2, 4, 7
+MCPT_TEX_SRGB = 1  # mcpt_texture_set.tex_flags bit 0: sRGB-encoded texels, decoded when read as a base colour
 
 
 class PathView(C.Structure):  # mcpt_path_view: path state at the shading stages' boundary
@@ -238,6 +243,13 @@ ABI = {
     "mcpt_material_normal_read": (C.c_int, [C.c_void_p, _i, _i, _i, _f, _f, _f, _f]),
     "mcpt_debug_texture_normal_stats": (C.c_int, [C.c_void_p, _i, _i]),
     "mcpt_tangents_from_uv": (C.c_int, [C.c_int32] + [_f] * 12),
+    "mcpt_material_texture_flags_read": (C.c_int, [C.c_void_p, _i, _u]),
+    "mcpt_debug_texture_srgb_stats": (C.c_int, [C.c_void_p, _i, _i]),
+    "mcpt_texture_sample_run_ex": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, _f, _f]),
+    "mcpt_scene_set_material_texture_ex": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_uint32]),
+    "mcpt_scene_get_texture_flags": (C.c_int, [C.c_void_p, C.POINTER(_u), _i]),
+    "mcpt_scene_load_glb_ex": (C.c_int, [C.c_void_p, C.c_char_p, _f, C.c_uint32]),
+    "mcpt_scene_glb_report": (C.c_int, [C.c_void_p, _i, C.c_char_p, C.c_int32]),
     "mcpt_scene_set_material_normal_texture": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.c_float]),
     "mcpt_scene_get_material_normal": (C.c_int, [C.c_void_p, C.POINTER(_i), C.POINTER(_f), _i]),
     "mcpt_scene_get_tangents": (C.c_int, [C.c_void_p, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), _i]),
@@ -266,6 +278,9 @@ ABI = {
     "mcpt_film_write_png": (C.c_int, [C.c_void_p, C.c_float, C.c_char_p]),
     "mcpt_film_write_pfm": (C.c_int, [C.c_void_p, C.c_char_p]),
     "mcpt_image_write_png": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8)]),
+    "mcpt_image_read_png_memory": (C.c_int, [C.c_char_p, C.c_size_t, _i, _i, C.POINTER(C.c_uint8), C.c_size_t]),
+    "mcpt_image_read_png": (C.c_int, [C.c_char_p, _i, _i, C.POINTER(C.c_uint8), C.c_size_t]),
+    "mcpt_image_read_png_error": (C.c_char_p, []),
     "mcpt_image_write_pfm": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
     "mcpt_debug_trace_profile": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]),
     "mcpt_debug_shade_sections": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int, C.c_int]),
@@ -355,7 +370,7 @@ def make_camera(position, yaw_deg=-90.0, pitch_deg=0.0, fovy_deg=45.0, aspect=1.
 def _arr(ptr, n, dtype):
     if n == 0 or not ptr:
         return np.zeros(0, dtype)
-    ct = {np.float32: C.c_float, np.int32: C.c_int32}[dtype]
+    ct = {np.float32: C.c_float, np.int32: C.c_int32, np.uint32: C.c_uint32}[dtype]
     return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ct)), shape=(n,)).copy()
 
 
@@ -404,9 +419,23 @@ class Scene:
         _check(rc)
         return self
 
-    def load_glb(self, path, xform=None):
+    def load_glb(self, path, xform=None, flags=0):
+        """Add a glb's meshes (mcpt_scene_load_glb_ex).  flags: MCPT_GLB_PBR_FACTORS, MCPT_GLB_TEXTURES,
+        MCPT_GLB_SRGB or MCPT_GLB_AS_AUTHORED (all three); 0 keeps TEXCOORD_0 and the
+        base-colour factor alone, as before.  glb_report() says what could not be honoured."""
         xf = None if xform is None else fptr(np.ascontiguousarray(xform, np.float32).reshape(16))
-        return self._ck(lib().mcpt_scene_load_glb(self.h, str(path).encode(), xf))
+        if not flags:
+            return self._ck(lib().mcpt_scene_load_glb(self.h, str(path).encode(), xf))
+        return self._ck(lib().mcpt_scene_load_glb_ex(self.h, str(path).encode(), xf, int(flags)))
+
+    def glb_report(self):
+        """Of the last load_glb: {"images_decoded", "images_skipped", "slots_attached", "slots_skipped": int,
+        "lines": [str]}, one line per image or material slot that could not be honoured (mcpt_scene_glb_report)."""
+        c = (C.c_int32 * 4)()
+        buf = C.create_string_buffer(1 << 16)
+        _check(lib().mcpt_scene_glb_report(self.h, c, buf, len(buf)))
+        return {"images_decoded": c[0], "images_skipped": c[1], "slots_attached": c[2], "slots_skipped": c[3],
+                "lines": [l for l in buf.value.decode().split("\n") if l]}
 
     def add_mesh(self, v0, v1, v2, n0, n1, n2, base_rgb=(1.0, 1.0, 1.0)):
         arrs = [np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (v0, v1, v2, n0, n1, n2)]
@@ -440,13 +469,17 @@ class Scene:
                 raise ValueError("uv0, uv1 and uv2 must have one row per triangle of the mesh")
         return self._ck(lib().mcpt_scene_set_mesh_uv(self.h, int(mat), *[fptr(a) for a in u]))
 
-    def set_texture(self, mat, img_u8):
+    def set_texture(self, mat, img_u8, srgb=False):
         """Attach a base-colour texture to material ``mat``: an (h, w, 4) or (h, w, 3) uint8 image, row 0
-        = v in [0, 1/h), used as stored (no sRGB decode; alpha ignored).  None detaches.
-        PathTracer.upload_scene installs the scene's textures after the upload."""
+        = v in [0, 1/h), alpha ignored.  Used as stored unless ``srgb``: then the texels are sRGB-encoded
+        (every glTF base-colour image is) and the lookup decodes them before filtering.
+        None detaches.  PathTracer.upload_scene installs the scene's textures after the upload."""
         if img_u8 is None:
             return self._ck(lib().mcpt_scene_set_material_texture(self.h, int(mat), 0, 0, None))
         img = _rgba8(img_u8)
+        if srgb:
+            return self._ck(lib().mcpt_scene_set_material_texture_ex(self.h, int(mat), img.shape[1], img.shape[0],
+                                                                     img.ctypes.data_as(C.POINTER(C.c_uint8)), MCPT_TEX_SRGB))
         return self._ck(lib().mcpt_scene_set_material_texture(self.h, int(mat), img.shape[1], img.shape[0],
                                                               img.ctypes.data_as(C.POINTER(C.c_uint8))))
 
@@ -483,7 +516,8 @@ class Scene:
         """None when no material has a texture of any kind, else {"textures": [(h, w, 4) uint8, ...],
         "mat_tex": int32 (nmat,), "mat_mr": int32 (nmat,)} (copies): per material the index of its
         base-colour and of its metallic-roughness texture in the one list, or -1; and, only when a material
-        has a normal map, "mat_nrm": int32 (nmat,) and "nrm_scale": float32 (nmat,)."""
+        has a normal map, "mat_nrm": int32 (nmat,) and "nrm_scale": float32 (nmat,); and, only when a texture
+        carries a flag (set_texture(..., srgb=True); section 22), "tex_flags": uint32 per texture."""
         t, mt, nt, nm = C.POINTER(Texture)(), _i(), C.c_int32(0), C.c_int32(0)
         _check(lib().mcpt_scene_get_textures(self.h, C.byref(t), C.byref(nt), C.byref(mt), C.byref(nm)))
         if not t or nt.value == 0:
@@ -500,6 +534,11 @@ class Scene:
             mn = _arr(mn, nn.value, np.int32)
             if (mn >= 0).any():
                 out["mat_nrm"], out["nrm_scale"] = mn, _arr(sc, nn.value, np.float32)
+        fl, nf = _u(), C.c_int32(0)
+        _check(lib().mcpt_scene_get_texture_flags(self.h, C.byref(fl), C.byref(nf)))
+        fl = _arr(fl, nf.value, np.uint32)
+        if fl.any():
+            out["tex_flags"] = fl
         return out
 
     def uv(self):
@@ -667,10 +706,12 @@ class PathTracer:
                 kw = {}
                 if "mat_nrm" in t:  # (section 21) normal maps come with the built scene's tangents
                     kw = dict(tangents=scene.tangents(), mat_nrm=t["mat_nrm"], nrm_scale=t["nrm_scale"])
+                if "tex_flags" in t:  # (section 22) a flagged texture: its sRGB flag comes along
+                    kw["tex_flags"] = t["tex_flags"]
                 self.set_textures(*scene.uv(), t["textures"], t["mat_tex"], mat_mr=t["mat_mr"] if (t["mat_mr"] >= 0).any() else None, **kw)
 
     def set_textures(self, uv0=None, uv1=None, uv2=None, textures=None, mat_tex=None, mat_mr=None, tangents=None, mat_nrm=None,
-                     nrm_scale=None):
+                     nrm_scale=None, tex_flags=None):
         """Base-colour textures (mcpt_set_material_textures): the corner uvs, (ntri, 2)
         each in the uploaded desc's triangle order, a list of (h, w, 4) / (h, w, 3) uint8 images, and per
         material a texture index or -1.  No arguments (or no textures) remove the set.  A change clears the
@@ -679,7 +720,9 @@ class PathTracer:
         metallic-roughness texture in the same list, or -1; None: no material has one (the older call).
         tangents, mat_nrm, nrm_scale (mcpt_set_material_texture_set; section 21): (tan0, tan1, tan2), (ntri, 4)
         each as tangents_from_uv returns them; per material the index of its normal map in the same list,
-        or -1; one scale per material.  Each may be None (absent); all None: the older calls."""
+        or -1; one scale per material.  Each may be None (absent); all None: the older calls.
+        tex_flags (section 22): one word per texture, bit 0 MCPT_TEX_SRGB (the texels are sRGB-encoded and
+        decoded when read as a base colour); None: absent, every texture used as stored."""
         if not textures:
             self._ck(lib().mcpt_set_material_textures(self.h, 0, None, None, None, 0, None, 0, None))
             return
@@ -692,7 +735,7 @@ class PathTracer:
             arr[k].w, arr[k].h = im.shape[1], im.shape[0]
             arr[k].rgba8 = im.ctypes.data_as(C.POINTER(C.c_uint8))
         mt = np.ascontiguousarray(mat_tex, np.int32).reshape(-1)
-        if tangents is not None or mat_nrm is not None or nrm_scale is not None:
+        if tangents is not None or mat_nrm is not None or nrm_scale is not None or tex_flags is not None:
             ts = TextureSet()
             ts.ntri, ts.uv0, ts.uv1, ts.uv2 = len(u[0]), fptr(u[0]), fptr(u[1]), fptr(u[2])
             ts.ntex, ts.textures, ts.nmat, ts.mat_tex = len(imgs), arr, len(mt), mt.ctypes.data_as(_i)
@@ -703,6 +746,12 @@ class PathTracer:
                     raise ValueError("tangents are three arrays with one row {T.xyz, s} per triangle")
                 ts.tan0, ts.tan1, ts.tan2 = (fptr(t) for t in tn)
                 keep += tn
+            if tex_flags is not None:
+                fl = np.ascontiguousarray(tex_flags, np.uint32).reshape(-1)
+                if len(fl) != len(imgs):
+                    raise ValueError("tex_flags must have one word per texture")
+                ts.tex_flags = fl.ctypes.data_as(_u)
+                keep.append(fl)
             for name, val, dt, ct in (("mat_mr", mat_mr, np.int32, _i), ("mat_nrm", mat_nrm, np.int32, _i),
                                       ("nrm_scale", nrm_scale, np.float32, _f)):
                 if val is not None:
@@ -725,7 +774,8 @@ class PathTracer:
 
     def textures(self):
         """The installed set as {"uv0", "uv1", "uv2": (ntri, 2), "textures": [(h, w, 4) uint8], "mat_tex":
-        int32 (nmat,), "mat_mr": int32 (nmat,)}, or None when none is installed."""
+        int32 (nmat,), "mat_mr": int32 (nmat,)}, or None when none is installed; "mat_nrm", "nrm_scale" and
+        "tangents" only while the set carries normal-map fields, "tex_flags" only while it carries flags."""
         nt, nx, nm = C.c_int32(0), C.c_int32(0), C.c_int32(0)
         L = lib().mcpt_material_textures_read
         self._ck(L(self.h, C.byref(nt), C.byref(nx), C.byref(nm), None, -1, None, None, None, None, None, None))
@@ -754,14 +804,25 @@ class PathTracer:
                 tn = [np.zeros((ntan.value, 4), np.float32) for _ in range(3)]
                 self._ck(L(self.h, None, None, mn.ctypes.data_as(_i), fptr(sc), fptr(tn[0]), fptr(tn[1]), fptr(tn[2])))
                 out.update(mat_nrm=mn, nrm_scale=sc, tangents=tuple(tn) if ntan.value else None)
+        n = C.c_int32(0)
+        self._ck(lib().mcpt_material_texture_flags_read(self.h, C.byref(n), None))
+        if n.value:  # the set carries texture flags (section 22): the key exists only then
+            fl = np.zeros(n.value, np.uint32)
+            self._ck(lib().mcpt_material_texture_flags_read(self.h, None, fl.ctypes.data_as(_u)))
+            out["tex_flags"] = fl
         return out
 
-    def texture_sample(self, img, uv):
+    def texture_sample(self, img, uv, srgb=False):
         """The texture lookup alone on the device (mcpt_texture_sample_run): (n, 3) float32 for (n, 2) uvs
-        over an (h, w, 4) / (h, w, 3) uint8 image.  Needs neither a scene nor a film."""
+        over an (h, w, 4) / (h, w, 3) uint8 image.  Needs neither a scene nor a film.  srgb: the base-colour
+        lookup of a texture flagged MCPT_TEX_SRGB (mcpt_texture_sample_run_ex)."""
         im = _rgba8(img)
         c = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
         out = np.zeros((len(c), 3), np.float32)
+        if srgb:
+            self._ck(lib().mcpt_texture_sample_run_ex(self.h, im.shape[1], im.shape[0], im.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                      MCPT_TEX_SRGB, len(c), fptr(c), fptr(out)))
+            return out
         self._ck(lib().mcpt_texture_sample_run(self.h, im.shape[1], im.shape[0], im.ctypes.data_as(C.POINTER(C.c_uint8)),
                                                len(c), fptr(c), fptr(out)))
         return out
@@ -774,7 +835,10 @@ class PathTracer:
         three keys it always returned (read the other two with .get).  While a set with normal-map fields
         (tangents, mat_nrm or nrm_scale) is installed also "nrm_materials", the materials
         with a normal map, and "nrm_in_effect", whether the normal-map kernels are
-        (mcpt_debug_texture_normal_stats); no other set, and no context without one, has these two keys."""
+        (mcpt_debug_texture_normal_stats); no other set, and no context without one, has these two keys.
+        While a set with texture flags (section 22) is installed also "srgb_materials", the materials whose
+        base-colour texture is flagged sRGB, and "srgb_in_effect", whether the sRGB kernels are
+        (mcpt_debug_texture_srgb_stats); again no other set has these two keys."""
         b, m, on = C.c_uint64(0), C.c_int32(0), C.c_int32(0)
         self._ck(lib().mcpt_debug_texture_stats(self.h, C.byref(b), C.byref(m), C.byref(on)))
         out = {"bytes": int(b.value), "textured_materials": int(m.value), "in_effect": bool(on.value)}
@@ -790,6 +854,11 @@ class PathTracer:
             if n.value:  # only while a set with normal-map fields is installed
                 self._ck(lib().mcpt_debug_texture_normal_stats(self.h, C.byref(m), C.byref(on)))
                 out["nrm_materials"], out["nrm_in_effect"] = int(m.value), bool(on.value)
+        n = C.c_int32(0)
+        self._ck(lib().mcpt_material_texture_flags_read(self.h, C.byref(n), None))
+        if n.value:  # only while a set with texture flags is installed
+            self._ck(lib().mcpt_debug_texture_srgb_stats(self.h, C.byref(m), C.byref(on)))
+            out["srgb_materials"], out["srgb_in_effect"] = int(m.value), bool(on.value)
         return out
 
     def set_emission(self, rgb=None):
@@ -1507,6 +1576,28 @@ def write_png(path, rgba8):
     rc = lib().mcpt_image_write_png(os.fsencode(path), w, h, a.ctypes.data_as(C.POINTER(C.c_uint8)))
     if rc != 0:
         raise McptError(f"mcpt_image_write_png failed ({rc})")
+
+
+def read_png(path_or_bytes):
+    """Decode a PNG file (a path) or payload (bytes) into an (h, w, 4) uint8 array, row 0 of the file first
+    (mcpt_image_read_png / _memory: the project's own inflate and PNG decoder; host-only, no GPU).  What
+    Scene.set_texture and PathTracer.set_textures take.  McptError with the decoder's reason for a file it
+    refuses (DESIGN.md section 22 lists what it accepts)."""
+    w, h = C.c_int32(0), C.c_int32(0)
+    mem = isinstance(path_or_bytes, (bytes, bytearray, memoryview))
+    if mem:
+        data = bytes(path_or_bytes)
+        call = lambda buf, cap: lib().mcpt_image_read_png_memory(data, len(data), C.byref(w), C.byref(h), buf, cap)
+    else:
+        name = os.fsencode(path_or_bytes)
+        call = lambda buf, cap: lib().mcpt_image_read_png(name, C.byref(w), C.byref(h), buf, cap)
+    rc = call(None, 0)
+    if rc == 0:
+        out = np.zeros((h.value, w.value, 4), np.uint8)
+        rc = call(out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size)
+    if rc != 0:
+        raise McptError(f"read_png failed ({rc}): {lib().mcpt_image_read_png_error().decode()}")
+    return out
 
 
 def write_pfm(path, rgb):

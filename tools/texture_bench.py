@@ -24,6 +24,11 @@ every depth (F_FZERO), so the cost per material evaluation is reported too.
 same walls as their normal map (R, G anywhere, B in 128..255, scale 1; tangents from mcpt.tangents_from_uv over
 the planar uvs), frames with base + MR and with base + MR + normal alternating on one context:
 k_material<TexMr, ...> against k_material<TexNrm, ...>.
+
+--srgb (profiles/textures_srgb.json): --normal's setup with the base-colour image flagged
+MCPT_TEX_SRGB, frames with base + MR + normal unflagged and flagged alternating on one context:
+k_material<TexNrm, ...> against k_material<TexSrgb, ...> (the decode table a literal array read per lane).  The
+frames' spread (min, max) comes with the medians.
 Prints one JSON line.
 """
 import argparse
@@ -51,6 +56,11 @@ def kstats(d):
             m = re.search(r"k_material<(\w+), (\w+), (\w+), (\w+)>", row["Name"])
             r = re.search(r"k_material<(?:\w+::)*TexMr, (\w+), (\w+), (\w+)>", row["Name"])
             n = re.search(r"k_material<(?:\w+::)*TexNrm, (\w+), (\w+), (\w+)>", row["Name"])
+            g = re.search(r"k_material<(?:\w+::)*TexSrgb, (\w+), (\w+), (\w+)>", row["Name"])
+            if g:
+                out["fixed=%s samp=%s mis=%s tex=srgb" % tuple(int(x in ("true", "1")) for x in g.groups())] = {
+                    "calls": int(row["Calls"]), "total_ms": float(row["TotalDurationNs"]) / 1e6, "us_per_launch": float(row["AverageNs"]) / 1e3}
+                continue
             if n:
                 out["fixed=%s samp=%s mis=%s tex=nrm" % tuple(int(x in ("true", "1")) for x in n.groups())] = {
                     "calls": int(row["Calls"]), "total_ms": float(row["TotalDurationNs"]) / 1e6, "us_per_launch": float(row["AverageNs"]) / 1e3}
@@ -82,6 +92,7 @@ def main():
     ap.add_argument("--spp", type=int, default=None)
     ap.add_argument("--mr", action="store_true", help="base-colour set against base + metallic-roughness (section 20)")
     ap.add_argument("--normal", action="store_true", help="base + MR against base + MR + normal map (section 21)")
+    ap.add_argument("--srgb", action="store_true", help="base + MR + normal against the same with the base image flagged sRGB (section 22)")
     ap.add_argument("--kstats", metavar="DIR", default=None, help="summarise a kernel trace of this program and exit")
     a = ap.parse_args()
     if a.kstats:
@@ -96,6 +107,7 @@ def main():
     walls = (0, 1, 2, 3, 4)
     uv, imgs, mat_tex = wall_set(scene.arrays(), a.size, walls)
     pt = mcpt.PathTracer(0, mcpt.default_config(spp=spp, max_depth=rc.max_depth))
+    a.normal = a.normal or a.srgb
     a.mr = a.mr or a.normal
     if a.mr:  # a second image on the same walls, both index arrays set
         imgs = imgs + [np.random.default_rng(20).integers(64, 256, (a.size, a.size, 4)).astype(np.uint8)]
@@ -119,12 +131,16 @@ def main():
             pt.set_textures(*uv, imgs, mat_tex, mat_mr=mat_mr)
         elif k == "walls_textured_mr_nrm":
             pt.set_textures(*uv, imgs, mat_tex, mat_mr=mat_mr, tangents=tans, mat_nrm=mat_nrm)
+        elif k == "walls_textured_mr_nrm_srgb":
+            pt.set_textures(*uv, imgs, mat_tex, mat_mr=mat_mr, tangents=tans, mat_nrm=mat_nrm, tex_flags=[mcpt.MCPT_TEX_SRGB, 0, 0])
         else:
             pt.set_textures()
 
     rows = {"walls_textured": [], "walls_textured_mr": []} if a.mr else {"none": [], "walls_textured": []}
     if a.normal:
         rows = {"walls_textured_mr": [], "walls_textured_mr_nrm": []}
+    if a.srgb:
+        rows = {"walls_textured_mr_nrm": [], "walls_textured_mr_nrm_srgb": []}
     shade = {k: [] for k in rows}
     iters, rays, stats = {}, {}, {}
     for i in range(a.warmup + a.repeats):
@@ -151,6 +167,7 @@ def main():
         "texture": [a.size, a.size], "textured_materials": list(walls), "device": pt.device,
         "ms_per_frame_median": {k: med(v) for k, v in rows.items()},
         "ms_per_frame_all": {k: [round(x, 3) for x in v] for k, v in rows.items()},
+        "ms_per_frame_min_max": {k: [round(min(v), 3), round(max(v), 3)] for k, v in rows.items()},
         "shade_stage_ms_per_iteration_median": {k: med(v) for k, v in shade.items()},
         "iterations_per_frame": iters, "rays": rays, "material_evaluations": {k: v[1] for k, v in rays.items()},
         "texture_stats": stats, **extra}))
